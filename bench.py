@@ -8,10 +8,12 @@ Headline (BASELINE.json metric "local-BA iters/sec (50 KF x 10k pts) + ICP Mpair
               7->6 tangent projection, J^T J / J^T r), Schur-eliminate the inverse depths, sparse + dense Cholesky, back-substitute,
               evaluate the candidate, accept/reject — closed on device (lvf_problem_solve, no host round trip per iteration);
   value     = LM iterations/s summed over all ranks (one independent window per GPU: weak scaling).
-The K steps are timed as a batch — solves of <= 20 iterations each from the same perturbed start, restored on device between them (so
-every batch does the same work and the problem never converges into a run of rejected steps) — and the batch is repeated 10 times, each
-repeat bracketed by barrier + synchronize with the maximum over ranks taken per repeat: `value` = K / the MEDIAN repeat, so a short
-`--steps 20` run reports the same rate as a long one; the slowest and fastest repeats ride along.
+The K = --steps steps are timed once, bracketed by barrier + synchronize, as solves of <= 20 iterations each from the same perturbed start,
+restored on device between them (so every solve does the same work and the problem never converges into a run of rejected steps):
+`ms_per_step` = the K steps' wall time (the slowest rank's) / K; the fastest, median and slowest solve ride along per step.  Warm-up runs
+at least --warmup iterations and 50 ms of the same solves.  --dump-outputs DIR writes what the last timed solve returned (state + summary).
+
+A plain run does only that.  Everything below is measured with --full:
 `roofline` is ONE object: the dominant kernel of the iteration by time (kernel, bound, achieved, peak, unit, frac, traffic);
 `roofline_all` lists it together with the merged linearisation (fp64 VALU issue) and the band Schur complement (MFMA).  All are timed
 live inside this run: every kernel of the chain is launched with its own start / stop HIP events (hipExtLaunchKernelGGL: the dispatch
@@ -21,7 +23,7 @@ batched-windows solver (8/16 windows per launch chain), the configs[1] PoseOnly 
 as 8d defines a pair, the window tick and the Ceres-surface solve.  `verified` says which legs were checked against the oracle in this
 run.  `cpu_baseline` is the restated reference CPU path (oracle) on a bounded sample — a reported baseline, not the target.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N>1 the driver uses torch.distributed.run.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]; for N>1 the driver uses torch.distributed.run.
 """
 import argparse
 import json
@@ -43,7 +45,6 @@ N_SIMD, CLOCK_GHZ = 1024, 2.4    # 256 CUs x 4 SIMDs; a wave64 VALU instruction 
 VALU_PEAK_GCYC = N_SIMD * CLOCK_GHZ   # SIMD-cycles per nanosecond the chip can spend issuing VALU work
 POSE_ONLY_BYTES_PER_BLOCK = 152  # ob 16 + 2 idx 8 + r 16 + J 112
 KNN_BYTES = lambda Q, M: 40 * Q + 16 * M   # SURVEY 8d kNN pass
-N_REPEATS = 10                   # timed batches of K steps each; the line reports their median
 CHUNK = 20                       # LM iterations per device-loop solve inside a batch
 
 
@@ -141,13 +142,31 @@ def fixed_iterations(api, n):
     return o
 
 
+def dump_outputs(directory, api, st, summary, prefix=""):
+    """What the last timed solve hands its caller, as float64 .npy files: the window's state after the solve (poses [n_kf][7], vel / ba / bg
+    [n_kf][3], inv_depth [n_lm]) and its summary (initial_cost, final_cost, num_iterations, num_successful_steps, num_unsuccessful_steps,
+    termination)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"poses": st.get(api.POSES).reshape(-1, 7), "vel": st.get(api.VEL).reshape(-1, 3), "ba": st.get(api.BA).reshape(-1, 3),
+              "bg": st.get(api.BG).reshape(-1, 3), "inv_depth": st.get(api.INV_DEPTH),
+              "summary": np.array([summary.initial_cost, summary.final_cost, summary.num_iterations, summary.num_successful_steps,
+                                   summary.num_unsuccessful_steps, summary.termination], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, prefix + name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed solve returned (the window's state and the solve summary) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: box calibration, roofline, the other legs, the CPU baseline, the oracle checks "
+                         "and, for --gpus > 1, the solo reference, the sharded relocalisation leg and ranks_seen.  A plain run only times the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other legs")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="process-group backend for --gpus > 1.  nccl (= RCCL over xGMI) is the product path and needs one GPU per rank; gloo exercises the SAME multi-rank "
                          "branch (timing all-gather, solo reference, sharded relocalisation + gather) with every rank on the visible GPU(s) round-robin and CPU tensors in "
@@ -158,8 +177,10 @@ def main():
                          "Off by default: torch brings its own RCCL into the process, and two RCCL builds in one process have been seen to refuse ncclCommInitRank "
                          "(tests/test_gpu_comm_world2.py exercises lvf_comm_* in torch-free processes instead)")
     ap.add_argument("--fail-rank", type=int, default=-1, help="test hook: this rank raises inside its share of the relocalisation leg (the collective must still complete)")
-    ap.add_argument("--legs", default="all", help="comma list of legs to run (default all): batched_windows_8,batched_windows_16,batched_windows_64,small_windows_100,pose_only_K1,icp,scan_match_frame,map_maintenance,window_tick,ceres_surface_solve,relocalize_8_candidates")
+    ap.add_argument("--legs", default="all", help="with --full: comma list of legs to run (default all): batched_windows_8,batched_windows_16,batched_windows_64,small_windows_100,pose_only_K1,icp,scan_match_frame,map_maintenance,window_tick,ceres_surface_solve,relocalize_8_candidates")
     args = ap.parse_args()
+    if args.legs != "all" and not args.full:
+        ap.error("--legs selects legs of the --full run")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -197,47 +218,51 @@ def main():
     opts = {n: fixed_iterations(api, n) for n in set(sizes)}
 
     def run_steps():
-        """K LM iterations as solves of <= CHUNK iterations from the restored start; returns (iterations done, last summary)"""
-        done, s = 0, None
+        """K LM iterations as solves of <= CHUNK iterations from the restored start; returns (iterations done, last summary, seconds per solve)"""
+        done, s, solve_s = 0, None, []
         for n in sizes:
+            t0 = time.perf_counter()
             st.copy_from(st0)
-            s = prob.solve(opts[n])
+            s = prob.solve(opts[n])          # returns after the device loop has finished (the summary is read back)
+            solve_s.append(time.perf_counter() - t0)
             done += int(s.num_iterations)
-        return done, s
+        return done, s, solve_s
 
     torch.zeros(8, dtype=torch.float64, device="cuda")   # forces torch's lazy CUDA init before timing
-    # warm-up: at least --warmup iterations AND at least 50 ms of device work (clocks, caches, first-touch allocations)
+    # warm-up: at least --warmup iterations AND at least 50 ms of device work (clocks, caches, first-touch allocations), in solves of the
+    # first timed solve's size
     done, t_w0 = 0, time.perf_counter()
     first_summary = None
     while done < args.warmup or time.perf_counter() - t_w0 < 0.05:
-        k, s = run_steps()
+        st.copy_from(st0)
+        s = prob.solve(opts[sizes[0]])
         first_summary = first_summary or s
-        done += k
+        done += int(s.num_iterations)
     # single-GPU reference time for the scaling line: rank 0 alone, the other ranks idle at the barrier
     t1_solo = None
-    if world > 1:
+    if world > 1 and args.full:
         barrier()
         if rank == 0:
             ts = []
             for _ in range(3):
                 ctx.synchronize(); t0 = time.perf_counter(); run_steps(); ts.append(time.perf_counter() - t0)
             t1_solo = float(np.median(ts))
-    repeat_s, executed = [], 0
-    for _ in range(N_REPEATS):
-        barrier()
-        t0 = time.perf_counter()
-        executed, _ = run_steps()
-        barrier()
-        repeat_s.append(time.perf_counter() - t0)
+    # the timed steps: exactly K LM iterations, once
+    barrier()
+    t0 = time.perf_counter()
+    executed, last_summary, solve_s = run_steps()
+    barrier()
+    elapsed = time.perf_counter() - t0
     per_rank = None
     if world > 1:
-        t = torch.tensor(repeat_s, dtype=torch.float64, device=coll_dev)
+        t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         allt = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(allt, t)
-        allt = torch.stack(allt).cpu().numpy()             # [rank][repeat]
-        per_rank = [float(np.median(r)) for r in allt]
-        repeat_s = [float(x) for x in allt.max(axis=0)]    # a repeat ends when its slowest rank does
-    elapsed = float(np.median(repeat_s))
+        per_rank = [float(x) for x in torch.cat(allt).cpu().numpy()]
+        elapsed = max(per_rank)                            # the K steps end when the slowest rank's do
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, api, st, last_summary, "" if world == 1 else f"rank{rank}_")
+    solve_ms_per_step = sorted(1e3 * dt / n for dt, n in zip(solve_s, sizes))
 
     out = None
     if rank == 0:
@@ -251,27 +276,29 @@ def main():
                                    f"({btc.n} TwoCamera + {btf.n} TwoFrame + {bpo.n} PoseOnly + {bimu.n if bimu else 0} IMU factors), device-resident LM loop, "
                                    "one independent window per GPU",
                        "n_kf": cfg["n_kf"], "n_lm": cfg["n_lm"], "parallelism": f"{world} independent windows",
-                       "timed_repeats_of_K_steps": N_REPEATS, "iterations_per_solve": CHUNK, "value_from": "median repeat (max over ranks per repeat)"},
+                       "timed_steps": K, "iterations_per_solve": CHUNK, "value_from": "the K timed steps, run once (the slowest rank's time)"},
             "steps_executed": executed,
-            "repeat_ms_per_step_min_median_max": [1e3 * min(repeat_s) / max(executed, 1), 1e3 * elapsed / max(executed, 1), 1e3 * max(repeat_s) / max(executed, 1)],
+            "solve_ms_per_step_min_median_max": [solve_ms_per_step[0], float(np.median(solve_ms_per_step)), solve_ms_per_step[-1]],
             "cost_first_to_last": [first_summary.initial_cost, first_summary.final_cost],
         }
         if world > 1:
-            out["per_rank_median_seconds_for_K_steps"] = per_rank
-            out["single_gpu_seconds_same_work"] = t1_solo
-            out["scaling_efficiency_T1_over_TN"] = (t1_solo / elapsed) if t1_solo else None
+            out["per_rank_seconds_for_K_steps"] = per_rank
+            if args.full:
+                out["single_gpu_seconds_same_work"] = t1_solo
+                out["scaling_efficiency_T1_over_TN"] = (t1_solo / elapsed) if t1_solo else None
             out["dist_backend"] = args.dist_backend
             if gloo:
                 out["dist_backend_note"] = (f"gloo dry run: {world} ranks on {torch.cuda.device_count()} visible GPU(s), CPU tensors in the collectives (RCCL refuses two ranks on one "
                                             "device); value / efficiency here say NOTHING about scaling — the product path is nccl = RCCL over xGMI, one GPU per rank")
+    # ---- everything below the headline runs with --full only
     # ---- what this box is worth for the latency-bound legs (the headline moves +-20 % from box to box on the pool: VERDICT r04 weak 3)
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             out["box_calibration"] = box_calibration(api, ctx, out["ms_per_step"])
         except Exception as e:
             out["box_calibration"] = {"error": repr(e)}
     # ---- roofline (rank 0): stage times of the iteration, live
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             out["roofline_all"], out["iteration_stages_us"], out["event_pair_us"] = roofline(api, ctx, prob, st, cfg, handles)
             keys = ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_us", "launches_per_iteration", "share_of_iteration", "note")
@@ -281,20 +308,20 @@ def main():
     verified = {}
     # ---- other legs + CPU baseline: rank 0, single-GPU runs only (keeps multi-GPU runs short)
     # (every optional leg is fenced: a failure there must never take the headline line down with it)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         try:
             out["legs"] = legs(api, syn, ctx, local_rank, verified, args.legs)
         except Exception as e:
             out["legs"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(api, cfg, prob, st, verified)
         except Exception as e:
             out["cpu_baseline"] = {"error": repr(e)}
-    if rank == 0:
+    if rank == 0 and args.full:
         out["verified"] = verified
     # configs[4] on N GPUs: 8 loop-closure candidates sharded rank-round-robin, one all_gather of the records over RCCL
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         from lvio_fusion_amd import relocalize as rl
         err = None
         table = rl.empty_records(rl.slots(8, world))
@@ -334,7 +361,7 @@ def main():
                                                        "error": err, "errors_by_rank": errs if gloo else None}}
     # what the N > 1 record proves about itself: ranks the process group saw, one device UUID per rank, a checksum of the
     # gathered table — and, on the product backend, the same table once more through the C-ABI communicator (lvf_comm_*: RCCL opened by the library)
-    if world > 1:
+    if world > 1 and args.full:
         seen = ranks_seen(api, ctx, dist, torch, rank, world, local_rank, coll_dev, gloo, rec if not args.no_extras else None, args.check_lvf_comm)
         if rank == 0:
             out["ranks_seen"] = seen
@@ -391,11 +418,12 @@ def compact_line(out):
     cfg = dict(out.get("config") or {})
     line["config"] = cfg
     line["steps_executed"] = out.get("steps_executed")
-    line["repeat_ms_per_step_min_median_max"] = out.get("repeat_ms_per_step_min_median_max")
-    r = out.get("roofline") or {}
-    line["roofline"] = r if "error" in r else _pick(r, ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_us", "launches_per_iteration", "share_of_iteration"))
-    if "traffic" not in line["roofline"] and "error" not in line["roofline"]:
-        line["roofline"]["traffic"] = None
+    line["solve_ms_per_step_min_median_max"] = out.get("solve_ms_per_step_min_median_max")
+    if "roofline" in out:
+        r = out["roofline"]
+        line["roofline"] = r if "error" in r else _pick(r, ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_us", "launches_per_iteration", "share_of_iteration"))
+        if "traffic" not in line["roofline"] and "error" not in line["roofline"]:
+            line["roofline"]["traffic"] = None
     cb = out.get("cpu_baseline")
     if isinstance(cb, dict):
         c = _pick(cb, ("value", "unit", "cores", "kind", "sample", "reference_functors_eval_ms", "error"))
@@ -435,13 +463,12 @@ def compact_line(out):
     rc = L.get("relocalize_8_candidates") if isinstance(L.get("relocalize_8_candidates"), dict) else {}
     if rc:
         line["relocalize_8_candidates"] = _pick(rc, ("ms_total", "candidates_per_sec", "ranks", "best", "error", "comm"))
-    bc = out.get("box_calibration") or {}
-    line["box_calibration"] = _pick(bc, ("ns_per_dependent_fp64_fma", "empty_launch_us_back_to_back", "effective_sclk_mhz", "lm_iteration_in_dependent_fma_times",
-                                         "lm_iteration_in_empty_launch_times", "error"))
-    for k in ("per_rank_median_seconds_for_K_steps", "single_gpu_seconds_same_work", "scaling_efficiency_T1_over_TN", "dist_backend", "ranks_seen"):
+    if "box_calibration" in out:
+        line["box_calibration"] = _pick(out["box_calibration"], ("ns_per_dependent_fp64_fma", "empty_launch_us_back_to_back", "effective_sclk_mhz",
+                                                                 "lm_iteration_in_dependent_fma_times", "lm_iteration_in_empty_launch_times", "error"))
+    for k in ("per_rank_seconds_for_K_steps", "single_gpu_seconds_same_work", "scaling_efficiency_T1_over_TN", "dist_backend", "ranks_seen", "verified"):
         if k in out:
             line[k] = out[k]
-    line["verified"] = out.get("verified")
     line["detail"] = "bench_legs.json"
     return _r(line, 5)
 

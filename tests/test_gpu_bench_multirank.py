@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LINE_LIMIT = 6000        # the driver keeps the last 8 KB of stdout: the final line must fit with room to spare
 
 
-def _run(extra, nproc=2, timeout=900, tmp=None):
+def _run(extra, nproc=2, timeout=900, tmp=None, full=True):
     """-> (the compact stdout line, the full record from the sidecar file)"""
     legs_file = os.path.join(tmp or ROOT, f"bench_legs_test_{os.getpid()}.json")
     if nproc > 1:
@@ -28,7 +28,7 @@ def _run(extra, nproc=2, timeout=900, tmp=None):
                os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "20", "--warmup", "5", "--dist-backend", "gloo"]
     else:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"]
-    cmd += ["--legs-file", legs_file] + extra
+    cmd += ["--legs-file", legs_file] + (["--full"] if full else []) + extra
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
@@ -69,7 +69,7 @@ def test_two_ranks_gloo_line_and_records(one_rank_records):
     assert out["n_gpus"] == 2 and out["steps"] == 20 and out["warmup"] == 5 and out["scaling"] == "weak" and out["dist_backend"] == "gloo"
     assert "gloo dry run" in out["dist_backend_note"]
     assert out["value"] > 0 and out["ms_per_step"] > 0 and out["steps_executed"] == 20
-    assert len(out["per_rank_median_seconds_for_K_steps"]) == 2 and all(t > 0 for t in out["per_rank_median_seconds_for_K_steps"])
+    assert len(out["per_rank_seconds_for_K_steps"]) == 2 and all(t > 0 for t in out["per_rank_seconds_for_K_steps"])
     assert out["single_gpu_seconds_same_work"] > 0 and out["scaling_efficiency_T1_over_TN"] > 0
     # value = the units all ranks processed / the slowest rank's time
     assert abs(out["value"] - 2 * out["steps_executed"] / (1e-3 * out["ms_per_step"] * out["steps_executed"])) <= 1e-6 * out["value"]
@@ -109,3 +109,21 @@ def test_one_rank_line_is_short_and_complete():
     assert all(line["verified"].values())
     assert json.loads(json.dumps(line)) == line
     assert full["value"] == pytest.approx(line["value"], rel=1e-3) and "legs" in full
+
+
+def test_plain_run_times_k_steps_and_dumps_outputs(tmp_path):
+    """without --full: exactly --steps timed LM iterations, the headline fields only, and --dump-outputs writes the last timed solve's results"""
+    line, full = _run(["--dump-outputs", str(tmp_path / "out")], nproc=1, tmp=str(tmp_path), full=False)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in line, k
+    assert line["steps"] == 20 and line["steps_executed"] == 20 and line["value"] == pytest.approx(1e3 / line["ms_per_step"], rel=1e-3)
+    for k in ("roofline", "box_calibration", "legs", "cpu_baseline", "verified"):
+        assert k not in full, k
+    d = tmp_path / "out"
+    want = {"poses": (50, 7), "vel": (50, 3), "ba": (50, 3), "bg": (50, 3), "inv_depth": (10000,), "summary": (6,)}
+    assert sorted(p.name for p in d.iterdir()) == sorted(k + ".npy" for k in want)
+    for k, shape in want.items():
+        a = np.load(d / (k + ".npy"))
+        assert a.dtype == np.float64 and a.shape == shape and np.all(np.isfinite(a)), k
+    summary = np.load(d / "summary.npy")
+    assert summary[2] == 20 and summary[1] < summary[0]     # one solve of 20 iterations, the cost went down

@@ -36,7 +36,7 @@ if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[2] == "--json":
         print(json.dumps(as_json(root), indent=1))
         sys.exit(0)
-    print("## bench.py --legs icp,scan_match_frame,relocalize_8_candidates")
+    print("## bench.py --full --legs icp,scan_match_frame,relocalize_8_candidates")
     kernel_stats(os.path.join(root, "icp_trace"))
     for sub, label in PASSES:
         if os.path.isdir(os.path.join(root, sub)):

@@ -8,9 +8,9 @@ OUT="$ROOT/gpurun_out/prof_$TAG"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/legs_trace" -o legs -- python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --legs $LEGS > "$OUT/legs_trace.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/legs_trace" -o legs -- python $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --legs $LEGS > "$OUT/legs_trace.log" 2>&1
 cd "$ROOT"
-{ echo "## bench.py --steps 20 --warmup 5 --no-cpu-baseline --legs $LEGS"; python - "$OUT/legs_trace" <<'PY'
+{ echo "## bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --legs $LEGS"; python - "$OUT/legs_trace" <<'PY'
 import sys
 sys.path.insert(0, "tools")
 import prof_summary

@@ -1,6 +1,6 @@
 #!/bin/bash
 ROOT=/root/repo; OUT=$ROOT/gpurun_out/prof_tick; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-timeout 600 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/t -o t -- python $ROOT/bench.py --steps 20 --no-cpu-baseline --legs window_tick > $OUT/log 2>&1
+timeout 600 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/t -o t -- python $ROOT/bench.py --full --steps 20 --no-cpu-baseline --legs window_tick > $OUT/log 2>&1
 cd $ROOT
 python - <<'PY'
 import csv,glob

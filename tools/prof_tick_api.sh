@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs ON THE GPU BOX: the HIP API calls of one window tick, in order (which copies / launches a tick makes).  usage: tools/prof_tick_api.sh
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"; OUT=$ROOT/gpurun_out/prof_tick_api; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-timeout 300 rocprofv3 --hip-runtime-trace --output-format csv -d $OUT/t -o t -- python $ROOT/bench.py --steps 4 --warmup 2 --no-cpu-baseline --legs window_tick > $OUT/log 2>&1
+timeout 300 rocprofv3 --hip-runtime-trace --output-format csv -d $OUT/t -o t -- python $ROOT/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --legs window_tick > $OUT/log 2>&1
 cd $ROOT
 python - "$OUT" <<'PY'
 import csv, glob, sys

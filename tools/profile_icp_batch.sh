@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON THE GPU BOX (via gpurun): the ICP half of the metric and the batched regime under the profiler.
-#   trace  : rocprofv3 --kernel-trace --stats of bench.py --legs icp,scan_match_frame,relocalize_8_candidates
+#   trace  : rocprofv3 --kernel-trace --stats of bench.py --full --legs icp,scan_match_frame,relocalize_8_candidates
 #   PMC    : separate passes (FETCH_SIZE | WRITE_SIZE | TCC_HIT/MISS | SQ_INSTS_VALU, SQ_WAVES, SQ_BUSY_CYCLES) of the icp leg
 #   batch  : kernel trace of tools/run_batch.py 30 <W> for W in 8, 64
 # usage: tools/profile_icp_batch.sh <tag>     outputs under gpurun_out/prof_<tag>/
@@ -11,9 +11,9 @@ OUT="$ROOT/gpurun_out/prof_$TAG"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-ICP="python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --legs icp,scan_match_frame,relocalize_8_candidates"
+ICP="python $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --legs icp,scan_match_frame,relocalize_8_candidates"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/icp_trace" -o icp -- $ICP > "$OUT/icp_trace.log" 2>&1
-ICP1="python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --legs icp,scan_match_frame"
+ICP1="python $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --legs icp,scan_match_frame"
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/icp_pmc_fetch" -o icp -- $ICP1 > "$OUT/icp_pmc_fetch.log" 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/icp_pmc_write" -o icp -- $ICP1 > "$OUT/icp_pmc_write.log" 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d "$OUT/icp_pmc_l2" -o icp -- $ICP1 > "$OUT/icp_pmc_l2.log" 2>&1
