@@ -58,11 +58,14 @@ struct SpSrc {
   GP<unsigned long long> dbg; // LVF_SP_TIMING=1: eight wall_clock64() stamps per workgroup (tile 0 of every node), else null
   int s_zero;              // the level has nothing below it (level 0, early form): its part of S is still all zeros, not read
   JacobiDev jac{nullptr, nullptr};
+  // fused chain (AccSel): *sel != 0 -> B and gc are read from the second accumulator set
+  GP<const int> sel{nullptr}; GP<const double> B1{nullptr}, gc1{nullptr};
 };
 struct SpArgs {          // one sparse level
   GP<const SpNode> nodes; int first, tiles; GP<const int> rows; GP<double> S; int ld; GP<double> W; int wstride; GP<double> Lout; GP<int> fail; int nblocks; GP<const int> done;
   SpSrc src;
 };
+template <bool SEL = false>
 __device__ __forceinline__ void sp_ride(const int vb, const SpArgs& a);     // workgroup vb of the level (defined with k_sp_eliminate)
 // SC_FAIL codes (raised with atomicMax: the largest wins): 1 + kb = dense block step kb met a non-positive pivot, kFailSparse + id = sparse
 // block id did, kFailHandover + id = a chained level gave up waiting for the level below (NOT a property of the problem: see SpSrc)
@@ -104,6 +107,7 @@ struct lvf_problem {
   lvf::DevBuf<double> Ldiag;                    // the factored diagonal blocks L_kk [nb][64][64] (NOT stored back into S: see chol_step_body)
   std::vector<int> perm_h;
   lvf::DevBuf<double> B, gc, C, gr, E, Cd, S, dxc, dxl, scal;
+  lvf::DevBuf<double> B1, gc1, C1, gr1, E1, slotB1;    // the second accumulator set of the fused chain (lvf::AccSel)
   lvf::DevBuf<double> jh0;                      // Jacobi scaling of the running solve: diag(J^T J) of its first pass (JacobiDev)
   lvf::DevBuf<double> poses2, vel2, ba2, bg2, invd2;   // candidate state x + dx
   lvf::DevBuf<uint8_t> pose_const;
@@ -112,6 +116,7 @@ struct lvf_problem {
   lvf::HostPin<lvf::TfWork> h_tf_work;
   std::vector<uint8_t> pose_const_h;
   bool linearized = false;
+  bool acc1_ready = false;            // the fused chain's second accumulator set is allocated and cleared for the current configuration (ensure_acc1)
   // TwoFrame blocks as the solver reads them: the batch's own arrays, or — when the blocks of a current-keyframe run come with their first
   // keyframes in no order (landmark ids not in creation order) — copies sorted by (current, first) keyframe made at problem_configure, so
   // that a wave's 64 blocks share a few first keyframes and their sums go through the group-wise reductions instead of 63 LDS atomics per
@@ -171,6 +176,15 @@ __device__ __forceinline__ void block_add(double v, double* dst) {
 
 struct StateP { GP<const double> poses, vel, ba, bg, inv_depth, w_kf; };
 
+// The fused chain (LVF_FUSED_LIN, default on) linearises at the CANDIDATE inside the cost + decision pass, so a problem keeps two sets of what
+// a linearisation writes — B, gc, C, g_rho, the E rows and the TwoFrame slot records — and LmCtl::aset names the set that holds the
+// linearisation at the current state.  An argument block whose `sel` is set picks its set on device (set 1: the pointers here; set 0: the
+// block's own); sel == nullptr (today's chain, the taps, a batch) always means set 0.
+struct AccSel { GP<const int> sel; GP<double> B, gc, C, gr, E, slotB; };
+__device__ __forceinline__ int acc_set(const AccSel& a) { return a.sel ? *a.sel : 0; }
+// SEL = false (the batched table launches, which never run the fused chain): set 0, the selection compiled out
+template <bool SEL> __device__ __forceinline__ int acc_set_t(const AccSel& a) { return SEL ? acc_set(a) : 0; }
+
 // Device-resident control block of one window's Levenberg-Marquardt loop.  Everything that changes from one iteration to the next
 // lives here (trust-region radius, costs, accept / reject, termination), so the arguments of every kernel of an iteration are
 // constant across iterations: the host enqueues iteration after iteration without waiting, k_lm_decide closes each one on device
@@ -187,6 +201,8 @@ struct LmCtl {
   int done, termination;                           // done != 0: the remaining launches of this window return immediately
   int why, rejected;                               // LVF_WHY_* reason of the termination ; rejected / invalid steps so far
   int jfrozen;                                     // Jacobi scaling taken (JacobiDev): 0 until the solve's first pass has been decided on
+  int aset;                                        // fused chain: the accumulator set holding the linearisation at the state (AccSel)
+  int lin_pending;                                 // fused chain: that set's TwoFrame slabs are not yet reduced into B / gc (an accepted candidate pass)
 };
 
 // lower-triangle accumulation of a 6x6 block pair J_a^T J_b into B at (ra, rb) block offsets (ra >= rb required
@@ -895,27 +911,33 @@ __device__ __forceinline__ void lin_imu_body4(const int vb, int n, int n_kf, con
       else if (lane < 21) g = 6 * kj + (lane - 15); else g = 6 * n_kf + 9 * kj + (lane - 21);
       sidx[lane] = g;
     }
-    for (int e = lane; e < 30; e += 64) {
-      const int row = e % 15, which = e / 15;            // which: 0 = pose_i, 1 = pose_j
-      const double* Jr = (which ? J.j[4] : J.j[0]) + (size_t)f * 105 + 7 * row;
-      const int kk = which ? kj : ki;
-      const double* q = poses + 7 * kk;
-      const double sc = (pose_const[kk] & 1) ? 0.0 : 1.0;
-      double l3[3];
-      quat_row_to_local(Jr, q, l3);
-      double* o = sJ + row * 30 + (which ? 15 : 0);
-      o[0] = sc * l3[0]; o[1] = sc * l3[1]; o[2] = sc * l3[2]; o[3] = sc * Jr[4]; o[4] = sc * Jr[5]; o[5] = sc * Jr[6];
+    // (static indices only: indexing the by-value pointer table with a run-time value puts it in scratch memory, and a kernel with a
+    // scratch segment pays several microseconds of dispatch set-up.  A select between two entries by a run-time value is folded into
+    // exactly such an index, so the block loops below are unrolled: every entry is named by a constant)
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {            // which: 0 = pose_i, 1 = pose_j
+      if (lane < 15) {
+        const int row = lane;
+        const double* Jr = J.j[which ? 4 : 0] + (size_t)f * 105 + 7 * row;
+        const int kk = which ? kj : ki;
+        const double* q = poses + 7 * kk;
+        const double sc = (pose_const[kk] & 1) ? 0.0 : 1.0;
+        double l3[3];
+        quat_row_to_local(Jr, q, l3);
+        double* o = sJ + row * 30 + (which ? 15 : 0);
+        o[0] = sc * l3[0]; o[1] = sc * l3[1]; o[2] = sc * l3[2]; o[3] = sc * Jr[4]; o[4] = sc * Jr[5]; o[5] = sc * Jr[6];
+      }
     }
-    for (int e = lane; e < 15 * 18; e += 64) {           // six 15x3 blocks
-      const int row = e / 18, c = e % 18, blk = c / 3, cc = c % 3;   // blk 0..2 -> (v,ba,bg)_i ; 3..5 -> _j
-      const int src = blk < 3 ? 1 + blk : 5 + (blk - 3);
-      // (static indices only: indexing the by-value pointer table with a run-time value puts it in scratch memory, and a kernel with a
-      // scratch segment pays several microseconds of dispatch set-up)
-      const double* jp = src == 1 ? J.j[1] : (src == 2 ? J.j[2] : (src == 3 ? J.j[3] : (src == 5 ? J.j[5] : (src == 6 ? J.j[6] : J.j[7]))));
+#pragma unroll
+    for (int blk = 0; blk < 6; ++blk) {                  // six 15x3 blocks: blk 0..2 -> (v,ba,bg)_i = J.j[1..3] ; 3..5 -> _j = J.j[5..7]
+      const double* jp = J.j[blk < 3 ? 1 + blk : 2 + blk];
       // a constant velocity / bias block (bits 1..3 of the keyframe's mask; Environment::Optimize holds all of them, environment.cpp:62-68) keeps
       // its residual but gets no Jacobian columns
       const double scv = ((pose_const[blk < 3 ? ki : kj] >> (1 + blk % 3)) & 1) ? 0.0 : 1.0;
-      sJ[row * 30 + (blk < 3 ? 6 + 3 * blk : 21 + 3 * (blk - 3)) + cc] = scv * jp[(size_t)f * 45 + 3 * row + cc];
+      if (lane < 45) {
+        const int row = lane / 3, cc = lane % 3;
+        sJ[row * 30 + (blk < 3 ? 6 + 3 * blk : 21 + 3 * (blk - 3)) + cc] = scv * jp[(size_t)f * 45 + 3 * row + cc];
+      }
     }
   }
   __syncthreads();
@@ -1052,32 +1074,43 @@ struct LinArgs {
   LinVisual v; int n_kf; StateP s; double huber; GP<const uint8_t> pose_const; GP<double> B; int ld; GP<double> gc; GP<double> E; int ldE; GP<double> C, gr, cost;
   int nblocks; GP<const int> done; GP<unsigned long long> dbg; int rows;
   GP<double> scal_reset;      // early sparse levels: the per-step scalars and the fail flag are reset HERE (the levels start before k_prepare, which resets them otherwise)
+  AccSel acc;                 // the second accumulator set (the fused candidate pass writes the set that is not active)
 };
 __device__ __forceinline__ void reset_step_scalars(double* scal) {
   for (int k = SC_COST_NEW + threadIdx.x; k < SC_N; k += kT) scal[k] = 0.0;
   if (threadIdx.x == 0) { *reinterpret_cast<int*>(scal + SC_FAIL) = 0; *reinterpret_cast<int*>(scal + SC_TICKET) = 0; }
 }
-__device__ __forceinline__ void lin_visual_body(const int bx, const LinArgs& A) {
-  if (bx >= A.nblocks || (A.done && *A.done)) return;
-  if (bx == 0 && A.scal_reset) reset_step_scalars(A.scal_reset);
+// set: the accumulator set written (1: A.acc's pointers); s: the state linearised at; cost: where 1/2 sum rho goes (striped)
+__device__ __forceinline__ void lin_visual_run(const int bx, const LinArgs& A, const int set, const StateP s, double* cost) {
   const LinVisual& a = A.v;
   // the ImuError workgroups come FIRST: each is a ~12 us chain with a one-lane section, and dispatched last (of the last window of a
   // batch) it would stick out behind everything else
   const int g_imu_first = a.imu.pre ? a.n_imu : 0;
   const int b = bx - g_imu_first;
-  const int n_kf = A.n_kf; const StateP s = A.s; const double huber = A.huber; const uint8_t* pose_const = A.pose_const;
-  double* B = A.B; const int ld = A.ld; double* gc = A.gc; double* E = A.E; const int ldE = A.ldE; double* C = A.C; double* gr = A.gr; double* cost = A.cost;
+  const int n_kf = A.n_kf; const double huber = A.huber; const uint8_t* pose_const = A.pose_const;
+  // (the set's pointers by arithmetic: a select between two fields of the by-value argument block is folded into a run-time index into it,
+  // which puts the block in scratch memory)
+  auto pick = [set](GP<double> p0, GP<double> p1) -> double* { return (double*)(p0.p + (p1.p - p0.p) * (ptrdiff_t)set); };
+  double* B = pick(A.B, A.acc.B); const int ld = A.ld; double* gc = pick(A.gc, A.acc.gc); double* E = pick(A.E, A.acc.E); const int ldE = A.ldE;
+  double* C = pick(A.C, A.acc.C); double* gr = pick(A.gr, A.acc.gr);
+  TfCompact cp = a.cp;
+  cp.slotB = pick(a.cp.slotB, A.acc.slotB);
   if (bx < g_imu_first)
     lin_imu_eval_body(bx, a.imu, n_kf, s, pose_const, B, ld, gc, cost, A.dbg ? A.dbg + (size_t)a.n_tfw * 8 : nullptr);
   else if (b < a.n_tfw)
     lin_tf_sorted_body<true>(b, a.work, n_kf, a.tf_fo, a.tf_ob, a.tf_lm, a.tf_k1, s, a.tf_left, a.tf_right, huber, pose_const, B, ld, gc, E, ldE, C, gr, cost,
-                       a.unique_lk2, A.dbg, a.cp, a.n_tfw);
+                       a.unique_lk2, A.dbg, cp, a.n_tfw);
   else if (b < a.n_tfw + a.g_tc)
     lin_tc_body<false>(b - a.n_tfw, a.n_tc, a.tc_lo, a.tc_ro, a.tc_lm, a.tc_kf, a.tc_w, s, a.tc_left, a.tc_right, huber, C, gr, cost);
   else if (b < a.n_tfw + a.g_tc + a.g_po)
     lin_po_body<false, true>(b - a.n_tfw - a.g_tc, a.n_po, n_kf, a.po_ob, a.po_kf, a.po_pwi, a.po_pw, s, a.po_cam, huber, pose_const, B, ld, gc, cost);
   else
     lin_imu_body4<true>(b - a.n_tfw - a.g_tc - a.g_po, a.n_imu, n_kf, a.imu_res, a.imu_J, a.imu_i, a.imu_j, s.poses, pose_const, B, ld, gc, cost);
+}
+__device__ __forceinline__ void lin_visual_body(const int bx, const LinArgs& A) {
+  if (bx >= A.nblocks || (A.done && *A.done)) return;
+  if (bx == 0 && A.scal_reset) reset_step_scalars(A.scal_reset);
+  lin_visual_run(bx, A, 0, A.s, A.cost);
 }
 // (three workgroups per CU: the register allocator is told so — left alone it lands one VGPR above the limit)
 __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(3))) void k_lin_visual(LinArgs a) { lin_visual_body(blockIdx.x, a); }
@@ -1093,12 +1126,29 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(3))) void k_
 struct TfReduceArgs {
   int n_kf, n_wg; GP<const int> run_first; GP<const double> slabP, slabQ; GP<double> B; int ld; GP<double> gc; int nblocks; GP<const int> done;
   int own_blocks; SpArgs ride;       // workgroups [own_blocks, nblocks): a sparse level riding in this launch (early form)
+  // fused chain: B / gc of the active set (acc); `pending` (LmCtl::lin_pending) == 0: the active set was reduced by an earlier iteration (the
+  // last step was rejected) and this launch leaves it alone; workgroups [nblocks, nblocks + zero_wgs) clear the set that is NOT active
+  // (stand0 when set 1 is active, stand1 otherwise) for the candidate pass at the end of the iteration — never gated
+  AccSel acc; GP<const int> pending; ZeroList stand0, stand1; int zero_wgs;
 };
+template <bool SEL>
 __device__ __forceinline__ void tf_reduce_body(const int bx0, const TfReduceArgs& A) {
-  if (bx0 >= A.nblocks || (A.done && *A.done)) return;
+  if (bx0 >= A.nblocks) {
+    const int zw = (int)bx0 - A.nblocks;
+    if (SEL && zw < A.zero_wgs) {
+      if (acc_set(A.acc)) zero_list_share(A.stand0, zw, A.zero_wgs);
+      else zero_list_share(A.stand1, zw, A.zero_wgs);
+    }
+    return;
+  }
+  if (A.done && *A.done) return;
   // (the riding level takes the FIRST workgroups: it is the longest piece of the launch, and in a batch the first workgroups of every
   // window are dispatched first — see the transposed table launches)
-  if (bx0 < A.ride.nblocks) { sp_ride(bx0, A.ride); return; }
+  if (bx0 < A.ride.nblocks) { sp_ride<SEL>(bx0, A.ride); return; }
+  if (SEL && A.pending && !*A.pending) return;
+  const bool s1 = acc_set_t<SEL>(A.acc) != 0;
+  double* const Bs = s1 ? (double*)A.acc.B : (double*)A.B;
+  double* const gcs = s1 ? (double*)A.acc.gc : (double*)A.gc;
   const int bx = bx0 - A.ride.nblocks;
   const int n_kf = A.n_kf;
   const int nchunk = (A.n_wg + 63) / 64;
@@ -1136,8 +1186,8 @@ __device__ __forceinline__ void tf_reduce_body(const int bx0, const TfReduceArgs
         if (threadIdx.x < 21) {
           int x = 0, rem = threadIdx.x;
           while (rem > x) { rem -= x + 1; ++x; }
-          atomicAdd(&A.B[(size_t)(6 * k + x) * A.ld + 6 * k + rem], t);
-        } else atomicAdd(&A.gc[6 * k + threadIdx.x - 21], t);
+          atomicAdd(&Bs[(size_t)(6 * k + x) * A.ld + 6 * k + rem], t);
+        } else atomicAdd(&gcs[6 * k + threadIdx.x - 21], t);
       }
     }
     return;
@@ -1164,14 +1214,14 @@ __device__ __forceinline__ void tf_reduce_body(const int bx0, const TfReduceArgs
   }
   if (acc != 0.0) {
     const int x = el / 6, y = el - 6 * x;                              // x: k2 tangent index, y: k1 tangent index
-    A.B[(size_t)(6 * k2 + x) * A.ld + 6 * k1 + y] += acc;
+    Bs[(size_t)(6 * k2 + x) * A.ld + 6 * k1 + y] += acc;
   }
 }
-__global__ __launch_bounds__(kT) void k_tf_reduce(TfReduceArgs a) { tf_reduce_body(blockIdx.x, a); }
-__global__ __launch_bounds__(kT) void k_tf_reduce_b(const TfReduceArgs* __restrict__ t) { tf_reduce_body(blockIdx.x, t[blockIdx.y]); }
+__global__ __launch_bounds__(kT) void k_tf_reduce(TfReduceArgs a) { tf_reduce_body<true>(blockIdx.x, a); }
+__global__ __launch_bounds__(kT) void k_tf_reduce_b(const TfReduceArgs* __restrict__ t) { tf_reduce_body<false>(blockIdx.x, t[blockIdx.y]); }
 // (transposed: blockIdx.x = window.  Workgroups are dispatched x-fastest, so the first workgroups of EVERY window — the riding / chained
 // sparse levels, the ImuError factors — start together at the head of the launch instead of each window's behind the previous window's bulk)
-__global__ __launch_bounds__(kT) void k_tf_reduce_bt(const TfReduceArgs* __restrict__ t) { tf_reduce_body(blockIdx.y, t[blockIdx.x]); }
+__global__ __launch_bounds__(kT) void k_tf_reduce_bt(const TfReduceArgs* __restrict__ t) { tf_reduce_body<false>(blockIdx.y, t[blockIdx.x]); }
 
 
 // ------------------------------------------------------------------------------------------------ pose priors
@@ -1300,19 +1350,25 @@ struct PrepArgs {
   int early, off;
   int own_blocks; SpArgs ride;       // workgroups [own_blocks, nblocks): a sparse level riding in this launch
   JacobiDev jac;
+  AccSel acc;                        // fused chain: B, gc, C, g_rho, the slot records and E of the active set
 };
+template <bool SEL>
 __device__ __forceinline__ void prepare_body(const unsigned bx0, const PrepArgs& A) {
   if (bx0 >= (unsigned)A.nblocks || (A.done && *A.done)) return;
-  if (bx0 < (unsigned)A.ride.nblocks) { sp_ride((int)bx0, A.ride); return; }      // (riders first: tf_reduce_body)
+  if (bx0 < (unsigned)A.ride.nblocks) { sp_ride<SEL>((int)bx0, A.ride); return; }      // (riders first: tf_reduce_body)
   const unsigned bx = bx0 - (unsigned)A.ride.nblocks;
-  const int ld = A.ld, dpad = A.dpad; const int* __restrict__ iperm = A.iperm; const double* __restrict__ B = A.B; const double* __restrict__ gc = A.gc;
+  const bool s1 = acc_set_t<SEL>(A.acc) != 0;
+  const int ld = A.ld, dpad = A.dpad; const int* __restrict__ iperm = A.iperm; const double* __restrict__ B = s1 ? (const double*)A.acc.B : (const double*)A.B;
+  const double* __restrict__ gc = s1 ? (const double*)A.acc.gc : (const double*)A.gc;
   const double inv_radius = 1.0 / *A.radius;
   const int jf = *A.jac.frozen;
   double* __restrict__ S = A.S; const unsigned nS_blocks = A.nS_blocks; const int n_lm = A.n_lm, dp = A.dp, ldE = A.ldE;
-  const double* __restrict__ C = A.C; const double* __restrict__ gr = A.gr; double* __restrict__ Cd = A.Cd; double* __restrict__ E = A.E; double* __restrict__ scal = A.scal;
+  const double* __restrict__ C = s1 ? (const double*)A.acc.C : (const double*)A.C; const double* __restrict__ gr = s1 ? (const double*)A.acc.gr : (const double*)A.gr;
+  double* __restrict__ Cd = A.Cd; double* __restrict__ E = s1 ? (double*)A.acc.E : (double*)A.E; double* __restrict__ scal = A.scal;
+  const double* const slotB = (s1 && A.slotB) ? (const double*)A.acc.slotB : (const double*)A.slotB;
   if (bx == 0 && scal) reset_step_scalars(scal);
   if (bx >= nS_blocks) {
-    if (A.slotB) {
+    if (slotB) {
       // atomic-free mode: C, g_rho of the landmark = its TwoCamera part (C, gr: atomics of the linearisation) + its slot records; the k1
       // columns of its E row = the sum of the records' first-keyframe parts.  8 lanes per landmark (lane j takes slots j, j + 8, ...: the
       // loads of a track are issued together instead of one dependent loop), DPP sum over the 8 lanes.  The totals go to separate arrays
@@ -1322,7 +1378,7 @@ __device__ __forceinline__ void prepare_body(const unsigned bx0, const PrepArgs&
       const int lc = live ? l : 0;
       const int k1 = A.kmin[lc], len = live ? max(0, A.kmax[lc] - k1) : 0;
       const double h0l = A.jac.h0[A.jl0 + lc];
-      const double2* sb = reinterpret_cast<const double2*>(A.slotB + (size_t)A.eoff[lc] * 8);
+      const double2* sb = reinterpret_cast<const double2*>(slotB + (size_t)A.eoff[lc] * 8);
       double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       for (int j = j0; j < len; j += 8) {
         const double2 b0 = sb[4 * j], b1 = sb[4 * j + 1], b2 = sb[4 * j + 2], cg = sb[4 * j + 3];
@@ -1379,9 +1435,9 @@ __device__ __forceinline__ void prepare_body(const unsigned bx0, const PrepArgs&
   if (!A.early) S[(size_t)I * ld + J] = v;
   else if (v != 0.0) atomicAdd(&S[(size_t)I * ld + J], v);
 }
-__global__ __launch_bounds__(kT) void k_prepare(PrepArgs a) { prepare_body(blockIdx.x, a); }
-__global__ __launch_bounds__(kT) void k_prepare_b(const PrepArgs* __restrict__ t) { prepare_body(blockIdx.x, t[blockIdx.y]); }
-__global__ __launch_bounds__(kT) void k_prepare_bt(const PrepArgs* __restrict__ t) { const PrepArgs a = t[blockIdx.x]; prepare_body(blockIdx.y, a); }
+__global__ __launch_bounds__(kT) void k_prepare(PrepArgs a) { prepare_body<true>(blockIdx.x, a); }
+__global__ __launch_bounds__(kT) void k_prepare_b(const PrepArgs* __restrict__ t) { prepare_body<false>(blockIdx.x, t[blockIdx.y]); }
+__global__ __launch_bounds__(kT) void k_prepare_bt(const PrepArgs* __restrict__ t) { const PrepArgs a = t[blockIdx.x]; prepare_body<false>(blockIdx.y, a); }
 
 // ------------------------------------------------------------------------------------------------ Schur reduce (MFMA f64)
 // T = Ea^T diag(1/Cd) Ea with Ea = [E | g_rho] (n_lm x ldE).  One wave per (16x16 output tile, K-chunk); tiles on or
@@ -2421,12 +2477,16 @@ __global__ __launch_bounds__(64) void k_band_work(int rows, int dp, const int* _
   }
 }
 
+template <bool SEL>
 __device__ __forceinline__ void sp_ride(const int vb, const SpArgs& a) {
   if (vb >= a.nblocks) return;
-  sp_eliminate_body(vb, a.nodes, a.first, a.tiles, a.rows, a.S, a.ld, a.W, a.wstride, a.Lout, a.fail, a.done, a.src);
+  if (!SEL) { sp_eliminate_body(vb, a.nodes, a.first, a.tiles, a.rows, a.S, a.ld, a.W, a.wstride, a.Lout, a.fail, a.done, a.src); return; }
+  SpSrc src = a.src;
+  if (src.sel && *src.sel) { src.B = src.B1; src.gc = src.gc1; }      // (fused chain: the active accumulator set)
+  sp_eliminate_body(vb, a.nodes, a.first, a.tiles, a.rows, a.S, a.ld, a.W, a.wstride, a.Lout, a.fail, a.done, src);
 }
-__global__ __launch_bounds__(256) void k_sp_eliminate(SpArgs a) { sp_ride(blockIdx.x, a); }
-__global__ __launch_bounds__(256) void k_sp_eliminate_b(const SpArgs* __restrict__ t) { sp_ride(blockIdx.x, t[blockIdx.y]); }
+__global__ __launch_bounds__(256) void k_sp_eliminate(SpArgs a) { sp_ride<true>(blockIdx.x, a); }
+__global__ __launch_bounds__(256) void k_sp_eliminate_b(const SpArgs* __restrict__ t) { sp_ride<false>(blockIdx.x, t[blockIdx.y]); }
 // The band-limited Schur complement and the FIRST sparse level in one launch: both only ADD (atomically) into entries of S the other
 // does not read — the Schur complement touches the pose corner and the pose part of the rhs row, level 0 reads its own (v,ba,bg)
 // columns — so they are independent; later levels depend on level 0 and stay launches of their own.
@@ -2436,31 +2496,34 @@ struct SchurSp0Args {
   SpArgs sp_b, sp_c;     // early form: the next two levels, chained behind it inside the launch (SpSrc::wait_counter)
   int nblocks; GP<const int> done; GP<unsigned long long> dbg; int rows;
   GP<const int4> work; int n_work;      // (slice, group, band lo | hi << 16, slice end) items; the sparse levels run in the first workgroups, the items behind
+  AccSel acc;                           // fused chain: E of the active set
 };
+template <bool SEL>
 __device__ __forceinline__ void schur_sp0_body(const int b, const SchurSp0Args& A) {
   if (b >= A.nblocks) return;
   if (A.work) {
     const int n_a = A.sp.nblocks, n_b = A.sp_b.nblocks, n_c = A.sp_c.nblocks, n_sp = n_a + n_b + n_c;
-    if (b < n_a) sp_ride(b, A.sp);
-    else if (b < n_a + n_b) sp_ride(b - n_a, A.sp_b);
-    else if (b < n_sp) sp_ride(b - n_a - n_b, A.sp_c);
+    if (b < n_a) sp_ride<SEL>(b, A.sp);
+    else if (b < n_a + n_b) sp_ride<SEL>(b - n_a, A.sp_b);
+    else if (b < n_sp) sp_ride<SEL>(b - n_a - n_b, A.sp_c);
     else {
       const int dv = done_flag_issue(A.done);
+      const int set = acc_set_t<SEL>(A.acc);
       const int4* item = A.work + (b - n_sp);
       const int4 it = *item;
       if (dv) return;
-      schur_band_body(it.x, it.y, A.dp, A.ldE, A.E, A.Cd, A.order, A.n_active, A.kmin, A.kmax, A.d_local, A.ldS, A.S_pose, A.dbg ? A.dbg + (size_t)(b - n_sp) * 8 : nullptr, A.rows, item);
+      schur_band_body(it.x, it.y, A.dp, A.ldE, set ? (const double*)A.acc.E : (const double*)A.E, A.Cd, A.order, A.n_active, A.kmin, A.kmax, A.d_local, A.ldS, A.S_pose, A.dbg ? A.dbg + (size_t)(b - n_sp) * 8 : nullptr, A.rows, item);
     }
     return;
   }
   if (A.done && *A.done) return;
   const int ns = A.n_slices * A.n_groups;
-  if (b < ns) schur_band_body(b % A.n_slices, b / A.n_slices, A.dp, A.ldE, A.E, A.Cd, A.order, A.n_active, A.kmin, A.kmax, A.d_local, A.ldS, A.S_pose, A.dbg ? A.dbg + (size_t)b * 8 : nullptr, A.rows);
-  else sp_ride(b - ns, A.sp);
+  if (b < ns) schur_band_body(b % A.n_slices, b / A.n_slices, A.dp, A.ldE, acc_set_t<SEL>(A.acc) ? (const double*)A.acc.E : (const double*)A.E, A.Cd, A.order, A.n_active, A.kmin, A.kmax, A.d_local, A.ldS, A.S_pose, A.dbg ? A.dbg + (size_t)b * 8 : nullptr, A.rows);
+  else sp_ride<SEL>(b - ns, A.sp);
 }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_schur_sp0(SchurSp0Args a) { schur_sp0_body(blockIdx.x, a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_schur_sp0_b(const SchurSp0Args* __restrict__ t) { schur_sp0_body(blockIdx.x, t[blockIdx.y]); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_schur_sp0_bt(const SchurSp0Args* __restrict__ t) { schur_sp0_body(blockIdx.y, t[blockIdx.x]); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_schur_sp0(SchurSp0Args a) { schur_sp0_body<true>(blockIdx.x, a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_schur_sp0_b(const SchurSp0Args* __restrict__ t) { schur_sp0_body<false>(blockIdx.x, t[blockIdx.y]); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_schur_sp0_bt(const SchurSp0Args* __restrict__ t) { schur_sp0_body<false>(blockIdx.y, t[blockIdx.x]); }
 struct SpBack {                    // what the back substitution needs of the plan
   SpLevels lv;
   int item0[kSpMaxLevels], items[kSpMaxLevels];   // the level's slice of rows/owner/W
@@ -2816,15 +2879,20 @@ struct TailArgs {
   int g_lm, n_lm, dp, ldE; GP<const double> E, C, Cd, gr, dxc; GP<double> dxl, scal; GP<const int> kmin, kmax; int n_kf; StateP s;
   GP<double> poses2, vel2, ba2, bg2, invd2; int d, ld; GP<const double> B, gc; GP<const double> radius; int nblocks; GP<const int> done;
   GP<const unsigned char> pose_const; JacobiDev jac;
+  AccSel acc;             // fused chain: E, B, gc of the active set (C, gr here are k_prepare's single totals Ct / grt: the chain needs compact mode)
 };
+template <bool SEL = true> __device__ __forceinline__ const double* tail_E(const TailArgs& A) { return acc_set_t<SEL>(A.acc) ? (const double*)A.acc.E : (const double*)A.E; }
+template <bool SEL = true> __device__ __forceinline__ const double* tail_B(const TailArgs& A) { return acc_set_t<SEL>(A.acc) ? (const double*)A.acc.B : (const double*)A.B; }
+template <bool SEL = true> __device__ __forceinline__ const double* tail_gc(const TailArgs& A) { return acc_set_t<SEL>(A.acc) ? (const double*)A.acc.gc : (const double*)A.gc; }
+template <bool SEL>
 __device__ __forceinline__ void step_tail_body(const int bx, const TailArgs& A) {
   if (bx >= A.nblocks || (A.done && *A.done)) return;
-  if (bx < A.g_lm) landmark_back_body(bx, A.g_lm, A.n_lm, A.dp, A.ldE, A.E, A.C, A.Cd, A.gr, A.dxc, A.s.inv_depth, A.dxl, A.invd2, A.scal, A.kmin, A.kmax);
-  else apply_step_body(bx - A.g_lm, A.n_kf, 0, A.s, A.dxc, A.dxl, A.poses2, A.vel2, A.ba2, A.bg2, A.invd2, A.scal, A.d, A.ld, A.B, A.gc, 1.0 / *A.radius, A.pose_const, A.jac);
+  if (bx < A.g_lm) landmark_back_body(bx, A.g_lm, A.n_lm, A.dp, A.ldE, tail_E<SEL>(A), A.C, A.Cd, A.gr, A.dxc, A.s.inv_depth, A.dxl, A.invd2, A.scal, A.kmin, A.kmax);
+  else apply_step_body(bx - A.g_lm, A.n_kf, 0, A.s, A.dxc, A.dxl, A.poses2, A.vel2, A.ba2, A.bg2, A.invd2, A.scal, A.d, A.ld, tail_B<SEL>(A), tail_gc<SEL>(A), 1.0 / *A.radius, A.pose_const, A.jac);
 }
-__global__ __launch_bounds__(kT) void k_step_tail(TailArgs a) { step_tail_body(blockIdx.x, a); }
-__global__ __launch_bounds__(kT) void k_step_tail_b(const TailArgs* __restrict__ t) { step_tail_body(blockIdx.x, t[blockIdx.y]); }
-__global__ __launch_bounds__(kT) void k_step_tail_bt(const TailArgs* __restrict__ t) { step_tail_body(blockIdx.y, t[blockIdx.x]); }
+__global__ __launch_bounds__(kT) void k_step_tail(TailArgs a) { step_tail_body<true>(blockIdx.x, a); }
+__global__ __launch_bounds__(kT) void k_step_tail_b(const TailArgs* __restrict__ t) { step_tail_body<false>(blockIdx.x, t[blockIdx.y]); }
+__global__ __launch_bounds__(kT) void k_step_tail_bt(const TailArgs* __restrict__ t) { step_tail_body<false>(blockIdx.y, t[blockIdx.x]); }
 
 // The back substitution and the step tail as ONE launch (single-window chain).  The landmark back-substitution needs the POSE part of the
 // step only, and the poses are solved first (dense corner, 16 of the back substitution's 28 us); the sparse levels behind it (the
@@ -2846,8 +2914,9 @@ __global__ __launch_bounds__(kBT) void k_backsolve_tail(BackTailArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     const double inv_radius = 1.0 / *T.radius;
+    const double* const Bt = tail_B(T); const double* const gct = tail_gc(T);
     for (int vb = 0; vb * kBT < max(T.d, T.n_kf); ++vb)
-      apply_step_body<kBT, 2>(vb, T.n_kf, 0, T.s, T.dxc, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, T.ld, T.B, T.gc, inv_radius, T.pose_const, T.jac);
+      apply_step_body<kBT, 2>(vb, T.n_kf, 0, T.s, T.dxc, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, T.ld, Bt, gct, inv_radius, T.pose_const, T.jac);
     if (a.back.sp.dbg && threadIdx.x == 0) a.back.sp.dbg[55] = wall_clock64();      // LVF_BACK_TIMING: the step is applied
     return;
   }
@@ -2870,11 +2939,12 @@ __global__ __launch_bounds__(kBT) void k_backsolve_tail(BackTailArgs a) {
     for (int i = threadIdx.x; i < T.dp; i += kBT) sdx_pose[i] = __hip_atomic_load(T.dxc + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     const double inv_radius = 1.0 / *T.radius;
+    const double* const Bt = tail_B(T); const double* const gct = tail_gc(T);
     for (int vb = 0; vb * kBT < max(T.dp, T.n_kf); ++vb)
-      apply_step_body<kBT, 1>(vb, T.n_kf, 0, T.s, sdx_pose, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, T.ld, T.B, T.gc, inv_radius, T.pose_const, T.jac);
+      apply_step_body<kBT, 1>(vb, T.n_kf, 0, T.s, sdx_pose, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, T.ld, Bt, gct, inv_radius, T.pose_const, T.jac);
     return;
   }
-  landmark_back_body<kBT, true>((int)blockIdx.x - 2, a.g_lm, T.n_lm, T.dp, T.ldE, T.E, T.C, T.Cd, T.gr, T.dxc, T.s.inv_depth, T.dxl, T.invd2, T.scal, T.kmin, T.kmax);
+  landmark_back_body<kBT, true>((int)blockIdx.x - 2, a.g_lm, T.n_lm, T.dp, T.ldE, tail_E(T), T.C, T.Cd, T.gr, T.dxc, T.s.inv_depth, T.dxl, T.invd2, T.scal, T.kmin, T.kmax);
   if (ldbg) ldbg[2] = wall_clock64();
 }
 
@@ -2890,6 +2960,7 @@ struct DecideArgs {
   GP<const double> poses2, vel2, ba2, bg2, invd2;      // the candidate
   GP<unsigned long long> dbg;                              // LVF_COST_TIMING=1: wall_clock64() stamps (100 MHz), else null
   GP<double> hist;                                         // LVF_LM_HISTORY=1: eight doubles per closed pass (64 passes), else null
+  int fused;                                               // closes a fused candidate pass (k_lin_cost_decide): see lm_decide_body
 };
 constexpr int kDT = 256;
 // COHERENT: the sums are read past the caches (the caller is the last workgroup of the launch that produced part of them)
@@ -2913,7 +2984,7 @@ __device__ __forceinline__ void lm_decide_body(const DecideArgs& A) {
   __syncthreads();
   if (s_skip) return;
   if (A.dbg && threadIdx.x == 0) A.dbg[2] = wall_clock64();
-  if (threadIdx.x < kStripes) const_cast<double*>((const double*)A.scal)[SC_COST + threadIdx.x] = 0.0;      // read above; the next linearisation adds into it
+  if (!A.fused && threadIdx.x < kStripes) const_cast<double*>((const double*)A.scal)[SC_COST + threadIdx.x] = 0.0;      // read above; the next linearisation adds into it
   if (threadIdx.x == 0) {
     // the fields of the control block are read up front (independent requests, one wait) and written back once at the end: read and
     // written where the logic uses them they were 1.2 us of dependent traffic.  (A whole-struct copy goes through a scratch segment.)
@@ -2987,6 +3058,12 @@ __device__ __forceinline__ void lm_decide_body(const DecideArgs& A) {
     c->iter = lc.iter; c->successes = lc.successes; c->invalid_run = lc.invalid_run; c->accepted = lc.accepted; c->solved = lc.solved;
     c->done = lc.done; c->termination = lc.termination; c->why = lc.why; c->rejected = lc.rejected;
     if (hfail < kFailHandover) c->jfrozen = 1;      // the Jacobi scaling of this solve is the first pass's (a pass that is re-run after a hand-over time-out takes it again)
+    if (A.fused) {
+      // the candidate pass linearised x + dx into the standby set: accepted, that set becomes the active one, its TwoFrame slabs still to be
+      // reduced (k_tf_reduce); rejected, the active set keeps the linearisation at x, already reduced
+      c->lin_pending = accepted ? 1 : 0;
+      if (accepted) c->aset = c->aset ^ 1;
+    }
     s_iter = lc.iter; s_done = lc.done;
     if (A.hist) {                                      // diagnostic: what this pass decided on
       double* h = A.hist + 8 * (it & 63);
@@ -3010,6 +3087,18 @@ __device__ __forceinline__ void lm_decide_body(const DecideArgs& A) {
     if ((A.n_lm & 1) && threadIdx.x == 0) A.invd[A.n_lm - 1] = A.invd2[A.n_lm - 1];
     for (int i = threadIdx.x; i < 7 * A.n_kf; i += kDT) A.poses[i] = A.poses2[i];
     for (int i = threadIdx.x; i < 3 * A.n_kf; i += kDT) { A.vel[i] = A.vel2[i]; A.ba[i] = A.ba2[i]; A.bg[i] = A.bg2[i]; }
+  }
+  if (A.fused) {
+    // no linearisation launch follows: the cost at the state the next iteration starts from is the candidate's (accepted) or stays what it
+    // was (rejected), and the per-step scalars are reset here (what k_lin_visual / k_prepare do in today's chain).  Stripe t is carried and
+    // cleared by thread t.  A pass that ENDS the loop clears the cost stripes as today's decision does: the launches behind it are gated, and
+    // the next solve's linearisation adds into them (lvf_problem::accum_clean)
+    double* sc = const_cast<double*>((const double*)A.scal);
+    if (threadIdx.x < kStripes) {
+      if (s_done) sc[SC_COST + threadIdx.x] = 0.0;
+      else if (s_commit) sc[SC_COST + threadIdx.x] = __hip_atomic_load(sc + SC_COST_NEW + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    reset_step_scalars(sc);
   }
   if (A.dbg && threadIdx.x == 0) A.dbg[4] = wall_clock64();
   // the host only polls `iter` and `done` of its mirror (wait_for_iteration): two uncached stores to the pinned record instead of a
@@ -3088,6 +3177,44 @@ __global__ __launch_bounds__(kT) void k_cost_decide(CostArgs a, DecideArgs d, in
 __global__ __launch_bounds__(kT) void k_cost_decide_b(const CostArgs* __restrict__ t, const DecideArgs* __restrict__ d, int end_zero) { cost_decide_body(blockIdx.x, t[blockIdx.y], d[blockIdx.y], end_zero); }
 __global__ __launch_bounds__(kT) void k_cost_decide_bt(const CostArgs* __restrict__ t, const DecideArgs* __restrict__ d, int end_zero) { cost_decide_body(blockIdx.y, t[blockIdx.x], d[blockIdx.x], end_zero); }
 
+// The fused chain's candidate pass: k_lin_visual's workgroups (same bodies, same block-to-workgroup mapping) at the candidate x + dx, into
+// the accumulator set that is NOT active, with the candidate cost taken from the residuals they form; the last workgroup closes the
+// iteration (lm_decide_body, fused mode: an accepted step makes this set the active one).  The next iteration then starts at k_tf_reduce —
+// the candidate is not evaluated a second time — and a rejected step re-uses the linearisation at x it already has.  The workgroup's cost
+// parts meet in LDS and leave as ONE returning atomic before its ticket (cost_decide_body has the ordering argument); workgroups
+// [nblocks, nblocks + zero_wgs) clear S and the arrival counters for the next iteration (the accumulator sets: k_tf_reduce).
+struct FusedArgs { LinArgs lin; DecideArgs dec; GP<double> cost_new; int nblocks; GP<const int> done; ZeroList zero; int zero_wgs; };
+__device__ __forceinline__ void lin_cost_decide_body(const int b, const FusedArgs& A) {
+  if (b >= A.nblocks) {
+    if (b - A.nblocks < A.zero_wgs) zero_list_share(A.zero, b - A.nblocks, A.zero_wgs);
+    return;
+  }
+  if (A.done && *A.done) return;
+  __shared__ double s_cost[kStripes];
+  __shared__ int s_last;
+  if (threadIdx.x < kStripes) s_cost[threadIdx.x] = 0.0;
+  const int standby = acc_set(A.lin.acc) ^ 1;
+  __syncthreads();
+  lin_visual_run(b, A.lin, standby, A.lin.s, s_cost);
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    double v = threadIdx.x < kStripes ? s_cost[threadIdx.x] : 0.0;
+    v = wave_sum(v);
+    if (threadIdx.x == 0) {
+      if (v != 0.0) {
+        const double old = atomicAdd(A.cost_new + (b & (kStripes - 1)), v);
+        asm volatile("" ::"v"(old) : "memory");
+      }
+      const int t = atomicAdd(A.dec.ticket, 1);
+      s_last = t == A.nblocks - 1;
+      if (s_last) atomicExch(A.dec.ticket, 0);
+    }
+  }
+  __syncthreads();
+  if (s_last) lm_decide_body<true>(A.dec);
+}
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(3))) void k_lin_cost_decide(FusedArgs a) { lin_cost_decide_body(blockIdx.x, a); }
+
 // ================================================================================================ host side
 static StateP state_ptrs(const lvf_state* st) { return StateP{st->poses.p, st->vel.p, st->ba.p, st->bg.p, st->inv_depth.p, st->w_visual.p}; }
 static inline int grid(int n) { return (n + kT - 1) / kT; }
@@ -3123,6 +3250,12 @@ struct Chain {
   bool back_tail_merged = false; BackTailArgs bt{}; size_t bt_lds = 0;      // k_backsolve_tail (single-window chain, chained levels allowed)
   CostArgs cost{};
   DecideArgs dec{};
+  // the fused chain (AccSel; LVF_FUSED_LIN=0 turns it off): the second accumulator set's pointers and the standby clears (k_tf_reduce: stand0
+  // clears set 0, stand1 set 1) — both filled by ensure_acc1 — and the candidate pass
+  bool fused_ok = false;
+  AccSel acc{};
+  ZeroList stand0{}, stand1{};
+  FusedArgs fused{};
 };
 
 void stage_clock_free(StageClock* k);
@@ -3495,6 +3628,27 @@ static int build_chain(lvf_problem* p) {
     a.hist = nullptr;
     if (lm_history) { LVF_TRY(p->dbg_hist.ensure(8 * 64)); a.hist = p->dbg_hist.p; }
   }
+  {
+    // the fused chain: the compact single-window chain with every reader of the accumulators selecting its set on device (problems with
+    // pose priors keep today's chain: their prior terms have no candidate linearisation)
+    static const bool fused_on = [] { const char* e = std::getenv("LVF_FUSED_LIN"); return !(e && e[0] == '0'); }();
+    c.fused_ok = fused_on && c.fast && p->compact && !c.has_prior && c.merged_level0 && p->n_lm > 0 && c.lin.nblocks > 0 && c.cost.nblocks > 0 &&
+                 (!c.has_imu || (c.imu_in_cost && c.lin.v.imu.pre));
+    p->acc1_ready = false;            // the second set is allocated and cleared by the first fused solve (ensure_acc1)
+    if (c.fused_ok) {
+      // what the candidate pass clears for the next iteration: zero_end less the accumulator sets (S, the arrival counters)
+      ZeroList fz{};
+      for (int k = 0; k < c.zero_end.count; ++k) {
+        double* q0 = c.zero_end.p[k];
+        if (q0 == p->B.p || q0 == p->gc.p || q0 == p->C.p || q0 == p->gr.p) continue;
+        fz.p[fz.count] = q0; fz.n[fz.count] = c.zero_end.n[k]; fz.tri[fz.count] = c.zero_end.tri[k]; ++fz.count;
+      }
+      FusedArgs& f = c.fused;
+      f.lin = c.lin; f.lin.s = s2; f.lin.cost = nullptr; f.lin.scal_reset = nullptr; f.lin.dbg = nullptr;
+      f.dec = c.dec; f.dec.fused = 1;
+      f.cost_new = p->scal.p + SC_COST_NEW; f.nblocks = c.lin.nblocks; f.done = done; f.zero = fz; f.zero_wgs = kEndZeroWgs;
+    }
+  }
   c.batchable = c.fast && p->compact && c.has_imu && !c.has_prior && c.merged_level0 && c.lin.nblocks > 0 && c.cost.nblocks > 0;
   { const StateP sp = state_ptrs(p->st); std::memcpy(p->chain_state, &sp, sizeof(sp)); }
   p->chain_tcw = p->tc && p->tc->wblk.n ? p->tc->wblk.p : nullptr;
@@ -3510,12 +3664,41 @@ static bool chain_stale(const lvf_problem* p) {
   const double* w = p->tc && p->tc->wblk.n ? p->tc->wblk.p : nullptr;
   return w != p->chain_tcw;
 }
+// The second accumulator set, allocated and cleared on the first fused solve after a configure (a problem that is only ever solved in a batch,
+// or one iteration at a time, never holds it).  E's and the slot records' zeros outside what a linearisation writes are set here, as for
+// set 0 in problem_configure; B, gc, C and g_rho need nothing: the first k_tf_reduce of every fused solve clears the standby set, which is
+// set 1 then (LmCtl::aset starts every solve at 0).
+static int ensure_acc1(lvf_problem* p) {
+  Chain& c = *p->chain;
+  if (!c.fused_ok || p->acc1_ready) return LVF_OK;
+  hipStream_t q = p->ctx->stream;
+  LVF_TRY(p->B1.ensure(p->B.n)); LVF_TRY(p->gc1.ensure(p->gc.n)); LVF_TRY(p->C1.ensure(p->C.n)); LVF_TRY(p->gr1.ensure(p->gr.n));
+  LVF_TRY(p->E1.ensure(p->E.n)); LVF_TRY(p->slotB1.ensure(p->slotB.n));
+  LVF_HIP(hipMemsetAsync(p->E1.p, 0, p->E1.n * 8, q));
+  hipLaunchKernelGGL(k_tf_slots_zero, dim3(256), dim3(kT), 0, q, 0, 0, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
+                     (int*)nullptr, p->n_slots.p, p->slotB1.p);
+  LVF_HIP(hipGetLastError());
+  c.acc = AccSel{&p->ctl.p->aset, p->B1.p, p->gc1.p, p->C1.p, p->gr1.p, p->E1.p, p->slotB1.p};
+  // the standby lists: one set's B, gc, C, g_rho (as zero_end clears set 0's)
+  c.stand0 = ZeroList{}; c.stand1 = ZeroList{};
+  for (int k = 0; k < c.zero_end.count; ++k) {
+    double* q0 = c.zero_end.p[k];
+    double* q1 = q0 == p->B.p ? p->B1.p : q0 == p->gc.p ? p->gc1.p : q0 == p->C.p ? p->C1.p : q0 == p->gr.p ? p->gr1.p : nullptr;
+    if (!q1) continue;
+    c.stand0.p[c.stand0.count] = q0; c.stand0.n[c.stand0.count] = c.zero_end.n[k]; c.stand0.tri[c.stand0.count] = c.zero_end.tri[k]; ++c.stand0.count;
+    c.stand1.p[c.stand1.count] = q1; c.stand1.n[c.stand1.count] = c.zero_end.n[k]; c.stand1.tri[c.stand1.count] = c.zero_end.tri[k]; ++c.stand1.count;
+  }
+  c.fused.lin.acc = c.acc;
+  p->acc1_ready = true;
+  return LVF_OK;
+}
 
 // the linearisation at the current state: cost, B, gc, E, C, gr.  `gated`: skipped on device once the LM loop has finished
 // HIP events between the stages of one LM iteration (lvf_problem_stage_times): event 0 before the first launch, event k + 1 after stage k
-enum { ST_IMU_LIN = 0, ST_LIN_VISUAL, ST_TF_REDUCE, ST_PREPARE, ST_SCHUR_SP0, ST_SP_LEVELS, ST_CHOL, ST_BACKSOLVE, ST_STEP_TAIL, ST_COST, ST_DECIDE, ST_N };
+enum { ST_IMU_LIN = 0, ST_LIN_VISUAL, ST_TF_REDUCE, ST_PREPARE, ST_SCHUR_SP0, ST_SP_LEVELS, ST_CHOL, ST_BACKSOLVE, ST_STEP_TAIL, ST_COST, ST_DECIDE, ST_FUSED, ST_N };
 static const char* const kStageNames[ST_N] = {"k_zero_multi (only when the accumulators are not known clean)", "k_lin_visual", "k_tf_reduce (+ sparse level 0)", "k_prepare (+ sparse level 1)", "k_schur_sp0 (+ a sparse level)", "k_sp_eliminate (the levels left)",
-                                             "k_chol_step (all block steps)", "k_chol_backsolve", "k_step_tail", "k_cost_decide (candidate cost incl. the ImuError factors; its last workgroup closes the iteration; + prior passes)", "k_lm_decide (windows without visual blocks)"};
+                                             "k_chol_step (all block steps)", "k_chol_backsolve", "k_step_tail", "k_cost_decide (candidate cost incl. the ImuError factors; its last workgroup closes the iteration; + prior passes)", "k_lm_decide (windows without visual blocks)",
+                                             "k_lin_cost_decide (fused chain: linearisation at the candidate + its cost; its last workgroup closes the iteration)"};
 // (one event set per timed iteration: the iterations are enqueued back to back and waited for ONCE, so every stage — the first one of an
 // iteration included — starts behind a busy queue like in the device loop; with a wait per iteration the first stage absorbed the idle
 // queue's start-up, ~6 us of k_lin_visual's figure)
@@ -3551,9 +3734,16 @@ static inline void stage_mark(lvf_problem* p, int stage_done, int launches) {
   k->launches[stage_done] = launches;
 }
 
+// a sparse level of the fused chain reads B / gc of the active accumulator set (early form only: the classic form does not read them)
+static inline void acc_patch(SpArgs& a, const AccSel* acc) {
+  if (acc && a.src.B) { a.src.sel = acc->sel; a.src.B1 = (const double*)(double*)acc->B; a.src.gc1 = (const double*)(double*)acc->gc; }
+}
+
 // `iteration`: the launches belong to a full LM iteration (enqueue_iteration) — only then do the early sparse levels ride along and are the
 // per-step scalars reset here; a stand-alone linearisation (gradient / cost taps) leaves S and the control block alone
-static int enqueue_linearize(lvf_problem* p, double huber, bool gated, bool iteration = false) {
+// `acc` (fused chain): every launch selects its accumulator set on device; `lin` == false: the active set already holds the linearisation
+// (the last iteration's candidate pass), only k_tf_reduce runs
+static int enqueue_linearize(lvf_problem* p, double huber, bool gated, bool iteration = false, const AccSel* acc = nullptr, bool lin = true) {
   hipStream_t q = p->ctx->stream;
   if (chain_stale(p)) LVF_TRY(build_chain(p));
   const Chain& c = *p->chain;
@@ -3562,7 +3752,7 @@ static int enqueue_linearize(lvf_problem* p, double huber, bool gated, bool iter
   bool imu_done = false;
   // the accumulators are cleared at the END of every iteration (extra workgroups of the cost + decision launch); a launch of its own is
   // only needed when they are not known to be clean (first linearisation after a configure, stand-alone gradient / reduced-system taps)
-  const bool clean = c.fast && p->accum_clean;
+  const bool clean = !lin || (c.fast && p->accum_clean);
   p->accum_clean = false;
   if (p->clk && p->clk->on) (void)hipEventRecord(p->clk->ev[p->clk->rep][0], q);
   if (!clean) LVF_CHAIN_LAUNCH(p, ST_IMU_LIN, k_zero_multi, dim3(512, c.zero.count), dim3(kT), 0, q, c.zero);
@@ -3576,13 +3766,19 @@ static int enqueue_linearize(lvf_problem* p, double huber, bool gated, bool iter
     static const bool lin_timing = std::getenv("LVF_LIN_TIMING") != nullptr;
     if (lin_timing) { LVF_TRY(p->dbg_lin.ensure((size_t)la.v.n_tfw * 24 + 8)); la.dbg = p->dbg_lin.p; }
     static const size_t lds_pad = [] { const char* e = std::getenv("LVF_LIN_LDS_PAD"); return e ? (size_t)std::atoi(e) : (size_t)0; }();      // experiment: fewer workgroups per CU
-    LVF_CHAIN_LAUNCH(p, ST_LIN_VISUAL, k_lin_visual, dim3(la.nblocks), dim3(kT), c.lin_lds + lds_pad, q, la);
-    stage_mark(p, ST_LIN_VISUAL, 1);
+    if (lin) LVF_CHAIN_LAUNCH(p, ST_LIN_VISUAL, k_lin_visual, dim3(la.nblocks), dim3(kT), c.lin_lds + lds_pad, q, la);      // (into set 0: a pass starts with LmCtl::aset = 0)
+    stage_mark(p, ST_LIN_VISUAL, lin ? 1 : 0);
     if (p->compact) {
       TfReduceArgs ra = c.red;
       if (!gated) ra.done = nullptr;
       if (!iteration) { ra.nblocks = ra.own_blocks; ra.ride.nblocks = 0; }
-      LVF_CHAIN_LAUNCH(p, ST_TF_REDUCE, k_tf_reduce, dim3(ra.nblocks), dim3(kT), ra.ride.nblocks > 0 ? c.red_lds : 0, q, ra);
+      int zero_wgs = 0;
+      if (acc) {
+        ra.acc = *acc; acc_patch(ra.ride, acc);
+        ra.pending = lin ? nullptr : &p->ctl.p->lin_pending;
+        ra.stand0 = c.stand0; ra.stand1 = c.stand1; ra.zero_wgs = zero_wgs = kEndZeroWgs;
+      }
+      LVF_CHAIN_LAUNCH(p, ST_TF_REDUCE, k_tf_reduce, dim3(ra.nblocks + zero_wgs), dim3(kT), ra.ride.nblocks > 0 ? c.red_lds : 0, q, ra);
     }
     stage_mark(p, ST_TF_REDUCE, p->compact ? 1 : 0);
     if (lin_timing) {
@@ -3677,12 +3873,13 @@ static int await_band_work(lvf_problem* p) {
 }
 
 // S (elimination order) = B + D - E^T Cd^-1 E, rhs row = -(gc - E^T Cd^-1 g_rho); radius read from `radius_dev`
-static int enqueue_reduced_system(lvf_problem* p, const double* radius_dev, bool reset_scalars, bool gated, bool* level0_done) {
+static int enqueue_reduced_system(lvf_problem* p, const double* radius_dev, bool reset_scalars, bool gated, bool* level0_done, const AccSel* acc = nullptr) {
   hipStream_t q = p->ctx->stream;
   const Chain& c = *p->chain;
   // the parity tap (level0_done == nullptr: the damped system alone, nothing eliminated) always takes the classic assembly
   const bool early = c.early && level0_done != nullptr;
   PrepArgs pa = early ? c.prep_early : c.prep;
+  if (acc) { pa.acc = *acc; acc_patch(pa.ride, acc); }
   pa.radius = radius_dev;
   if (!reset_scalars) pa.scal = nullptr;
   if (!gated) pa.done = nullptr;
@@ -3698,6 +3895,7 @@ static int enqueue_reduced_system(lvf_problem* p, const double* radius_dev, bool
     LVF_TRY(await_band_work(p));                       // (patches c.ssp0: `c` refers to the problem's chain)
     if (c.merged_level0) {
       SchurSp0Args sa = c.ssp0;
+      if (acc) { sa.acc = *acc; acc_patch(sa.sp, acc); acc_patch(sa.sp_b, acc); acc_patch(sa.sp_c, acc); }
       if (!gated) sa.done = nullptr;
       if (!level0_done) { sa.nblocks = sa.n_work; sa.sp.nblocks = 0; sa.sp_b.nblocks = 0; sa.sp_c.nblocks = 0; }       // the Schur complement alone (parity tap)
       static const bool schur_timing = std::getenv("LVF_SCHUR_TIMING") != nullptr;
@@ -3731,10 +3929,15 @@ static int enqueue_reduced_system(lvf_problem* p, const double* radius_dev, bool
 }
 
 // one complete LM iteration of one window on its stream, closed on device by k_lm_decide; nothing is waited for
-static int enqueue_iteration(lvf_problem* p, bool end_zero) {
+// `fused` (Chain::fused_ok, a device-loop solve only): kFusedOn = every launch selects its accumulator set on device; kFusedNoLin = the iteration
+// starts at k_tf_reduce (the last one's candidate pass linearised); kFusedTail = it ends with the candidate pass k_lin_cost_decide
+enum { kFusedOn = 1, kFusedNoLin = 2, kFusedTail = 4 };
+static int enqueue_iteration(lvf_problem* p, bool end_zero, int fused = 0) {
   hipStream_t q = p->ctx->stream;
   if (chain_stale(p)) LVF_TRY(build_chain(p));
   const Chain& c = *p->chain;
+  if (!c.fused_ok || !p->acc1_ready) fused = 0;
+  const AccSel* acc = (fused & kFusedOn) ? &c.acc : nullptr;
   static const bool sp_timing = std::getenv("LVF_SP_TIMING") != nullptr;
   if (sp_timing && c.early) {
     // diagnostic: the levels' stamps (the chain is rebuilt with the debug pointer in every level's arguments; printed by the next call)
@@ -3761,12 +3964,15 @@ static int enqueue_iteration(lvf_problem* p, bool end_zero) {
       }
     }
   }
-  LVF_TRY(enqueue_linearize(p, p->huber, true, true));
+  LVF_TRY(enqueue_linearize(p, p->huber, true, true, acc, !(fused & kFusedNoLin)));
   bool level0_done = false;
-  LVF_TRY(enqueue_reduced_system(p, &p->ctl.p->radius, true, true, &level0_done));
+  LVF_TRY(enqueue_reduced_system(p, &p->ctl.p->radius, true, true, &level0_done, acc));
   const int own0 = level0_done ? c.first_own_level : 0;      // (levels below rode in the launches above)
-  for (int lv = own0; lv < c.n_levels; ++lv)
-    LVF_CHAIN_LAUNCH(p, ST_SP_LEVELS, k_sp_eliminate, dim3(c.sp[lv].nblocks), dim3(256), c.sp_lds[lv], q, c.sp[lv]);
+  for (int lv = own0; lv < c.n_levels; ++lv) {
+    SpArgs la = c.sp[lv];
+    acc_patch(la, acc);
+    LVF_CHAIN_LAUNCH(p, ST_SP_LEVELS, k_sp_eliminate, dim3(la.nblocks), dim3(256), c.sp_lds[lv], q, la);
+  }
   stage_mark(p, ST_SP_LEVELS, std::max(0, c.n_levels - own0));
   for (int kb = 0; kb < p->nb; ++kb) {
     CholArgs cha = c.chol;
@@ -3782,15 +3988,30 @@ static int enqueue_iteration(lvf_problem* p, bool end_zero) {
     if (c.back_tail_merged) {
       BackTailArgs bt = c.bt;
       if (back_timing) bt.back.sp.dbg = p->dbg.p;
+      if (acc) bt.tail.acc = *acc;
       LVF_CHAIN_LAUNCH(p, ST_BACKSOLVE, k_backsolve_tail, dim3(2 + c.bt.g_lm), dim3(kBT), c.bt_lds, q, bt);
       stage_mark(p, ST_BACKSOLVE, 1);
       stage_mark(p, ST_STEP_TAIL, 0);
     } else {
       LVF_CHAIN_LAUNCH(p, ST_BACKSOLVE, k_chol_backsolve, dim3(1), dim3(kBT), c.back_lds, q, ba);
       stage_mark(p, ST_BACKSOLVE, 1);
-      LVF_CHAIN_LAUNCH(p, ST_STEP_TAIL, k_step_tail, dim3(c.tail.nblocks), dim3(kT), c.tail_lds, q, c.tail);
+      TailArgs ta = c.tail;
+      if (acc) ta.acc = *acc;
+      LVF_CHAIN_LAUNCH(p, ST_STEP_TAIL, k_step_tail, dim3(ta.nblocks), dim3(kT), c.tail_lds, q, ta);
       stage_mark(p, ST_STEP_TAIL, 1);
     }
+  }
+  if (fused & kFusedTail) {
+    // the candidate pass linearises x + dx into the standby set and closes the iteration (k_lin_cost_decide)
+    FusedArgs fa = c.fused;
+    fa.lin.huber = p->huber;
+    LVF_CHAIN_LAUNCH(p, ST_FUSED, k_lin_cost_decide, dim3(fa.nblocks + fa.zero_wgs), dim3(kT), c.lin_lds, q, fa);
+    stage_mark(p, ST_COST, 0);
+    stage_mark(p, ST_FUSED, 1);
+    p->accum_clean = false;
+    p->linearized = false;
+    LVF_HIP(hipGetLastError());
+    return LVF_OK;
   }
   // candidate cost: the small passes first, then the visual pass whose last workgroup closes the iteration
   CostArgs ca = c.cost;
@@ -3854,6 +4075,7 @@ static int rearm_after_handover(lvf_problem* p, LmCtl* c) {
   p->no_chain = true; p->unchained_solves = 0; p->chain_ready = false; p->handover_retries += 1;
   if (p->force_handover_timeouts > 0) p->force_handover_timeouts -= 1;
   c->done = 0; c->termination = 1; c->why = LVF_WHY_MAX_ITERATIONS;
+  c->aset = 0; c->lin_pending = 0;           // (the re-run linearises into set 0 with today's chain)
   p->accum_clean = false;                    // (the aborted iteration's partial sums: cleared by an explicit launch before the re-run)
   return upload_ctl(p, *c);                  // rebuilds the chain
 }
@@ -4555,15 +4777,19 @@ int lvf_problem_stage_times2(lvf_problem* p, const lvf_solver_options* o, double
   ctl_from_options(o, radius, 2.0, reps + 2, false, &c);
   p->huber = o->huber_a;
   LVF_TRY(upload_ctl(p, c));
-  LVF_TRY(enqueue_iteration(p, true));             // (un-timed: the timed iterations queue up behind it)
+  // the device loop's chain: with the fused chain every timed iteration starts at k_tf_reduce and ends with the candidate pass
+  const bool fz = p->chain->fused_ok && !p->no_chain;
+  if (fz) LVF_TRY(ensure_acc1(p));
+  LVF_TRY(enqueue_iteration(p, true, fz ? kFusedOn | kFusedTail : 0));             // (un-timed: the timed iterations queue up behind it)
   int nk = 0;
   for (int r = 0; r < reps; ++r) {
     k.on = true; k.rep = r; k.nk = 0;
-    const int rc = enqueue_iteration(p, true);
+    const int rc = enqueue_iteration(p, true, fz ? kFusedOn | kFusedNoLin | kFusedTail : 0);
     k.on = false;
     nk = k.nk;
     LVF_TRY(rc);
   }
+  if (fz) LVF_TRY(enqueue_iteration(p, true, kFusedOn | kFusedNoLin));          // (un-timed: the plain cost pass leaves both accumulator sets clean)
   LVF_HIP(hipStreamSynchronize(q));
   for (int r = 0; r < reps; ++r) {
     for (int i = 0; i < ST_N; ++i) {
@@ -4664,12 +4890,30 @@ int lvf_problem_solve_then(lvf_problem* p, const lvf_solver_options* o, lvf_solv
   const auto wall0 = std::chrono::steady_clock::now();
   bool timed_out = false;
   for (int first = 0;;) {
+    // the fused chain (Chain::fused_ok): the pass's first iteration linearises at the state as today, every later one starts from the
+    // linearisation the previous iteration's candidate pass made, and the last one enqueued for the solve ends with the plain cost pass (a
+    // re-run after a hand-over time-out takes today's chain: no_chain)
+    const bool fz = p->chain->fused_ok && !p->no_chain && o->max_num_iterations - first >= 2;
+    if (fz) LVF_TRY(ensure_acc1(p));
+    bool fused_tail = false;
     for (int it = first; it < o->max_num_iterations; ++it) {
-      LVF_TRY(enqueue_iteration(p, true));
+      const int f = fz ? kFusedOn | (it > first ? kFusedNoLin : 0) | (it + 1 < o->max_num_iterations ? kFusedTail : 0) : 0;
+      LVF_TRY(enqueue_iteration(p, true, f));
+      fused_tail = (f & kFusedTail) != 0;
       if (it >= first + 1) LVF_TRY(wait_for_iteration(p, it));          // iteration it-1 is closed; iteration `it` keeps the device busy meanwhile
       if (p->rec->done) break;
       if (o->max_solver_time_in_seconds > 0.0 &&
           std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() >= o->max_solver_time_in_seconds) { timed_out = true; break; }
+    }
+    if (fused_tail) {
+      // the loop ended before the last iteration: the active set was not cleared by a plain cost pass — both sets are, here, with the cost stripes
+      const Chain& ch = *p->chain;
+      ZeroList z = ch.stand0;
+      for (int k = 0; k < ch.stand1.count && z.count < kZeroListMax; ++k) { z.p[z.count] = ch.stand1.p[k]; z.n[z.count] = ch.stand1.n[k]; z.tri[z.count] = ch.stand1.tri[k]; ++z.count; }
+      hipLaunchKernelGGL(k_zero_multi, dim3(512, z.count), dim3(kT), 0, p->ctx->stream, z);
+      LVF_HIP(hipGetLastError());
+      LVF_HIP(hipMemsetAsync(p->scal.p + SC_COST, 0, kStripes * 8, p->ctx->stream));
+      p->accum_clean = ch.stand0.count + ch.stand1.count <= kZeroListMax;
     }
     // the caller's launches ride behind the last iteration — unless the host already KNOWS this pass ended in a hand-over time-out (the mirror
     // carries `why`): the state is not final then, the re-run's pass enqueues them.  (A time-out in the very last iteration enqueued is only
