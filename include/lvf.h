@@ -496,6 +496,59 @@ int lvf_forward_update(lvf_ctx* ctx, const double* transform7, int n, double* po
 /* the same on a device-resident state: keyframes [first_kf, n_kf) of st (poses and velocities), nothing crosses PCIe but the transform */
 int lvf_state_forward_update(lvf_state* st, const double* transform7, int first_kf);
 
+/* ---- GNSS (NavSat) alignment: navsat_error.hpp + Navsat::{Initialize, OptimizeBC, Optimize, QuickFix} ----------------- */
+/* All arithmetic fp64.  Poses are [qx,qy,qz,qw,tx,ty,tz], rpyxyz / para is [yaw,pitch,roll,x,y,z].  cov is the diagonal covariance the
+ * reference hands to cov2sqrt_info (navsat_error.hpp:9-15): sqrt_info_k = sqrt(1.0 / cov_k); every cov_k must be > 0.
+ * NavsatInitError <3,1,1,1> (navsat_error.hpp:17-51) batched: block i = NavsatInitError(p0[i], p1[i], cov[i]) at the shared x3 = (yaw, x, y).
+ * residuals [n][3]; jacobians [n][3][3] row-major with columns (yaw, x, y), or NULL. */
+int lvf_navsat_init_evaluate(lvf_ctx* ctx, int n, const double* p0, const double* p1, const double* cov, const double* x3, double* residuals,
+                             double* jacobians);
+/* NavsatRXError <3,1,1,1,1,1,1> (navsat_error.hpp:53-91) batched: block i = NavsatRXError(p0[i], p1[i], pose7, cov[i]) at the shared
+ * x6 = (yaw, pitch, roll, x, y, z).  residuals [n][3]; jacobians [n][3][6] row-major, or NULL. */
+int lvf_navsat_rx_evaluate(lvf_ctx* ctx, int n, const double* p0, const double* p1, const double* pose7, const double* cov, const double* x6,
+                           double* residuals, double* jacobians);
+/* NavsatRError <1,1> (navsat_error.hpp:93-120): NavsatRError(y3, pose7) at roll; one residual, one derivative (jacobian may be NULL). */
+int lvf_navsat_r_evaluate(lvf_ctx* ctx, const double* y3, const double* pose7, double roll, double* residual, double* jacobian);
+/* Navsat::Initialize (navsat.cpp:100-133): n blocks NavsatInitError(position[i], raw[i], cov[i]) (the keyframes that have a fix), no loss;
+ * stage 1 solves yaw with x, y constant, stage 2 continues with all three free; both stages are ONE device launch.  para6 receives para
+ * (only yaw, x, y can be non-zero), extrinsic7 = rpyxyz2se3(para).  n == 0: para = 0, extrinsic = identity, no launch. */
+int lvf_navsat_initialize(lvf_ctx* ctx, int n, const double* position, const double* raw, const double* cov, const lvf_solver_options* o,
+                          double* para6, double* extrinsic7, lvf_solver_summary* stage1, lvf_solver_summary* stage2);
+typedef struct lvf_navsat_bc_options {
+  int mode;                     /* bit i set = para[i] constant (navsat.cpp:210-214); 0b000000 for the section, 0b110111 per keyframe */
+  double distance;              /* frames_distance(frame->time, end) */
+  double trust_distance_yaw;    /* PoseGraph::min_BC_distance at construction (navsat.h:51) */
+  double trust_distance_pitch;  /* accuracy * 10 (navsat.h:52) */
+  double z_lower, z_upper;      /* A.z - B.z -/+ trust_distance_z * section.degree / 360 (navsat.cpp:244-246); used when z is free */
+  double huber_a;               /* HuberLoss(0.1) (navsat.cpp:200) */
+  lvf_solver_options solver;    /* ceres::Solver::Options defaults (huber_a of this member is not used) */
+} lvf_navsat_bc_options;
+typedef struct lvf_navsat_bc_result {
+  int skipped;                  /* 1: the early return of navsat.cpp:195-197 was taken: nothing ran, the arrays are untouched */
+  int line_search_contractions; /* step-size contractions of the bounded solve's projected line search (0 when z is constant) */
+  double para[6];
+  double transform[7];          /* new_pose * old_pose^-1: what every later pose was multiplied with */
+  lvf_solver_summary roll;      /* the roll pre-solve (navsat.cpp:216-232); all zero when it did not run */
+  lvf_solver_summary main;
+} lvf_navsat_bc_result;
+void lvf_navsat_bc_options_default(lvf_navsat_bc_options* o);
+/* Navsat::OptimizeBC (navsat.cpp:192-269) in ONE device launch.  poses [n + n_update][7]: the n active keyframes GetKeyFrames(frame->time, end)
+ * with the frame itself first, then n_update further poses (up to C) that only receive the forward update; has_fix[n], fix_point[n][3]
+ * (what GetFixPoint returned; read where has_fix), cov[n][3].  Follows the function's control flow: the early return; the roll pre-solve
+ * (one NavsatRError over all active keyframes) when roll is free and distance > trust_distance_yaw, roll constant afterwards; pitch constant
+ * when distance < trust_distance_pitch; z inside [z_lower, z_upper] when free; one NavsatRXError(fix_i, frame^-1 * t_i, frame, cov_i) under
+ * HuberLoss(huber_a) per keyframe with a fix; then poses[0] <- poses[0] * rpyxyz2se3(para) and poses[1..] <- (new * old^-1) * pose, in place.
+ * No keyframe with a fix: para = 0 and the products are still applied, as in the reference.  Costs are those of the reduced program. */
+int lvf_navsat_optimize_bc(lvf_ctx* ctx, int n, int n_update, double* poses, const int32_t* has_fix, const double* fix_point, const double* cov,
+                           const lvf_navsat_bc_options* opt, lvf_navsat_bc_result* result);
+/* The per-keyframe loop of Navsat::Optimize / QuickFix (navsat.cpp:150-155, :171-176) in ONE device launch.  poses [n][7]: the keyframes strictly
+ * after B in time order, the last one being C (updated, not solved).  For k = 0 .. n-2: OptimizeBC(k, t_k + epsilon, 0b110111) — only x free, one
+ * NavsatRXError(fix_k, pose_k^-1 * t_k, pose_k, cov_k) under HuberLoss(huber_a) if has_fix[k] — then the forward update of poses k+1 .. n-1.
+ * has_fix[n-1], fix_point[n-1][3], cov[n-1][3].  Out: poses in place, x[n-1] (may be NULL), iterations[n-1] (may be NULL) = num_iterations of
+ * each step's solve, summary = sums over the steps (termination: the worst).  n < 2: nothing to do. */
+int lvf_navsat_fix_chain(lvf_ctx* ctx, int n, double* poses, const int32_t* has_fix, const double* fix_point, const double* cov, double huber_a,
+                         const lvf_solver_options* o, double* x, int32_t* iterations, lvf_solver_summary* summary);
+
 /* ---- multi-GPU: the path's only exchange, for a C / C++ host ----------------------------------------------------------- */
 /* Independent windows / loop-closure candidates shard one per GPU: one process per GPU, one lvf_ctx each, no data-path collective.  The
  * single exchange is an all-gather of fixed-size records (score, relative_o_c[7], candidate id: relocator.cpp:196-206) over RCCL / xGMI.

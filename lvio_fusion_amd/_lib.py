@@ -84,6 +84,16 @@ class SolverSummary(C.Structure):
         return self.WHY[self.termination_reason]
 
 
+class NavsatBcOptions(C.Structure):
+    _fields_ = [("mode", C.c_int), ("distance", C.c_double), ("trust_distance_yaw", C.c_double), ("trust_distance_pitch", C.c_double),
+                ("z_lower", C.c_double), ("z_upper", C.c_double), ("huber_a", C.c_double), ("solver", SolverOptions)]
+
+
+class NavsatBcResult(C.Structure):
+    _fields_ = [("skipped", C.c_int), ("line_search_contractions", C.c_int), ("para", C.c_double * 6), ("transform", C.c_double * 7),
+                ("roll", SolverSummary), ("main", SolverSummary)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into liblvf_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".hpp"))]
@@ -133,6 +143,16 @@ _SIGS = {
     "lvf_relocate_rotation_solve": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(SolverOptions), C.POINTER(SolverSummary)]),
     "lvf_forward_update": (C.c_int, [_VP, c_double_p, C.c_int, c_double_p, c_double_p]),
     "lvf_state_forward_update": (C.c_int, [_VP, c_double_p, C.c_int]),
+    "lvf_navsat_init_evaluate": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "lvf_navsat_rx_evaluate": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "lvf_navsat_r_evaluate": (C.c_int, [_VP, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p]),
+    "lvf_navsat_initialize": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(SolverOptions), c_double_p, c_double_p,
+                                        C.POINTER(SolverSummary), C.POINTER(SolverSummary)]),
+    "lvf_navsat_bc_options_default": (None, [C.POINTER(NavsatBcOptions)]),
+    "lvf_navsat_optimize_bc": (C.c_int, [_VP, C.c_int, C.c_int, c_double_p, c_int_p, c_double_p, c_double_p, C.POINTER(NavsatBcOptions),
+                                         C.POINTER(NavsatBcResult)]),
+    "lvf_navsat_fix_chain": (C.c_int, [_VP, C.c_int, c_double_p, c_int_p, c_double_p, c_double_p, C.c_double, C.POINTER(SolverOptions), c_double_p, c_int_p,
+                                       C.POINTER(SolverSummary)]),
     "lvf_window_reject_outliers": (C.c_int, [_VP, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int)]),
     "lvf_comm_get_unique_id": (C.c_int, [_VP]),
     "lvf_comm_create": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.POINTER(_VP)]),

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, SolverOptions, SolverSummary
+from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, SolverOptions, SolverSummary, NavsatBcOptions, NavsatBcResult
 
 POSES, VEL, BA, BG, INV_DEPTH, W_VISUAL = range(6)
 IMU_BLOCK_SIZES = (7, 3, 3, 3, 7, 3, 3, 3)
@@ -232,6 +232,108 @@ def forward_update(ctx, transform, poses, vw=None):
     T = _d(transform); P = _d(poses).copy(); V = None if vw is None else _d(vw).copy()
     _chk(ctx.L.lvf_forward_update(ctx.h, _dp(T), P.shape[0], _dp(P), _dp(V) if V is not None else None))
     return P, V
+
+
+def navsat_init_evaluate(ctx, p0, p1, cov, x3, jacobians=True):
+    """NavsatInitError <3,1,1,1> batched at x3 = (yaw, x, y): returns r[n][3], J[n][3][3] or None."""
+    a, b, c, x = _d(p0).reshape(-1, 3), _d(p1).reshape(-1, 3), _d(cov).reshape(-1, 3), _d(x3)
+    n = a.shape[0]
+    r = np.empty((n, 3)); J = np.empty((n, 3, 3)) if jacobians else None
+    _chk(ctx.L.lvf_navsat_init_evaluate(ctx.h, n, _dp(a), _dp(b), _dp(c), _dp(x), _dp(r), _dp(J) if jacobians else None))
+    return r, J
+
+
+def navsat_rx_evaluate(ctx, p0, p1, pose, cov, x6, jacobians=True):
+    """NavsatRXError <3,1,1,1,1,1,1> batched at x6 = (yaw, pitch, roll, x, y, z): returns r[n][3], J[n][3][6] or None."""
+    a, b, c, P, x = _d(p0).reshape(-1, 3), _d(p1).reshape(-1, 3), _d(cov).reshape(-1, 3), _d(pose), _d(x6)
+    n = a.shape[0]
+    r = np.empty((n, 3)); J = np.empty((n, 3, 6)) if jacobians else None
+    _chk(ctx.L.lvf_navsat_rx_evaluate(ctx.h, n, _dp(a), _dp(b), _dp(P), _dp(c), _dp(x), _dp(r), _dp(J) if jacobians else None))
+    return r, J
+
+
+def navsat_r_evaluate(ctx, y3, pose, roll, jacobians=True):
+    """NavsatRError <1,1>: returns (residual, d residual / d roll or None)."""
+    y, P = _d(y3), _d(pose)
+    r, J = C.c_double(), C.c_double()
+    _chk(ctx.L.lvf_navsat_r_evaluate(ctx.h, _dp(y), _dp(P), C.c_double(roll), C.byref(r), C.byref(J) if jacobians else None))
+    return r.value, (J.value if jacobians else None)
+
+
+def navsat_initialize(ctx, position, raw, cov, opt=None):
+    """Navsat::Initialize; returns (para6, extrinsic7, summary of stage 1, summary of stage 2)."""
+    a, b, c = _d(position).reshape(-1, 3), _d(raw).reshape(-1, 3), _d(cov).reshape(-1, 3)
+    opt = opt or default_solver_options()
+    para, ext = np.empty(6), np.empty(7)
+    s1, s2 = _lib.SolverSummary(), _lib.SolverSummary()
+    _chk(ctx.L.lvf_navsat_initialize(ctx.h, a.shape[0], _dp(a), _dp(b), _dp(c), C.byref(opt), _dp(para), _dp(ext), C.byref(s1), C.byref(s2)))
+    return para, ext, s1, s2
+
+
+def navsat_bc_options(**kw):
+    o = NavsatBcOptions()
+    _lib.lib().lvf_navsat_bc_options_default(C.byref(o))
+    for k, v in kw.items():
+        if k == "solver":
+            o.solver = v
+        else:
+            getattr(o, k)          # (an unknown field is an error, not a new attribute)
+            setattr(o, k, v)
+    return o
+
+
+def navsat_optimize_bc(ctx, poses, n_active, has_fix, fix_point, cov, opt):
+    """Navsat::OptimizeBC on the host array `poses` ([n_active + n_update][7], frame first), updated IN PLACE; returns NavsatBcResult."""
+    if not (isinstance(poses, np.ndarray) and poses.dtype == np.float64 and poses.flags.c_contiguous):
+        raise TypeError("poses must be a C-contiguous float64 array (it is updated in place)")
+    n = int(n_active)
+    total = poses.size // 7
+    h, f, c = _i(has_fix), _d(fix_point).reshape(-1, 3), _d(cov).reshape(-1, 3)
+    if not (0 <= n <= total and h.size == n and f.shape[0] == n and c.shape[0] == n):
+        raise ValueError("navsat_optimize_bc: has_fix / fix_point / cov must have one entry per active keyframe")
+    res = NavsatBcResult()
+    _chk(ctx.L.lvf_navsat_optimize_bc(ctx.h, n, total - n, _dp(poses), _ip(h), _dp(f), _dp(c), C.byref(opt), C.byref(res)))
+    return res
+
+
+def navsat_fix_chain(ctx, poses, has_fix, fix_point, cov, huber_a=0.1, opt=None):
+    """The per-keyframe loop of Navsat::Optimize / QuickFix on the host array `poses` ([n][7]: the keyframes after B, C last), updated IN
+    PLACE; returns (x[n-1], iterations[n-1], SolverSummary)."""
+    if not (isinstance(poses, np.ndarray) and poses.dtype == np.float64 and poses.flags.c_contiguous):
+        raise TypeError("poses must be a C-contiguous float64 array (it is updated in place)")
+    n = poses.size // 7
+    steps = max(n - 1, 0)
+    h, f, c = _i(has_fix), _d(fix_point).reshape(-1, 3), _d(cov).reshape(-1, 3)
+    if not (h.size == steps and f.shape[0] == steps and c.shape[0] == steps):
+        raise ValueError("navsat_fix_chain: has_fix / fix_point / cov must have n - 1 entries")
+    opt = opt or default_solver_options()
+    x, it = np.zeros(steps), np.zeros(steps, np.int32)
+    summ = _lib.SolverSummary()
+    _chk(ctx.L.lvf_navsat_fix_chain(ctx.h, n, _dp(poses), _ip(h), _dp(f), _dp(c), C.c_double(huber_a), C.byref(opt), _dp(x), _ip(it), C.byref(summ)))
+    return x, it, summ
+
+
+def navsat_quick_fix(ctx, poses, has_fix, fix_point, cov, bc_opt, between=None):
+    """Navsat::QuickFix's two steps (navsat.cpp:169-176) on poses [n][7] = the keyframes B .. C in time order, updated in place:
+    OptimizeBC(B, C, mode 0) over all of them, then the per-keyframe chain over the keyframes strictly after B.  has_fix / fix_point / cov have
+    one entry per keyframe.  `between` (navsat_optimize's OptimizeAB) runs between the two.  Host composition only.
+    Returns (NavsatBcResult, x, iterations, chain summary)."""
+    n = poses.size // 7
+    h, f, c = _i(has_fix), _d(fix_point).reshape(-1, 3), _d(cov).reshape(-1, 3)
+    o = NavsatBcOptions.from_buffer_copy(bc_opt)
+    o.mode = 0
+    res = navsat_optimize_bc(ctx, poses, n, h, f, c, o)
+    if between is not None:
+        between(poses)
+    tail = poses.reshape(-1, 7)[1:]
+    x, it, summ = navsat_fix_chain(ctx, tail, h[1:n - 1], f[1:n - 1], c[1:n - 1], o.huber_a, o.solver) if n >= 1 else (np.zeros(0), np.zeros(0, np.int32), _lib.SolverSummary())
+    return res, x, it, summ
+
+
+def navsat_optimize(ctx, poses, has_fix, fix_point, cov, bc_opt, optimize_ab):
+    """Navsat::Optimize (navsat.cpp:135-156): OptimizeBC(B, C, mode 0), the caller's OptimizeAB (a callable handed the pose array; it stays on
+    the host: INTEGRATION.md), then the per-keyframe chain."""
+    return navsat_quick_fix(ctx, poses, has_fix, fix_point, cov, bc_opt, between=optimize_ab)
 
 
 def prior3_evaluate(ctx, mode, target3, weight, x3):

@@ -12,11 +12,10 @@
 // (djet.hpp).  The problem has 3 tangent unknowns and a few dozen blocks: the whole LM loop (linearise, damped 3x3 solve, candidate
 // cost, accept / reject, trust-region update, termination tests) is ONE launch of one workgroup; the host reads one record.
 #include "lvf_internal.hpp"
+#include "loop_dev.hpp"
 #include "se3_jet.hpp"
 
 namespace lvf {
-
-constexpr int kLT = 256;
 
 // residual r[7] (+ ambient J[7][4], row-major) of one block at quaternion q (x,y,z,w)
 template <bool WITH_J>
@@ -58,18 +57,6 @@ __global__ __launch_bounds__(64) void k_relocate_r(int n, const double* __restri
 
 struct RelocOpts { int max_iters; double function_tol, gradient_tol, parameter_tol, min_rel_decrease, radius0; };
 struct RelocRecord { double q[4]; double initial_cost, final_cost; int iters, successes, termination, pad; };
-
-// sums `v` over the workgroup; every thread returns the total (two barriers)
-__device__ __forceinline__ double wg_sum(double v, double* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < kLT / 64; ++k) s += red[k];
-  return s;
-}
 
 __global__ __launch_bounds__(kLT) void k_relocate_solve(int n, const double* __restrict__ relocated, const double* __restrict__ unrelocated,
                                                         const double* __restrict__ q_in, RelocOpts o, RelocRecord* __restrict__ out) {
@@ -174,29 +161,13 @@ __global__ __launch_bounds__(kLT) void k_relocate_solve(int n, const double* __r
   }
 }
 
-// PoseGraph::ForwardUpdate: Sophus SE3 product (Hamilton product re-normalised; translation through Eigen's _transformVector)
+// PoseGraph::ForwardUpdate: Sophus SE3 product (Hamilton product re-normalised; translation through Eigen's _transformVector): loop_dev.hpp
 __global__ __launch_bounds__(kLT) void k_forward_update(int n, const double* __restrict__ T, double* __restrict__ poses, double* __restrict__ vw) {
   const int i = blockIdx.x * kLT + threadIdx.x;
   if (i >= n) return;
-  const double qn = sqrt(T[0] * T[0] + T[1] * T[1] + T[2] * T[2] + T[3] * T[3]);
-  const double ux = T[0] / qn, uy = T[1] / qn, uz = T[2] / qn, uw = T[3] / qn;
   double* p = poses + (size_t)7 * i;
-  const double bx = p[0], by = p[1], bz = p[2], bw = p[3];
-  const double w = uw * bw - ux * bx - uy * by - uz * bz, x = uw * bx + ux * bw + uy * bz - uz * by, y = uw * by + uy * bw + uz * bx - ux * bz,
-               z = uw * bz + uz * bw + ux * by - uy * bx;
-  const double nn = sqrt(w * w + x * x + y * y + z * z);
-  {
-    const double v0 = p[4], v1 = p[5], v2 = p[6];
-    const double cx = 2.0 * (uy * v2 - uz * v1), cy = 2.0 * (uz * v0 - ux * v2), cz = 2.0 * (ux * v1 - uy * v0);
-    p[4] = T[4] + (v0 + uw * cx + (uy * cz - uz * cy)); p[5] = T[5] + (v1 + uw * cy + (uz * cx - ux * cz)); p[6] = T[6] + (v2 + uw * cz + (ux * cy - uy * cx));
-  }
-  p[0] = x / nn; p[1] = y / nn; p[2] = z / nn; p[3] = w / nn;
-  if (vw) {
-    double* v = vw + (size_t)3 * i;
-    const double v0 = v[0], v1 = v[1], v2 = v[2];
-    const double cx = 2.0 * (uy * v2 - uz * v1), cy = 2.0 * (uz * v0 - ux * v2), cz = 2.0 * (ux * v1 - uy * v0);
-    v[0] = v0 + uw * cx + (uy * cz - uz * cy); v[1] = v1 + uw * cy + (uz * cx - ux * cz); v[2] = v2 + uw * cz + (ux * cy - uy * cx);
-  }
+  forward_update_pose(T, p, p);
+  if (vw) forward_update_velocity(T, vw + (size_t)3 * i);
 }
 
 }  // namespace lvf
