@@ -67,6 +67,7 @@ typedef struct lvf_window lvf_window;
 typedef struct lvf_problem lvf_problem;
 typedef struct lvf_comm lvf_comm;
 typedef struct lvf_problem_batch lvf_problem_batch;
+typedef struct lvf_image lvf_image;
 
 /* Camera = intrinsics + sensor->robot extrinsic (include/lvio_fusion/sensor.h:41-44, visual/camera.h:74). */
 typedef struct lvf_camera {
@@ -548,6 +549,50 @@ int lvf_navsat_optimize_bc(lvf_ctx* ctx, int n, int n_update, double* poses, con
  * each step's solve, summary = sums over the steps (termination: the worst).  n < 2: nothing to do. */
 int lvf_navsat_fix_chain(lvf_ctx* ctx, int n, double* poses, const int32_t* has_fix, const double* fix_point, const double* cov, double huber_a,
                          const lvf_solver_options* o, double* x, int32_t* iterations, lvf_solver_summary* summary);
+
+/* ---- front-end tracking: utility.cpp optical_flow + triangulate, LocalMap::Triangulate, Frontend::TrackLastFrame --------------------------- */
+/* The semantics of cv::calcOpticalFlowPyrLK are DECLARED (tests/klt_ref.py): OpenCV's structure with floating-point interpolation,
+ * not a bit pin against OpenCV.  Points are cv::Point2f = float[2]; images are 8-bit grey.
+ * lvf_image: what a cv::Mat image becomes once it is tracked on the device (frame->image_left / image_right, frame.h): the uint8 pyramid of
+ * max_level + 1 levels (5-tap decimation as cv::buildOpticalFlowPyramid) and, per level, the Scharr derivative pair.  Built once per image
+ * and used in every role the image plays (current, then last; left / right).  data: height rows of width pixels, stride bytes apart (host
+ * memory; from lvf_host_alloc the upload is plain DMA).  The pixels may be overwritten as soon as the call returns.  0 <= max_level <= 7. */
+int lvf_image_create(lvf_ctx* ctx, const uint8_t* data, int width, int height, size_t stride, int max_level, lvf_image** out);
+int lvf_image_destroy(lvf_image* img);
+int lvf_image_size(const lvf_image* img, int* width, int* height, int* levels);      /* levels = max_level + 1; any pointer may be NULL */
+/* Debug / tests: one pyramid level, tightly packed: gray[h][w] and deriv[h][w][2] = (Sx, Sy) (either may be NULL); *width, *height (may be
+ * NULL) receive the level's size ((w + 1) / 2, (h + 1) / 2 per level). */
+int lvf_image_download_level(const lvf_image* img, int level, int* width, int* height, uint8_t* gray, int16_t* deriv);
+typedef struct lvf_flow_options {
+  int win, max_level;           /* forward pass: cv::Size(21, 21), maxLevel 3 (utility.cpp:64); win <= 21 */
+  int back_win, back_max_level; /* backward pass: cv::Size(3, 3), maxLevel 1 (utility.cpp:71) */
+  int max_iter;                 /* TermCriteria COUNT 30 (utility.cpp:65) */
+  double eps;                   /* TermCriteria EPS 0.01 (utility.cpp:65) */
+  double min_eig;               /* minEigThreshold 1e-4, the default the reference leaves in place */
+  double fb_max;                /* forward-backward distance gate 0.5 (utility.cpp:79) */
+} lvf_flow_options;
+void lvf_flow_options_default(lvf_flow_options* o);
+/* optical_flow (utility.cpp:55-89) in ONE device launch, one wavefront per point: the forward pass prev_img -> next_img started at next_pts
+ * (OPTFLOW_USE_INITIAL_FLOW), the backward pass started at prev_pts, and the gate of :78-81.  next_pts [n][2]: in = initial flow, out = the
+ * forward pass's result (for every point, as OpenCV leaves it); status [n] = 1 / 0; fb [n] (may be NULL) = the forward-backward distance,
+ * +inf where a pass failed.  n == 0 returns at once (:59-60).  opt == NULL: the defaults.  Both images of one context and one size. */
+int lvf_optical_flow(const lvf_image* prev_img, const lvf_image* next_img, int n, const float* prev_pts, float* next_pts, uint8_t* status, float* fb,
+                     const lvf_flow_options* opt);
+/* LocalMap::Triangulate (local_map.cpp:233-269) without the map bookkeeping: kps_right = the left pixel at depth 50 * baseline seen by camera 1
+ * (:240-242), optical_flow(left, right) (:245), triangulate (utility.cpp:7-18; one-sided Jacobi SVD of the 4x4 in fp64) with the inverse
+ * extrinsics and Pixel2Sensor of both pixels (:255).  status [n]: 0 = lost by the flow, 1 = landmark accepted, 2 = tracked but
+ * Robot2Sensor_0(pb).z <= 0 (:256).  inv_depth [n] = 1 / Robot2Sensor_1(pb).z — camera ONE, as :258 has it; p_robot [n][3] = pb.  Both are
+ * zero where status == 0.  What lvf_window_add_landmark takes: (kps_left, kps_right, inv_depth) of the points with status 1. */
+int lvf_stereo_triangulate(const lvf_image* left, const lvf_image* right, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n,
+                           const float* kps_left, float* kps_right, uint8_t* status, double* inv_depth, double* p_robot, const lvf_flow_options* opt);
+/* The numeric part of Frontend::TrackLastFrame (frontend.cpp:163-256): predictions = World2Pixel(pw[i], current_pose) (:168-170), optical_flow
+ * (last, current, kps_last, predictions) (:189), deviation = prediction - tracked minus its mean over the tracked points (:195-212), class
+ * per point cls [n]: 0 lost, 1 far (Camera::Far, camera.h:38-41), 2 near (!remove_moving_points or |deviation| < 30, :220), 3 moving;
+ * *num_good = far + near if that exceeds num_features_tracking_bad, else 0 (:236).  kps_current [n][2] = the tracked pixels; predictions
+ * [n][2] may be NULL.  What lvf_window_add_observation takes: kps_current of the points of class 1 or 2 when *num_good > 0. */
+int lvf_track_last_frame(const lvf_image* last, const lvf_image* current, const lvf_camera* cam0, double baseline, const double* current_pose, int n,
+                         const double* pw, const float* kps_last, int remove_moving_points, int num_features_tracking_bad, float* kps_current,
+                         float* predictions, uint8_t* cls, int* num_good, const lvf_flow_options* opt);
 
 /* ---- multi-GPU: the path's only exchange, for a C / C++ host ----------------------------------------------------------- */
 /* Independent windows / loop-closure candidates shard one per GPU: one process per GPU, one lvf_ctx each, no data-path collective.  The

@@ -94,6 +94,11 @@ class NavsatBcResult(C.Structure):
                 ("roll", SolverSummary), ("main", SolverSummary)]
 
 
+class FlowOptions(C.Structure):
+    _fields_ = [("win", C.c_int), ("max_level", C.c_int), ("back_win", C.c_int), ("back_max_level", C.c_int), ("max_iter", C.c_int),
+                ("eps", C.c_double), ("min_eig", C.c_double), ("fb_max", C.c_double)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into liblvf_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".hpp"))]
@@ -153,6 +158,16 @@ _SIGS = {
                                          C.POINTER(NavsatBcResult)]),
     "lvf_navsat_fix_chain": (C.c_int, [_VP, C.c_int, c_double_p, c_int_p, c_double_p, c_double_p, C.c_double, C.POINTER(SolverOptions), c_double_p, c_int_p,
                                        C.POINTER(SolverSummary)]),
+    "lvf_image_create": (C.c_int, [_VP, c_u8_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_VP)]),
+    "lvf_image_destroy": (C.c_int, [_VP]),
+    "lvf_image_size": (C.c_int, [_VP, c_int_p, c_int_p, c_int_p]),
+    "lvf_image_download_level": (C.c_int, [_VP, C.c_int, c_int_p, c_int_p, c_u8_p, C.POINTER(C.c_int16)]),
+    "lvf_flow_options_default": (None, [C.POINTER(FlowOptions)]),
+    "lvf_optical_flow": (C.c_int, [_VP, _VP, C.c_int, c_float_p, c_float_p, c_u8_p, c_float_p, C.POINTER(FlowOptions)]),
+    "lvf_stereo_triangulate": (C.c_int, [_VP, _VP, C.POINTER(Camera), C.POINTER(Camera), C.c_double, C.c_int, c_float_p, c_float_p, c_u8_p, c_double_p,
+                                         c_double_p, C.POINTER(FlowOptions)]),
+    "lvf_track_last_frame": (C.c_int, [_VP, _VP, C.POINTER(Camera), C.c_double, c_double_p, C.c_int, c_double_p, c_float_p, C.c_int, C.c_int, c_float_p,
+                                       c_float_p, c_u8_p, c_int_p, C.POINTER(FlowOptions)]),
     "lvf_window_reject_outliers": (C.c_int, [_VP, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int)]),
     "lvf_comm_get_unique_id": (C.c_int, [_VP]),
     "lvf_comm_create": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.POINTER(_VP)]),

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, SolverOptions, SolverSummary, NavsatBcOptions, NavsatBcResult
+from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, SolverOptions, SolverSummary, NavsatBcOptions, NavsatBcResult, FlowOptions
 
 POSES, VEL, BA, BG, INV_DEPTH, W_VISUAL = range(6)
 IMU_BLOCK_SIZES = (7, 3, 3, 3, 7, 3, 3, 3)
@@ -334,6 +334,101 @@ def navsat_optimize(ctx, poses, has_fix, fix_point, cov, bc_opt, optimize_ab):
     """Navsat::Optimize (navsat.cpp:135-156): OptimizeBC(B, C, mode 0), the caller's OptimizeAB (a callable handed the pose array; it stays on
     the host: INTEGRATION.md), then the per-keyframe chain."""
     return navsat_quick_fix(ctx, poses, has_fix, fix_point, cov, bc_opt, between=optimize_ab)
+
+
+class Image:
+    """Device image of the feature tracker: the uint8 pyramid (max_level + 1 levels) with the Scharr pair of every level.  `gray` is a 2-D
+    uint8 array; a view with padded rows (a row stride larger than the width) is uploaded as it is."""
+
+    def __init__(self, ctx, gray, max_level=3):
+        g = np.asarray(gray)
+        if g.dtype != np.uint8 or g.ndim != 2:
+            raise ValueError("Image: a 2-D uint8 array is expected")
+        if g.strides[1] != 1 or g.strides[0] < g.shape[1]:
+            g = np.ascontiguousarray(g)
+        self.ctx, self._keep = ctx, g
+        self.h = C.c_void_p()
+        _chk(ctx.L.lvf_image_create(ctx.h, C.cast(C.c_void_p(g.ctypes.data), _lib.c_u8_p), g.shape[1], g.shape[0], g.strides[0], int(max_level), C.byref(self.h)))
+        self._keep = None
+        self.width, self.height, self.levels = g.shape[1], g.shape[0], int(max_level) + 1
+
+    def size(self):
+        w, h, l = C.c_int32(), C.c_int32(), C.c_int32()
+        _chk(self.ctx.L.lvf_image_size(self.h, C.byref(w), C.byref(h), C.byref(l)))
+        return w.value, h.value, l.value
+
+    def level(self, level):
+        """(gray [h, w] uint8, deriv [h, w, 2] int16) of one pyramid level (debug / tests)"""
+        w, h = C.c_int32(), C.c_int32()
+        _chk(self.ctx.L.lvf_image_download_level(self.h, int(level), C.byref(w), C.byref(h), None, None))
+        g, d = np.empty((h.value, w.value), np.uint8), np.empty((h.value, w.value, 2), np.int16)
+        _chk(self.ctx.L.lvf_image_download_level(self.h, int(level), None, None, g.ctypes.data_as(_lib.c_u8_p), d.ctypes.data_as(C.POINTER(C.c_int16))))
+        return g, d
+
+    def close(self):
+        if self.h:
+            self.ctx.L.lvf_image_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def flow_options(**kw):
+    """lvf_flow_options with the reference's values (utility.cpp:64-79), fields overridden by keyword."""
+    o = FlowOptions()
+    _lib.lib().lvf_flow_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise ValueError(f"flow_options: no field {k}")
+        setattr(o, k, v)
+    return o
+
+
+def _fp(a):
+    return a.ctypes.data_as(_lib.c_float_p)
+
+
+def _u8p(a):
+    return a.ctypes.data_as(_lib.c_u8_p)
+
+
+def _pts(a):
+    return np.array(a, dtype=np.float32, order="C").reshape(-1, 2)
+
+
+def optical_flow(prev_img, next_img, prev_pts, next_init, opt=None):
+    """optical_flow (utility.cpp:55-89): returns next [n, 2] float32, status [n] uint8, fb [n] float32 (forward-backward distance)."""
+    p, q = _pts(prev_pts), _pts(next_init)
+    if p.shape != q.shape:
+        raise ValueError("optical_flow: prev_pts and next_init differ in shape")
+    n = len(p)
+    st, fb = np.zeros(n, np.uint8), np.zeros(n, np.float32)
+    _chk(prev_img.ctx.L.lvf_optical_flow(prev_img.h, next_img.h, n, _fp(p), _fp(q), _u8p(st), _fp(fb), C.byref(opt) if opt is not None else None))
+    return q, st, fb
+
+
+def stereo_triangulate(left, right, cam0, cam1, baseline, kps_left, opt=None):
+    """LocalMap::Triangulate (local_map.cpp:233-269): returns kps_right [n, 2] float32, status [n] (0 lost, 1 accepted, 2 behind camera 0),
+    inv_depth [n], p_robot [n, 3]."""
+    p = _pts(kps_left)
+    n = len(p)
+    q, st, inv, pb = np.zeros((n, 2), np.float32), np.zeros(n, np.uint8), np.zeros(n), np.zeros((n, 3))
+    c0, c1 = make_camera(cam0), make_camera(cam1)
+    _chk(left.ctx.L.lvf_stereo_triangulate(left.h, right.h, C.byref(c0), C.byref(c1), C.c_double(baseline), n, _fp(p), _fp(q), _u8p(st), _dp(inv), _dp(pb),
+                                           C.byref(opt) if opt is not None else None))
+    return q, st, inv, pb
+
+
+def track_last_frame(last, current, cam0, baseline, current_pose, pw, kps_last, remove_moving_points=True, num_features_tracking_bad=20, opt=None):
+    """Frontend::TrackLastFrame's numeric part (frontend.cpp:163-256): returns kps_current [n, 2] float32, cls [n] (0 lost, 1 far, 2 near,
+    3 moving), the number of good points, and the predictions [n, 2] float32."""
+    p, w, pose = _pts(kps_last), _d(pw).reshape(-1, 3), _d(current_pose)
+    n = len(p)
+    if len(w) != n:
+        raise ValueError("track_last_frame: pw and kps_last differ in length")
+    q, pred, cls, good = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32), np.zeros(n, np.uint8), C.c_int32(0)
+    c0 = make_camera(cam0)
+    _chk(last.ctx.L.lvf_track_last_frame(last.h, current.h, C.byref(c0), C.c_double(baseline), _dp(pose), n, _dp(w), _fp(p), int(bool(remove_moving_points)),
+                                         int(num_features_tracking_bad), _fp(q), _fp(pred), _u8p(cls), C.byref(good), C.byref(opt) if opt is not None else None))
+    return q, cls, good.value, pred
 
 
 def prior3_evaluate(ctx, mode, target3, weight, x3):
