@@ -594,6 +594,70 @@ int lvf_track_last_frame(const lvf_image* last, const lvf_image* current, const 
                          const double* pw, const float* kps_last, int remove_moving_points, int num_features_tracking_bad, float* kps_current,
                          float* predictions, uint8_t* cls, int* num_good, const lvf_flow_options* opt);
 
+/* ---- ORB features: Extractor's pyramid, FAST score, orientation and rBRIEF (extractor.cpp), LocalMap::Search (local_map.cpp:313-368) -------- */
+/* The semantics are DECLARED (tests/orb_ref.py): integer arithmetic is bit equal to the restatement, nothing is pinned against
+ * OpenCV.  lvf_orb holds what Extractor holds: the options' derived tables, the rBRIEF pattern and the scale pyramid of the last image. */
+typedef struct lvf_orb lvf_orb;
+typedef struct lvf_orb_options {
+  int num_features;               /* 500 (extractor.h:26) */
+  float scale_factor;             /* 1.2f */
+  int num_levels;                 /* 4; 1 .. 8 */
+  int ini_th_fast, min_th_fast;   /* 14, 7; 1 <= min_th_fast <= ini_th_fast <= 254 */
+  int patch_size, edge_threshold; /* 31, 31: any other value is refused */
+  int max_candidates;             /* 16384: FAST corners (after the per-cell NMS) one level may hold before the quadtree; more is an error, never a
+                                   * silent truncation; 1 .. 65536 */
+} lvf_orb_options;
+#define LVF_ERR_ORB_CAPACITY 5   /* lvf_orb_detect: `capacity` is smaller than the number of keypoints found (see lvf_orb_capacity) */
+#define LVF_ERR_ORB_OVERFLOW 6   /* lvf_orb_detect: a level holds more than max_candidates corners */
+void lvf_orb_options_default(lvf_orb_options* o);
+/* pattern: int8 [256][4] = (x1, y1, x2, y2) of bit 8 j + k of byte j, every |coordinate| <= 13; NULL: the built-in table (a documented
+ * integer generator, tests/orb_ref.py builtin_pattern — NOT OpenCV's learned bit_pattern_31_; INTEGRATION.md tells how to pass that one). */
+int lvf_orb_create(lvf_ctx* ctx, const lvf_orb_options* opt, const int8_t* pattern, lvf_orb** out);
+int lvf_orb_destroy(lvf_orb* orb);
+int lvf_orb_pattern(const lvf_orb* orb, int8_t* pattern);                                  /* the table in use, [256][4] */
+/* scale_factor_per_levels_[level] (float32 running product), num_desired_features_[level] (extractor.cpp:14-45); pointers may be NULL */
+int lvf_orb_level_info(const lvf_orb* orb, int level, float* scale, int* num_desired);
+/* Extractor::ComputePyramid (extractor.cpp:455-477) of level 0 of an lvf_image (the frame's image is uploaded once, for tracking and here),
+ * device to device: level L = fixed-point bilinear resize of level L - 1 to (cvRound(float(w) / scale_L), cvRound(float(h) / scale_L)); then
+ * the FAST-9/16 corner score of every level in one launch (uint8; 0 = no corner at min_th_fast; pixels closer than 31 to an edge are 0).
+ * The pyramid stays in `orb` until the next call, as Extractor::image_pyramid_ does. */
+int lvf_orb_set_image(lvf_orb* orb, const lvf_image* img);
+/* The exact upper bound of what lvf_orb_detect can return for a width x height image: per level with a usable area, the quadtree ends with at
+ * most max(num_desired + 2, 4 * initial nodes) nodes (tests/orb_ref.py capacity). */
+int lvf_orb_capacity(const lvf_orb* orb, int width, int height, int* max_keypoints);
+/* Extractor::Detect (extractor.cpp:368-502) in one launch chain with one download at its end: lvf_orb_set_image, then per 30 x 30 cell the
+ * non-maximum suppression with the ini -> min threshold fallback (:372-429; one workgroup per cell, every level in one launch), the quadtree
+ * (DistributeQuadTree :160-366, one workgroup per level; count ties broken by smaller (UL.y, UL.x), the best point of a node = maximum response,
+ * ties to the smallest (y, x)) and ICAngle.  Out: *n keypoints in level-major order, each level sorted by (y, x): level_count [num_levels],
+ * pt [n][2] = (level pixel) * scale_level, octave [n], angle [n], response [n] = the FAST score, size [n] = float(int(31 * scale_level)).
+ * A level whose usable area (cols - 56) x (rows - 56) is smaller than one 30 x 30 cell has no keypoints.  LVF_ERR_ORB_CAPACITY when more than
+ * `capacity` keypoints were found (*n = that number, the arrays untouched), LVF_ERR_ORB_OVERFLOW when a level exceeds max_candidates; the
+ * object stays usable after either.  Image sides up to 4096. */
+int lvf_orb_detect(lvf_orb* orb, const lvf_image* img, int capacity, int* n, int32_t* level_count, float* pt, int32_t* octave, float* angle, float* response,
+                   float* size);
+/* Keypoints are (pt [n][2] in level-0 pixels as Extractor::Detect returns them, octave [n]); their level coordinates rint(pt / scale_octave)
+ * must lie at least 19 pixels inside the level (the reference's own keypoints lie 31 inside), else LVF_ERR_INVALID.  n == 0 returns at once.
+ * lvf_orb_orientation: ICAngle (extractor.cpp:66-93) with exact integer moments, one wavefront per keypoint; angle [n] = atan2(m01, m10) in
+ * degrees in [0, 360), evaluated in fp64 and rounded to float (cv::fastAtan2's polynomial is not reproduced).
+ * lvf_orb_compute: Extractor::Compute (extractor.cpp:504-530) as ORB-SLAM2's computeDescriptors has it: the levels named by `octave` are
+ * blurred (7 x 7, sigma 2, integer, reflect-101) and rBRIEF is read at the LEVEL coordinates with the pattern rotated by `angle` (an input,
+ * as the reference passes its keypoints back in); desc [n][32]. */
+int lvf_orb_orientation(lvf_orb* orb, int n, const float* pt, const int32_t* octave, float* angle);
+int lvf_orb_compute(lvf_orb* orb, int n, const float* pt, const int32_t* octave, const float* angle, uint8_t* desc);
+/* Debug / tests: one level, tightly packed [h][w] each (any pointer may be NULL); `blurred` blurs the level if it has not been yet. */
+int lvf_orb_download_level(lvf_orb* orb, int level, int* width, int* height, uint8_t* gray, uint8_t* blurred, uint8_t* score);
+/* The numeric part of LocalMap::Search (local_map.cpp:313-368), one wavefront per current feature.  last_*: the features of the last
+ * keyframe; cur_pw [n_cur][3]: the current features' landmark positions.  Per current feature with skip[i] == 0 (skip may be NULL):
+ * pc = World2Sensor(pw, last_pose), none if pc.z < 0; p = float(Sensor2Pixel(pc)); candidates = last features of levels octave and octave + 1
+ * (< num_levels) with |angle_last - angle| < 15 (no wrap-around, as the reference) and |p - pt_last| < 31 * scale_factors_[level] (the
+ * fp64 running product of the float scale_factor, local_map.h:26-31); Hamming 2-NN, ties to the lower (level, index); accepted iff >= 2
+ * candidates, best < 50 and float(best) < 0.8f * float(second).  match [n_cur] = index into last_* or -1; best / second [n_cur] (may be
+ * NULL) = the two distances, -1 where there is no such candidate.  The keyframe loop and the map insertion stay with the caller. */
+int lvf_orb_search(lvf_ctx* ctx, const lvf_orb_options* opt, const lvf_camera* cam0, const double* last_pose, int n_last, const float* last_pt,
+                   const int32_t* last_octave, const float* last_angle, const uint8_t* last_desc, int n_cur, const double* cur_pw,
+                   const int32_t* cur_octave, const float* cur_angle, const uint8_t* cur_desc, const uint8_t* skip, int32_t* match, int32_t* best,
+                   int32_t* second);
+
 /* ---- multi-GPU: the path's only exchange, for a C / C++ host ----------------------------------------------------------- */
 /* Independent windows / loop-closure candidates shard one per GPU: one process per GPU, one lvf_ctx each, no data-path collective.  The
  * single exchange is an all-gather of fixed-size records (score, relative_o_c[7], candidate id: relocator.cpp:196-206) over RCCL / xGMI.

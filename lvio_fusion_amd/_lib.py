@@ -99,6 +99,11 @@ class FlowOptions(C.Structure):
                 ("eps", C.c_double), ("min_eig", C.c_double), ("fb_max", C.c_double)]
 
 
+class OrbOptions(C.Structure):
+    _fields_ = [("num_features", C.c_int), ("scale_factor", C.c_float), ("num_levels", C.c_int), ("ini_th_fast", C.c_int), ("min_th_fast", C.c_int),
+                ("patch_size", C.c_int), ("edge_threshold", C.c_int), ("max_candidates", C.c_int)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into liblvf_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".hpp"))]
@@ -168,6 +173,19 @@ _SIGS = {
                                          c_double_p, C.POINTER(FlowOptions)]),
     "lvf_track_last_frame": (C.c_int, [_VP, _VP, C.POINTER(Camera), C.c_double, c_double_p, C.c_int, c_double_p, c_float_p, C.c_int, C.c_int, c_float_p,
                                        c_float_p, c_u8_p, c_int_p, C.POINTER(FlowOptions)]),
+    "lvf_orb_options_default": (None, [C.POINTER(OrbOptions)]),
+    "lvf_orb_create": (C.c_int, [_VP, C.POINTER(OrbOptions), C.POINTER(C.c_int8), C.POINTER(_VP)]),
+    "lvf_orb_destroy": (C.c_int, [_VP]),
+    "lvf_orb_pattern": (C.c_int, [_VP, C.POINTER(C.c_int8)]),
+    "lvf_orb_level_info": (C.c_int, [_VP, C.c_int, c_float_p, c_int_p]),
+    "lvf_orb_capacity": (C.c_int, [_VP, C.c_int, C.c_int, c_int_p]),
+    "lvf_orb_set_image": (C.c_int, [_VP, _VP]),
+    "lvf_orb_detect": (C.c_int, [_VP, _VP, C.c_int, c_int_p, c_int_p, c_float_p, c_int_p, c_float_p, c_float_p, c_float_p]),
+    "lvf_orb_orientation": (C.c_int, [_VP, C.c_int, c_float_p, c_int_p, c_float_p]),
+    "lvf_orb_compute": (C.c_int, [_VP, C.c_int, c_float_p, c_int_p, c_float_p, c_u8_p]),
+    "lvf_orb_download_level": (C.c_int, [_VP, C.c_int, c_int_p, c_int_p, c_u8_p, c_u8_p, c_u8_p]),
+    "lvf_orb_search": (C.c_int, [_VP, C.POINTER(OrbOptions), C.POINTER(Camera), c_double_p, C.c_int, c_float_p, c_int_p, c_float_p, c_u8_p, C.c_int, c_double_p,
+                                 c_int_p, c_float_p, c_u8_p, c_u8_p, c_int_p, c_int_p, c_int_p]),
     "lvf_window_reject_outliers": (C.c_int, [_VP, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int)]),
     "lvf_comm_get_unique_id": (C.c_int, [_VP]),
     "lvf_comm_create": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.POINTER(_VP)]),

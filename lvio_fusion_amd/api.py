@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, SolverOptions, SolverSummary, NavsatBcOptions, NavsatBcResult, FlowOptions
+from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, SolverOptions, SolverSummary, NavsatBcOptions, NavsatBcResult, FlowOptions, OrbOptions
 
 POSES, VEL, BA, BG, INV_DEPTH, W_VISUAL = range(6)
 IMU_BLOCK_SIZES = (7, 3, 3, 3, 7, 3, 3, 3)
@@ -429,6 +429,111 @@ def track_last_frame(last, current, cam0, baseline, current_pose, pw, kps_last, 
     _chk(last.ctx.L.lvf_track_last_frame(last.h, current.h, C.byref(c0), C.c_double(baseline), _dp(pose), n, _dp(w), _fp(p), int(bool(remove_moving_points)),
                                          int(num_features_tracking_bad), _fp(q), _fp(pred), _u8p(cls), C.byref(good), C.byref(opt) if opt is not None else None))
     return q, cls, good.value, pred
+
+
+def orb_options(**kw):
+    """lvf_orb_options with the reference's values (extractor.h:26), fields overridden by keyword."""
+    o = OrbOptions()
+    _lib.lib().lvf_orb_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise ValueError(f"orb_options: no field {k}")
+        setattr(o, k, v)
+    return o
+
+
+ERR_ORB_CAPACITY, ERR_ORB_OVERFLOW = 5, 6
+
+
+class Orb:
+    """Extractor on the device: the scale pyramid of the last image, FAST / quadtree detection, ICAngle and rBRIEF.  `pattern`:
+    int8 [256, 4] = (x1, y1, x2, y2) per descriptor bit, None for the built-in table."""
+
+    def __init__(self, ctx, opt=None, pattern=None):
+        self.ctx, self.opt = ctx, opt if opt is not None else orb_options()
+        self.h = C.c_void_p()
+        pat = None
+        if pattern is not None:
+            pat = np.ascontiguousarray(pattern, dtype=np.int8)
+            if pat.shape != (256, 4):
+                raise ValueError("Orb: the pattern is int8 [256, 4]")
+        _chk(ctx.L.lvf_orb_create(ctx.h, C.byref(self.opt), pat.ctypes.data_as(C.POINTER(C.c_int8)) if pat is not None else None, C.byref(self.h)))
+
+    def pattern(self):
+        p = np.zeros((256, 4), np.int8)
+        _chk(self.ctx.L.lvf_orb_pattern(self.h, p.ctypes.data_as(C.POINTER(C.c_int8))))
+        return p
+
+    def level_info(self, level):
+        """(scale_factor_per_levels_[level] as float32, num_desired_features_[level])"""
+        s, n = C.c_float(), C.c_int32()
+        _chk(self.ctx.L.lvf_orb_level_info(self.h, int(level), C.byref(s), C.byref(n)))
+        return np.float32(s.value), n.value
+
+    def capacity(self, width, height):
+        n = C.c_int32()
+        _chk(self.ctx.L.lvf_orb_capacity(self.h, int(width), int(height), C.byref(n)))
+        return n.value
+
+    def set_image(self, img):
+        """pyramid and FAST score maps of level 0 of an api.Image, without detection (for compute / orientation of tracked points)"""
+        _chk(self.ctx.L.lvf_orb_set_image(self.h, img.h))
+
+    def detect(self, img, capacity=None):
+        """Extractor::Detect: dict(level_count, pt [n, 2] float32, octave, angle, response, size), level-major, each level sorted by (y, x)"""
+        cap = self.capacity(img.width, img.height) if capacity is None else int(capacity)
+        n, lc = C.c_int32(), np.zeros(self.opt.num_levels, np.int32)
+        pt, octave = np.zeros((cap, 2), np.float32), np.zeros(cap, np.int32)
+        angle, resp, size = np.zeros(cap, np.float32), np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        _chk(self.ctx.L.lvf_orb_detect(self.h, img.h, cap, C.byref(n), _ip(lc), _fp(pt), _ip(octave), _fp(angle), _fp(resp), _fp(size)))
+        k = n.value
+        return dict(level_count=lc, pt=pt[:k].copy(), octave=octave[:k].copy(), angle=angle[:k].copy(), response=resp[:k].copy(), size=size[:k].copy())
+
+    def orientation(self, pt, octave):
+        p, o = _pts(pt), _i(octave)
+        a = np.zeros(len(p), np.float32)
+        _chk(self.ctx.L.lvf_orb_orientation(self.h, len(p), _fp(p), _ip(o), _fp(a)))
+        return a
+
+    def compute(self, pt, octave, angle):
+        """Extractor::Compute: descriptors [n, 32] uint8 of keypoints of the image of the last detect / set_image"""
+        p, o, a = _pts(pt), _i(octave), _f(angle)
+        d = np.zeros((len(p), 32), np.uint8)
+        _chk(self.ctx.L.lvf_orb_compute(self.h, len(p), _fp(p), _ip(o), _fp(a), _u8p(d)))
+        return d
+
+    def level(self, level):
+        """(gray, blurred, score) [h, w] uint8 of one pyramid level (debug / tests)"""
+        w, h = C.c_int32(), C.c_int32()
+        _chk(self.ctx.L.lvf_orb_download_level(self.h, int(level), C.byref(w), C.byref(h), None, None, None))
+        g, b, s = (np.empty((h.value, w.value), np.uint8) for _ in range(3))
+        _chk(self.ctx.L.lvf_orb_download_level(self.h, int(level), None, None, _u8p(g), _u8p(b), _u8p(s)))
+        return g, b, s
+
+    def close(self):
+        if self.h:
+            self.ctx.L.lvf_orb_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def orb_search(ctx, cam0, last_pose, last_pt, last_octave, last_angle, last_desc, cur_pw, cur_octave, cur_angle, cur_desc, skip=None, opt=None):
+    """The numeric part of LocalMap::Search (local_map.cpp:313-368): returns match [n_cur] (index into the last features, -1 where none),
+    best, second [n_cur] (the two Hamming distances, -1 where there is no such candidate)."""
+    lp, lo, la = _pts(last_pt), _i(last_octave), _f(last_angle)
+    ld = np.ascontiguousarray(last_desc, dtype=np.uint8).reshape(-1, 32)
+    pw, co, ca = _d(cur_pw).reshape(-1, 3), _i(cur_octave), _f(cur_angle)
+    cd = np.ascontiguousarray(cur_desc, dtype=np.uint8).reshape(-1, 32)
+    if not (len(lp) == len(lo) == len(la) == len(ld)) or not (len(pw) == len(co) == len(ca) == len(cd)):
+        raise ValueError("orb_search: feature arrays differ in length")
+    n = len(pw)
+    sk = np.ascontiguousarray(skip, dtype=np.uint8) if skip is not None else None
+    if sk is not None and len(sk) != n:
+        raise ValueError("orb_search: skip and the current features differ in length")
+    m, b, s2 = np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    c0 = make_camera(cam0)
+    _chk(ctx.L.lvf_orb_search(ctx.h, C.byref(opt) if opt is not None else None, C.byref(c0), _dp(_d(last_pose)), len(lp), _fp(lp), _ip(lo), _fp(la), _u8p(ld), n,
+                              _dp(pw), _ip(co), _fp(ca), _u8p(cd), _u8p(sk) if sk is not None else None, _ip(m), _ip(b), _ip(s2)))
+    return m, b, s2
 
 
 def prior3_evaluate(ctx, mode, target3, weight, x3):

@@ -407,6 +407,11 @@ inline int grid_of(size_t n) { return (int)((n + kT - 1) / kT); }
 
 }  // namespace
 
+const uint8_t* lvf::image_level0(const lvf_image* img, int* width, int* height, lvf_ctx** ctx) {
+  *width = img->w; *height = img->h; *ctx = img->ctx;
+  return img->gray.p;
+}
+
 extern "C" {
 
 int lvf_image_create(lvf_ctx* ctx, const uint8_t* data, int width, int height, size_t stride, int max_level, lvf_image** out) {

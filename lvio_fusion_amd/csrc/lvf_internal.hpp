@@ -569,6 +569,8 @@ int device_scan1_on(lvf_ctx* ctx, hipStream_t q, int lane, const int* in, int ca
 int side_stream(lvf_ctx* ctx, hipStream_t* out);
 // every extern "C" entry point starts here: selects the context's device and allocator for the calling thread
 int enter(lvf_ctx* ctx);
+// level 0 of an lvf_image (klt_kernels.hip) for the ORB pyramid (orb_kernels.hip): tightly packed rows, device memory of img's context
+const uint8_t* image_level0(const lvf_image* img, int* width, int* height, lvf_ctx** ctx);
 int device_exclusive_scan_i32(lvf_ctx* ctx, const int* in, int n, int* out);
 int compact_points(lvf_ctx* ctx, const float4* pts, int n, const int* flags_dev, lvf_cloud** out);
 // the PCL tail of the feature extraction with the counts on the device, and what reads its state back (cloud_kernels.hip)
