@@ -594,6 +594,31 @@ int lvf_track_last_frame(const lvf_image* last, const lvf_image* current, const 
                          const double* pw, const float* kps_last, int remove_moving_points, int num_features_tracking_bad, float* kps_current,
                          float* predictions, uint8_t* cls, int* num_good, const lvf_flow_options* opt);
 
+/* ---- image undistortion: the cv::undistort of Estimator::InputImage (estimator.cpp:178-179) with Camera's K, D (camera.h:22-26, 81-89) ------ */
+/* The semantics are DECLARED (tests/undistort_ref.py): cv::undistort's structure — initUndistortRectifyMap with R = I and the new
+ * camera matrix = K into a fixed-point map, then remap(INTER_LINEAR, BORDER_CONSTANT 0) — with the map evaluated directly per pixel in fp64
+ * and exact integer weights; the device is bit equal to the restatement, nothing is pinned against OpenCV.
+ * lvf_distortion: D = (k1, k2, p1, p2, 0) as camera.h:89 builds it (k3 and the rational terms are zero in the reference). */
+typedef struct lvf_distortion { double k1, k2, p1, p2; } lvf_distortion;
+/* lvf_undistort: what a Camera's K, D and the image size become: the map, built ONCE per camera and size on the host and kept on the device,
+ * and a device staging buffer for the raw pixels (no allocation per frame beyond what lvf_image_create does).  Of `cam` only fx, fy, cx, cy
+ * are read.  d == NULL: zero distortion (the output equals the input bit for bit).  LVF_ERR_INVALID: fx or fy <= 0, a non-finite intrinsic
+ * or coefficient, a side outside [1, 4096] (the limit lvf_orb_detect states). */
+typedef struct lvf_undistort lvf_undistort;
+int lvf_undistort_create(lvf_ctx* ctx, const lvf_camera* cam, const lvf_distortion* d, int width, int height, lvf_undistort** out);
+int lvf_undistort_destroy(lvf_undistort* u);
+/* Debug / tests: the map in the declared layout: xy [h][w][2] = the integer source pixel (x, y) of the top-left tap, saturated to int16;
+ * frac [h][w] = b * 32 + a, the 5-bit fractions along y and x (either pointer may be NULL). */
+int lvf_undistort_download_map(const lvf_undistort* u, int16_t* xy, uint16_t* frac);
+/* lvf_image_create of the undistorted image: the raw pixels are uploaded once, the remap writes level 0 of the new lvf_image on the device and
+ * the pyramid / derivative chain of lvf_image_create follows.  An ordinary lvf_image comes back: every consumer takes it unchanged.  width
+ * and height must be the map's.  raw: as `data` of lvf_image_create; it may be overwritten as soon as the call returns. */
+int lvf_image_create_undistorted(lvf_undistort* u, const uint8_t* raw, int width, int height, size_t stride, int max_level, lvf_image** out);
+/* Estimator::InputImage's two cv::undistort calls in one: both uploads, both remaps and both pyramid / derivative chains are queued on the
+ * context's stream with ONE wait at the end.  u0 and u1 (one context, one size; they may be the same object) are the two cameras' maps. */
+int lvf_image_pair_create_undistorted(lvf_undistort* u0, lvf_undistort* u1, const uint8_t* raw0, const uint8_t* raw1, int width, int height,
+                                      size_t stride0, size_t stride1, int max_level, lvf_image** out0, lvf_image** out1);
+
 /* ---- ORB features: Extractor's pyramid, FAST score, orientation and rBRIEF (extractor.cpp), LocalMap::Search (local_map.cpp:313-368) -------- */
 /* The semantics are DECLARED (tests/orb_ref.py): integer arithmetic is bit equal to the restatement, nothing is pinned against
  * OpenCV.  lvf_orb holds what Extractor holds: the options' derived tables, the rBRIEF pattern and the scale pyramid of the last image. */

@@ -99,6 +99,10 @@ class FlowOptions(C.Structure):
                 ("eps", C.c_double), ("min_eig", C.c_double), ("fb_max", C.c_double)]
 
 
+class Distortion(C.Structure):
+    _fields_ = [("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double)]
+
+
 class OrbOptions(C.Structure):
     _fields_ = [("num_features", C.c_int), ("scale_factor", C.c_float), ("num_levels", C.c_int), ("ini_th_fast", C.c_int), ("min_th_fast", C.c_int),
                 ("patch_size", C.c_int), ("edge_threshold", C.c_int), ("max_candidates", C.c_int)]
@@ -173,6 +177,11 @@ _SIGS = {
                                          c_double_p, C.POINTER(FlowOptions)]),
     "lvf_track_last_frame": (C.c_int, [_VP, _VP, C.POINTER(Camera), C.c_double, c_double_p, C.c_int, c_double_p, c_float_p, C.c_int, C.c_int, c_float_p,
                                        c_float_p, c_u8_p, c_int_p, C.POINTER(FlowOptions)]),
+    "lvf_undistort_create": (C.c_int, [_VP, C.POINTER(Camera), C.POINTER(Distortion), C.c_int, C.c_int, C.POINTER(_VP)]),
+    "lvf_undistort_destroy": (C.c_int, [_VP]),
+    "lvf_undistort_download_map": (C.c_int, [_VP, C.POINTER(C.c_int16), C.POINTER(C.c_uint16)]),
+    "lvf_image_create_undistorted": (C.c_int, [_VP, c_u8_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_VP)]),
+    "lvf_image_pair_create_undistorted": (C.c_int, [_VP, _VP, c_u8_p, c_u8_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(_VP), C.POINTER(_VP)]),
     "lvf_orb_options_default": (None, [C.POINTER(OrbOptions)]),
     "lvf_orb_create": (C.c_int, [_VP, C.POINTER(OrbOptions), C.POINTER(C.c_int8), C.POINTER(_VP)]),
     "lvf_orb_destroy": (C.c_int, [_VP]),

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, SolverOptions, SolverSummary, NavsatBcOptions, NavsatBcResult, FlowOptions, OrbOptions
+from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, SolverOptions, SolverSummary, NavsatBcOptions, NavsatBcResult, FlowOptions, OrbOptions, Distortion
 
 POSES, VEL, BA, BG, INV_DEPTH, W_VISUAL = range(6)
 IMU_BLOCK_SIZES = (7, 3, 3, 3, 7, 3, 3, 3)
@@ -336,21 +336,35 @@ def navsat_optimize(ctx, poses, has_fix, fix_point, cov, bc_opt, optimize_ab):
     return navsat_quick_fix(ctx, poses, has_fix, fix_point, cov, bc_opt, between=optimize_ab)
 
 
+def _gray(gray, who):
+    """a 2-D uint8 array whose rows are contiguous (a padded row stride is kept)"""
+    g = np.asarray(gray)
+    if g.dtype != np.uint8 or g.ndim != 2:
+        raise ValueError(f"{who}: a 2-D uint8 array is expected")
+    if g.strides[1] != 1 or g.strides[0] < g.shape[1]:
+        g = np.ascontiguousarray(g)
+    return g
+
+
 class Image:
     """Device image of the feature tracker: the uint8 pyramid (max_level + 1 levels) with the Scharr pair of every level.  `gray` is a 2-D
     uint8 array; a view with padded rows (a row stride larger than the width) is uploaded as it is."""
 
     def __init__(self, ctx, gray, max_level=3):
-        g = np.asarray(gray)
-        if g.dtype != np.uint8 or g.ndim != 2:
-            raise ValueError("Image: a 2-D uint8 array is expected")
-        if g.strides[1] != 1 or g.strides[0] < g.shape[1]:
-            g = np.ascontiguousarray(g)
+        g = _gray(gray, "Image")
         self.ctx, self._keep = ctx, g
         self.h = C.c_void_p()
         _chk(ctx.L.lvf_image_create(ctx.h, C.cast(C.c_void_p(g.ctypes.data), _lib.c_u8_p), g.shape[1], g.shape[0], g.strides[0], int(max_level), C.byref(self.h)))
         self._keep = None
         self.width, self.height, self.levels = g.shape[1], g.shape[0], int(max_level) + 1
+
+    @classmethod
+    def _adopt(cls, ctx, h, width, height, max_level):
+        """an lvf_image the library has already built (Undistort.image / pair)"""
+        im = cls.__new__(cls)
+        im.ctx, im._keep, im.h = ctx, None, h
+        im.width, im.height, im.levels = width, height, int(max_level) + 1
+        return im
 
     def size(self):
         w, h, l = C.c_int32(), C.c_int32(), C.c_int32()
@@ -368,6 +382,49 @@ class Image:
     def close(self):
         if self.h:
             self.ctx.L.lvf_image_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class Undistort:
+    """cv::undistort of Estimator::InputImage on the device (DESIGN 15): the fixed-point map of one camera (cam: fx, fy, cx, cy; dist =
+    (k1, k2, p1, p2), None for zero distortion) and image size, built once.  image() / pair() return ordinary api.Image objects."""
+
+    def __init__(self, ctx, cam, dist, width, height):
+        self.ctx, self.width, self.height = ctx, int(width), int(height)
+        k = Camera()
+        k.fx, k.fy, k.cx, k.cy = cam["fx"], cam["fy"], cam["cx"], cam["cy"]
+        k.extrinsic[3] = 1.0
+        d = Distortion(*[float(c) for c in dist]) if dist is not None else None
+        self.h = C.c_void_p()
+        _chk(ctx.L.lvf_undistort_create(ctx.h, C.byref(k), C.byref(d) if d is not None else None, self.width, self.height, C.byref(self.h)))
+
+    def map(self):
+        """(xy [h, w, 2] int16 = top-left source tap, frac [h, w] uint16 = b * 32 + a) (debug / tests)"""
+        xy, frac = np.empty((self.height, self.width, 2), np.int16), np.empty((self.height, self.width), np.uint16)
+        _chk(self.ctx.L.lvf_undistort_download_map(self.h, xy.ctypes.data_as(C.POINTER(C.c_int16)), frac.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return xy, frac
+
+    def image(self, raw, max_level=3):
+        """api.Image of the undistorted `raw` (2-D uint8; a padded row stride is uploaded as it is)"""
+        g = _gray(raw, "Undistort.image")
+        h = C.c_void_p()
+        _chk(self.ctx.L.lvf_image_create_undistorted(self.h, C.cast(C.c_void_p(g.ctypes.data), _lib.c_u8_p), g.shape[1], g.shape[0], g.strides[0], int(max_level),
+                                                     C.byref(h)))
+        return Image._adopt(self.ctx, h, g.shape[1], g.shape[0], max_level)
+
+    def pair(self, other, raw0, raw1, max_level=3):
+        """Estimator::InputImage: (api.Image, api.Image) of raw0 through this map and raw1 through `other`'s, one wait for both"""
+        g0, g1 = _gray(raw0, "Undistort.pair"), _gray(raw1, "Undistort.pair")
+        if g0.shape != g1.shape:
+            raise ValueError("Undistort.pair: the two images differ in size")
+        h0, h1 = C.c_void_p(), C.c_void_p()
+        _chk(self.ctx.L.lvf_image_pair_create_undistorted(self.h, other.h, C.cast(C.c_void_p(g0.ctypes.data), _lib.c_u8_p), C.cast(C.c_void_p(g1.ctypes.data), _lib.c_u8_p),
+                                                          g0.shape[1], g0.shape[0], g0.strides[0], g1.strides[0], int(max_level), C.byref(h0), C.byref(h1)))
+        return Image._adopt(self.ctx, h0, g0.shape[1], g0.shape[0], max_level), Image._adopt(other.ctx, h1, g0.shape[1], g0.shape[0], max_level)
+
+    def close(self):
+        if self.h:
+            self.ctx.L.lvf_undistort_destroy(self.h)
             self.h = C.c_void_p()
 
 

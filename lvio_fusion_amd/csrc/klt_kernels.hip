@@ -34,6 +34,7 @@ struct lvf_image {
   DevBuf<uint8_t> gray;
   DevBuf<short2> deriv;              // (Sx, Sy) interleaved: one 4-byte load fetches the pair
   DevBuf<KltLevel> table;            // the level table the kernels read (wave-uniform loads)
+  KltLevel host_table[kMaxLevels] = {};      // what `table` is copied from (lives as long as the copy may be in flight)
 };
 
 namespace {
@@ -412,15 +413,9 @@ const uint8_t* lvf::image_level0(const lvf_image* img, int* width, int* height, 
   return img->gray.p;
 }
 
-extern "C" {
-
-int lvf_image_create(lvf_ctx* ctx, const uint8_t* data, int width, int height, size_t stride, int max_level, lvf_image** out) {
-  LVF_REQUIRE(ctx && data && out, "lvf_image_create: null argument");
-  LVF_REQUIRE(width >= 1 && height >= 1 && (size_t)width * height <= ((size_t)1 << 28), "lvf_image_create: bad image size %d x %d", width, height);
-  LVF_REQUIRE(stride >= (size_t)width, "lvf_image_create: row stride %zu is smaller than the width %d", stride, width);
-  LVF_REQUIRE(max_level >= 0 && max_level < kMaxLevels, "lvf_image_create: max_level must be in [0, %d]", kMaxLevels - 1);
-  LVF_TRY(lvf::enter(ctx));
-  hipStream_t s = ctx->stream;
+int lvf::image_begin(const char* who, lvf_ctx* ctx, int width, int height, int max_level, lvf_image** out, uint8_t** level0) {
+  LVF_REQUIRE(width >= 1 && height >= 1 && (size_t)width * height <= ((size_t)1 << 28), "%s: bad image size %d x %d", who, width, height);
+  LVF_REQUIRE(max_level >= 0 && max_level < kMaxLevels, "%s: max_level must be in [0, %d]", who, kMaxLevels - 1);
   std::unique_ptr<lvf_image> im(new lvf_image());
   im->ctx = ctx; im->w = width; im->h = height; im->levels = max_level + 1;
   size_t total = 0;
@@ -430,12 +425,17 @@ int lvf_image_create(lvf_ctx* ctx, const uint8_t* data, int width, int height, s
   }
   LVF_TRY(im->gray.alloc(total));
   LVF_TRY(im->deriv.alloc(total));
-  KltLevel tab[kMaxLevels] = {};
-  for (int L = 0; L <= max_level; ++L) tab[L] = KltLevel{im->gray.p + im->off[L], im->deriv.p + im->off[L], im->lw[L], im->lh[L]};
+  for (int L = 0; L <= max_level; ++L) im->host_table[L] = KltLevel{im->gray.p + im->off[L], im->deriv.p + im->off[L], im->lw[L], im->lh[L]};
   LVF_TRY(im->table.alloc(kMaxLevels));
-  LVF_HIP(hipMemcpyAsync(im->table.p, tab, sizeof(tab), hipMemcpyHostToDevice, s));
-  LVF_HIP(hipMemcpy2DAsync(im->gray.p, (size_t)width, data, stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice, s));
-  for (int L = 0; L <= max_level; ++L) {
+  LVF_HIP(hipMemcpyAsync(im->table.p, im->host_table, sizeof(im->host_table), hipMemcpyHostToDevice, ctx->stream));
+  *level0 = im->gray.p;
+  *out = im.release();
+  return LVF_OK;
+}
+
+int lvf::image_chain(lvf_image* im) {
+  hipStream_t s = im->ctx->stream;
+  for (int L = 0; L < im->levels; ++L) {
     const size_t npx = (size_t)im->lw[L] * im->lh[L];
     if (L > 0)
       hipLaunchKernelGGL(k_klt_pyr_down, dim3(grid_of(npx)), dim3(kT), 0, s, im->gray.p + im->off[L - 1], im->lw[L - 1], im->lh[L - 1], im->gray.p + im->off[L],
@@ -443,7 +443,27 @@ int lvf_image_create(lvf_ctx* ctx, const uint8_t* data, int width, int height, s
     hipLaunchKernelGGL(k_klt_scharr, dim3(grid_of(npx)), dim3(kT), 0, s, im->gray.p + im->off[L], im->lw[L], im->lh[L], im->deriv.p + im->off[L]);
   }
   LVF_HIP(hipGetLastError());
-  LVF_HIP(hipStreamSynchronize(s));      // the caller's pixel buffer (and the table above) may go on return
+  return LVF_OK;
+}
+
+extern "C" {
+
+int lvf_image_create(lvf_ctx* ctx, const uint8_t* data, int width, int height, size_t stride, int max_level, lvf_image** out) {
+  LVF_REQUIRE(ctx && data && out, "lvf_image_create: null argument");
+  LVF_REQUIRE(width >= 1 && height >= 1 && (size_t)width * height <= ((size_t)1 << 28), "lvf_image_create: bad image size %d x %d", width, height);
+  LVF_REQUIRE(stride >= (size_t)width, "lvf_image_create: row stride %zu is smaller than the width %d", stride, width);
+  LVF_REQUIRE(max_level >= 0 && max_level < kMaxLevels, "lvf_image_create: max_level must be in [0, %d]", kMaxLevels - 1);
+  LVF_TRY(lvf::enter(ctx));
+  hipStream_t s = ctx->stream;
+  lvf_image* raw_im = nullptr;
+  uint8_t* level0 = nullptr;
+  LVF_TRY(lvf::image_begin("lvf_image_create", ctx, width, height, max_level, &raw_im, &level0));
+  std::unique_ptr<lvf_image> im(raw_im);
+  lvf::StreamWaitGuard wait(s);            // (an error below: the queued copies end before the image goes)
+  LVF_HIP(hipMemcpy2DAsync(level0, (size_t)width, data, stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice, s));
+  LVF_TRY(lvf::image_chain(im.get()));
+  LVF_HIP(hipStreamSynchronize(s));      // the caller's pixel buffer may go on return
+  wait.dismiss();
   *out = im.release();
   return LVF_OK;
 }

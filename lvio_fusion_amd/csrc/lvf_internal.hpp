@@ -571,6 +571,12 @@ int side_stream(lvf_ctx* ctx, hipStream_t* out);
 int enter(lvf_ctx* ctx);
 // level 0 of an lvf_image (klt_kernels.hip) for the ORB pyramid (orb_kernels.hip): tightly packed rows, device memory of img's context
 const uint8_t* image_level0(const lvf_image* img, int* width, int* height, lvf_ctx** ctx);
+// lvf_image_create in its two halves (klt_kernels.hip), for whoever writes level 0 on the device (undistort_kernels.hip).  image_begin checks
+// the size and max_level, allocates the image and queues its level table; *level0 = width * height bytes, tightly packed rows.  image_chain
+// queues the pyramid / derivative launches behind whatever filled level 0.  Neither waits: the caller waits for ctx->stream ONCE before it
+// returns or destroys the image (the level table is copied from the image object itself).
+int image_begin(const char* who, lvf_ctx* ctx, int width, int height, int max_level, lvf_image** out, uint8_t** level0);
+int image_chain(lvf_image* img);
 int device_exclusive_scan_i32(lvf_ctx* ctx, const int* in, int n, int* out);
 int compact_points(lvf_ctx* ctx, const float4* pts, int n, const int* flags_dev, lvf_cloud** out);
 // the PCL tail of the feature extraction with the counts on the device, and what reads its state back (cloud_kernels.hip)
