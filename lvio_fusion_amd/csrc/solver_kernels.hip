@@ -1876,7 +1876,9 @@ static int launch_schur(hipStream_t q, int n_lm, int dp, int ldE, const double* 
 // Right-looking, block 64, ONE launch per block step (k_chol_step): every workgroup of the step's column re-factors the 64x64 diagonal
 // block (redundantly: all of them run it concurrently, which removes a dependent launch) while its own panel block rides along in the
 // same sweep, and the trailing update of the previous step is folded into the same launch (chol_step_body).
-// The sequential critical path is ~64 x (rsqrt + broadcast) per block; everything else is wide.
+// The sequential critical path is ~64 x (rsqrt + broadcast) per block; everything else is wide.  Two sweeps over the 64 pivots exist: the
+// 16-pivot sub-block sweep (sub_pivots, the default) and the pair-pivot sweep it replaced (factor_diag_wave / factor_panel_wave,
+// LVF_CHOL_SUBBLOCK=0); loads, the previous step's update, the stores and everything another launch reads are common to both.
 constexpr int kNB = 64, kLd = 65;
 
 __device__ __forceinline__ void load_row64(const double* __restrict__ g, double a[kNB]) {
@@ -2022,6 +2024,60 @@ __device__ __forceinline__ void factor_panel_wave(double b[16], const int r, con
   }
 }
 
+// ---- 16-pivot sub-blocks (the default sweep; LVF_CHOL_SUBBLOCK=0 selects the pair-pivot sweep above)
+// The 64 pivots of a block are four stages of 16.  Both halves of the block live in LDS between the stages (the diagonal block in Pj,
+// the panel block in Pi, row stride kLd); in stage q ONE diagonal wave (q) and ONE panel wave take the column group 16q..16q+15 of their
+// half into registers, run the 16 pivots with no LDS access and no barrier, and put the finished columns back; the next column group
+// then takes the stage's contribution as 16x16 tile products on the matrix cores (one tile per wave), and the column groups behind it
+// take theirs under the next stage's sweep, from waves that do not sweep.
+// Inside the sweep every operand that is uniform over a row group comes from the DPP row_newbcast operand: the 16x16 diagonal tile D sits
+// replicated in all four 16-lane rows (lane i of each row holds row i of D in d[0..15]), so lane t of ANY row can hand out L_tj, and the
+// same instructions carry one 16-row group per DPP row in b[0..15] (rows 16g+i of the wave's half: x_j = b_j / L_jj, b_t -= x_j L_tj).
+// Hazards the assembler does not check for inline asm: a VALU write of a VGPR needs 2 wait states before a DPP instruction reads it
+// (the scaled column is written by an asm multiply that carries its own s_nop; the pivot broadcast waits in front), an EXEC change needs 5
+// (the first broadcast of a sweep waits for them).
+template <int N>
+__device__ __forceinline__ void fnmac_row_bcast(double& acc, double lv, double m) {     // acc -= (lane N of each 16-lane row of lv) * m
+  asm("v_fmac_f64_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(lv), "v"(m), "n"(N));
+}
+template <int T>
+__device__ __forceinline__ void sub_rank1(double d[16], double b[16], const double dj, const double xj) {
+  if constexpr (T < 16) {
+    fnmac_row_bcast<T>(d[T], dj, dj);                 // D_it -= L_ij L_tj  (the next pivot's own column first)
+    fnmac_row_bcast<T>(b[T], dj, xj);                 // B_rt -= x_rj L_tj
+    sub_rank1<T + 1>(d, b, dj, xj);
+  }
+}
+// H[16g.., 16c..] -= H[16g.., 16s..] * Pj[16c.., 16s..]^T on the matrix cores (H: Pj, the diagonal block, or Pi, the panel block; A[i = lc][k = lk],
+// B[k = lk][j = lc], D: col = lc, row = lk + 4 reg, as in chol_update_tile)
+__device__ __forceinline__ void sub_tile_update(double* H, const double* Pj, const int g, const int c, const int s, const int lk, const int lc) {
+  double* Tc = H + (16 * g + lk) * kLd + 16 * c + lc;
+  const double* Ta = H + (16 * g + lc) * kLd + 16 * s + lk;
+  const double* Tb = Pj + (16 * c + lc) * kLd + 16 * s + lk;
+  double4_t ac;
+#pragma unroll
+  for (int rg = 0; rg < 4; ++rg) ac[rg] = Tc[4 * rg * kLd];
+#pragma unroll
+  for (int k0 = 0; k0 < 16; k0 += 4) ac = __builtin_amdgcn_mfma_f64_16x16x4f64(-Ta[k0], Tb[k0], ac, 0, 0, 0);
+#pragma unroll
+  for (int rg = 0; rg < 4; ++rg) Tc[4 * rg * kLd] = ac[rg];
+}
+template <int J>
+__device__ __forceinline__ void sub_pivots(double d[16], double b[16], bool& bad) {
+  double djj = 0.0;                                   // D_jj of lane j, to every lane of the row: 0 + bcast * 1 (exact)
+  if (J == 0) asm("s_nop 4\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(djj) : "v"(d[J]), "v"(1.0), "n"(J));
+  else asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(djj) : "v"(d[J]), "v"(1.0), "n"(J));
+  bad |= !(djj > 0.0);
+  const double y0 = __builtin_amdgcn_rsq(djj);
+  const double e = fma(-djj * y0, y0, 1.0);
+  const double inv_l = fma(y0 * e, fma(e, 0.375, 0.5), y0);
+  double dj;
+  asm("v_mul_f64 %0, %1, %2\n\ts_nop 1" : "=v"(dj) : "v"(d[J]), "v"(inv_l));
+  const double xj = b[J] * inv_l;
+  d[J] = dj; b[J] = xj;
+  if constexpr (J < 15) { sub_rank1<J + 1>(d, b, dj, xj); sub_pivots<J + 1>(d, b, bad); }
+}
+
 // ONE launch per block step kb (grid = chol_step_grid), 512 threads per workgroup:
 //   workgroups [0, 2 + below)  — the column of step kb.  For kb > 0 each first applies step kb-1's trailing update to the two tiles it
 //       reads, A_kk -= P_k P_k^T (diagonal waves) and A_ik -= P_i P_k^T (panel waves) (P = the panel of column kb-1, staged in LDS;
@@ -2086,6 +2142,8 @@ __device__ __forceinline__ void chol_update_tile(double* S, int ld, int kp, int 
     for (int rg = 0; rg < 4; ++rg) out[(size_t)(lk + 4 * rg) * ld + 16 * ct + lc] = o[ct][rg] - acc[ct][rg];
 }
 
+// SUB: the 16-pivot sub-block sweep (default); !SUB: the pair-pivot sweep (factor_diag_wave / factor_panel_wave)
+template <bool SUB>
 __device__ __forceinline__ void chol_step_body(const int bx, const CholArgs& A, const int kb) {
   const int below = A.nb - kb - 1;
   if (bx >= chol_step_grid(A.nb, kb)) return;                          // (workgroup-uniform: no barrier is skipped by part of a workgroup)
@@ -2165,20 +2223,81 @@ __device__ __forceinline__ void chol_step_body(const int bx, const CholArgs& A, 
         for (int rg = 0; rg < 4; ++rg) Pw[(16 * t_m[n] + lk + 4 * rg) * kLd + 16 * t_c[n] + lc] = ac[n][rg];
       }
     __syncthreads();
-    const double* Pw = panel_wave ? Pi : Pj;
+    double* Pw = panel_wave ? Pi : Pj;
     if (!panel_wave || panel_wg)
 #pragma unroll
       for (int c = 0; c < 16; ++c) a[c] -= Pw[r * kLd + 16 * q + c];     // (entries right of the diagonal are never read as values of A)
+    if (SUB && (!panel_wave || bx > 0))               // the updated halves stay in LDS, in place of the products (own entries only)
+#pragma unroll
+      for (int c = 0; c < 16; ++c) Pw[r * kLd + 16 * q + c] = a[c];
     __syncthreads();                                  // the factorisation reuses both buffers
+  } else if (SUB) {
+    double* Pw = panel_wave ? Pi : Pj;
+    if (!panel_wave || bx > 0)
+#pragma unroll
+      for (int c = 0; c < 16; ++c) Pw[r * kLd + 16 * q + c] = a[c];
+    __syncthreads();
   }
   if (dbg) { dbg[3] = wall_clock64(); dbg[6] = clock64(); }
   const FactorLds F{Pi, Pj, Linv};
   bool bad = false;
   // pivot groups to run: all of them, except in the last block where only the real columns (the rest is identity padding) need any
   const int ncols = (kb == A.nb - 1 && A.last_cols > 0) ? min(A.last_cols, kNB) : kNB;
-  const int nsteps = (ncols + kPG - 1) / kPG + 1;
-  if (panel_wave) factor_panel_wave(a, r, q, F, nsteps);
-  else bad = factor_diag_wave(a, r, q, F, nsteps);
+  if constexpr (SUB) {
+    // stages to run: those that hold a real column (the padding's pivots are 1 and its off-diagonal entries 0: a stage made of padding
+    // alone changes nothing, and neither does the update it would take from the stages before it).  Workgroup-uniform: barriers match.
+    const int nstages = (ncols + 15) >> 4;
+    const int wu = __builtin_amdgcn_readfirstlane(wv), qu = wu >= 4 ? ((wu + 2) & 3) : wu;      // scalar copies: the branches below are not EXEC masks
+    const bool has_panel = bx > 0;
+    const int lane = tid & 63, lk = lane >> 4, lc = lane & 15;
+    double* Ph = wu >= 4 ? Pi : Pj;                   // the wave's half: diagonal block / panel block (identity in the inverse workgroup)
+    unsigned long long* dbs = (dbg && kb < 8) ? A.dbg + 64 + 8 * kb : nullptr;
+#pragma unroll 1
+    for (int s = 0; s < nstages; ++s) {
+      if (qu == s && (wu < 4 || has_panel)) {
+        double d[16];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) a[c] = Ph[r * kLd + 16 * s + c];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) d[c] = Pj[(16 * s + (r & 15)) * kLd + 16 * s + c];
+        sub_pivots<0>(d, a, bad);
+        // L[:, 16s..] / X[:, 16s..] go back for the tile products; a[] keeps them for the stores.  The diagonal wave puts back the rows
+        // BELOW the tile only: the panel wave of this stage reads D from Pj with no barrier between, so D must stay as it is (nothing
+        // reads rows <= 16s + 15 of this column group from LDS afterwards: the products take row groups > s, the Ldiag store takes a[])
+        if (wu >= 4 || r >= 16 * (s + 1))
+#pragma unroll
+          for (int c = 0; c < 16; ++c) Ph[r * kLd + 16 * s + c] = a[c];
+      }
+      else if (s > 0 && (((wu - s) & 1) != 0)) {
+        // the tiles right of column group s take stage s - 1's columns NOW, under the sweep of stage s: the sweeping waves read and write
+        // column group s only, these waves read column group s - 1 (final since the last stage) and write column groups > s.  Dealt to
+        // the four waves on the two SIMDs that host no sweeping wave
+        const int sp = s - 1, nd = 3 - sp, rd = nd * (nd - 1) / 2, n_def = rd + (has_panel ? 4 * (nd - 1) : 0);
+        const int slot = (((wu - s - 1) & 3) >> 1) * 2 + (wu >> 2);
+#pragma unroll 1
+        for (int u = slot; u < n_def; u += 4) {
+          if (u < rd) { const bool first = u < nd - 1; sub_tile_update(Pj, Pj, first ? sp + 2 + u : sp + 3, first ? sp + 2 : sp + 3, sp, lk, lc); }
+          else sub_tile_update(Pi, Pj, (u - rd) & 3, sp + 2 + ((u - rd) >> 2), sp, lk, lc);
+        }
+      }
+      __syncthreads();
+      if (dbs) dbs[2 * s] = wall_clock64();
+      if (s + 1 < nstages) {
+        // column group s + 1 takes stage s's columns before its own sweep: L21 L21^T on the 3 - s lower tiles of the diagonal block and
+        // X L21^T on the four panel tiles, one tile per wave.  A tile is updated by one wave, in place; the column group s it is
+        // updated from is not written in this phase.
+        const int nd = 3 - s;
+        if (wu < nd) sub_tile_update(Pj, Pj, s + 1 + wu, s + 1, s, lk, lc);
+        else if (has_panel && wu < nd + 4) sub_tile_update(Pi, Pj, wu - nd, s + 1, s, lk, lc);
+        __syncthreads();
+        if (dbs) dbs[2 * s + 1] = wall_clock64();
+      }
+    }
+  } else {
+    const int nsteps = (ncols + kPG - 1) / kPG + 1;
+    if (panel_wave) factor_panel_wave(a, r, q, F, nsteps);
+    else bad = factor_diag_wave(a, r, q, F, nsteps);
+  }
   if (dbg) { dbg[4] = wall_clock64(); dbg[7] = clock64(); }
   if (bad && r == 0) atomicMax(fail, 1 + kb);
   if (bx == 0 && !panel_wave) {
@@ -2200,9 +2319,14 @@ __device__ __forceinline__ void chol_step_body(const int bx, const CholArgs& A, 
   }
   if (dbg) dbg[5] = wall_clock64();
 }
-__global__ __launch_bounds__(kCT) void k_chol_step(CholArgs a, int kb) { chol_step_body(blockIdx.x, a, kb); }
-__global__ __launch_bounds__(kCT) void k_chol_step_b(const CholArgs* __restrict__ t, int kb) { chol_step_body(blockIdx.x, t[blockIdx.y], kb); }
-__global__ __launch_bounds__(kCT) void k_chol_step_bt(const CholArgs* __restrict__ t, int kb) { chol_step_body(blockIdx.y, t[blockIdx.x], kb); }
+__global__ __launch_bounds__(kCT) void k_chol_step(CholArgs a, int kb) { chol_step_body<true>(blockIdx.x, a, kb); }
+__global__ __launch_bounds__(kCT) void k_chol_step_b(const CholArgs* __restrict__ t, int kb) { chol_step_body<true>(blockIdx.x, t[blockIdx.y], kb); }
+__global__ __launch_bounds__(kCT) void k_chol_step_bt(const CholArgs* __restrict__ t, int kb) { chol_step_body<true>(blockIdx.y, t[blockIdx.x], kb); }
+// LVF_CHOL_SUBBLOCK=0: the pair-pivot sweep, as second instantiations (no branch inside the chain)
+__global__ __launch_bounds__(kCT) void k_chol_step_pp(CholArgs a, int kb) { chol_step_body<false>(blockIdx.x, a, kb); }
+__global__ __launch_bounds__(kCT) void k_chol_step_pp_b(const CholArgs* __restrict__ t, int kb) { chol_step_body<false>(blockIdx.x, t[blockIdx.y], kb); }
+__global__ __launch_bounds__(kCT) void k_chol_step_pp_bt(const CholArgs* __restrict__ t, int kb) { chol_step_body<false>(blockIdx.y, t[blockIdx.x], kb); }
+static bool chol_subblock_on() { static const bool on = [] { const char* e = std::getenv("LVF_CHOL_SUBBLOCK"); return !(e && e[0] == '0'); }(); return on; }
 
 // ------------------------------------------------------------------------------------------------ elimination order
 // The (v, ba, bg) blocks only meet each other and the poses through ImuError factors, i.e. along the IMU chain: block k touches
@@ -3977,8 +4101,9 @@ static int enqueue_iteration(lvf_problem* p, bool end_zero, int fused = 0) {
   for (int kb = 0; kb < p->nb; ++kb) {
     CholArgs cha = c.chol;
     static const bool chol_timing = std::getenv("LVF_CHOL_TIMING") != nullptr;
-    if (chol_timing) { LVF_TRY(p->dbg.ensure(64)); cha.dbg = p->dbg.p; }
-    LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step, dim3(chol_step_grid(p->nb, kb)), dim3(kCT), 0, q, cha, kb);
+    if (chol_timing) { LVF_TRY(p->dbg.ensure(128)); cha.dbg = p->dbg.p; }      // [0, 64): phases of 8 block steps; [64, 128): their sub-block stages
+    if (chol_subblock_on()) LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step, dim3(chol_step_grid(p->nb, kb)), dim3(kCT), 0, q, cha, kb);
+    else LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step_pp, dim3(chol_step_grid(p->nb, kb)), dim3(kCT), 0, q, cha, kb);
   }
   {
     BackArgs ba = c.back;
@@ -4096,10 +4221,15 @@ static int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* rad
     LVF_TRY(download_ctl(p, &c));
   }
   if (p->dbg.p && std::getenv("LVF_CHOL_TIMING")) {
-    unsigned long long t[64];
+    unsigned long long t[128];
     LVF_HIP(hipMemcpy(t, p->dbg.p, sizeof(t), hipMemcpyDeviceToHost));
     for (int kb = 0; kb < p->nb && kb < 8; ++kb) {
       const unsigned long long* u = t + 8 * kb;
+      if (chol_subblock_on() && kb + 2 < p->nb + 1) {      // a full block: per stage, sweep + exchange | tile products (seen by wave 0 of workgroup 1)
+        const unsigned long long* v = t + 64 + 8 * kb;
+        std::fprintf(stderr, "chol step %d stages (us): %.2f | %.2f ; %.2f | %.2f ; %.2f | %.2f ; %.2f\n", kb, (double)(v[0] - u[3]) * 0.01, (double)(v[1] - v[0]) * 0.01,
+                     (double)(v[2] - v[1]) * 0.01, (double)(v[3] - v[2]) * 0.01, (double)(v[4] - v[3]) * 0.01, (double)(v[5] - v[4]) * 0.01, (double)(v[6] - v[5]) * 0.01);
+      }
       if (kb == 0) std::fprintf(stderr, "chol step 0 (us): loads %.2f | factor %.2f (%llu shader clocks) | store %.2f\n", (double)(u[3] - u[0]) * 0.01, (double)(u[4] - u[3]) * 0.01, u[7] - u[6], (double)(u[5] - u[4]) * 0.01);
       else if (kb + 2 < p->nb + 1) std::fprintf(stderr, "chol step %d (us): stage %.2f | mfma %.2f | relayout %.2f | factor %.2f | store %.2f ; since previous step's end %.2f\n", kb, (double)(u[1] - u[0]) * 0.01,
                         (double)(u[2] - u[1]) * 0.01, (double)(u[3] - u[2]) * 0.01, (double)(u[4] - u[3]) * 0.01, (double)(u[5] - u[4]) * 0.01, (double)(u[0] - u[-3]) * 0.01);
@@ -4653,8 +4783,8 @@ static int batch_enqueue_iteration(lvf_problem_batch* b, bool end_zero) {
   for (int lv = b->first_own_level; lv < b->max_levels; ++lv)
     if (b->g_sp[lv] > 0) hipLaunchKernelGGL(k_sp_eliminate_b, dim3(b->g_sp[lv], W), dim3(256), b->lds_sp[lv], q, b->sp[lv].p);
   for (int kb = 0; kb < b->max_nb; ++kb) {
-    if (tr & 16) hipLaunchKernelGGL(k_chol_step_bt, dim3(W, chol_step_grid(b->max_nb, kb)), dim3(kCT), 0, q, b->chol.p, kb);
-    else hipLaunchKernelGGL(k_chol_step_b, dim3(chol_step_grid(b->max_nb, kb), W), dim3(kCT), 0, q, b->chol.p, kb);
+    if (tr & 16) hipLaunchKernelGGL(chol_subblock_on() ? k_chol_step_bt : k_chol_step_pp_bt, dim3(W, chol_step_grid(b->max_nb, kb)), dim3(kCT), 0, q, b->chol.p, kb);
+    else hipLaunchKernelGGL(chol_subblock_on() ? k_chol_step_b : k_chol_step_pp_b, dim3(chol_step_grid(b->max_nb, kb), W), dim3(kCT), 0, q, b->chol.p, kb);
   }
   hipLaunchKernelGGL(k_chol_backsolve_b, dim3(1, W), dim3(kBT), b->lds_back, q, b->back.p);
   if ((tr & 32) && b->g_tail <= 65535) hipLaunchKernelGGL(k_step_tail_bt, dim3(W, b->g_tail), dim3(kT), b->lds_tail, q, b->tail.p);
