@@ -22,6 +22,9 @@
  *                         src/association.cpp:270-384, src/mapping.cpp:154-178
  *   lvf_cloud_*        <- Mapping::MergeScan/ToWorld/BuildMapFrame, pcl::VoxelGrid / RadiusOutlierRemoval / SACSegmentation
  *                         src/mapping.cpp:78-137,193-220, src/association.cpp:210-268
+ *   lvf_trajectory_* / lvf_cloud_deskew / lvf_lidar_extract_deskewed
+ *                      <- Map::ComputePose, FeatureAssociation::UndistortPointCloud, the TODO of AdjustDistortion
+ *                         src/map.cpp:92-102, src/association.cpp:65-83, :142-145
  *   lvf_scan_match     <- Mapping::Optimize's per-frame body / Mapping::Relocate   src/mapping.cpp:147-178, :251-300
  *   lvf_window_*       <- Backend::BuildProblem's assembly kept incrementally          src/backend.cpp:96-183
  *   lvf_problem_*      <- adapt::Problem::{AddParameterBlock,AddResidualBlock,SetParameterBlockConstant}
@@ -300,6 +303,50 @@ int lvf_lidar_extract(lvf_ctx* ctx, const float* points, int n, int stride_float
  * before the next stage is sized: 13 stream waits per scan) instead of the device-counted one (one wait); returns the previous setting.  The
  * environment variable LVF_EXTRACT_HOST_COUNTS=1 sets the initial value.  Not part of the reference surface. */
 int lvf_debug_extract_host_counts(int on);
+/* Test hook, process-wide: the number of scans, since the library was loaded, that entered the device-counted path and were handed to the
+ * host-counted one (parameters outside the tail's plan, or the tail's verdict).  A test that compares the two paths reads it before and after
+ * to show which one produced a result.  Not part of the reference surface. */
+int lvf_debug_extract_fallbacks(void);
+
+/* ---- LiDAR sweep deskew: motion compensation along a stamped trajectory ------------------------------------------------------------------ */
+/* The step the reference declares and never calls: the `deskew` key of its configs (estimator.cpp:152), FeatureAssociation::deskew_
+ * (association.h:22,65), the `//TODO:deskew` of AdjustDistortion (association.cpp:142-145), and the implementation written for it
+ * (association.cpp:65-83, map.cpp:92-102).  The semantics are DECLARED (tests/deskew_ref.py): the reference's arithmetic with two
+ * deviations — the bracket of a time is (last stamp <= t, the next stamp) and the fraction s is not clamped, so the end brackets extrapolate
+ * (Map::ComputePose's lower_bound / upper_bound pair names ONE keyframe for every time that is not a stamp: t_t = 0); the time offset of a
+ * point is I - floorf(I + 0.5f) (UndistortPoint's I - int(I) is a second off for a negative offset on ring >= 1). */
+/* lvf_trajectory: Map::keyframes as ComputePose reads it (map.h: time -> Frame, Frame::pose): n >= 1 stamps, strictly increasing, with
+ * poses [qx,qy,qz,qw,tx,ty,tz] (the quaternion is normalised on entry, as Sophus' SE3d(q, t) constructor does), mirrored on the device.
+ * _append adds a keyframe behind the last one; _set_pose replaces the pose of keyframe i (the backend moves keyframes after they were
+ * inserted); both are in effect for the next call.  LVF_ERR_INVALID, before anything touches the device: n < 1, a stamp that does not
+ * increase, a non-finite stamp or pose, a zero quaternion, an index outside [0, size). */
+typedef struct lvf_trajectory lvf_trajectory;
+int lvf_trajectory_create(lvf_ctx* ctx, const double* stamps, const double* poses7, int n, lvf_trajectory** out);
+int lvf_trajectory_append(lvf_trajectory* traj, double stamp, const double* pose7);
+int lvf_trajectory_set_pose(lvf_trajectory* traj, int i, const double* pose7);
+int lvf_trajectory_size(const lvf_trajectory* traj);
+int lvf_trajectory_destroy(lvf_trajectory* traj);
+/* Map::ComputePose (map.cpp:92-102) for m times, evaluated on the device by the function the cloud kernel calls: n == 1 returns that pose;
+ * else i = clamp(#{stamps <= t} - 1, 0, n - 2), s = (t - stamp_i) / (stamp_i+1 - stamp_i), Eigen's slerp(s, q_i, q_i+1) normalised, and
+ * (1 - s) t_i + s t_i+1.  poses7_out: [m][7] host doubles. */
+int lvf_trajectory_compute_pose(const lvf_trajectory* traj, const double* times, int m, double* poses7_out);
+/* FeatureAssociation::UndistortPointCloud (association.cpp:65-83) on a SENSOR-frame cloud whose intensity carries ring + time offset as
+ * AdjustDistortion writes it (association.cpp:141-143; lvf_lidar_extract's picks): for every point, t = frame_time - cycle_time / 2 + offset,
+ * p1 = ComputePose(t) * extrinsic * p (Sensor2World, sensor.h:21-24), p2 = extrinsic^-1 * frame_pose^-1 * p1 (World2Sensor, sensor.h:16-19),
+ * in double, rounded to float; intensity copied.  A new cloud of the same size and order; a point with a non-finite field is copied
+ * unchanged; with a one-pose trajectory the cloud is copied bit for bit.  cycle_time must lie in (0, 0.4): the offset has to stay inside
+ * (-0.5, 0.5) for the ring to be recoverable.  LVF_ERR_INVALID on the host for a null trajectory, non-finite arguments or a zero quaternion. */
+int lvf_cloud_deskew(const lvf_cloud* in, const lvf_trajectory* traj, double frame_time, const double* frame_pose7, double cycle_time, const double* extrinsic7,
+                     lvf_cloud** out);
+/* lvf_lidar_extract with the deskew applied where AdjustDistortion's TODO stands (association.cpp:144).  Everything behind that line that
+ * reads coordinates is the PCL tail (association.cpp:210-232) — the smoothness and the six-sector picks read segmented_info.range and flags
+ * only (:149-207) — so the pass runs on ExtractFeatures' two pick clouds ahead of their VoxelGrid: a few thousand points, inside the same
+ * one-wait launch chain.  The outputs equal lvf_cloud_deskew of the plain call's picks pushed through lvf_cloud_voxel_filter /
+ * _radius_outlier_filter / _segment_plane / _transform bit for bit; dbg->ground_raw / surf_raw hold the DESKEWED picks, the other taps
+ * are lvf_lidar_extract's.  cycle_time is prm->cycle_time. */
+int lvf_lidar_extract_deskewed(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7,
+                               const lvf_trajectory* traj, double frame_time, const double* frame_pose7, lvf_cloud** ground_out, lvf_cloud** surf_out,
+                               lvf_lidar_extract_debug* dbg);
 /* kNN index / query scan straight from device-resident clouds (no host round trip) */
 int lvf_map_create_from_cloud(const lvf_cloud* c, float max_radius2, lvf_map** out);
 /* ... of n device-resident clouds in one call (lvf_map_create_batch's shared waits and launches, no upload): the old-frame maps of a set of

@@ -251,7 +251,17 @@ _SIGS = {
     "lvf_scan_create_from_cloud": (C.c_int, [_VP, C.POINTER(_VP)]),
     "lvf_lidar_params_default": (None, [C.POINTER(LidarParams)]),
     "lvf_debug_extract_host_counts": (C.c_int, [C.c_int]),
+    "lvf_debug_extract_fallbacks": (C.c_int, []),
     "lvf_lidar_extract": (C.c_int, [_VP, c_float_p, C.c_int, C.c_int, C.POINTER(LidarParams), c_double_p, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(LidarExtractDebug)]),
+    "lvf_trajectory_create": (C.c_int, [_VP, c_double_p, c_double_p, C.c_int, C.POINTER(_VP)]),
+    "lvf_trajectory_append": (C.c_int, [_VP, C.c_double, c_double_p]),
+    "lvf_trajectory_set_pose": (C.c_int, [_VP, C.c_int, c_double_p]),
+    "lvf_trajectory_size": (C.c_int, [_VP]),
+    "lvf_trajectory_destroy": (C.c_int, [_VP]),
+    "lvf_trajectory_compute_pose": (C.c_int, [_VP, c_double_p, C.c_int, c_double_p]),
+    "lvf_cloud_deskew": (C.c_int, [_VP, _VP, C.c_double, c_double_p, C.c_double, c_double_p, C.POINTER(_VP)]),
+    "lvf_lidar_extract_deskewed": (C.c_int, [_VP, c_float_p, C.c_int, C.c_int, C.POINTER(LidarParams), c_double_p, _VP, C.c_double, c_double_p, C.POINTER(_VP),
+                                             C.POINTER(_VP), C.POINTER(LidarExtractDebug)]),
     "lvf_scan_match_options_default": (None, [C.POINTER(ScanMatchOptions), C.c_double]),
     "lvf_scan_match": (C.c_int, [_VP, _VP, _VP, _VP, c_double_p, c_double_p, c_double_p, C.POINTER(ScanMatchOptions), C.POINTER(ScanMatchResult)]),
     "lvf_scan_match_batch": (C.c_int, [_VP, C.POINTER(ScanMatchJob), C.c_int, C.POINTER(ScanMatchOptions), C.c_int, C.POINTER(ScanMatchResult), c_int_p]),

@@ -663,6 +663,13 @@ class Cloud:
         _chk(self.ctx.L.lvf_cloud_segment_plane(self.h, float(thr), int(max_iterations), int(seed), C.byref(h), _dp(co), C.byref(it)))
         return Cloud(self.ctx, _h=h), co, it.value
 
+    def deskew(self, traj, frame_time, frame_pose, cycle_time, extrinsic):
+        """FeatureAssociation::UndistortPointCloud on a sensor-frame cloud whose intensity carries ring + time offset (DESIGN 16)"""
+        fp, e = _d(frame_pose), _d(extrinsic)
+        h = C.c_void_p()
+        _chk(self.ctx.L.lvf_cloud_deskew(self.h, traj.h if traj is not None else None, float(frame_time), _dp(fp), float(cycle_time), _dp(e), C.byref(h)))
+        return Cloud(self.ctx, _h=h)
+
     @staticmethod
     def concat(ctx, parts):
         arr = (C.c_void_p * len(parts))(*[p.h for p in parts])
@@ -683,6 +690,41 @@ class Cloud:
             self.h = C.c_void_p()
 
 
+class Trajectory:
+    """Map::keyframes as Map::ComputePose reads it, on the device (DESIGN 16): stamps [n] strictly increasing, poses [n, 7] = [qx,qy,qz,qw,tx,ty,tz]."""
+
+    def __init__(self, ctx, stamps, poses):
+        self.ctx = ctx
+        t, p = _d(stamps).reshape(-1), _d(poses).reshape(-1, 7)
+        if len(t) != len(p):
+            raise ValueError("Trajectory: %d stamps for %d poses" % (len(t), len(p)))
+        self.h = C.c_void_p()
+        _chk(ctx.L.lvf_trajectory_create(ctx.h, _dp(t), _dp(p), len(t), C.byref(self.h)))
+
+    def __len__(self):
+        return self.ctx.L.lvf_trajectory_size(self.h)
+
+    def append(self, stamp, pose):
+        p = _d(pose)
+        _chk(self.ctx.L.lvf_trajectory_append(self.h, float(stamp), _dp(p)))
+
+    def set_pose(self, i, pose):
+        p = _d(pose)
+        _chk(self.ctx.L.lvf_trajectory_set_pose(self.h, int(i), _dp(p)))
+
+    def compute_pose(self, times):
+        """Map::ComputePose for every time: [m, 7]"""
+        t = _d(times).reshape(-1)
+        out = np.empty((len(t), 7))
+        _chk(self.ctx.L.lvf_trajectory_compute_pose(self.h, _dp(t), len(t), _dp(out)))
+        return out
+
+    def close(self):
+        if self.h:
+            self.ctx.L.lvf_trajectory_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 def lidar_params(**kw):
     p = LidarParams()
     _lib.lib().lvf_lidar_params_default(C.byref(p))
@@ -696,8 +738,12 @@ def extract_host_counts(ctx, on):
     return bool(ctx.L.lvf_debug_extract_host_counts(1 if on else 0))
 
 
-def lidar_extract(ctx, points, extrinsic, params=None, debug=False):
-    """FeatureAssociation::Process on device: raw sensor-frame scan -> (ground Cloud, surf Cloud[, debug dict])."""
+def extract_fallbacks(ctx):
+    """test hook: scans that entered the device-counted path and were handed to the host-counted one, since the library was loaded"""
+    return int(ctx.L.lvf_debug_extract_fallbacks())
+
+
+def _lidar_extract(ctx, points, extrinsic, params, debug, call):
     a = _f(points); e = _d(extrinsic)
     prm = params if params is not None else lidar_params()
     hg, hs = C.c_void_p(), C.c_void_p()
@@ -711,8 +757,7 @@ def lidar_extract(ctx, points, extrinsic, params=None, debug=False):
         dbg.label_mat = keep["label_mat"].ctypes.data_as(C.POINTER(C.c_int32)); dbg.ground_mat = keep["ground_mat"].ctypes.data_as(C.POINTER(C.c_int8))
         dbg.range_mat = keep["range_mat"].ctypes.data_as(_lib.c_float_p); dbg.ground_raw = keep["ground_raw"].ctypes.data_as(_lib.c_float_p)
         dbg.surf_raw = keep["surf_raw"].ctypes.data_as(_lib.c_float_p)
-    _chk(ctx.L.lvf_lidar_extract(ctx.h, a.ctypes.data_as(_lib.c_float_p), a.shape[0], a.shape[1], C.byref(prm), _dp(e), C.byref(hg), C.byref(hs),
-                                 C.byref(dbg) if dbg is not None else None))
+    _chk(call(a, prm, e, hg, hs, C.byref(dbg) if dbg is not None else None))
     g, s = Cloud(ctx, _h=hg), Cloud(ctx, _h=hs)
     if not debug:
         return g, s
@@ -721,6 +766,21 @@ def lidar_extract(ctx, points, extrinsic, params=None, debug=False):
                ground_raw=keep["ground_raw"][:dbg.n_ground_raw].copy(), surf_raw=keep["surf_raw"][:dbg.n_surf_raw].copy(),
                n_filtered=dbg.n_filtered, n_segmented=dbg.n_segmented)
     return g, s, out
+
+
+def lidar_extract(ctx, points, extrinsic, params=None, debug=False):
+    """FeatureAssociation::Process on device: raw sensor-frame scan -> (ground Cloud, surf Cloud[, debug dict])."""
+    return _lidar_extract(ctx, points, extrinsic, params, debug, lambda a, prm, e, hg, hs, dbg: ctx.L.lvf_lidar_extract(
+        ctx.h, a.ctypes.data_as(_lib.c_float_p), a.shape[0], a.shape[1], C.byref(prm), _dp(e), C.byref(hg), C.byref(hs), dbg))
+
+
+def lidar_extract_deskewed(ctx, points, extrinsic, traj, frame_time, frame_pose, params=None, debug=False):
+    """lidar_extract with the sweep deskewed along `traj` where AdjustDistortion's TODO stands; the debug dict's ground_raw /
+    surf_raw are the deskewed picks."""
+    fp = _d(frame_pose)
+    return _lidar_extract(ctx, points, extrinsic, params, debug, lambda a, prm, e, hg, hs, dbg: ctx.L.lvf_lidar_extract_deskewed(
+        ctx.h, a.ctypes.data_as(_lib.c_float_p), a.shape[0], a.shape[1], C.byref(prm), _dp(e), traj.h if traj is not None else None, float(frame_time), _dp(fp),
+        C.byref(hg), C.byref(hs), dbg))
 
 
 class Map:

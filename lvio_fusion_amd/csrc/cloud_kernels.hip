@@ -706,9 +706,11 @@ static int dc_voxel_filters(lvf_ctx* ctx, DcState* st, int n_jobs, DcVoxelJob* j
   return LVF_OK;
 }
 
-// The tail.  surf_raw / ground_raw: the picks (capacity `cap`, counts on the device).  Every coordinate is known to lie within max_range of the
-// origin (Preprocess' range gate; centroids stay inside), which bounds the voxel keys' width and the radius grid's size BEFORE anything is
-// measured; a scan that breaks the bound raises st->err.  The surf chain (VoxelGrid -> RadiusOutlierRemoval) and the ground chain (VoxelGrid ->
+// The tail.  surf_raw / ground_raw: the picks (capacity `cap`, counts on the device).  Picks that come straight from Preprocess' range gate
+// lie within max_range of the origin (centroids stay inside), which sizes the plan — the voxel keys' width, the radius grid's cells — BEFORE
+// anything is measured.  Deskewed picks may lie outside that ball: the grids themselves are laid over the MEASURED box
+// (k_dc_bounds), so such picks are handled like any others while the box fits the plan; a scan whose box does not fit raises st->err and
+// the caller takes the host-counted path.  The surf chain (VoxelGrid -> RadiusOutlierRemoval) and the ground chain (VoxelGrid ->
 // plane) share nothing: the surf chain goes on the context's stream, the ground chain on its side stream, forked behind what produced the picks
 // and joined before this returns — two chains of ~25 launches of a few microseconds each run beside each other instead of one after the other.
 // Scratch of BOTH chains lives in `keep` until the caller has waited for the stream (the pool hands a released block to the next allocation

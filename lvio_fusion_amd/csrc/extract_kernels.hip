@@ -337,11 +337,14 @@ __device__ __forceinline__ void pick_body(const int k, const int m, int Cn, cons
 using namespace lvf;
 
 static std::atomic<int> g_extract_host_counts{[] { const char* e = std::getenv("LVF_EXTRACT_HOST_COUNTS"); return (e && e[0] == '1') ? 1 : 0; }()};
+static std::atomic<int> g_extract_fallbacks{0};      // scans the device-counted path handed to the host-counted one (lvf_debug_extract_fallbacks)
 
 // The host-counted path (rounds 2-4; kept as the fallback of the device-counted one and as its reference in the tests): every stage reads its
 // output count back before the next one is sized — 13 stream waits per scan.
+// dk (here and in the device-counted path; null: none, exactly lvf_lidar_extract's launches): the deskew of the two pick clouds, in place, where
+// AdjustDistortion's TODO stands — nothing between that line and the PCL tail reads a coordinate (association.cpp:144-208)
 static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7, const ExP& P,
-                                lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg) {
+                                const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg) {
   hipStream_t s = ctx->stream;
   const int npix = P.R * P.Cn;
   // ---- Preprocess
@@ -405,6 +408,10 @@ static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int st
   }
   LVF_TRY(compact_points(ctx, seg.p, num, pick_g.p, &g_raw)); guard.add(g_raw);
   LVF_TRY(compact_points(ctx, seg.p, num, pick_s.p, &s_raw)); guard.add(s_raw);
+  if (dk) {
+    LVF_TRY(deskew_launch(s, g_raw->n, nullptr, g_raw->pts.p, g_raw->pts.p, *dk));
+    LVF_TRY(deskew_launch(s, s_raw->n, nullptr, s_raw->pts.p, s_raw->pts.p, *dk));
+  }
   if (dbg) {
     dbg->n_filtered = m; dbg->n_segmented = num; dbg->n_ground_raw = g_raw->n; dbg->n_surf_raw = s_raw->n;
     if (dbg->label_mat) LVF_HIP(hipMemcpyAsync(dbg->label_mat, label.p, (size_t)4 * npix, hipMemcpyDeviceToHost, s));
@@ -432,8 +439,10 @@ static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int st
 // (device_scan1); the start / end orientations are taken by a one-thread launch with the host's arithmetic; the PCL tail is dc_pcl_tail.
 // The counts (and the tail's verdict) come back in one read before the two extrinsic transforms, which are then sized exactly.
 // *done = false: a scan outside what the path was sized for (the tail's a-priori bounds) — the caller takes the host-counted path.
+// (Deskewed picks may leave the range gate's ball the tail's plan is sized from.  The tail derives its voxel keys and its radius grid from the
+// MEASURED box of what it is given and raises its verdict when they do not fit the plan: such a scan goes through the host-counted path.)
 static int extract_device_counted(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7, const ExP& P,
-                                  lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg, bool* done) {
+                                  const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg, bool* done) {
   hipStream_t s = ctx->stream;
   *done = false;
   static const bool timing = std::getenv("LVF_EXTRACT_TIMING") != nullptr;
@@ -497,7 +506,9 @@ static int extract_device_counted(lvf_ctx* ctx, const float* points, int n, int 
   SideGuard side_fork_guard{ctx};      // declared AFTER every buffer the side stream touches (seg, pick_g, g_raw, ground_pre ...): on an error return it waits for stream2 before they go back to the pool
   LVF_TRY(dc_tail_fork(ctx, plan, &q));
   LVF_TRY(device_scan1_on(ctx, q, plan.lane_ground, pick_g.p, capseg, num_dev, nullptr, &ex->cnt[2], seg.p, g_raw.p));
+  if (dk) LVF_TRY(deskew_launch(q, capseg, &ex->cnt[2], g_raw.p, g_raw.p, *dk));      // (each on the stream of its compaction: no wait is added)
   LVF_TRY(device_scan1_on(ctx, s, 0, pick_s.p, capseg, num_dev, nullptr, &ex->cnt[3], seg.p, s_raw.p));
+  if (dk) LVF_TRY(deskew_launch(s, capseg, &ex->cnt[3], s_raw.p, s_raw.p, *dk));
   LVF_TRY(dc_tail_run(ctx, plan, q, s_raw.p, &ex->cnt[3], g_raw.p, &ex->cnt[2], (unsigned long long)prm->ransac_seed, tail_state, tail_keep, surf_pre, ground_pre));
   // ---- the one read-back: the four counts here, the tail's four and its verdict
   int hc[4] = {0, 0, 0, 0}, ht[5] = {0, 0, 0, 0, 0};
@@ -530,21 +541,28 @@ static int extract_device_counted(lvf_ctx* ctx, const float* points, int n, int 
   return LVF_OK;
 }
 
-extern "C" {
-
-void lvf_lidar_params_default(lvf_lidar_params* p) {
+extern "C" void lvf_lidar_params_default(lvf_lidar_params* p) {
   if (!p) return;
   p->num_scans = 64; p->horizon_scan = 1800; p->ang_res_y = 0.427f; p->ang_bottom = 24.9f; p->ground_rows = 60;   // config/kitti.yaml:35-39
   p->cycle_time = 0.1036; p->min_range = 5.0f; p->max_range = 30.0f; p->resolution = 0.2f;                        // :40-45
   p->ransac_seed = 12345;
 }
 
-int lvf_lidar_extract(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7,
-                      lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg) {
-  LVF_REQUIRE(ctx && prm && extrinsic7 && ground_out && surf_out, "lvf_lidar_extract: null argument");
-  LVF_REQUIRE(n >= 0 && (n == 0 || points) && stride_floats >= 3, "lvf_lidar_extract: bad scan (n=%d stride=%d)", n, stride_floats);
+// lvf_lidar_extract and lvf_lidar_extract_deskewed (traj != null)
+static int extract_entry(const char* who, lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7,
+                         const lvf_trajectory* traj, double frame_time, const double* frame_pose7, lvf_cloud** ground_out, lvf_cloud** surf_out,
+                         lvf_lidar_extract_debug* dbg) {
+  LVF_REQUIRE(ctx && prm && extrinsic7 && ground_out && surf_out, "%s: null argument", who);
+  LVF_REQUIRE(n >= 0 && (n == 0 || points) && stride_floats >= 3, "%s: bad scan (n=%d stride=%d)", who, n, stride_floats);
   LVF_REQUIRE(prm->num_scans > 1 && prm->num_scans <= 64 && prm->horizon_scan > 0 && prm->ground_rows >= 0 && prm->ground_rows < prm->num_scans,
-              "lvf_lidar_extract: unsupported geometry (num_scans <= 64, 0 <= ground_rows < num_scans)");
+              "%s: unsupported geometry (num_scans <= 64, 0 <= ground_rows < num_scans)", who);
+  DeskewP dkp;
+  const DeskewP* dk = nullptr;
+  if (traj) {
+    bool active = false;
+    LVF_TRY(deskew_prepare(who, ctx, traj, frame_time, frame_pose7, prm->cycle_time, extrinsic7, &dkp, &active));
+    if (active) dk = &dkp;
+  }
   LVF_TRY(lvf::enter(ctx));
   ExP P;
   P.R = prm->num_scans; P.Cn = prm->horizon_scan; P.ground_rows = prm->ground_rows;
@@ -557,13 +575,30 @@ int lvf_lidar_extract(lvf_ctx* ctx, const float* points, int n, int stride_float
   *ground_out = nullptr; *surf_out = nullptr;
   if (n > 0 && !g_extract_host_counts.load()) {
     bool done = false;
-    LVF_TRY(extract_device_counted(ctx, points, n, stride_floats, prm, extrinsic7, P, ground_out, surf_out, dbg, &done));
+    LVF_TRY(extract_device_counted(ctx, points, n, stride_floats, prm, extrinsic7, P, dk, ground_out, surf_out, dbg, &done));
     if (done) return LVF_OK;
+    g_extract_fallbacks.fetch_add(1);
   }
-  return extract_host_counted(ctx, points, n, stride_floats, prm, extrinsic7, P, ground_out, surf_out, dbg);
+  return extract_host_counted(ctx, points, n, stride_floats, prm, extrinsic7, P, dk, ground_out, surf_out, dbg);
+}
+
+extern "C" {
+
+int lvf_lidar_extract(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7,
+                      lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg) {
+  return extract_entry("lvf_lidar_extract", ctx, points, n, stride_floats, prm, extrinsic7, nullptr, 0.0, nullptr, ground_out, surf_out, dbg);
+}
+
+int lvf_lidar_extract_deskewed(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7,
+                               const lvf_trajectory* traj, double frame_time, const double* frame_pose7, lvf_cloud** ground_out, lvf_cloud** surf_out,
+                               lvf_lidar_extract_debug* dbg) {
+  LVF_REQUIRE(traj, "lvf_lidar_extract_deskewed: null trajectory");
+  return extract_entry("lvf_lidar_extract_deskewed", ctx, points, n, stride_floats, prm, extrinsic7, traj, frame_time, frame_pose7, ground_out, surf_out, dbg);
 }
 
 // Test / A-B hook: 1 = lvf_lidar_extract takes the host-counted path (process-wide).  Not part of the reference surface.
 int lvf_debug_extract_host_counts(int on) { const int was = g_extract_host_counts.exchange(on ? 1 : 0); return was; }
+// Test hook: how many scans entered the device-counted path and left it for the host-counted one (process-wide, since the library was loaded)
+int lvf_debug_extract_fallbacks(void) { return g_extract_fallbacks.load(); }
 
 }  // extern "C"

@@ -588,6 +588,21 @@ int dc_tail_run(lvf_ctx* ctx, const DcTailPlan& plan, hipStream_t q, const float
 int dc_state_bytes();
 int dc_state_counts_offset();      // int cnt[4] (surf voxels, surf features, ground voxels, ground features), then int err
 int transform_points(lvf_ctx* ctx, const float4* in, int n, const double* pose, lvf_cloud** out);
+// LiDAR sweep deskew (deskew_kernels.hip): what one launch of k_deskew needs.  A rigid map as a matrix, the trajectory's knots ([n][8]: stamp, q, t)
+// on the device, the knots staged in LDS (k0 .. k0 + nk; nk = 0: every point searches the whole array) and the time window they are exact for.
+constexpr int kDeskewFastKnots = 8;
+struct DeskewRt { double R[9], t[3]; };
+struct DeskewP {
+  const double* knots; int n, k0, nk;
+  double t_lo, t_hi, t0;             // t0 = frame_time - cycle_time / 2: a point's time is t0 + its offset
+  DeskewRt E, A;                     // E = extrinsic, A = extrinsic^-1 frame_pose^-1
+};
+// checks the arguments on the host (LVF_ERR_INVALID, nothing launched) and fills *P.  *active = false: a one-pose trajectory, the deskew is the
+// identity and the caller launches nothing.
+int deskew_prepare(const char* who, lvf_ctx* ctx, const lvf_trajectory* tr, double frame_time, const double* frame_pose7, double cycle_time, const double* extrinsic7,
+                   DeskewP* P, bool* active);
+// out[i] = deskewed in[i] for i < min(cap, *n_dev) (n_dev may be null) on stream q; in == out is allowed
+int deskew_launch(hipStream_t q, int cap, const int* n_dev, const float4* in, float4* out, const DeskewP& P);
 // kernels / launchers implemented in the .hip translation units
 int launch_pose_only(lvf_batch* b, const lvf_state* st, bool want_j);
 int launch_two_frame(lvf_batch* b, const lvf_state* st, bool want_j);

@@ -1,0 +1,357 @@
+"""GPU parity of the LiDAR sweep deskew against its declared semantics, tests/deskew_ref.py (pinned on the CPU by test_deskew_ref.py):
+lvf_trajectory_compute_pose = Map::ComputePose, lvf_cloud_deskew = FeatureAssociation::UndistortPointCloud, lvf_lidar_extract_deskewed =
+lvf_lidar_extract with the pass applied where AdjustDistortion's TODO stands.
+
+Tolerances.  Interpolation: 1e-12 absolute on each unit-quaternion component (up to the common sign) and 1e-12 max(1, |t|) on each translation
+component — the acos / sin weights are insensitive to acos' ill-conditioning near 1 (the error of theta enters multiplied by theta), so
+double rounding predicts ~1e-16 |t|; the cap sits four orders above that and six below the float32 ulp the cloud tests resolve.  Cloud:
+|out - p2| <= 2^-23 |p2| + 1e-9 per component against the restatement's float64 p2 BEFORE rounding — one float32 ulp, because a double
+rounding difference may flip the final rounding; 1e-9 m covers components near zero, where the double error (~1e-11 for world coordinates
+<= 1e3 m, which every trajectory here respects) exceeds their ulp.  Extraction: bit equality with the composition of calls that already exist.
+
+Negative time offsets (AdjustDistortion's rel_time reaches -0.25): the 600-firing scans' GROUND picks contain them (checked through the oracle
+in test_extract_picks_and_clouds_equal_the_composition); the hand-made cloud of test_cloud_negative_offsets covers them on chosen rings."""
+import numpy as np
+import pytest
+
+from lvio_fusion_amd import synthetic as syn
+from tests import deskew_cases as dc
+from tests import deskew_ref as dr
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from lvio_fusion_amd import api
+    c = api.Context(0)
+    yield c
+    c.close()
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def assert_pose_parity(got, ref, what):
+    sgn = np.where((got[:, :4] * ref[:, :4]).sum(1) < 0, -1.0, 1.0)[:, None]
+    eq, et = np.abs(got[:, :4] - sgn * ref[:, :4]), np.abs(got[:, 4:] - ref[:, 4:]) / np.maximum(1.0, np.abs(ref[:, 4:]))
+    print("%s: max quaternion error %.3e, max translation error / max(1, |t|) %.3e" % (what, eq.max(), et.max()))
+    assert eq.max() <= 1e-12 and et.max() <= 1e-12, what
+
+
+# ---- interpolation -------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n", [1, 2, 3, 40])
+def test_compute_pose(ctx, n):
+    """before the first stamp, on every stamp, inside every bracket, after the last stamp; translations up to 1e3 m"""
+    from lvio_fusion_amd import api
+    stamps, poses = dc.far_trajectory(n)
+    assert 900.0 < np.abs(poses[:, 4:]).max() < 1000.0
+    times = dc.query_times(stamps, per_bracket=3, seed=n)
+    tr = api.Trajectory(ctx, stamps, poses)
+    assert len(tr) == n
+    assert_pose_parity(tr.compute_pose(times), dr.compute_pose(stamps, poses, times), "N = %d" % n)
+    assert tr.compute_pose([]).shape == (0, 7)
+    tr.close()
+
+
+def test_compute_pose_negative_dot_and_identical_rotation(ctx):
+    from lvio_fusion_amd import api
+    stamps, poses = dc.far_trajectory(5)
+    stamps, poses = dc.with_negative_dot(stamps, poses, 2)
+    stamps, poses = dc.with_identical_rotation(stamps, poses, 3)
+    P = dr.normalized(poses)
+    dots = (P[:-1, :4] * P[1:, :4]).sum(1)
+    assert dots[1] < 0 and dots[2] < 0 and abs(dots[3]) >= 1.0 - dr.DBL_EPSILON
+    times = dc.query_times(stamps, per_bracket=4, seed=8)
+    tr = api.Trajectory(ctx, stamps, poses)
+    assert_pose_parity(tr.compute_pose(times), dr.compute_pose(stamps, poses, times), "negative dot / identical rotation")
+    tr.close()
+
+
+def test_trajectory_append_and_set_pose(ctx):
+    """a trajectory grown keyframe by keyframe (the device array re-allocates on the way) and then moved, as the backend moves keyframes after
+    they were inserted, equals one created whole"""
+    from lvio_fusion_amd import api
+    stamps, poses = dc.far_trajectory(40, seed=5)
+    tr = api.Trajectory(ctx, stamps[:1], poses[:1])
+    for k in range(1, 40):
+        tr.append(stamps[k], poses[k])
+    assert len(tr) == 40
+    times = dc.query_times(stamps, per_bracket=1, seed=2)
+    assert_pose_parity(tr.compute_pose(times), dr.compute_pose(stamps, poses, times), "appended")
+    moved = poses.copy()
+    moved[[0, 17, 39]] = dc.far_trajectory(40, seed=6)[1][[0, 17, 39]]
+    for k in (0, 17, 39):
+        tr.set_pose(k, moved[k])
+    assert_pose_parity(tr.compute_pose(times), dr.compute_pose(stamps, moved, times), "moved")
+    tr.close()
+
+
+# ---- cloud ---------------------------------------------------------------------------------------------------------------------------------
+
+def check_cloud(ctx, cloud, stamps, poses, frame_time, frame_pose, cycle, what):
+    from lvio_fusion_amd import api
+    E = syn.lidar_extrinsic()
+    assert np.abs(poses[:, 4:]).max() <= 1e3
+    tr = api.Trajectory(ctx, stamps, poses)
+    c = api.Cloud(ctx, cloud)
+    d = c.deskew(tr, frame_time, frame_pose, cycle, E)
+    got = d.download()
+    for h in (d, c, tr):
+        h.close()
+    p2, ref = dr.deskew(cloud, stamps, poses, frame_time, frame_pose, cycle, E)
+    assert got.shape == cloud.shape, what                                                  # size (and, with the comparisons below, order)
+    assert np.array_equal(bits(got[:, 3]), bits(cloud[:, 3])), what + ": intensity bits"
+    ok = np.isfinite(cloud).all(1)
+    assert np.array_equal(bits(got[~ok]), bits(cloud[~ok])), what + ": a point with a non-finite field is copied"
+    if ok.any():
+        err = np.abs(got[ok, :3].astype(np.float64) - p2[ok])
+        bound = 2.0 ** -23 * np.abs(p2[ok]) + 1e-9
+        print("%s: %d points, max |out - p2| / bound = %.3f, %d of %d components differ from the rounded restatement" %
+              (what, int(ok.sum()), (err / bound).max(), int((bits(got[ok, :3]) != bits(ref[ok, :3])).sum()), 3 * int(ok.sum())))
+        assert (err <= bound).all(), what
+    return got
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 257, 5000])
+def test_cloud_sizes(ctx, n):
+    """one wave short of, exactly and one past a wave; more than one workgroup; many workgroups.  The sweep straddles the middle keyframe: two brackets"""
+    stamps, poses = dc.drive()
+    got = check_cloud(ctx, dc.sweep_cloud(n, seed=n), stamps, poses, 0.1, poses[1], dc.CYCLE, "n = %d" % n)
+    if n >= 63:
+        assert np.abs(got[:, :3] - dc.sweep_cloud(n, seed=n)[:, :3]).max() > 0.3
+
+
+@pytest.mark.parametrize("case", ["one_bracket", "two_brackets", "three_brackets", "second_half_extrapolated", "all_extrapolated", "before_the_first_stamp",
+                                  "imu_rate_knots"])
+def test_cloud_brackets(ctx, case):
+    cloud = dc.sweep_cloud(257, seed=11, nan_every=29)
+    cycle = dc.CYCLE
+    if case == "one_bracket":                  # a short cycle inside (0.1, 0.2), the offsets' quarter-cycle margins included
+        stamps, poses = dc.trajectory(4, seed=4); cycle = 0.05; cloud = dc.sweep_cloud(257, cycle=cycle, seed=11, nan_every=29); ft = 0.15
+    elif case == "two_brackets":
+        stamps, poses = dc.trajectory(4, seed=4); ft = 0.2
+    elif case == "three_brackets":             # knots 0.07 apart: times in [0.097, 0.253] fall into [0.07, 0.14], [0.14, 0.21], [0.21, 0.28]
+        stamps, poses = dc.trajectory(5, dt=0.07, seed=4); ft = 0.175
+    elif case == "second_half_extrapolated":   # the newest keyframe's sweep
+        stamps, poses = dc.trajectory(3, seed=4); ft = stamps[-1]
+    elif case == "all_extrapolated":
+        stamps, poses = dc.trajectory(3, seed=4); ft = stamps[-1] + 0.3
+    elif case == "before_the_first_stamp":
+        stamps, poses = dc.trajectory(3, seed=4); ft = stamps[0] - 0.2
+    else:                                      # a knot every millisecond: the sweep spans ~150 knots, far more than the fast path stages
+        stamps, poses = dc.trajectory(400, dt=0.001, seed=4); ft = 0.2
+    _, _, t = dr.point_times(cloud[np.isfinite(cloud).all(1), 3], ft, cycle)
+    nb = len(np.unique(dr.bracket(stamps, t)))
+    want = dict(one_bracket=(1, 1), two_brackets=(2, 2), three_brackets=(3, 3), second_half_extrapolated=(1, 1), all_extrapolated=(1, 1), before_the_first_stamp=(1, 1),
+                imu_rate_knots=(100, 400))[case]
+    assert want[0] <= nb <= want[1], (case, nb)
+    fp = dr.compute_pose(stamps, poses, [ft])[0]
+    check_cloud(ctx, cloud, stamps, poses, ft, fp, cycle, case)
+
+
+def test_cloud_negative_offsets(ctx):
+    """hand-made intensities with negative offsets on rings 1, 5, 17, 63: each point gets a time just before the sweep's start (the reference's
+    int() would put it 0.97 .. 1 s later, more than 14 m off at this speed)"""
+    stamps, poses = dc.drive()
+    cloud = dc.negative_offset_cloud()
+    ring, delta, _ = dr.point_times(cloud[:, 3], 0.1, dc.CYCLE)
+    assert (delta < 0).sum() == 12 and (ring[delta < 0] >= 1).all()
+    got = check_cloud(ctx, cloud, stamps, poses, 0.1, poses[1], dc.CYCLE, "negative offsets")
+    assert np.abs(got[:, :3] - cloud[:, :3]).max() < 3.0
+
+
+def test_cloud_stray_offsets_leave_the_staged_window(ctx):
+    """3 knots: the fast path stages them (the sweep's window brackets at most 3 <= 8 knots), and six hand-made points carry offsets of
+    +-0.4 s, so their times lie outside the window the stage was narrowed to: exactly those points take the bisection over the whole
+    trajectory while their workgroup neighbours count staged stamps.  Both find the declared bracket (extrapolated, here)."""
+    stamps, poses = dc.drive()
+    cloud = dc.stray_offset_cloud()
+    ft = 0.1
+    _, delta, t = dr.point_times(cloud[:, 3], ft, dc.CYCLE)
+    outside = (t < ft - 0.75 * dc.CYCLE) | (t > ft + 0.75 * dc.CYCLE)
+    assert outside.sum() == 6 and (np.abs(np.abs(delta[outside]) - 0.4) < 1e-5).all() and (t[outside] < stamps[0]).sum() == 3 and (t[outside] > stamps[-1]).sum() == 3
+    assert len(stamps) <= 8                                                                # every knot fits the stage
+    got = check_cloud(ctx, cloud, stamps, poses, ft, poses[1], dc.CYCLE, "stray offsets")
+    assert np.abs(got[outside, :3] - cloud[outside, :3]).max() > 3.0                       # 0.3 .. 0.45 s at 15 m/s
+
+
+def test_cloud_one_pose_is_a_copy(ctx):
+    from lvio_fusion_amd import api
+    stamps, poses = dc.drive()
+    cloud = dc.sweep_cloud(300, seed=12, nan_every=31)
+    tr = api.Trajectory(ctx, stamps[:1], poses[:1])
+    c = api.Cloud(ctx, cloud)
+    d = c.deskew(tr, 0.1, poses[1], dc.CYCLE, syn.lidar_extrinsic())
+    assert np.array_equal(bits(d.download()), bits(cloud))
+    for h in (d, c, tr):
+        h.close()
+
+
+# ---- extraction ----------------------------------------------------------------------------------------------------------------------------
+
+PRM600 = dict(horizon_scan=600)
+
+
+def scan_case(name):
+    """(scan, lidar_params keywords).  third_*: syn.raw_scan(seed)[::3] — these keep no adjacent rings, so their picks are EMPTY: every launch
+    behind the segmentation, the deskew's included, sees a device count of zero.  az600_*: 600 firings with horizon_scan = 600 — the smallest
+    scans with real picks and features.  full: the whole 115 200-point revolution, once."""
+    kind, seed = name.split("_")
+    if kind == "third":
+        return dc.scan_every_third(int(seed)), {}
+    if kind == "az600":
+        return dc.scan600(int(seed)), PRM600
+    return dc.scan_full(int(seed)), {}
+
+
+def extract_both(ctx, scan, kw, stamps, poses, frame_time, frame_pose, host):
+    """(plain, deskewed) = ((ground, surf, dbg) as arrays) through one of the two count paths.  host = False asserts that the device-counted
+    path FINISHED both calls (lvf_debug_extract_fallbacks did not move): it neither refused the plan nor raised the tail's verdict, so what
+    comes back is that path's result and not the host-counted fallback's"""
+    from lvio_fusion_amd import api
+    E = syn.lidar_extrinsic()
+    tr = api.Trajectory(ctx, stamps, poses)
+    was = api.extract_host_counts(ctx, host)
+    fell = api.extract_fallbacks(ctx)
+    try:
+        g0, s0, d0 = api.lidar_extract(ctx, scan, E, params=api.lidar_params(**kw), debug=True)
+        g1, s1, d1 = api.lidar_extract_deskewed(ctx, scan, E, tr, frame_time, frame_pose, params=api.lidar_params(**kw), debug=True)
+        assert api.extract_fallbacks(ctx) == fell, "the device-counted path handed a scan to the host-counted one" if not host else "the host-counted path was not taken directly"
+        out = (g0.download(), s0.download(), d0), (g1.download(), s1.download(), d1)
+        for h in (g0, s0, g1, s1):
+            h.close()
+    finally:
+        api.extract_host_counts(ctx, was)
+        tr.close()
+    return out
+
+
+def composition(ctx, picks_g, picks_s, kw, stamps, poses, frame_time, frame_pose):
+    """the yardstick: existing calls on lvf_cloud_deskew of the plain call's picks"""
+    from lvio_fusion_amd import api
+    E = syn.lidar_extrinsic()
+    prm = api.lidar_params(**kw)
+    tr = api.Trajectory(ctx, stamps, poses)
+    res = prm.resolution
+    cg, cs = api.Cloud(ctx, picks_g.reshape(-1, 4)), api.Cloud(ctx, picks_s.reshape(-1, 4))
+    dg, ds = cg.deskew(tr, frame_time, frame_pose, prm.cycle_time, E), cs.deskew(tr, frame_time, frame_pose, prm.cycle_time, E)
+    sv = ds.voxel_filter(2 * res); sr = sv.radius_outlier_filter(4 * res, 4); sf = sr.transform(E)
+    gv = dg.voxel_filter(2 * res); gp, _, _ = gv.segment_plane(np.float32(0.1) * np.float32(res), 100, prm.ransac_seed); gf = gp.transform(E)
+    out = dg.download(), ds.download(), gf.download(), sf.download()
+    for h in (cg, cs, dg, ds, sv, sr, sf, gv, gp, gf, tr):
+        h.close()
+    return out
+
+
+@pytest.mark.parametrize("host", [False, True], ids=["device_counts", "host_counts"])
+@pytest.mark.parametrize("name,newest", [("third_31", True), ("az600_31", True), ("az600_32", False)])
+def test_extract_picks_and_clouds_equal_the_composition(ctx, oracle, name, newest, host):
+    """3 keyframes 0.1 s apart at 15 m/s and 0.3 rad/s; the frame is the newest keyframe (second half of the sweep extrapolated) or the middle one"""
+    scan, kw = scan_case(name)
+    stamps, poses = dc.drive()
+    k = 2 if newest else 1
+    (g0, s0, d0), (g1, s1, d1) = extract_both(ctx, scan, kw, stamps, poses, stamps[k], poses[k], host)
+    dg, ds, gf, sf = composition(ctx, d0["ground_raw"], d0["surf_raw"], kw, stamps, poses, stamps[k], poses[k])
+    assert d1["ground_raw"].shape == dg.shape and np.array_equal(bits(d1["ground_raw"]), bits(dg)), "deskewed ground picks"
+    assert d1["surf_raw"].shape == ds.shape and np.array_equal(bits(d1["surf_raw"]), bits(ds)), "deskewed surf picks"
+    assert g1.shape == gf.shape and np.array_equal(bits(g1), bits(gf)), "points_ground"
+    assert s1.shape == sf.shape and np.array_equal(bits(s1), bits(sf)), "points_surf"
+    for key in ("label_mat", "ground_mat", "range_mat"):          # the other taps are the plain call's
+        assert np.array_equal(d1[key], d0[key]), key
+    assert d1["n_filtered"] == d0["n_filtered"] and d1["n_segmented"] == d0["n_segmented"]
+    if name.startswith("third"):
+        assert len(dg) == 0 and len(ds) == 0 and len(g1) == 0 and len(s1) == 0          # (see scan_case)
+        return
+    assert len(dg) > 5000 and len(ds) > 5000 and len(g1) > 200 and len(s1) > 200
+    assert np.abs(dg[:, :3] - d0["ground_raw"][:, :3]).max() > 0.3 and not np.array_equal(bits(g1), bits(g0))
+    # negative time offsets: the oracle's picks of this scan (equal to the device's, test_gpu_extract.py) carry them in the ground cloud
+    ref = oracle.lidar_extract(scan, syn.lidar_extrinsic(), horizon_scan=600)
+    _, delta, _ = dr.point_times(ref["ground_raw"][:, 3], 0.0, dc.CYCLE)
+    assert np.array_equal(bits(ref["ground_raw"]), bits(d0["ground_raw"])) and (delta < 0).sum() > 50
+
+
+def test_extract_full_scan_once(ctx):
+    scan, kw = scan_case("full_33")
+    stamps, poses = dc.drive()
+    (g0, s0, d0), (g1, s1, d1) = extract_both(ctx, scan, kw, stamps, poses, stamps[2], poses[2], False)
+    dg, ds, gf, sf = composition(ctx, d0["ground_raw"], d0["surf_raw"], kw, stamps, poses, stamps[2], poses[2])
+    assert len(dg) > 20000 and len(ds) > 20000
+    assert np.array_equal(bits(d1["ground_raw"]), bits(dg)) and np.array_equal(bits(d1["surf_raw"]), bits(ds))
+    assert g1.shape == gf.shape and np.array_equal(bits(g1), bits(gf)) and s1.shape == sf.shape and np.array_equal(bits(s1), bits(sf))
+
+
+@pytest.mark.parametrize("name,speed,yaw_rate", [("third_31", 15.0, 0.3), ("az600_31", 15.0, 0.3), ("az600_32", -120.0, 2.0)])
+def test_extract_count_paths_agree(ctx, name, speed, yaw_rate):
+    """device-counted against host-counted path, bit for bit — the last case with a motion large enough (120 m/s in reverse: the far picks ahead
+    were taken from further ahead) that deskewed picks leave the max_range ball the device-counted tail would otherwise size its voxel keys and
+    radius grid from"""
+    from lvio_fusion_amd import api
+    scan, kw = scan_case(name)
+    stamps, poses = dc.drive(speed=speed, yaw_rate=yaw_rate)
+    out = {host: extract_both(ctx, scan, kw, stamps, poses, stamps[2], poses[2], host) for host in (False, True)}
+    for k in (0, 1):
+        assert out[False][1][k].shape == out[True][1][k].shape and np.array_equal(bits(out[False][1][k]), bits(out[True][1][k])), (name, k)
+    for key in ("ground_raw", "surf_raw", "label_mat", "range_mat"):
+        assert np.array_equal(bits(out[False][1][2][key]), bits(out[True][1][2][key])), (name, key)
+    if abs(speed) > 100.0:
+        # chosen on the CPU: the restatement's deskew of the plain picks leaves the range gate
+        d0 = out[False][0][2]
+        p2 = np.concatenate([dr.deskew(d0[key], stamps, poses, stamps[2], poses[2], dc.CYCLE, syn.lidar_extrinsic())[0] for key in ("ground_raw", "surf_raw")])
+        beyond = int((np.linalg.norm(p2, axis=1) > api.lidar_params().max_range).sum())
+        print("%d of %d deskewed picks lie beyond max_range" % (beyond, len(p2)))
+        assert beyond >= 1
+        assert len(out[False][1][0]) > 50 and len(out[False][1][1]) > 50
+
+
+def test_extract_one_pose_equals_plain(ctx):
+    scan, kw = scan_case("az600_31")
+    stamps, poses = dc.drive()
+    for host in (False, True):
+        (g0, s0, d0), (g1, s1, d1) = extract_both(ctx, scan, kw, stamps[:1], poses[:1], stamps[2], poses[2], host)
+        assert np.array_equal(bits(g0), bits(g1)) and np.array_equal(bits(s0), bits(s1)) and len(g0) > 200
+        assert np.array_equal(bits(d0["ground_raw"]), bits(d1["ground_raw"])) and np.array_equal(bits(d0["surf_raw"]), bits(d1["surf_raw"]))
+
+
+def test_refusals_on_the_host(ctx):
+    """bad stamps, a null trajectory, a zero quaternion, non-finite values: LVF_ERR_INVALID with a text, before anything is launched"""
+    import ctypes as C
+    from lvio_fusion_amd import api
+    stamps, poses = dc.drive()
+    E = syn.lidar_extrinsic()
+    zero_q = poses.copy(); zero_q[1, :4] = 0.0
+    nan_t = poses.copy(); nan_t[2, 5] = np.nan
+
+    def refused(fn, needle):
+        with pytest.raises(api.LvfError) as e:
+            fn()
+        assert "lvf error 1" in str(e.value) and needle in str(e.value), str(e.value)
+
+    refused(lambda: api.Trajectory(ctx, stamps[[0, 2, 1]], poses), "increase")
+    refused(lambda: api.Trajectory(ctx, stamps[[0, 1, 1]], poses), "increase")
+    refused(lambda: api.Trajectory(ctx, stamps, zero_q), "quaternion")
+    refused(lambda: api.Trajectory(ctx, stamps, nan_t), "non-finite")
+    refused(lambda: api.Trajectory(ctx, np.array([0.0, np.inf, 1.0]), poses), "finite")
+    h = C.c_void_p()
+    assert ctx.L.lvf_trajectory_create(ctx.h, api._dp(stamps), api._dp(poses), 0, C.byref(h)) == 1 and b"at least one" in ctx.L.lvf_last_error()
+    tr = api.Trajectory(ctx, stamps, poses)
+    refused(lambda: tr.append(stamps[-1], poses[0]), "after the last")
+    refused(lambda: tr.append(1.0, zero_q[1]), "quaternion")
+    refused(lambda: tr.set_pose(3, poses[0]), "outside")
+    refused(lambda: tr.set_pose(0, nan_t[2]), "non-finite")
+    assert len(tr) == 3
+    c = api.Cloud(ctx, dc.sweep_cloud(10))
+    refused(lambda: c.deskew(None, 0.1, poses[1], dc.CYCLE, E), "null trajectory")
+    refused(lambda: c.deskew(tr, 0.1, zero_q[1], dc.CYCLE, E), "quaternion")
+    refused(lambda: c.deskew(tr, np.nan, poses[1], dc.CYCLE, E), "frame time")
+    refused(lambda: c.deskew(tr, 0.1, poses[1], 0.0, E), "cycle_time")
+    scan = dc.sweep_cloud(64)
+    refused(lambda: api.lidar_extract_deskewed(ctx, scan, E, None, 0.1, poses[1]), "null trajectory")
+    refused(lambda: api.lidar_extract_deskewed(ctx, scan, E, tr, 0.1, zero_q[1]), "quaternion")
+    # nothing was left behind: the objects still work
+    d = c.deskew(tr, 0.1, poses[1], dc.CYCLE, E)
+    assert len(d) == 10
+    for x in (d, c, tr):
+        x.close()
