@@ -523,6 +523,12 @@ int lvf_problem_gradient(lvf_problem* p, const lvf_solver_options* o, double* gc
  * after 20 us, so the retry path (LVF_WHY_HANDOVER -> un-chained re-run, lvf_solver_summary::hand_over_retries) can be exercised on an
  * idle GPU.  Also re-enables chaining for the problem.  Not part of the reference surface. */
 int lvf_problem_debug_force_handover_timeout(lvf_problem* p, int n);
+/* Diagnostic: 1 when the problem's current launch chain takes the (v, ba, bg) back substitution as one product with the matrix G formed
+ * under the dense factorisation, 0 when it runs the sequential sparse levels (environment LVF_BACK_PRODUCT=0, more sparse levels than block
+ * steps, or the two-launch back substitution); negative on error.  Builds the chain if it is stale.  It describes the problem's OWN
+ * single-window chain: a batch (lvf_problem_batch_*) always runs the sequential levels, whatever this returns for its members.  Not part of
+ * the reference surface. */
+int lvf_problem_debug_back_product(lvf_problem* p);
 /* Diagnostic (environment LVF_LM_HISTORY=1 when the problem's launch chain is built): out512 receives eight doubles per closed pass of the
  * last device-loop solve, slot = iteration & 63: {iteration, cost at the point, candidate cost, model cost change, accepted, failure flag,
  * trust-region radius used, gradient max norm}.  LVF_ERR_STATE without the environment variable. */

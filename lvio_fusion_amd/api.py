@@ -1108,6 +1108,10 @@ class Problem:
         """test hook: the next n chained hand-overs of this problem time out (lvf_problem_debug_force_handover_timeout)"""
         _chk(self.ctx.L.lvf_problem_debug_force_handover_timeout(self.h, int(n)))
 
+    def debug_back_product(self):
+        """1 when the current chain takes the (v, ba, bg) back substitution as a product with G, 0 for the sequential levels (lvf_problem_debug_back_product)"""
+        return int(self.ctx.L.lvf_problem_debug_back_product(self.h))
+
     def stage_times(self, opt, radius=1e4, reps=10, spans=False):
         """[(stage name, average microseconds, launches)] of `reps` LM iterations from the current state: the sum of the stage's KERNEL
         durations (start / stop events recorded with every launch — the dispatch timestamps rocprofv3's kernel trace reports).

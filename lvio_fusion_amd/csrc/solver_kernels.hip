@@ -104,6 +104,9 @@ struct lvf_problem {
   lvf::DevBuf<double> dbg_hist;                 // LVF_LM_HISTORY=1: the decisions of the last solve (lvf_problem_debug_history)
   lvf::DevBuf<double> sp_sync;                  // arrival counters of sparse levels chained inside one launch (one 8-byte slot per level, an int in each; cleared with the accumulators)
   lvf::DevBuf<double> sp_W, sp_L, Dinv;         // Dinv: L_kk^-T of every 64x64 diagonal block of the dense corner
+  // product form of the sparse back substitution (lvf::GRide): G [9 n_nodes][ldG], allocated by the chain that uses it; sp_gmap [n_nodes][ldG]:
+  // which of a node's own rows (index into sp_rows) a dense-corner / augmented column is, or -1
+  lvf::DevBuf<double> sp_G; lvf::DevBuf<int> sp_gmap; int ldG = 0;
   lvf::DevBuf<double> Ldiag;                    // the factored diagonal blocks L_kk [nb][64][64] (NOT stored back into S: see chol_step_body)
   std::vector<int> perm_h;
   lvf::DevBuf<double> B, gc, C, gr, E, Cd, S, dxc, dxl, scal;
@@ -2319,11 +2322,66 @@ __device__ __forceinline__ void chol_step_body(const int bx, const CholArgs& A, 
   }
   if (dbg) dbg[5] = wall_clock64();
 }
-__global__ __launch_bounds__(kCT) void k_chol_step(CholArgs a, int kb) { chol_step_body<true>(blockIdx.x, a, kb); }
+// The product form of the sparse back substitution (Chain::back_product).  x_b = L_bb^-T (y_b - W_b^T x_N) is linear in the dense-corner
+// solution: composed over the levels, x_sparse = G [x_dense ; -1] with nine rows of G per eliminated (v, ba, bg) node and one column per
+// dense-corner unknown plus the augmented column (leading dimension ldG, a multiple of 16; the padding columns are zero).  With node b's row
+// list N, its stored W (component-major) and Linv = L_bb^-1:
+//     G_b[q][:] = sum_{t >= q} Linv_b[t][q] * sum_{r in N} (-W_b[r][t]) X_r[:]
+// where X_r is the unit row of column r for a dense-corner / augmented row and the G row of the owning node for a sparse row (always of a
+// higher level; the node of sparse column c is c / 9, so that row is G row c).  Nothing here depends on the step, and W / Linv are final
+// before the first block step of the dense factorisation: the rows are formed by workgroups riding BEHIND the block-step launches (which
+// leave most of the chip idle), level n_levels - 1 - kb in launch kb, so the launch boundaries order the levels.  One workgroup per node, one
+// thread per column, no LDS and no barrier: the row list is ascending, i.e. the sparse neighbours come first, and `map` (host-built with the
+// plan) tells a column which of the node's own rows it is.
+struct GRide { int n, first; GP<const SpNode> nodes; GP<const int> rows; GP<const double> W; int wstride; GP<const double> Linv; GP<const int> map; GP<double> G; int ldG, off; GP<const int> done; };
+__device__ __forceinline__ void back_product_ride(const int vb, const GRide& R) {
+  if (vb >= R.n) return;
+  if (R.done && *R.done) return;
+  const int b = R.first + vb;
+  const SpNode nd = R.nodes[b];
+  const int* rows = R.rows + nd.row_off;
+  const double* W = R.W + nd.row_off;                  // component t of the node's row r: W[t * wstride + r]
+  const double* Li = R.Linv + (size_t)b * 81;
+  double* G = R.G;
+  int ms = 0;
+  while (ms < nd.m && rows[ms] < R.off) ++ms;          // the sparse neighbours' rows
+  for (int j = threadIdx.x; j < R.ldG; j += kCT) {
+    double T[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) T[t] = 0.0;
+    for (int r = 0; r < ms; ++r) {
+      const double x = G[(size_t)rows[r] * R.ldG + j];
+#pragma unroll
+      for (int t = 0; t < 9; ++t) T[t] -= W[(size_t)t * R.wstride + r] * x;
+    }
+    const int g = R.map[(size_t)b * R.ldG + j];        // (global item index: already includes row_off)
+    if (g >= 0) {
+#pragma unroll
+      for (int t = 0; t < 9; ++t) T[t] -= R.W[(size_t)t * R.wstride + g];
+    }
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+      double v = 0.0;
+#pragma unroll
+      for (int t = q; t < 9; ++t) v += Li[t * 9 + q] * T[t];
+      G[(size_t)(9 * b + q) * R.ldG + j] = v;
+    }
+  }
+}
+// (the column and trailing-update workgroups keep the lowest indices — they are the critical path and are dispatched first; the riders sit behind them)
+__global__ __launch_bounds__(kCT) void k_chol_step(CholArgs a, int kb, GRide g) {
+  const int own = chol_step_grid(a.nb, kb);
+  if ((int)blockIdx.x >= own) { back_product_ride((int)blockIdx.x - own, g); return; }
+  chol_step_body<true>(blockIdx.x, a, kb);
+}
 __global__ __launch_bounds__(kCT) void k_chol_step_b(const CholArgs* __restrict__ t, int kb) { chol_step_body<true>(blockIdx.x, t[blockIdx.y], kb); }
 __global__ __launch_bounds__(kCT) void k_chol_step_bt(const CholArgs* __restrict__ t, int kb) { chol_step_body<true>(blockIdx.y, t[blockIdx.x], kb); }
 // LVF_CHOL_SUBBLOCK=0: the pair-pivot sweep, as second instantiations (no branch inside the chain)
-__global__ __launch_bounds__(kCT) void k_chol_step_pp(CholArgs a, int kb) { chol_step_body<false>(blockIdx.x, a, kb); }
+__global__ __launch_bounds__(kCT) void k_chol_step_pp(CholArgs a, int kb, GRide g) {
+  const int own = chol_step_grid(a.nb, kb);
+  if ((int)blockIdx.x >= own) { back_product_ride((int)blockIdx.x - own, g); return; }
+  chol_step_body<false>(blockIdx.x, a, kb);
+}
 __global__ __launch_bounds__(kCT) void k_chol_step_pp_b(const CholArgs* __restrict__ t, int kb) { chol_step_body<false>(blockIdx.x, t[blockIdx.y], kb); }
 __global__ __launch_bounds__(kCT) void k_chol_step_pp_bt(const CholArgs* __restrict__ t, int kb) { chol_step_body<false>(blockIdx.y, t[blockIdx.x], kb); }
 static bool chol_subblock_on() { static const bool on = [] { const char* e = std::getenv("LVF_CHOL_SUBBLOCK"); return !(e && e[0] == '0'); }(); return on; }
@@ -2681,6 +2739,10 @@ constexpr int kBT = 512, kBParts = kBT / 64, kBackPre = 256 / kBParts, kBackInv 
 // pose_ready (merged back-substitution + step tail, k_backsolve_tail): once the dense corner is solved the POSE part of the step (natural
 // unknowns [0, n_pose)) is written out and *pose_ready is raised (release, agent scope) — what the landmark back-substitution waits for
 struct BackArgs { GP<const double> Sd; int ld, d; GP<const double> Dinv; GP<double> xout; SpBack sp; GP<const int> done; GP<const double> Ldiag; GP<int> pose_ready = nullptr; int n_pose = 0; int pose_fenced = 0; };
+// LEVELS = false (the product form, k_backsolve_tail with Chain::back_product): the dense corner only.  The WHOLE dense-corner solution is
+// published — the plan may leave (v, ba, bg) blocks in the corner's padding, and the sibling workgroups' product with G reads them — and the
+// sparse items, the stored L_bb^-1 and the levels are neither requested nor run.
+template <bool LEVELS = true>
 __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
   const int dv = done_flag_issue(A.done);
   const double* S = A.Sd; const int ld = A.ld, d = A.d; const double* Dinv = A.Dinv; double* xout = A.xout; const SpBack& sp = A.sp;
@@ -2729,6 +2791,7 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
   // the stored L_bb^-1 and the node table go to LDS: ALL of a thread's requests are issued before the first LDS write (written as a
   // copy loop the compiler waits for every load in turn — eight dependent round trips at 50 keyframes, 4 of this kernel's 30 us)
   constexpr int kLinvPre = 8;
+  if constexpr (LEVELS) {
   double lpre[kLinvPre];
   const int n_linv = sp.linv_in_lds ? 81 * sp.n_nodes : 0;
 #pragma unroll
@@ -2741,14 +2804,16 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
   if (tid < sp.n_nodes) { snode[2 * tid] = ndpre.row_off; snode[2 * tid + 1] = ndpre.m; }
   for (int i = tid + kBT; i < sp.n_nodes; i += kBT) { const SpNode nd = sp.nodes[i]; snode[2 * i] = nd.row_off; snode[2 * i + 1] = nd.m; }
   asm volatile("" ::: "memory");
+  }
   // ---- requests for the sparse tail, AFTER the first dense prefetch: loads return in order, so the dense corner does not wait
   // for them and they land while it is being solved
-  int tR[kTailPre], tK[kTailPre];
-  double tW[kTailPre][9];
+  constexpr int kTailRegs = LEVELS ? kTailPre : 1;      // (the product form holds none of them)
+  int tR[kTailRegs], tK[kTailRegs];
+  double tW[kTailRegs][9];
 #pragma unroll
-  for (int u = 0; u < kTailPre; ++u) {
+  for (int u = 0; u < kTailRegs; ++u) {
     const int g = tid + kBT * u;
-    const bool ok = g < sp.total_items;
+    const bool ok = LEVELS && g < sp.total_items;
     tR[u] = -1; tK[u] = 0;
 #pragma unroll
     for (int q = 0; q < 9; ++q) tW[u][q] = 0.0;
@@ -2810,7 +2875,15 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
     // L2).  pose_fenced (LVF_CHAIN_FENCE=2) adds the fences back for A/B.
     {
       int last = -1;
-      for (int i = tid; i < A.n_pose; i += kBT) { __hip_atomic_store(xout + i, sm[sp.perm[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); last = i; }
+      if constexpr (LEVELS) {
+        for (int i = tid; i < A.n_pose; i += kBT) { __hip_atomic_store(xout + i, sm[sp.perm[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); last = i; }
+      } else {
+        // every unknown that lives in the dense corner: the poses and the (v, ba, bg) blocks the plan left there
+        for (int i = tid; i < sp.d_total; i += kBT) {
+          const int pi = sp.perm[i];
+          if (pi >= sp.off) { __hip_atomic_store(xout + i, sm[pi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); last = i; }
+        }
+      }
       // (a store is acknowledged to the wave before it is necessarily performed; a load of the same address is ordered behind it and RETURNS:
       // once it is back — the s_waitcnt below — the store is where the consumers read.  Round 3 met the same with returnless atomic adds.)
       if (last >= 0) { const double chk = __hip_atomic_load(xout + last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); asm volatile("" ::"v"(chk)); }
@@ -2819,6 +2892,11 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");          // every wave's stores have been performed before the flag goes up
     if (tid == 0) __hip_atomic_store((int*)A.pose_ready, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  if constexpr (!LEVELS) {
+    mark();
+    if (sp.dbg && tid == 0) sp.dbg[63] = (unsigned long long)stamp;
+    return;
+  }
   // ---- sparse levels, last eliminated first
   for (int lv = sp.lv.n - 1; lv >= 0; --lv) {
     const int first = sp.lv.first[lv], count = sp.lv.count[lv], item0 = sp.item0[lv], item1 = item0 + sp.items[lv];
@@ -2826,7 +2904,7 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
     if (staged) {
       // (1) products -W x_r of every (block, row) item into LDS (stride 9 doubles: conflict-free)
 #pragma unroll
-      for (int u = 0; u < kTailPre; ++u) {
+      for (int u = 0; u < kTailRegs; ++u) {
         const int g = tid + kBT * u;
         if (g >= item0 && g < item1) {
           const double xr = (tR[u] == sp.aug) ? -1.0 : sm[tR[u]];          // the rhs row carries y_b itself
@@ -3026,10 +3104,117 @@ __global__ __launch_bounds__(kT) void k_step_tail_bt(const TailArgs* __restrict_
 // (apply_step_body) — and workgroups 1.. are the landmark pass: they wait for the pose increments inside the launch (bounded, like the
 // chained sparse levels: on a time-out the hand-over flag is raised, the pass is not judged and the host re-runs it with the two launches
 // of old; SpSrc has the rules) and then walk the landmarks.  One launch boundary less and the two tails overlap: 39 -> 29 us at configs[3].
-struct BackTailArgs { BackArgs back; TailArgs tail; int g_lm; int fenced; unsigned timeout_ticks; GP<int> fail; };
+// Product form (g_prod > 0, Chain::back_product): workgroup 0 solves the dense corner only and publishes all of it; the (v, ba, bg) part of
+// the step no longer runs behind it as five sequential levels but in g_prod further sibling workgroups, each owning kpw keyframes: they
+// wait for the same flag as the landmark workgroups, take one product with their rows of G (formed under the dense factorisation:
+// back_product_ride) and apply the (v, ba, bg) part of the step for their keyframes.  The launch then ends at flag + max(landmark pass,
+// product) instead of flag + levels.
+struct BackTailArgs { BackArgs back; TailArgs tail; int g_lm; int fenced; unsigned timeout_ticks; GP<int> fail;
+                      int g_prod = 0, kpw = 0, ldG = 0; GP<const double> G = nullptr; GP<const int> iperm = nullptr; };
+// the bounded wait of the consumers of pose_ready (SpSrc has the rules)
+__device__ __forceinline__ void wait_pose_ready(const BackTailArgs& a) {
+  if (threadIdx.x == 0) {
+    const unsigned long long t0 = wall_clock64();
+    while (__hip_atomic_load((int*)a.back.pose_ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
+      __builtin_amdgcn_s_sleep(16);
+      if (wall_clock64() - t0 > (unsigned long long)a.timeout_ticks) { atomicMax(a.fail, kFailHandover + 90000); break; }
+    }
+  }
+  __syncthreads();
+  if (a.fenced) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+// G workgroup vb: keyframes [vb kpw, vb kpw + kpw).  Row (keyframe k, component c) is natural unknown dp + 9 k + c and S column perm[..]:
+// below `off` it is G row perm[..] (an eliminated node), otherwise the block stayed in the dense corner and its increment is read from the
+// published solution — either way it is applied here, exactly once.  16 lanes per row, 32 rows per pass; a lane's share of the first pass
+// is requested into a fixed register window BEFORE the wait (what does not fit, and further passes, are read from memory afterwards).
+constexpr int kGPre = 24;
+__device__ __forceinline__ void back_product_body(const int vb, const BackTailArgs& a) {
+  const TailArgs& T = a.tail; const SpBack& sp = a.back.sp;
+  extern __shared__ double gsm[];          // xd[ldG]: [x_dense ; -1 ; 0 ..] | xs[9 kpw]: this workgroup's rows of the step
+  double* xd = gsm; double* xs = gsm + a.ldG;
+  const int tid = threadIdx.x, q = tid & 15, row = tid >> 4, ldG = a.ldG, nu = ldG >> 4;
+  const int k0 = vb * a.kpw, nrows = 9 * min(a.kpw, T.n_kf - k0), i0 = T.dp + 9 * k0;      // the rows' natural unknowns are contiguous from i0
+  unsigned long long* dbg = (sp.dbg && vb == 0 && tid == 0) ? sp.dbg + 40 : nullptr;
+  if (dbg) dbg[0] = wall_clock64();
+  // ---- requests: nothing below depends on the step
+  const int scol = row < nrows ? sp.perm[i0 + row] : -1;
+  const bool in_g = scol >= 0 && scol < sp.off;
+  const double* grow = a.G + (size_t)(in_g ? scol : 0) * ldG + q;
+  double g[kGPre];
+#pragma unroll
+  for (int u = 0; u < kGPre; ++u) g[u] = (in_g && u < nu) ? grow[16 * u] : 0.0;
+  const int ip0 = tid < ldG ? a.iperm[sp.off + tid] : -1;
+  // the operands of this thread's unknown (thread t < nrows applies row t)
+  const bool mine = tid < nrows;
+  const int ui = i0 + (mine ? tid : 0), uk = k0 + (mine ? tid / 9 : 0), uc = mine ? tid % 9 : 0;
+  const double* const Bt = tail_B(T); const double* const gct = tail_gc(T);
+  const double* sv = uc < 3 ? (const double*)T.s.vel : (uc < 6 ? (const double*)T.s.ba : (const double*)T.s.bg);
+  double* cv = uc < 3 ? (double*)T.vel2 : (uc < 6 ? (double*)T.ba2 : (double*)T.bg2);
+  const double h = mine ? Bt[(size_t)ui * T.ld + ui] : 0.0, h0d = mine ? T.jac.h0[ui] : 0.0, gci = mine ? gct[ui] : 0.0;
+  const double sval = mine ? sv[3 * uk + uc % 3] : 0.0;
+  const int cm = (mine && T.pose_const) ? T.pose_const[uk] : 0;      // bit 0: pose, bits 1..3: v, ba, bg held constant
+  const int frozen = *T.jac.frozen;
+  const double inv_radius = 1.0 / *T.radius;
+  wait_pose_ready(a);
+  if (dbg) dbg[1] = wall_clock64();
+  // ---- the dense solution, read at the coherence point
+  for (int j = tid; j < ldG; j += kBT) {
+    const int ip = j == tid ? ip0 : a.iperm[sp.off + j];
+    xd[j] = ip >= 0 ? __hip_atomic_load(T.dxc + ip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (ip == -2 ? -1.0 : 0.0);      // (-2: the augmented column)
+  }
+  __syncthreads();
+  if (dbg) dbg[2] = wall_clock64();
+  // ---- rows of x
+  {
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < kGPre; ++u) if (u < nu) s += g[u] * xd[q + 16 * u];
+    if (in_g) for (int u = kGPre; u < nu; ++u) s += grow[16 * u] * xd[q + 16 * u];
+    s = row16_sum(s);
+    if (q == 0 && row < nrows) {
+      if (in_g) { xs[row] = s; a.back.xout[i0 + row] = s; }      // (a block of the dense corner was written out by workgroup 0)
+      else xs[row] = xd[scol - sp.off];
+    }
+  }
+  for (int r0 = kBT / 16; r0 < nrows; r0 += kBT / 16) {             // further passes (more than 3 keyframes per workgroup)
+    const int rw = r0 + row;
+    const int sc = rw < nrows ? sp.perm[i0 + rw] : -1;
+    const bool ing = sc >= 0 && sc < sp.off;
+    double s = 0.0;
+    if (ing) { const double* gr = a.G + (size_t)sc * ldG + q; for (int u = 0; u < nu; ++u) s += gr[16 * u] * xd[q + 16 * u]; }
+    s = row16_sum(s);
+    if (q == 0 && rw < nrows) {
+      if (ing) { xs[rw] = s; a.back.xout[i0 + rw] = s; }
+      else xs[rw] = xd[sc - sp.off];
+    }
+  }
+  __syncthreads();
+  if (dbg) dbg[3] = wall_clock64();
+  // ---- the (v, ba, bg) part of the step for these keyframes: candidate state and the unknowns' share of the model cost change, the norms
+  // and the gradient's max norm (apply_step_body's PARTS bit 1, one thread per unknown)
+  double m = 0.0, n2 = 0.0, gm = 0.0, x2 = 0.0;
+  if (mine) {
+    const double dx = xs[tid];
+    cv[3 * uk + uc % 3] = sval + dx;
+    m = -0.5 * dx * (lm_damping(h, frozen ? h0d : h) * inv_radius * dx - gci);
+    n2 = dx * dx;
+    gm = fabs(gci);
+    x2 = (cm & (2 << (uc / 3))) ? 0.0 : sval * sval;
+  }
+  block_add(m, T.scal + SC_MODEL); block_add(n2, T.scal + SC_DXNORM); block_add(x2, T.scal + SC_XNORM);
+  for (int o = 32; o > 0; o >>= 1) gm = fmax(gm, __shfl_down(gm, o));
+  if ((tid & 63) == 0 && gm != 0.0) atomicMax(reinterpret_cast<unsigned long long*>(T.scal + SC_GMAX + (blockIdx.x & (kStripes - 1))), (unsigned long long)__double_as_longlong(gm));
+  if (dbg) dbg[4] = wall_clock64();
+}
 __global__ __launch_bounds__(kBT) void k_backsolve_tail(BackTailArgs a) {
   if (a.back.done && *a.back.done) return;                      // (every workgroup tests the same flag: nobody waits for a producer that has left)
   const TailArgs& T = a.tail;
+  if (blockIdx.x == 0 && a.g_prod > 0) {
+    chol_backsolve_body<false>(a.back);
+    if (a.back.sp.dbg && threadIdx.x == 0) a.back.sp.dbg[55] = wall_clock64();      // LVF_BACK_TIMING: workgroup 0 is done
+    return;
+  }
+  if ((int)blockIdx.x >= 2 + a.g_lm) { back_product_body((int)blockIdx.x - 2 - a.g_lm, a); return; }
   if (blockIdx.x == 0) {
     chol_backsolve_body(a.back);
     // the whole step is in xout (this workgroup wrote it): the velocities' and biases' part is applied here, with its share of the model cost
@@ -3044,17 +3229,9 @@ __global__ __launch_bounds__(kBT) void k_backsolve_tail(BackTailArgs a) {
     if (a.back.sp.dbg && threadIdx.x == 0) a.back.sp.dbg[55] = wall_clock64();      // LVF_BACK_TIMING: the step is applied
     return;
   }
-  unsigned long long* ldbg = (a.back.sp.dbg && (blockIdx.x == 2 || blockIdx.x == gridDim.x - 1) && threadIdx.x == 0) ? a.back.sp.dbg + (blockIdx.x == 2 ? 56 : 59) : nullptr;
+  unsigned long long* ldbg = (a.back.sp.dbg && (blockIdx.x == 2 || (int)blockIdx.x == 1 + a.g_lm) && threadIdx.x == 0) ? a.back.sp.dbg + (blockIdx.x == 2 ? 56 : 59) : nullptr;
   if (ldbg) ldbg[0] = wall_clock64();
-  if (threadIdx.x == 0) {
-    const unsigned long long t0 = wall_clock64();
-    while (__hip_atomic_load((int*)a.back.pose_ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-      __builtin_amdgcn_s_sleep(16);
-      if (wall_clock64() - t0 > (unsigned long long)a.timeout_ticks) { atomicMax(a.fail, kFailHandover + 90000); break; }
-    }
-  }
-  __syncthreads();
-  if (a.fenced) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  wait_pose_ready(a);
   if (ldbg) ldbg[1] = wall_clock64();
   if (blockIdx.x == 1) {
     // the pose part of the step: candidate poses and the pose unknowns' share of the model cost change / step norm (the increments are read
@@ -3372,6 +3549,8 @@ struct Chain {
   BackArgs back{}; size_t back_lds = 0;
   TailArgs tail{}; size_t tail_lds = 0;
   bool back_tail_merged = false; BackTailArgs bt{}; size_t bt_lds = 0;      // k_backsolve_tail (single-window chain, chained levels allowed)
+  // the sparse back substitution as ONE product with G, formed by riders of the block-step launches (GRide; LVF_BACK_PRODUCT=0 turns it off)
+  bool back_product = false; GRide gride{};
   CostArgs cost{};
   DecideArgs dec{};
   // the fused chain (AccSel; LVF_FUSED_LIN=0 turns it off): the second accumulator set's pointers and the standby clears (k_tf_reduce: stand0
@@ -3721,9 +3900,30 @@ static int build_chain(lvf_problem* p) {
       c.bt_lds = std::max(c.back_lds, c.tail_lds);
       if (c.bt_lds > 64 * 1024 && !bt_big_lds) c.back_tail_merged = false;
     }
+    // The product form: on where the levels can be dealt one to a block-step launch (n_levels <= nb; level n_levels - 1 - kb rides in launch
+    // kb) and the merged launch is in use.  Its G workgroups must fit the chip in ONE round beside workgroup 0, the pose workgroup and the
+    // landmark workgroups (about one workgroup of this launch fits a compute unit; a workgroup that has to wait for one starts after the
+    // others are done), each owns whole keyframes, one thread per unknown.
+    static const bool prod_on = [] { const char* e = std::getenv("LVF_BACK_PRODUCT"); return !(e && e[0] == '0'); }();
+    c.back_product = false; c.gride = GRide{}; c.gride.n = 0;
+    if (prod_on && c.back_tail_merged && c.n_levels >= 1 && c.n_levels <= p->nb && p->ldG > 0) {
+      static const int n_cu = [] { int dev = 0, n = 0; return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }();
+      const int room = n_cu - 2 - c.bt.g_lm;
+      const int kpw = room >= 1 ? (p->n_kf + std::min(room, p->n_kf) - 1) / std::min(room, p->n_kf) : 0;
+      const int n_nodes = p->sp_levels.first[c.n_levels - 1] + p->sp_levels.count[c.n_levels - 1];
+      if (kpw >= 1 && 9 * kpw <= kBT) {
+        LVF_TRY(p->sp_G.ensure((size_t)9 * n_nodes * p->ldG));
+        BackTailArgs& m = c.bt;
+        m.kpw = kpw; m.g_prod = (p->n_kf + kpw - 1) / kpw; m.ldG = p->ldG; m.G = p->sp_G.p; m.iperm = p->iperm.p;
+        c.bt_lds = std::max(c.bt_lds, (size_t)(p->ldG + 9 * kpw) * sizeof(double));
+        c.gride = GRide{0, 0, p->sp_nodes.p, p->sp_rows.p, p->sp_W.p, p->sp_wstride, p->sp_L.p, p->sp_gmap.p, p->sp_G.p, p->ldG, p->off, done};
+        c.back_product = true;
+      }
+    }
     static const bool chain_info = std::getenv("LVF_CHAIN_INFO") != nullptr;
-    if (chain_info) std::fprintf(stderr, "chain: n_kf %d n_lm %d fast %d has_imu %d early %d compact %d levels %d no_chain %d merged_level0 %d back_tail_merged %d (g_lm %d, lds %zu)\n", p->n_kf, p->n_lm, (int)c.fast, (int)c.has_imu,
-                                 (int)c.early, (int)p->compact, c.n_levels, (int)p->no_chain, (int)c.merged_level0, (int)c.back_tail_merged, c.bt.g_lm, c.bt_lds);
+    if (chain_info) std::fprintf(stderr, "chain: n_kf %d n_lm %d fast %d has_imu %d early %d compact %d levels %d no_chain %d merged_level0 %d back_tail_merged %d (g_lm %d, lds %zu) back_product %d (nb %d, %d G workgroups of %d keyframes)\n", p->n_kf, p->n_lm, (int)c.fast, (int)c.has_imu,
+                                 (int)c.early, (int)p->compact, c.n_levels, (int)p->no_chain, (int)c.merged_level0, (int)c.back_tail_merged, c.bt.g_lm, c.bt_lds,
+                                 (int)c.back_product, p->nb, c.bt.g_prod, c.bt.kpw);
   }
   fill_cost_visual(p, c.cost.a);
   c.cost.n_kf = p->n_kf; c.cost.s = s2; c.cost.huber = 0.0; c.cost.cost = p->scal.p + SC_COST_NEW; c.cost.done = done;
@@ -4102,8 +4302,11 @@ static int enqueue_iteration(lvf_problem* p, bool end_zero, int fused = 0) {
     CholArgs cha = c.chol;
     static const bool chol_timing = std::getenv("LVF_CHOL_TIMING") != nullptr;
     if (chol_timing) { LVF_TRY(p->dbg.ensure(128)); cha.dbg = p->dbg.p; }      // [0, 64): phases of 8 block steps; [64, 128): their sub-block stages
-    if (chol_subblock_on()) LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step, dim3(chol_step_grid(p->nb, kb)), dim3(kCT), 0, q, cha, kb);
-    else LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step_pp, dim3(chol_step_grid(p->nb, kb)), dim3(kCT), 0, q, cha, kb);
+    GRide gr = c.gride;                                   // the riders that form G: the top level first, one level per launch
+    const int glv = c.n_levels - 1 - kb;
+    if (c.back_product && glv >= 0) { gr.first = p->sp_levels.first[glv]; gr.n = p->sp_levels.count[glv]; } else gr.n = 0;
+    if (chol_subblock_on()) LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step, dim3(chol_step_grid(p->nb, kb) + gr.n), dim3(kCT), 0, q, cha, kb, gr);
+    else LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step_pp, dim3(chol_step_grid(p->nb, kb) + gr.n), dim3(kCT), 0, q, cha, kb, gr);
   }
   {
     BackArgs ba = c.back;
@@ -4114,7 +4317,7 @@ static int enqueue_iteration(lvf_problem* p, bool end_zero, int fused = 0) {
       BackTailArgs bt = c.bt;
       if (back_timing) bt.back.sp.dbg = p->dbg.p;
       if (acc) bt.tail.acc = *acc;
-      LVF_CHAIN_LAUNCH(p, ST_BACKSOLVE, k_backsolve_tail, dim3(2 + c.bt.g_lm), dim3(kBT), c.bt_lds, q, bt);
+      LVF_CHAIN_LAUNCH(p, ST_BACKSOLVE, k_backsolve_tail, dim3(2 + c.bt.g_lm + c.bt.g_prod), dim3(kBT), c.bt_lds, q, bt);
       stage_mark(p, ST_BACKSOLVE, 1);
       stage_mark(p, ST_STEP_TAIL, 0);
     } else {
@@ -4251,6 +4454,9 @@ static int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* rad
       std::fprintf(stderr, " | merged launch, us after workgroup 0's start: step applied %.2f ; first landmark workgroup starts %.2f, sees the poses %.2f, done %.2f ; last one starts %.2f, sees %.2f, done %.2f",
                    (double)(t[55] - t[0]) * 0.01, (double)(t[56] - t[0]) * 0.01, (double)(t[57] - t[0]) * 0.01, (double)(t[58] - t[0]) * 0.01, (double)(t[59] - t[0]) * 0.01,
                    (double)(t[60] - t[0]) * 0.01, (double)(t[61] - t[0]) * 0.01);
+    if (p->chain && p->chain->back_product)
+      std::fprintf(stderr, " | product form (\"step applied\" = workgroup 0 done): first G workgroup starts %.2f, sees the flag %.2f, has the dense solution %.2f, its rows %.2f, applied %.2f",
+                   (double)(t[40] - t[0]) * 0.01, (double)(t[41] - t[0]) * 0.01, (double)(t[42] - t[0]) * 0.01, (double)(t[43] - t[0]) * 0.01, (double)(t[44] - t[0]) * 0.01);
     std::fprintf(stderr, "\n");
   }
   out->cost_before = c.cost_before; out->cost_after = c.cost_after; out->model = c.model; out->dxnorm = c.dxnorm; out->xnorm = c.xnorm; out->gmax = c.gmax;
@@ -4418,6 +4624,7 @@ static int build_elimination_plan(lvf_problem* p) {
   p->sp_levels = lv;
   hipStream_t q = p->ctx->stream;
   LVF_TRY(p->perm.assign(p->perm_h.data(), p->perm_h.size(), q)); LVF_TRY(p->iperm.assign(iperm.data(), iperm.size(), q));
+  p->ldG = 0;
   if (ns) {
     rows_nat.resize(rows.size());
     for (size_t i = 0; i < rows.size(); ++i) rows_nat[i] = iperm[rows[i]];
@@ -4425,6 +4632,12 @@ static int build_elimination_plan(lvf_problem* p) {
     LVF_TRY(p->sp_nodes.assign(dn.data(), dn.size(), q)); LVF_TRY(p->sp_rows.assign(rows.data(), rows.size(), q)); LVF_TRY(p->sp_owner.assign(owner.data(), owner.size(), q));
     LVF_TRY(p->sp_W.ensure(rows.size() * 9)); LVF_TRY(p->sp_L.ensure((size_t)ns * 81));
     p->sp_wstride = (int)rows.size();
+    p->ldG = ((p->ndense + 1 + 15) / 16) * 16;
+    std::vector<int> gmap((size_t)ns * p->ldG, -1);
+    for (int s_ = 0; s_ < ns; ++s_)
+      for (int r = 0; r < dn[s_].m; ++r) { const int R = rows[dn[s_].row_off + r]; if (R >= p->off) gmap[(size_t)s_ * p->ldG + (R - p->off)] = dn[s_].row_off + r; }
+    LVF_TRY(p->sp_gmap.assign(gmap.data(), gmap.size(), q));
+    LVF_HIP(hipStreamSynchronize(q));    // (gmap goes out of scope with this block)
   }
   LVF_HIP(hipStreamSynchronize(q));      // the host vectors above go out of scope
   p->plan_key = std::move(key);
@@ -5115,6 +5328,12 @@ int lvf_problem_debug_history(lvf_problem* p, double* out512) {
   LVF_HIP(hipMemcpyAsync(out512, p->dbg_hist.p, 512 * 8, hipMemcpyDeviceToHost, p->ctx->stream));
   LVF_HIP(hipStreamSynchronize(p->ctx->stream));
   return LVF_OK;
+}
+// 1: the current chain takes the sparse back substitution as a product with G, 0: it runs the sequential levels (builds the chain if stale)
+int lvf_problem_debug_back_product(lvf_problem* p) {
+  if (!p || lvf::enter(p->ctx) != LVF_OK) return -1;
+  if (chain_stale(p) && build_chain(p) != LVF_OK) return -1;
+  return p->chain->back_product ? 1 : 0;
 }
 // test hook (see lvf.h)
 int lvf_problem_debug_force_handover_timeout(lvf_problem* p, int n) {
