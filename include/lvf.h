@@ -533,6 +533,32 @@ int lvf_problem_debug_back_product(lvf_problem* p);
  * last device-loop solve, slot = iteration & 63: {iteration, cost at the point, candidate cost, model cost change, accepted, failure flag,
  * trust-region radius used, gradient max norm}.  LVF_ERR_STATE without the environment variable. */
 int lvf_problem_debug_history(lvf_problem* p, double* out512);
+/* Test tap of the reduced solve (tests/test_gpu_reduced_solve.py): S [d x d] (symmetric, only the lower triangle is read) and rhs [d] in the
+ * layout and natural unknown order of lvf_problem_download_reduced are COPIED (the caller's arrays are free afterwards), and from then on every
+ * iteration of lvf_problem_lm_iteration / lvf_problem_solve on this problem linearises as usual, assembles its own damped system the way
+ * lvf_problem_download_reduced does (so the elimination order, the identity padding of the last block, Dinv / Ldiag are production's), writes
+ * the caller's d x d entries and rhs row over the assembled ones and then runs the production chain on that: the (v, ba, bg) elimination
+ * levels (each a launch of its own), the block steps with their G riders, the back substitution lvf_problem_debug_back_product reports, the
+ * candidate cost and the decision.  Not used while it is set: the placement of the early levels inside the launches ahead of them, and the
+ * fused candidate pass.  The step satisfies S x = rhs; the model cost change the decision judges still comes from the problem's own gradient
+ * and blocks.  The system must keep the sparsity pattern of the problem's own (the elimination plan reads no other entry of the (v, ba, bg)
+ * columns).  Both NULL: clear (clearing twice is fine); one NULL: LVF_ERR_INVALID.  After a change of the problem's size the override must
+ * be set again (LVF_ERR_INVALID from the iteration).  lvf_problem_batch_* calls on a batch holding such a problem return LVF_ERR_STATE. */
+int lvf_problem_debug_override_reduced(lvf_problem* p, const double* S, const double* rhs);
+/* The reduced step x [d] of the last lvf_problem_lm_iteration / lvf_problem_solve iteration, in the natural unknown order and the coordinates of
+ * the system it solved (the chain solves the unscaled system: Jacobi scaling only shapes the damping), and the raw failure flag that iteration
+ * left: 0, 1 + kb (block step kb of the dense corner met a non-positive or NaN pivot), the sparse base + keyframe (an elimination level did),
+ * or the hand-over base + ... (lvf_debug_fail_codes).  After a failed factor x is not meaningful.  A solve that ran the fused candidate pass
+ * has reset the flag.  LVF_ERR_STATE before any iteration. */
+int lvf_problem_debug_download_step(lvf_problem* p, double* x, int* fail);
+/* 1 / 0: the last iteration's linear solve succeeded (no failure flag, finite model and candidate cost) or not; -1 before any iteration. */
+int lvf_problem_debug_last_solved(lvf_problem* p);
+/* What the elimination plan made of the problem (after a configure, i.e. after any iteration; LVF_ERR_STATE before): *nb = block steps of the
+ * dense corner (the largest dense failure code), dense_kf[n_kf] (may be NULL) = 1 where the keyframe's (v, ba, bg) block was left in the dense
+ * corner instead of an elimination level. */
+int lvf_problem_debug_plan(lvf_problem* p, int* nb, int* dense_kf);
+/* The bases of the failure flag's sparse-level and hand-over codes (either pointer may be NULL). */
+void lvf_debug_fail_codes(int* sparse_base, int* handover_base);
 
 /* ---- loop-correction tail: Relocator::UpdateNewSubmap / PoseGraph::ForwardUpdate ---------------------------------- */
 /* RelocateRError <7,4> (pose_error.hpp:192-222) batched: block i = RelocateRError(relocated[i], unrelocated[i]) evaluated at the shared

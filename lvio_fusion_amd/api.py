@@ -1067,6 +1067,14 @@ class Comm:
             self.h = C.c_void_p()
 
 
+def fail_codes():
+    """(sparse base, hand-over base) of the failure flag debug_step() returns (lvf_debug_fail_codes): 1 + kb below the first = block step kb of
+    the dense corner, [sparse, hand-over) = an elimination level, from the second on = a hand-over time-out"""
+    a, b = C.c_int(), C.c_int()
+    _lib.lib().lvf_debug_fail_codes(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
+
+
 def default_solver_options():
     o = SolverOptions()
     _lib.lib().lvf_solver_options_default(C.byref(o))
@@ -1111,6 +1119,39 @@ class Problem:
     def debug_back_product(self):
         """1 when the current chain takes the (v, ba, bg) back substitution as a product with G, 0 for the sequential levels (lvf_problem_debug_back_product)"""
         return int(self.ctx.L.lvf_problem_debug_back_product(self.h))
+
+    def debug_override_reduced(self, S, rhs):
+        """test tap: every further iteration of this problem solves (S, rhs) — layout of reduced_system(), lower triangle read — with the
+        production chain instead of the system it assembled (lvf_problem_debug_override_reduced).  A single None or a wrong size raises."""
+        d = self.ctx.L.lvf_problem_reduced_dim(self.h)
+        if S is None or rhs is None:
+            _chk(self.ctx.L.lvf_problem_debug_override_reduced(self.h, None if S is None else _dp(_d(S)), None if rhs is None else _dp(_d(rhs))))
+            return
+        S, rhs = _d(S), _d(rhs)
+        if S.shape != (d, d) or rhs.shape != (d,):
+            raise ValueError(f"debug_override_reduced: S {S.shape} / rhs {rhs.shape}, the problem's reduced system is {d} x {d}")
+        _chk(self.ctx.L.lvf_problem_debug_override_reduced(self.h, _dp(S), _dp(rhs)))
+
+    def debug_clear_override(self):
+        _chk(self.ctx.L.lvf_problem_debug_override_reduced(self.h, None, None))
+
+    def debug_last_solved(self):
+        """True / False: the last iteration's linear solve succeeded or not (lvf_problem_debug_last_solved); None before any iteration"""
+        v = self.ctx.L.lvf_problem_debug_last_solved(self.h)
+        return None if v < 0 else bool(v)
+
+    def debug_plan(self):
+        """(nb, dense_kf [n_kf] bool): block steps of the dense corner, and which keyframes' (v, ba, bg) blocks stayed in it (lvf_problem_debug_plan)"""
+        nb = C.c_int(); dense = np.zeros(self.state.n_kf, np.int32)
+        _chk(self.ctx.L.lvf_problem_debug_plan(self.h, C.byref(nb), _ip(dense)))
+        return int(nb.value), dense.astype(bool)
+
+    def debug_step(self):
+        """(x [d], fail): the reduced step of the last iteration in reduced_system()'s order, and its raw failure flag (lvf_problem_debug_download_step)"""
+        d = self.ctx.L.lvf_problem_reduced_dim(self.h)
+        x = np.empty(d); fail = C.c_int()
+        _chk(self.ctx.L.lvf_problem_debug_download_step(self.h, _dp(x), C.byref(fail)))
+        return x, int(fail.value)
 
     def stage_times(self, opt, radius=1e4, reps=10, spans=False):
         """[(stage name, average microseconds, launches)] of `reps` LM iterations from the current state: the sum of the stage's KERNEL

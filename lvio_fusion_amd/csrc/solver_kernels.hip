@@ -70,6 +70,11 @@ __device__ __forceinline__ void sp_ride(const int vb, const SpArgs& a);     // w
 // SC_FAIL codes (raised with atomicMax: the largest wins): 1 + kb = dense block step kb met a non-positive pivot, kFailSparse + id = sparse
 // block id did, kFailHandover + id = a chained level gave up waiting for the level below (NOT a property of the problem: see SpSrc)
 constexpr int kFailSparse = 100000, kFailHandover = 300000;
+// Test tap (lvf_problem_debug_override_reduced): a caller's reduced system S [d x d] / rhs [d] in the natural unknown order, written over the
+// assembled one before any elimination level starts
+struct ReducedOverride { int d = 0; DevBuf<double> S, rhs; };
+// (debug_taps.hip: the copy kernel lives in a translation unit of its own, so this file's device code is what it is without the tap)
+int launch_override_reduced(hipStream_t q, int d, int ld, int aug, const int* perm, const double* Sov, const double* rhs, double* S);
 }
 struct lvf_problem {
   lvf_ctx* ctx = nullptr;
@@ -150,6 +155,9 @@ struct lvf_problem {
   const void* chain_state[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};    // the state pointers the chain was built for
   double huber = 1.0;
   hipGraphExec_t graph_exec = nullptr;
+  std::unique_ptr<lvf::ReducedOverride> ov;     // test tap: non-null while a reduced system is overridden (enqueue_iteration)
+  bool step_ready = false;            // dxc / the fail flag hold the step of an iteration (lvf_problem_debug_download_step)
+  int last_solved = -1;               // LmCtl::solved of the last iteration (lvf_problem_debug_last_solved)
   ~lvf_problem();
 };
 
@@ -4260,7 +4268,9 @@ static int enqueue_iteration(lvf_problem* p, bool end_zero, int fused = 0) {
   hipStream_t q = p->ctx->stream;
   if (chain_stale(p)) LVF_TRY(build_chain(p));
   const Chain& c = *p->chain;
-  if (!c.fused_ok || !p->acc1_ready) fused = 0;
+  const ReducedOverride* ov = p->ov.get();    // test tap (null in production)
+  if (ov) LVF_REQUIRE(ov->d == p->d, "the overridden reduced system has %d unknowns, the problem now has %d: clear or set it again", ov->d, p->d);      // (before any launch)
+  if (!c.fused_ok || !p->acc1_ready || ov) fused = 0;
   const AccSel* acc = (fused & kFusedOn) ? &c.acc : nullptr;
   static const bool sp_timing = std::getenv("LVF_SP_TIMING") != nullptr;
   if (sp_timing && c.early) {
@@ -4288,13 +4298,23 @@ static int enqueue_iteration(lvf_problem* p, bool end_zero, int fused = 0) {
       }
     }
   }
-  LVF_TRY(enqueue_linearize(p, p->huber, true, true, acc, !(fused & kFusedNoLin)));
+  // With an override the damped system is assembled the classic way (no level rides in the launches ahead: they would read B), the caller's
+  // entries go over it, and every level is a launch of its own reading S alone; from the block steps on the chain is production's.
+  // (iteration = false also takes the reset of the per-step scalars and of SC_FAIL out of the linearisation launch: the classic k_prepare
+  // below does it, as in the chain without early levels, so a flag raised by one iteration never reaches the next.)
+  LVF_TRY(enqueue_linearize(p, p->huber, true, !ov, acc, !(fused & kFusedNoLin)));
   bool level0_done = false;
-  LVF_TRY(enqueue_reduced_system(p, &p->ctl.p->radius, true, true, &level0_done, acc));
+  LVF_TRY(enqueue_reduced_system(p, &p->ctl.p->radius, true, true, ov ? nullptr : &level0_done, acc));
+  if (ov) {
+    // (a plain launch: a test-only copy is no stage of lvf_problem_stage_times.  Not gated by the loop's `done` flag either — after the end of a
+    // solve it only rewrites S, which nothing reads any more)
+    LVF_TRY(launch_override_reduced(q, p->d, p->ld, p->aug, p->perm.p, ov->S.p, ov->rhs.p, p->S.p));
+  }
   const int own0 = level0_done ? c.first_own_level : 0;      // (levels below rode in the launches above)
   for (int lv = own0; lv < c.n_levels; ++lv) {
     SpArgs la = c.sp[lv];
     acc_patch(la, acc);
+    if (ov) { SpSrc& sr = la.src; sr.B = nullptr; sr.ldB = 0; sr.dp = 0; sr.gc = nullptr; sr.radius = nullptr; sr.rows_nat = nullptr; sr.s_zero = 0; }      // the classic form
     LVF_CHAIN_LAUNCH(p, ST_SP_LEVELS, k_sp_eliminate, dim3(la.nblocks), dim3(256), c.sp_lds[lv], q, la);
   }
   stage_mark(p, ST_SP_LEVELS, std::max(0, c.n_levels - own0));
@@ -4462,6 +4482,7 @@ static int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* rad
   out->cost_before = c.cost_before; out->cost_after = c.cost_after; out->model = c.model; out->dxnorm = c.dxnorm; out->xnorm = c.xnorm; out->gmax = c.gmax;
   out->solved = c.solved != 0; out->accepted = c.accepted != 0;
   p->last_radius = c.last_radius;
+  p->step_ready = true; p->last_solved = c.solved;
   *radius = c.radius; *decrease = c.decrease;
   return LVF_OK;
 }
@@ -4834,6 +4855,7 @@ int problem_configure(lvf_problem* p) {
   // no stream wait here: every host source above is pinned and owned by the problem (or was waited for by the plan builder)
   p->linearized = false;
   p->chain_ready = false;
+  p->step_ready = false;
   return LVF_OK;
 }
 
@@ -4897,6 +4919,8 @@ static int batch_build_tables(lvf_problem_batch* b, double huber) {
   bool all = true;
   static const int batch_rows = [] { const char* e = std::getenv("LVF_BATCH_BAND_ROWS"); return e ? std::atoi(e) : 128; }();
   if (b->orphaned) { set_error("lvf_problem_batch: a member problem was destroyed before the batch"); return LVF_ERR_STATE; }
+  for (size_t w = 0; w < b->probs.size(); ++w)
+    if (b->probs[w]->ov) { set_error("lvf_problem_batch: window %d has an overridden reduced system (lvf_problem_debug_override_reduced): the batched chains have no such tap", (int)w); return LVF_ERR_STATE; }
   for (lvf_problem* p : b->probs) {
     if (chain_stale(p)) LVF_TRY(build_chain(p));
     LVF_TRY(await_band_work(p));             // (the member's own list: its count shares the pinned slot build_band_work reads below)
@@ -5236,7 +5260,7 @@ int lvf_problem_solve_then(lvf_problem* p, const lvf_solver_options* o, lvf_solv
     // the fused chain (Chain::fused_ok): the pass's first iteration linearises at the state as today, every later one starts from the
     // linearisation the previous iteration's candidate pass made, and the last one enqueued for the solve ends with the plain cost pass (a
     // re-run after a hand-over time-out takes today's chain: no_chain)
-    const bool fz = p->chain->fused_ok && !p->no_chain && o->max_num_iterations - first >= 2;
+    const bool fz = p->chain->fused_ok && !p->no_chain && !p->ov && o->max_num_iterations - first >= 2;
     if (fz) LVF_TRY(ensure_acc1(p));
     bool fused_tail = false;
     for (int it = first; it < o->max_num_iterations; ++it) {
@@ -5269,6 +5293,7 @@ int lvf_problem_solve_then(lvf_problem* p, const lvf_solver_options* o, lvf_solv
     first = c.iter;
   }
   p->last_radius = c.last_radius;
+  p->step_ready = true; p->last_solved = c.solved;
   summary_from_ctl(p, c, summary);
   if (timed_out && !c.done) summary->termination_reason = LVF_WHY_TIME;
   return LVF_OK;
@@ -5296,6 +5321,52 @@ int lvf_problem_download_reduced(lvf_problem* p, double* S, double* rhs) {
     }
   for (int j = 0; j < d; ++j) rhs[j] = h[(size_t)p->aug * ld + pm[j]];
   return LVF_OK;
+}
+
+// test tap (see lvf.h): the caller's reduced system replaces the assembled one in every iteration of this problem; both NULL clears it
+int lvf_problem_debug_override_reduced(lvf_problem* p, const double* S, const double* rhs) {
+  LVF_REQUIRE(p, "lvf_problem_debug_override_reduced: null problem");
+  LVF_REQUIRE((S == nullptr) == (rhs == nullptr), "lvf_problem_debug_override_reduced: S and rhs must both be given, or both be NULL (clear)");
+  LVF_TRY(lvf::enter(p->ctx));
+  hipStream_t q = p->ctx->stream;
+  if (!S) {
+    LVF_HIP(hipStreamSynchronize(q));          // (launches that read the copies may still be in flight)
+    p->ov.reset();
+    return LVF_OK;
+  }
+  LVF_REQUIRE(p->d > 0, "lvf_problem_debug_override_reduced: the problem has no unknowns");
+  std::unique_ptr<ReducedOverride> ov(new ReducedOverride());
+  ov->d = p->d;
+  LVF_TRY(ov->S.upload(S, (size_t)p->d * p->d, q));
+  LVF_TRY(ov->rhs.upload(rhs, (size_t)p->d, q));
+  LVF_HIP(hipStreamSynchronize(q));            // the caller's arrays are free from here on (and the previous copies are no longer read)
+  p->ov = std::move(ov);
+  return LVF_OK;
+}
+// the reduced step of the last iteration (natural order, the coordinates of the system: the chain solves the unscaled system, the Jacobi
+// scaling only enters the damping) and the raw SC_FAIL flag
+int lvf_problem_debug_download_step(lvf_problem* p, double* x, int* fail) {
+  LVF_REQUIRE(p && x && fail, "lvf_problem_debug_download_step: null argument");
+  if (!p->step_ready) { set_error("lvf_problem_debug_download_step: no iteration yet"); return LVF_ERR_STATE; }
+  LVF_TRY(lvf::enter(p->ctx));
+  hipStream_t q = p->ctx->stream;
+  LVF_HIP(hipMemcpyAsync(x, p->dxc.p, (size_t)p->d * 8, hipMemcpyDeviceToHost, q));
+  LVF_HIP(hipMemcpyAsync(fail, reinterpret_cast<const int*>(p->scal.p + SC_FAIL), sizeof(int), hipMemcpyDeviceToHost, q));
+  LVF_HIP(hipStreamSynchronize(q));
+  return LVF_OK;
+}
+int lvf_problem_debug_last_solved(lvf_problem* p) { return (p && p->step_ready) ? p->last_solved : -1; }
+// the layout the elimination plan gave the factorised matrix: block steps of the dense corner; per keyframe, whether its (v, ba, bg) block stayed there
+int lvf_problem_debug_plan(lvf_problem* p, int* nb, int* dense_kf) {
+  LVF_REQUIRE(p && nb, "lvf_problem_debug_plan: null argument");
+  if ((int)p->perm_h.size() < p->d || p->d != 15 * p->n_kf) { set_error("lvf_problem_debug_plan: no elimination plan yet"); return LVF_ERR_STATE; }
+  *nb = p->nb;
+  if (dense_kf) for (int k = 0; k < p->n_kf; ++k) dense_kf[k] = p->perm_h[(size_t)p->dp + 9 * k] >= p->off ? 1 : 0;
+  return LVF_OK;
+}
+void lvf_debug_fail_codes(int* sparse_base, int* handover_base) {
+  if (sparse_base) *sparse_base = kFailSparse;
+  if (handover_base) *handover_base = kFailHandover;
 }
 
 // ---- batch of windows
