@@ -529,6 +529,11 @@ int lvf_problem_debug_force_handover_timeout(lvf_problem* p, int n);
  * single-window chain: a batch (lvf_problem_batch_*) always runs the sequential levels, whatever this returns for its members.  Not part of
  * the reference surface. */
 int lvf_problem_debug_back_product(lvf_problem* p);
+/* Diagnostic: 1 when the problem's current launch chain runs the dense part of the back substitution on the block products
+ * T_kj = -Dinv_k L_jk^T that riders of the block-step launches store, 0 when it reads the factor and Dinv (one block, a corner with more
+ * blocks than the kernel holds products for, a dense corner of a multiple of 64 unknowns, LVF_BACK_BLOCKS=0, the re-run after a hand-over
+ * time-out); negative on error.  Builds the chain if it is stale; a batch never takes the block form.  Not part of the reference surface. */
+int lvf_problem_debug_back_blocks(lvf_problem* p);
 /* Diagnostic (environment LVF_LM_HISTORY=1 when the problem's launch chain is built): out512 receives eight doubles per closed pass of the
  * last device-loop solve, slot = iteration & 63: {iteration, cost at the point, candidate cost, model cost change, accepted, failure flag,
  * trust-region radius used, gradient max norm}.  LVF_ERR_STATE without the environment variable. */
@@ -559,6 +564,9 @@ int lvf_problem_debug_last_solved(lvf_problem* p);
 int lvf_problem_debug_plan(lvf_problem* p, int* nb, int* dense_kf);
 /* The bases of the failure flag's sparse-level and hand-over codes (either pointer may be NULL). */
 void lvf_debug_fail_codes(int* sparse_base, int* handover_base);
+/* Diagnostic: how many entries of a landmark's E band, counted from the 16-aligned start of the band, the landmark workgroups of the merged
+ * back-substitution launch request before they wait for the pose increments (the rest of a longer band is read afterwards). */
+int lvf_debug_landmark_window(void);
 
 /* ---- loop-correction tail: Relocator::UpdateNewSubmap / PoseGraph::ForwardUpdate ---------------------------------- */
 /* RelocateRError <7,4> (pose_error.hpp:192-222) batched: block i = RelocateRError(relocated[i], unrelocated[i]) evaluated at the shared

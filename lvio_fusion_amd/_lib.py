@@ -207,12 +207,14 @@ _SIGS = {
     "lvf_problem_batch_size": (C.c_int, [_VP]),
     "lvf_problem_debug_force_handover_timeout": (C.c_int, [_VP, C.c_int]),
     "lvf_problem_debug_back_product": (C.c_int, [_VP]),
+    "lvf_problem_debug_back_blocks": (C.c_int, [_VP]),
     "lvf_problem_debug_history": (C.c_int, [_VP, c_double_p]),
     "lvf_problem_debug_override_reduced": (C.c_int, [_VP, c_double_p, c_double_p]),
     "lvf_problem_debug_download_step": (C.c_int, [_VP, c_double_p, C.POINTER(C.c_int)]),
     "lvf_problem_debug_last_solved": (C.c_int, [_VP]),
     "lvf_problem_debug_plan": (C.c_int, [_VP, C.POINTER(C.c_int), c_int_p]),
     "lvf_debug_fail_codes": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lvf_debug_landmark_window": (C.c_int, []),
     "lvf_problem_batch_uses_tables": (C.c_int, [_VP, C.POINTER(SolverOptions)]),
     "lvf_problem_batch_lm_iteration": (C.c_int, [_VP, C.POINTER(SolverOptions), c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "lvf_problem_batch_solve": (C.c_int, [_VP, C.POINTER(SolverOptions), C.POINTER(SolverSummary)]),

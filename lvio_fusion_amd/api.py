@@ -1075,6 +1075,11 @@ def fail_codes():
     return int(a.value), int(b.value)
 
 
+def debug_landmark_window():
+    """entries of a landmark's E band (from its 16-aligned start) requested before the wait for the pose increments (lvf_debug_landmark_window)"""
+    return int(_lib.lib().lvf_debug_landmark_window())
+
+
 def default_solver_options():
     o = SolverOptions()
     _lib.lib().lvf_solver_options_default(C.byref(o))
@@ -1119,6 +1124,10 @@ class Problem:
     def debug_back_product(self):
         """1 when the current chain takes the (v, ba, bg) back substitution as a product with G, 0 for the sequential levels (lvf_problem_debug_back_product)"""
         return int(self.ctx.L.lvf_problem_debug_back_product(self.h))
+
+    def debug_back_blocks(self):
+        """1 when the current chain solves the dense corner on the stored block products T_kj, 0 when it reads S and Dinv (lvf_problem_debug_back_blocks)"""
+        return int(self.ctx.L.lvf_problem_debug_back_blocks(self.h))
 
     def debug_override_reduced(self, S, rhs):
         """test tap: every further iteration of this problem solves (S, rhs) — layout of reduced_system(), lower triangle read — with the

@@ -112,6 +112,7 @@ struct lvf_problem {
   // product form of the sparse back substitution (lvf::GRide): G [9 n_nodes][ldG], allocated by the chain that uses it; sp_gmap [n_nodes][ldG]:
   // which of a node's own rows (index into sp_rows) a dense-corner / augmented column is, or -1
   lvf::DevBuf<double> sp_G; lvf::DevBuf<int> sp_gmap; int ldG = 0;
+  lvf::DevBuf<double> sp_T;      // block form of the dense back substitution (lvf::TRide): nb x nb blocks of 64 x 64, block (k, j) used for k < j
   lvf::DevBuf<double> Ldiag;                    // the factored diagonal blocks L_kk [nb][64][64] (NOT stored back into S: see chol_step_body)
   std::vector<int> perm_h;
   lvf::DevBuf<double> B, gc, C, gr, E, Cd, S, dxc, dxl, scal;
@@ -2121,6 +2122,15 @@ __device__ __forceinline__ void stage_commit(const Stage64& st, int t, double* _
   }
 }
 
+// the two 64 x 65 panel buffers of a block-step workgroup: ONE pair per kernel, shared by the column / trailing-update workgroups and by the
+// riders that form the back substitution's block products (a pair of their own would double the launch's static LDS)
+struct PanelLds { double* Pi; double* Pj; };
+__device__ __forceinline__ PanelLds panel_lds() {
+  __shared__ double Pi[kNB * kLd];
+  __shared__ double Pj[kNB * kLd];
+  return PanelLds{Pi, Pj};
+}
+
 // trailing update of one tile: A[bi][bj] -= P_bi P_bj^T with the panels of column kp.  Wave wv produces rows 16 (wv & 3) .. + 15 of the
 // column half wv >> 2 (A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15], D: col = lane&15, row = (lane>>4) + 4 reg).
 __device__ __forceinline__ void chol_update_tile(double* S, int ld, int kp, int bi, int bj, double* Pi, double* Pj) {
@@ -2153,6 +2163,42 @@ __device__ __forceinline__ void chol_update_tile(double* S, int ld, int kp, int 
     for (int rg = 0; rg < 4; ++rg) out[(size_t)(lk + 4 * rg) * ld + 16 * ct + lc] = o[ct][rg] - acc[ct][rg];
 }
 
+// The block form of the dense back substitution (Chain::back_blocks).  x_k = Dinv_k (y_k - sum_{j > k} L_jk^T x_j) is a chain of nb links
+// with two products each; with T_kj = -Dinv_k L_jk^T it is x_k = sum_{j > k} T_kj x_j (y rides along as column d of the last block row,
+// met by a -1 in the multiplier), one short product per link.  Both factors of T_kj are final when launch k ends, and nothing in launch
+// k + 1 writes them: rider vb of launch kb forms the block k = kb - 1, j = kb + vb like a trailing-update tile (P_i = L_jk, P_j = Dinv_k,
+// two 16x16 tiles per wave on the matrix cores).  Stored TRANSPOSED, block (k, j) at T + (k nb + j) 64^2, entry [r][c] = T_kj[c][r]: the
+// back substitution's wave `part` reads rows 8 part .. 8 part + 7, each one contiguous run of 64 doubles.
+// Riders wait for nothing and raise no flag; a poisoned factor sends its NaN through here into a step the failure flag rejects.
+struct TRide { int n; GP<double> T; };
+__device__ __forceinline__ void back_block_ride(const int vb, const CholArgs& A, const int kb, const TRide& R) {
+  if (vb >= R.n || kb < 1 || kb + vb >= A.nb) return;
+  if (A.done && *A.done) return;
+  const int k = kb - 1, j = kb + vb;
+  const PanelLds PL = panel_lds();
+  const int wv = threadIdx.x >> 6, w = wv & 3, ch = wv >> 2, lane = threadIdx.x & 63, lk = lane >> 4, lc = lane & 15;
+  {
+    Stage64 st;
+    const int t = threadIdx.x & 255;
+    if (ch) stage_issue((const double*)A.Dinv + (size_t)k * kNB * kNB, kNB, t, st);
+    else stage_issue((const double*)A.Sd + (size_t)(j * kNB) * A.ld + k * kNB, A.ld, t, st);
+    stage_commit(st, t, ch ? PL.Pj : PL.Pi);
+  }
+  __syncthreads();
+  double4_t acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+  for (int k0 = 0; k0 < kNB; k0 += 4) {
+    const double av = PL.Pi[(16 * w + lc) * kLd + k0 + lk];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, PL.Pj[(32 * ch + 16 * ct + lc) * kLd + k0 + lk], acc[ct], 0, 0, 0);
+  }
+  double* out = (double*)R.T + ((size_t)k * A.nb + j) * kNB * kNB + (size_t)(16 * w) * kNB + 32 * ch;
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) out[(lk + 4 * rg) * kNB + 16 * ct + lc] = -acc[ct][rg];
+}
+
 // SUB: the 16-pivot sub-block sweep (default); !SUB: the pair-pivot sweep (factor_diag_wave / factor_panel_wave)
 template <bool SUB>
 __device__ __forceinline__ void chol_step_body(const int bx, const CholArgs& A, const int kb) {
@@ -2160,8 +2206,8 @@ __device__ __forceinline__ void chol_step_body(const int bx, const CholArgs& A, 
   if (bx >= chol_step_grid(A.nb, kb)) return;                          // (workgroup-uniform: no barrier is skipped by part of a workgroup)
   const int dv = done_flag_issue(A.done);
   double* S = A.Sd; const int ld = A.ld; int* __restrict__ fail = A.fail; double* __restrict__ Dinv = A.Dinv;
-  __shared__ double Pi[kNB * kLd];
-  __shared__ double Pj[kNB * kLd];
+  const PanelLds PL = panel_lds();
+  double* const Pi = PL.Pi; double* const Pj = PL.Pj;
   __shared__ double Linv[kNB];
   if (bx >= 2 + below) {                              // trailing tiles of step kb-1 right of column kb
     int t = bx - (2 + below), ii = 0;
@@ -2377,17 +2423,22 @@ __device__ __forceinline__ void back_product_ride(const int vb, const GRide& R) 
   }
 }
 // (the column and trailing-update workgroups keep the lowest indices — they are the critical path and are dispatched first; the riders sit behind them)
-__global__ __launch_bounds__(kCT) void k_chol_step(CholArgs a, int kb, GRide g) {
+// (behind the G riders: the nb - kb riders of the back substitution's block products, back_block_ride)
+__device__ __forceinline__ void chol_step_riders(const int vb, const CholArgs& a, const int kb, const GRide& g, const TRide& tr) {
+  if (vb < g.n) back_product_ride(vb, g);
+  else back_block_ride(vb - g.n, a, kb, tr);
+}
+__global__ __launch_bounds__(kCT) void k_chol_step(CholArgs a, int kb, GRide g, TRide tr) {
   const int own = chol_step_grid(a.nb, kb);
-  if ((int)blockIdx.x >= own) { back_product_ride((int)blockIdx.x - own, g); return; }
+  if ((int)blockIdx.x >= own) { chol_step_riders((int)blockIdx.x - own, a, kb, g, tr); return; }
   chol_step_body<true>(blockIdx.x, a, kb);
 }
 __global__ __launch_bounds__(kCT) void k_chol_step_b(const CholArgs* __restrict__ t, int kb) { chol_step_body<true>(blockIdx.x, t[blockIdx.y], kb); }
 __global__ __launch_bounds__(kCT) void k_chol_step_bt(const CholArgs* __restrict__ t, int kb) { chol_step_body<true>(blockIdx.y, t[blockIdx.x], kb); }
 // LVF_CHOL_SUBBLOCK=0: the pair-pivot sweep, as second instantiations (no branch inside the chain)
-__global__ __launch_bounds__(kCT) void k_chol_step_pp(CholArgs a, int kb, GRide g) {
+__global__ __launch_bounds__(kCT) void k_chol_step_pp(CholArgs a, int kb, GRide g, TRide tr) {
   const int own = chol_step_grid(a.nb, kb);
-  if ((int)blockIdx.x >= own) { back_product_ride((int)blockIdx.x - own, g); return; }
+  if ((int)blockIdx.x >= own) { chol_step_riders((int)blockIdx.x - own, a, kb, g, tr); return; }
   chol_step_body<false>(blockIdx.x, a, kb);
 }
 __global__ __launch_bounds__(kCT) void k_chol_step_pp_b(const CholArgs* __restrict__ t, int kb) { chol_step_body<false>(blockIdx.x, t[blockIdx.y], kb); }
@@ -2746,7 +2797,13 @@ __device__ __forceinline__ T ld_off32(const T* base, unsigned byte_off) {     //
 constexpr int kBT = 512, kBParts = kBT / 64, kBackPre = 256 / kBParts, kBackInv = 64 / kBParts, kTailPre = 6;
 // pose_ready (merged back-substitution + step tail, k_backsolve_tail): once the dense corner is solved the POSE part of the step (natural
 // unknowns [0, n_pose)) is written out and *pose_ready is raised (release, agent scope) — what the landmark back-substitution waits for
-struct BackArgs { GP<const double> Sd; int ld, d; GP<const double> Dinv; GP<double> xout; SpBack sp; GP<const int> done; GP<const double> Ldiag; GP<int> pose_ready = nullptr; int n_pose = 0; int pose_fenced = 0; };
+// T (block form, back_block_ride): the stored products T_kj of this iteration's factor, or null for the form that reads S and Dinv
+struct BackArgs { GP<const double> Sd; int ld, d; GP<const double> Dinv; GP<double> xout; SpBack sp; GP<const int> done; GP<const double> Ldiag; GP<int> pose_ready = nullptr; int n_pose = 0; int pose_fenced = 0;
+                  GP<const double> T = nullptr; };
+// block form: links j = nblk - 1 .. 1 whose products a thread holds in registers, eight doubles per block (k, j), k < j.  The dense-corner-only
+// body has the room for a corner of five blocks (ten products); beside the sparse levels' items they take the place of the gather operands
+// (three products: three blocks).  A corner with more blocks keeps the S / Dinv form (build_chain).
+constexpr int kBackTJ = 4, kBackTJLevels = 2;
 // LEVELS = false (the product form, k_backsolve_tail with Chain::back_product): the dense corner only.  The WHOLE dense-corner solution is
 // published — the plan may leave (v, ba, bg) blocks in the corner's padding, and the sibling workgroups' product with G reads them — and the
 // sparse items, the stored L_bb^-1 and the levels are neither requested nor run.
@@ -2756,6 +2813,8 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
   const double* S = A.Sd; const int ld = A.ld, d = A.d; const double* Dinv = A.Dinv; double* xout = A.xout; const SpBack& sp = A.sp;
   extern __shared__ double sm[];          // xs[off] | x[nblk*64] | partial[kBParts][64] | rhs[64] | accs[9 max_count] | linv[81 n_nodes]
   const int tid = threadIdx.x, c = tid & 63, part = tid >> 6;
+  const double* Tb = A.T;
+  const bool blocks = Tb != nullptr;       // (where it is set nblk - 1 <= kBackTJ / kBackTJLevels and d is no multiple of 64, so the factor has nblk blocks: build_chain)
   const int nblk = (d + kNB - 1) / kNB, n = nblk * kNB;
   double* x = sm + sp.off;
   double* partial = x + n;
@@ -2770,7 +2829,8 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
   mark();
   // ---- dense corner
   const int rend = min(n, d);
-  double gl[kBackPre], xi[kBackInv], yv;
+  constexpr int kTJ = LEVELS ? kBackTJLevels : kBackTJ, kGl = kBackPre > 4 * kTJ * (kTJ + 1) ? kBackPre : 4 * kTJ * (kTJ + 1);
+  double gl[kGl], xi[kBackInv], yv;        // gl: the gather operands of one block, or every block product of the block form
   // The kernel is ISSUE-bound (one workgroup, two waves per SIMD): every request below is a wave-uniform base (SALU) plus a 32-bit
   // per-lane byte offset, i.e. one VMEM instruction and no VALU address arithmetic, and the row tests are scalar branches -- with
   // 64-bit per-lane addresses and per-lane predicates issuing one block's 41 requests took 1.2-1.8 us of its 2.3-3.4.
@@ -2813,6 +2873,21 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
   for (int i = tid + kBT; i < sp.n_nodes; i += kBT) { const SpNode nd = sp.nodes[i]; snode[2 * i] = nd.row_off; snode[2 * i + 1] = nd.m; }
   asm volatile("" ::: "memory");
   }
+  // block form: every link's share of T_kj, in the order the links run (k = j - 1, the one the next link waits for, first): all of it is in
+  // flight while the first block is solved, and no link requests anything
+  auto request_T = [&]() {
+#pragma unroll
+    for (int j = kTJ; j >= 1; --j)
+      if (j < nblk) {
+#pragma unroll
+        for (int k = j - 1; k >= 0; --k) {
+          const double* tb = Tb + ((size_t)k * nblk + j) * (kNB * kNB) + (size_t)(kBackInv * part_u) * kNB;
+#pragma unroll
+          for (int t = 0; t < kBackInv; ++t) gl[8 * (j * (j - 1) / 2 + k) + t] = ld_off32(tb + t * kNB, c_off);
+        }
+      }
+  };
+  if (blocks) request_T();
   // ---- requests for the sparse tail, AFTER the first dense prefetch: loads return in order, so the dense corner does not wait
   // for them and they land while it is being solved
   constexpr int kTailRegs = LEVELS ? kTailPre : 1;      // (the product form holds none of them)
@@ -2836,7 +2911,8 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
   for (int i = tid; i < sp.off + n; i += kBT) sm[i] = 0.0;
   lds_barrier();
   mark();
-  for (int kb = nblk - 1; kb >= 0; --kb) {
+  const int kb_last = blocks ? nblk - 1 : 0;      // block form: the first solved block (its right-hand side sits in Ldiag) only
+  for (int kb = nblk - 1; kb >= kb_last; --kb) {
     const int r0 = kb * kNB;
     double s = 0.0;
 #pragma unroll
@@ -2851,7 +2927,7 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
 #pragma unroll
     for (int t = 0; t < kBackInv; ++t) xc[t] = xi[t];
     const double yc = yv;
-    if (kb > 0) prefetch(kb - 1);          // in flight during the reductions below
+    if (kb > kb_last) prefetch(kb - 1);    // in flight during the reductions below
     lds_barrier();
     if (part == 0) {
       double a = yc;
@@ -2869,10 +2945,40 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
       double a = 0.0;
 #pragma unroll
       for (int pp = 0; pp < kBParts; ++pp) a += partial[pp * kNB + c];
-      x[r0 + c] = (r0 + c < d) ? a : 0.0;
+      // (block form: the multiplier carries -1 at the augmented row d, which meets column d - r0 of T_k,last = -Dinv_k y_k)
+      x[r0 + c] = (r0 + c < d) ? a : ((blocks && r0 + c == d) ? -1.0 : 0.0);
     }
     lds_barrier();
     mark();
+  }
+  if (blocks) {
+    // x_k = sum_{j > k} T_kj x_j: once x_j is in LDS every thread adds its eight terms for EVERY k < j to running sums; only block j - 1 is
+    // reduced across the parts now — one write, two barriers and eight multiply-adds on the critical link
+    double acc[kTJ];
+#pragma unroll
+    for (int k = 0; k < kTJ; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int j = kTJ; j >= 1; --j)
+      if (j < nblk) {
+        double xv[kBackInv];
+#pragma unroll
+        for (int t = 0; t < kBackInv; ++t) xv[t] = x[j * kNB + kBackInv * part_u + t];
+#pragma unroll
+        for (int k = j - 1; k >= 0; --k) {
+#pragma unroll
+          for (int t = 0; t < kBackInv; ++t) acc[k] += gl[8 * (j * (j - 1) / 2 + k) + t] * xv[t];
+        }
+        partial[part * kNB + c] = acc[j - 1];
+        lds_barrier();
+        if (part == 0) {
+          double a = 0.0;
+#pragma unroll
+          for (int pp = 0; pp < kBParts; ++pp) a += partial[pp * kNB + c];
+          x[(j - 1) * kNB + c] = a;
+        }
+        lds_barrier();
+        mark();
+      }
   }
   if (A.pose_ready) {
     // the pose increments are final (every pose row lives in the dense corner): out they go, so that the landmark back-substitution — which
@@ -2976,21 +3082,82 @@ __global__ __launch_bounds__(kBT) void k_chol_backsolve_b(const BackArgs* __rest
 // (on DENSE rows one thread per landmark beat a wave per landmark, 25.6 vs 29.9 us; with the row limited to the landmark's track
 // a per-thread walk diverges (41-54 us) and 16 lanes per landmark is the right shape)
 // COH_DX: the pose increments were published by a sibling workgroup of THIS launch as agent-scope atomic stores: read past the non-coherent cache levels
-template <int NT = kT, bool COH_DX = false>
-__device__ __forceinline__ void landmark_back_body(const int vb, const int nwg, int n_lm, int dp, int ldE, const double* __restrict__ E,
-                                                   const double* __restrict__ C, const double* __restrict__ Cd, const double* __restrict__ gr,
-                                                   const double* __restrict__ dxc, const double* __restrict__ inv_depth,
+// PRE > 0 (the landmark workgroups of k_backsolve_tail, which spend the dense solve waiting for the pose increments): nothing but the step
+// depends on it, so the operands of the workgroup's first PRE passes are requested BEFORE `wait` (the bounded wait for the increments) — the
+// track limits, then per lane a window of kLmEPre entries of the E band (16 lanes: 128 entries less the alignment slack, 18 keyframes; the
+// tracks of synthetic.config4_window are geometric with mean 10) and gr / Cd / C / inv_depth.  Behind the wait these passes are the step
+// into LDS, multiply-adds from registers, row16_sum and the stores; the rest of a longer band and any further pass are read as before.
+// Two passes of 32 landmarks over 224 workgroups hold 14 336 landmarks: the 10 000 of the headline window need nothing else.
+// (What is requested early is NOT __restrict__ then: LLVM would sink the requests past the wait to their uses, as in chol_backsolve_body.)
+constexpr int kLmEPre = 8;
+struct NoWait { __device__ __forceinline__ void operator()() const {} };
+template <bool R, typename T> struct RestrictIf { typedef T* __restrict__ type; };
+template <typename T> struct RestrictIf<false, T> { typedef T* type; };
+template <int NT = kT, bool COH_DX = false, int PRE = 0, typename Wait = NoWait>
+__device__ __forceinline__ void landmark_back_body(const int vb, const int nwg, int n_lm, int dp, int ldE, typename RestrictIf<PRE == 0, const double>::type E,
+                                                   typename RestrictIf<PRE == 0, const double>::type C, typename RestrictIf<PRE == 0, const double>::type Cd,
+                                                   typename RestrictIf<PRE == 0, const double>::type gr,
+                                                   const double* __restrict__ dxc, typename RestrictIf<PRE == 0, const double>::type inv_depth,
                                                    double* __restrict__ dxl, double* __restrict__ invd2, double* __restrict__ scal,
-                                                   const int* __restrict__ kmin, const int* __restrict__ kmax) {
+                                                   typename RestrictIf<PRE == 0, const int>::type kmin, typename RestrictIf<PRE == 0, const int>::type kmax,
+                                                   const Wait wait = Wait()) {
   extern __shared__ double sdx[];
+  const int q = threadIdx.x & 15;
+  constexpr int kP = PRE > 0 ? PRE : 1;
+  int pb[kP], pi1[kP];
+  double pe[kP][kLmEPre], pg[kP], pcd[kP], pc[kP], pid[kP];
+  if constexpr (PRE > 0) {
+#pragma unroll
+    for (int p = 0; p < PRE; ++p) {
+      const int l = vb * (NT / 16) + (threadIdx.x >> 4) + p * nwg * (NT / 16);
+      const bool ok = l < n_lm;
+      const int i0 = (ok && kmin) ? 6 * min(kmin[l], dp / 6) : 0;
+      pi1[p] = ok ? (kmin ? 6 * (kmax[l] + 1) : dp) : 0;
+      pb[p] = (i0 & ~15) + q;
+      const double* e = E + (size_t)(ok ? l : 0) * ldE + pb[p];
+#pragma unroll
+      for (int u = 0; u < kLmEPre; ++u) pe[p][u] = pb[p] + 16 * u < pi1[p] ? e[16 * u] : 0.0;
+      pg[p] = ok ? gr[l] : 0.0; pcd[p] = ok ? Cd[l] : 1.0; pc[p] = ok ? C[l] : 0.0; pid[p] = ok ? inv_depth[l] : 0.0;
+    }
+    // the values are consumed HERE, ahead of the wait: whatever the optimiser makes of the pointers, the requests cannot sink behind it
+#pragma unroll
+    for (int p = 0; p < PRE; ++p) {
+#pragma unroll
+      for (int u = 0; u < kLmEPre; ++u) asm volatile("" ::"v"(pe[p][u]));
+      asm volatile("" ::"v"(pg[p]), "v"(pcd[p]), "v"(pc[p]), "v"(pid[p]));
+    }
+    wait();
+  }
   for (int i = threadIdx.x; i < dp; i += NT) sdx[i] = COH_DX ? __hip_atomic_load(dxc + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : dxc[i];
   __syncthreads();
   // 16 lanes per landmark: the band of a row is a few 128-byte runs, read coalesced and reduced with four shuffles; the grid is
   // capped and strides over the landmarks so that the three scalar sums cost one atomic per WORKGROUP (thousands of per-wave
   // atomics on the 32 striped slots were most of this kernel's time)
-  const int q = threadIdx.x & 15;
   double m = 0.0, n2 = 0.0, x2 = 0.0, gmx = 0.0;
-  for (int l = vb * (NT / 16) + (threadIdx.x >> 4); l < n_lm; l += nwg * (NT / 16)) {
+  if constexpr (PRE > 0) {
+#pragma unroll
+    for (int p = 0; p < PRE; ++p) {
+      const int l = vb * (NT / 16) + (threadIdx.x >> 4) + p * nwg * (NT / 16);
+      double ed = 0.0;
+#pragma unroll
+      for (int u = 0; u < kLmEPre; ++u) if (pb[p] + 16 * u < pi1[p]) ed += pe[p][u] * sdx[pb[p] + 16 * u];
+      if (pb[p] + 16 * kLmEPre < pi1[p]) {        // the rest of a band longer than the window
+        const double* e = E + (size_t)l * ldE;
+        for (int i = pb[p] + 16 * kLmEPre; i < pi1[p]; i += 16) ed += e[i] * sdx[i];
+      }
+      ed = row16_sum(ed);
+      if (q == 0 && l < n_lm) {
+        const double g_l = pg[p];
+        const double dl = (-g_l - ed) / pcd[p];
+        gmx = fmax(gmx, fabs(g_l));
+        dxl[l] = dl;
+        invd2[l] = pid[p] + dl;
+        m += -0.5 * dl * ((pcd[p] - pc[p]) * dl - g_l);
+        n2 += dl * dl; x2 += pid[p] * pid[p];
+      }
+    }
+  }
+  for (int l = vb * (NT / 16) + (threadIdx.x >> 4) + PRE * nwg * (NT / 16); l < n_lm; l += nwg * (NT / 16)) {
     const double* e = E + (size_t)l * ldE;
     double ed = 0.0;
     const int i0 = kmin ? 6 * min(kmin[l], dp / 6) : 0, i1 = kmin ? 6 * (kmax[l] + 1) : dp;   // the row is zero outside the landmark's track
@@ -3031,27 +3198,44 @@ __device__ __forceinline__ void landmark_back_body(const int vb, const int nwg, 
 // ... fused with the camera part of the model cost change (k_model_cam's body; d <= 15 n_kf threads of the same grid)
 // PARTS: bit 0 = the pose unknowns (sums over [0, 6 n_kf), candidate poses), bit 1 = the (v, ba, bg) unknowns (sums over [6 n_kf, d), candidate
 // velocities / biases); 3 = everything (k_step_tail).  k_backsolve_tail runs the two parts in different workgroups at different times.
+// What apply_step_body reads for thread i (unknown i, keyframe i) that does not depend on the step: the pose workgroup of k_backsolve_tail
+// requests it before it waits for the increments (the pointers are not __restrict__: the requests must stay where they are written).
+struct StepOps { double h, h0d, gci, p[7]; int frozen, cm_kf; };
+template <int PARTS>
+__device__ __forceinline__ StepOps step_ops_load(const int i, int n_kf, StateP s, int d, int ld, const double* B, const double* gc,
+                                                 const unsigned char* pose_const, const JacobiDev jac) {
+  StepOps o{};
+  if (i < d && ((PARTS & 1) || i >= 6 * n_kf) && ((PARTS & 2) || i < 6 * n_kf)) {
+    o.h = B[(size_t)i * ld + i]; o.h0d = jac.h0[i]; o.gci = gc[i]; o.frozen = *jac.frozen;
+  }
+  o.cm_kf = (i < n_kf && pose_const) ? pose_const[i] : 0;      // bit 0: pose, bits 1..3: v, ba, bg held constant
+  if (i < n_kf && (PARTS & 1)) {
+    const double* sp = s.poses;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) o.p[c] = sp[7 * i + c];
+  }
+  return o;
+}
 template <int NT = kT, int PARTS = 3>
-__device__ __forceinline__ void apply_step_body(const int vb, int n_kf, int n_lm, StateP s, const double* __restrict__ dxc, const double* __restrict__ dxl,
-                                                double* __restrict__ poses2, double* __restrict__ vel2, double* __restrict__ ba2,
-                                                double* __restrict__ bg2, double* __restrict__ invd2, double* __restrict__ scal, int d, int ld,
-                                                const double* __restrict__ B, const double* __restrict__ gc, double inv_radius,
-                                                const unsigned char* __restrict__ pose_const, const JacobiDev jac) {
+__device__ __forceinline__ void apply_step_ops(const int vb, int n_kf, int n_lm, StateP s, const double* __restrict__ dxc, const double* __restrict__ dxl,
+                                               double* __restrict__ poses2, double* __restrict__ vel2, double* __restrict__ ba2,
+                                               double* __restrict__ bg2, double* __restrict__ invd2, double* __restrict__ scal, int d, double inv_radius,
+                                               const StepOps& ops) {
   const int i = vb * NT + threadIdx.x;
   // step_norm / x_norm as Ceres takes them (trust_region_minimizer.cc): |x - x_plus_delta| and |x| over the AMBIENT parameter vector of the
   // reduced program — the quaternion's four coefficients, not its three tangent increments; constant pose blocks are not part of it
   double m = 0.0, n2 = 0.0, g = 0.0, x2 = 0.0;
   if (i < d && ((PARTS & 1) || i >= 6 * n_kf) && ((PARTS & 2) || i < 6 * n_kf)) {
     const double dx = dxc[i];
-    const double h = B[(size_t)i * ld + i], h0d = jac.h0[i];
-    m = -0.5 * dx * (lm_damping(h, *jac.frozen ? h0d : h) * inv_radius * dx - gc[i]);      // (first pass: H0 = H, being recorded by the assembly)
+    const double h = ops.h, h0d = ops.h0d;
+    m = -0.5 * dx * (lm_damping(h, ops.frozen ? h0d : h) * inv_radius * dx - ops.gci);      // (first pass: H0 = H, being recorded by the assembly)
     const bool rot = i < 6 * n_kf && (i % 6) < 3;           // rotation increments enter through the quaternion difference below
     n2 = rot ? 0.0 : dx * dx;
-    g = fabs(gc[i]);
+    g = fabs(ops.gci);
   }
-  const int cm_kf = (i < n_kf && pose_const) ? pose_const[i] : 0;      // bit 0: pose, bits 1..3: v, ba, bg held constant
+  const int cm_kf = ops.cm_kf;
   if (i < n_kf && (PARTS & 1)) {
-    const double* p = s.poses + 7 * i; const double* dlt = dxc + 6 * i;
+    const double* p = ops.p; const double* dlt = dxc + 6 * i;
     const double nrm = sqrt(dlt[0] * dlt[0] + dlt[1] * dlt[1] + dlt[2] * dlt[2]);
     double* o = poses2 + 7 * i;
     if (nrm > 0.0) {
@@ -3081,6 +3265,15 @@ __device__ __forceinline__ void apply_step_body(const int vb, int n_kf, int n_lm
     if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(scal + SC_GMAX + (vb & (kStripes - 1))), (unsigned long long)__double_as_longlong(g));
   }
   block_add(x2, scal + SC_XNORM);
+}
+template <int NT = kT, int PARTS = 3>
+__device__ __forceinline__ void apply_step_body(const int vb, int n_kf, int n_lm, StateP s, const double* __restrict__ dxc, const double* __restrict__ dxl,
+                                                double* __restrict__ poses2, double* __restrict__ vel2, double* __restrict__ ba2,
+                                                double* __restrict__ bg2, double* __restrict__ invd2, double* __restrict__ scal, int d, int ld,
+                                                const double* __restrict__ B, const double* __restrict__ gc, double inv_radius,
+                                                const unsigned char* __restrict__ pose_const, const JacobiDev jac) {
+  const StepOps ops = step_ops_load<PARTS>(vb * NT + threadIdx.x, n_kf, s, d, ld, B, gc, pose_const, jac);
+  apply_step_ops<NT, PARTS>(vb, n_kf, n_lm, s, dxc, dxl, poses2, vel2, ba2, bg2, invd2, scal, d, inv_radius, ops);
 }
 
 // landmark back-substitution and the camera-side step / model terms as ONE launch: workgroups [0, g_lm) walk the landmarks,
@@ -3118,7 +3311,8 @@ __global__ __launch_bounds__(kT) void k_step_tail_bt(const TailArgs* __restrict_
 // back_product_ride) and apply the (v, ba, bg) part of the step for their keyframes.  The launch then ends at flag + max(landmark pass,
 // product) instead of flag + levels.
 struct BackTailArgs { BackArgs back; TailArgs tail; int g_lm; int fenced; unsigned timeout_ticks; GP<int> fail;
-                      int g_prod = 0, kpw = 0, ldG = 0; GP<const double> G = nullptr; GP<const int> iperm = nullptr; };
+                      int g_prod = 0, kpw = 0, ldG = 0; GP<const double> G = nullptr; GP<const int> iperm = nullptr;
+                      int early = 1; };      // early: the landmark and pose workgroups request their operands before the wait (LVF_BACK_EARLY=0: behind it)
 // the bounded wait of the consumers of pose_ready (SpSrc has the rules)
 __device__ __forceinline__ void wait_pose_ready(const BackTailArgs& a) {
   if (threadIdx.x == 0) {
@@ -3135,7 +3329,7 @@ __device__ __forceinline__ void wait_pose_ready(const BackTailArgs& a) {
 // below `off` it is G row perm[..] (an eliminated node), otherwise the block stayed in the dense corner and its increment is read from the
 // published solution — either way it is applied here, exactly once.  16 lanes per row, 32 rows per pass; a lane's share of the first pass
 // is requested into a fixed register window BEFORE the wait (what does not fit, and further passes, are read from memory afterwards).
-constexpr int kGPre = 24;
+constexpr int kGPre = 24, kLmPre = 2;      // kLmPre: passes of a landmark workgroup whose operands are requested before the wait (landmark_back_body)
 __device__ __forceinline__ void back_product_body(const int vb, const BackTailArgs& a) {
   const TailArgs& T = a.tail; const SpBack& sp = a.back.sp;
   extern __shared__ double gsm[];          // xd[ldG]: [x_dense ; -1 ; 0 ..] | xs[9 kpw]: this workgroup's rows of the step
@@ -3239,21 +3433,40 @@ __global__ __launch_bounds__(kBT) void k_backsolve_tail(BackTailArgs a) {
   }
   unsigned long long* ldbg = (a.back.sp.dbg && (blockIdx.x == 2 || (int)blockIdx.x == 1 + a.g_lm) && threadIdx.x == 0) ? a.back.sp.dbg + (blockIdx.x == 2 ? 56 : 59) : nullptr;
   if (ldbg) ldbg[0] = wall_clock64();
-  wait_pose_ready(a);
-  if (ldbg) ldbg[1] = wall_clock64();
   if (blockIdx.x == 1) {
     // the pose part of the step: candidate poses and the pose unknowns' share of the model cost change / step norm (the increments are read
-    // at the coherence point into LDS; apply_step_body takes them from there)
+    // at the coherence point into LDS; apply_step_ops takes them from there).  What the first 512 unknowns / keyframes read beside the
+    // increments — B's diagonal, h0, the gradient, the poses, the constant flags, the radius — is requested and consumed before the wait
+    // (a.early; LVF_BACK_EARLY=0: behind it, as it was).
     extern __shared__ double sdx_pose[];
+    const double* const Bt = tail_B(T); const double* const gct = tail_gc(T);
+    StepOps ops{}; double radius = 0.0;
+    if (a.early) {
+      ops = step_ops_load<1>(threadIdx.x, T.n_kf, T.s, T.d, T.ld, Bt, gct, T.pose_const, T.jac);
+      radius = *T.radius;
+      asm volatile("" ::"v"(ops.h), "v"(ops.h0d), "v"(ops.gci), "v"(ops.frozen), "v"(ops.cm_kf), "v"(radius));
+#pragma unroll
+      for (int c = 0; c < 7; ++c) asm volatile("" ::"v"(ops.p[c]));
+    }
+    wait_pose_ready(a);
     for (int i = threadIdx.x; i < T.dp; i += kBT) sdx_pose[i] = __hip_atomic_load(T.dxc + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    const double inv_radius = 1.0 / *T.radius;
-    const double* const Bt = tail_B(T); const double* const gct = tail_gc(T);
-    for (int vb = 0; vb * kBT < max(T.dp, T.n_kf); ++vb)
+    if (!a.early) { ops = step_ops_load<1>(threadIdx.x, T.n_kf, T.s, T.d, T.ld, Bt, gct, T.pose_const, T.jac); radius = *T.radius; }
+    const double inv_radius = 1.0 / radius;
+    apply_step_ops<kBT, 1>(0, T.n_kf, 0, T.s, sdx_pose, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, inv_radius, ops);
+    for (int vb = 1; vb * kBT < max(T.dp, T.n_kf); ++vb)
       apply_step_body<kBT, 1>(vb, T.n_kf, 0, T.s, sdx_pose, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, T.ld, Bt, gct, inv_radius, T.pose_const, T.jac);
+    if (a.back.sp.dbg && threadIdx.x == 0) a.back.sp.dbg[62] = wall_clock64();      // LVF_BACK_TIMING: the pose part is applied
     return;
   }
-  landmark_back_body<kBT, true>((int)blockIdx.x - 2, a.g_lm, T.n_lm, T.dp, T.ldE, tail_E(T), T.C, T.Cd, T.gr, T.dxc, T.s.inv_depth, T.dxl, T.invd2, T.scal, T.kmin, T.kmax);
+  if (a.early)
+    landmark_back_body<kBT, true, kLmPre>((int)blockIdx.x - 2, a.g_lm, T.n_lm, T.dp, T.ldE, tail_E(T), T.C, T.Cd, T.gr, T.dxc, T.s.inv_depth, T.dxl, T.invd2, T.scal, T.kmin, T.kmax,
+                                          [&]() { wait_pose_ready(a); if (ldbg) ldbg[1] = wall_clock64(); });
+  else {
+    wait_pose_ready(a);
+    if (ldbg) ldbg[1] = wall_clock64();
+    landmark_back_body<kBT, true>((int)blockIdx.x - 2, a.g_lm, T.n_lm, T.dp, T.ldE, tail_E(T), T.C, T.Cd, T.gr, T.dxc, T.s.inv_depth, T.dxl, T.invd2, T.scal, T.kmin, T.kmax);
+  }
   if (ldbg) ldbg[2] = wall_clock64();
 }
 
@@ -3559,6 +3772,8 @@ struct Chain {
   bool back_tail_merged = false; BackTailArgs bt{}; size_t bt_lds = 0;      // k_backsolve_tail (single-window chain, chained levels allowed)
   // the sparse back substitution as ONE product with G, formed by riders of the block-step launches (GRide; LVF_BACK_PRODUCT=0 turns it off)
   bool back_product = false; GRide gride{};
+  // the dense back substitution on stored block products T_kj, formed by riders of the block-step launches (TRide; LVF_BACK_BLOCKS=0 turns it off)
+  bool back_blocks = false; TRide tride{};
   CostArgs cost{};
   DecideArgs dec{};
   // the fused chain (AccSel; LVF_FUSED_LIN=0 turns it off): the second accumulator set's pointers and the standby clears (k_tf_reduce: stand0
@@ -3904,6 +4119,8 @@ static int build_chain(lvf_problem* p) {
       static const int bt_wgs = [] { const char* e = std::getenv("LVF_BACK_TAIL_WGS"); return e ? std::max(1, std::atoi(e)) : 224; }();
       m.g_lm = std::min(bt_wgs, (p->n_lm + kBT / 16 - 1) / (kBT / 16));
       m.fenced = bt_fenced == 2; m.back.pose_fenced = bt_fenced == 2; m.timeout_ticks = bt_timeout; m.fail = fail;
+      static const int bt_early = [] { const char* e = std::getenv("LVF_BACK_EARLY"); return (e && e[0] == '0') ? 0 : 1; }();
+      m.early = bt_early;
       if (p->force_handover_timeouts > 1) { m.back.pose_ready = reinterpret_cast<int*>(p->sp_sync.p) + 2 * kSpMaxLevels - 4; m.timeout_ticks = 2000u; }      // test hook (n >= 2): a flag nobody raises
       c.bt_lds = std::max(c.back_lds, c.tail_lds);
       if (c.bt_lds > 64 * 1024 && !bt_big_lds) c.back_tail_merged = false;
@@ -3928,10 +4145,23 @@ static int build_chain(lvf_problem* p) {
         c.back_product = true;
       }
     }
+    // The block form: on for every single-window chain of two or more blocks (the riders go with k_chol_step / k_chol_step_pp whether or not
+    // the G product is on) whose link products fit the registers of the body that will run — five blocks for the dense-corner-only body of the
+    // product form, three beside the sparse levels' items.  Off where the augmented row sits alone in the last factor block (d a multiple of
+    // 64: the first solved block would take its right-hand side from a panel, not from Ldiag — a corner the plan's cost steers away from, it
+    // pays a block step for one row) and in the chain-free re-run after a hand-over time-out; those read S and Dinv as before.
+    static const bool blocks_on = [] { const char* e = std::getenv("LVF_BACK_BLOCKS"); return !(e && e[0] == '0'); }();
+    c.back_blocks = false; c.tride = TRide{0, nullptr};
+    if (blocks_on && !p->no_chain && p->nb >= 2 && p->ndense % kNB != 0 && p->nb - 1 <= (c.back_product ? kBackTJ : kBackTJLevels)) {
+      LVF_TRY(p->sp_T.ensure((size_t)p->nb * p->nb * kNB * kNB));
+      c.tride = TRide{0, p->sp_T.p};
+      c.back_blocks = true;
+    }
     static const bool chain_info = std::getenv("LVF_CHAIN_INFO") != nullptr;
     if (chain_info) std::fprintf(stderr, "chain: n_kf %d n_lm %d fast %d has_imu %d early %d compact %d levels %d no_chain %d merged_level0 %d back_tail_merged %d (g_lm %d, lds %zu) back_product %d (nb %d, %d G workgroups of %d keyframes)\n", p->n_kf, p->n_lm, (int)c.fast, (int)c.has_imu,
                                  (int)c.early, (int)p->compact, c.n_levels, (int)p->no_chain, (int)c.merged_level0, (int)c.back_tail_merged, c.bt.g_lm, c.bt_lds,
                                  (int)c.back_product, p->nb, c.bt.g_prod, c.bt.kpw);
+    if (chain_info) std::fprintf(stderr, "chain: back_blocks %d\n", (int)c.back_blocks);
   }
   fill_cost_visual(p, c.cost.a);
   c.cost.n_kf = p->n_kf; c.cost.s = s2; c.cost.huber = 0.0; c.cost.cost = p->scal.p + SC_COST_NEW; c.cost.done = done;
@@ -4325,17 +4555,21 @@ static int enqueue_iteration(lvf_problem* p, bool end_zero, int fused = 0) {
     GRide gr = c.gride;                                   // the riders that form G: the top level first, one level per launch
     const int glv = c.n_levels - 1 - kb;
     if (c.back_product && glv >= 0) { gr.first = p->sp_levels.first[glv]; gr.n = p->sp_levels.count[glv]; } else gr.n = 0;
-    if (chol_subblock_on()) LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step, dim3(chol_step_grid(p->nb, kb) + gr.n), dim3(kCT), 0, q, cha, kb, gr);
-    else LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step_pp, dim3(chol_step_grid(p->nb, kb) + gr.n), dim3(kCT), 0, q, cha, kb, gr);
+    TRide tr = c.tride;                                   // the riders that form T_kj, k = kb - 1: both factors are final since launch kb - 1
+    tr.n = (c.back_blocks && kb >= 1) ? p->nb - kb : 0;
+    if (chol_subblock_on()) LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step, dim3(chol_step_grid(p->nb, kb) + gr.n + tr.n), dim3(kCT), 0, q, cha, kb, gr, tr);
+    else LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step_pp, dim3(chol_step_grid(p->nb, kb) + gr.n + tr.n), dim3(kCT), 0, q, cha, kb, gr, tr);
   }
   {
     BackArgs ba = c.back;
     static const bool back_timing = std::getenv("LVF_BACK_TIMING") != nullptr;
     if (back_timing) { LVF_TRY(p->dbg.ensure(64)); ba.sp.dbg = p->dbg.p; }
+    if (c.back_blocks) ba.T = p->sp_T.p;
     stage_mark(p, ST_CHOL, p->nb);
     if (c.back_tail_merged) {
       BackTailArgs bt = c.bt;
       if (back_timing) bt.back.sp.dbg = p->dbg.p;
+      bt.back.T = ba.T;
       if (acc) bt.tail.acc = *acc;
       LVF_CHAIN_LAUNCH(p, ST_BACKSOLVE, k_backsolve_tail, dim3(2 + c.bt.g_lm + c.bt.g_prod), dim3(kBT), c.bt_lds, q, bt);
       stage_mark(p, ST_BACKSOLVE, 1);
@@ -4474,6 +4708,7 @@ static int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* rad
       std::fprintf(stderr, " | merged launch, us after workgroup 0's start: step applied %.2f ; first landmark workgroup starts %.2f, sees the poses %.2f, done %.2f ; last one starts %.2f, sees %.2f, done %.2f",
                    (double)(t[55] - t[0]) * 0.01, (double)(t[56] - t[0]) * 0.01, (double)(t[57] - t[0]) * 0.01, (double)(t[58] - t[0]) * 0.01, (double)(t[59] - t[0]) * 0.01,
                    (double)(t[60] - t[0]) * 0.01, (double)(t[61] - t[0]) * 0.01);
+    if (p->chain && p->chain->back_tail_merged) std::fprintf(stderr, " ; pose workgroup done %.2f", (double)(t[62] - t[0]) * 0.01);
     if (p->chain && p->chain->back_product)
       std::fprintf(stderr, " | product form (\"step applied\" = workgroup 0 done): first G workgroup starts %.2f, sees the flag %.2f, has the dense solution %.2f, its rows %.2f, applied %.2f",
                    (double)(t[40] - t[0]) * 0.01, (double)(t[41] - t[0]) * 0.01, (double)(t[42] - t[0]) * 0.01, (double)(t[43] - t[0]) * 0.01, (double)(t[44] - t[0]) * 0.01);
@@ -5364,6 +5599,7 @@ int lvf_problem_debug_plan(lvf_problem* p, int* nb, int* dense_kf) {
   if (dense_kf) for (int k = 0; k < p->n_kf; ++k) dense_kf[k] = p->perm_h[(size_t)p->dp + 9 * k] >= p->off ? 1 : 0;
   return LVF_OK;
 }
+int lvf_debug_landmark_window(void) { return 16 * kLmEPre; }
 void lvf_debug_fail_codes(int* sparse_base, int* handover_base) {
   if (sparse_base) *sparse_base = kFailSparse;
   if (handover_base) *handover_base = kFailHandover;
@@ -5399,6 +5635,12 @@ int lvf_problem_debug_history(lvf_problem* p, double* out512) {
   LVF_HIP(hipMemcpyAsync(out512, p->dbg_hist.p, 512 * 8, hipMemcpyDeviceToHost, p->ctx->stream));
   LVF_HIP(hipStreamSynchronize(p->ctx->stream));
   return LVF_OK;
+}
+// 1: the current chain runs the dense back substitution on the stored block products T_kj, 0: on S and Dinv (builds the chain if stale)
+int lvf_problem_debug_back_blocks(lvf_problem* p) {
+  if (!p || lvf::enter(p->ctx) != LVF_OK) return -1;
+  if (chain_stale(p) && build_chain(p) != LVF_OK) return -1;
+  return p->chain->back_blocks ? 1 : 0;
 }
 // 1: the current chain takes the sparse back substitution as a product with G, 0: it runs the sequential levels (builds the chain if stale)
 int lvf_problem_debug_back_product(lvf_problem* p) {
