@@ -542,7 +542,7 @@ __device__ __forceinline__ bool cell_runs(int c, int& start, int& len) {
 // TwoFrame work list; called by lvf_problem_create and, every tick, by the persistent window (window.hip)
 int problem_configure(lvf_problem* p);
 }  // namespace lvf
-// lvf_problem_solve with a caller's launches enqueued behind the last iteration and ahead of the wait that ends the solve (solver_kernels.hip).
+// lvf_problem_solve with a caller's launches enqueued behind the last iteration and ahead of the wait that ends the solve (solver_api.hip).
 // CONTRACT: tail(user) MUST be idempotent — pure enqueues that can be repeated (pack + copy, as window.hip's): it runs once per pass of the
 // hand-over retry loop, and when a chained hand-over times out in the LAST iteration enqueued (seen only after the wait) it has already run on a
 // state that is not final and runs again behind the un-chained re-run.  A tail that accumulates, consumes a buffer or enqueues once-only work

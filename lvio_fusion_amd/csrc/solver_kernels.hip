@@ -9,171 +9,20 @@
 // kept dense [n_lm x ldE] (ldE = 6 n_kf rounded up to 16, +1 column carrying g_rho) and the rank-n_lm update is one
 // v_mfma_f64_16x16x4_f64 SYRK ("MFMA only for the dense Schur reduce").  The right-hand side rides along as an
 // augmented ROW of S (index d), so the forward substitution comes out of the Cholesky for free.
-#include <hip/hip_ext.h>
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdlib>
-#include <memory>
-#include <unordered_map>
-
+// Device code only: the argument blocks and constants are in solver_args.hpp, the host side that builds and launches the chain in
+// solver_chain.hip, solver_plan.hip, solver_batch.hip and solver_api.hip.
 #include "factor_eval.hpp"
 #include "prior_eval.hpp"
 #include "lvf_internal.hpp"
 #include "imu_eval.hpp"
+#include "solver_args.hpp"
 
 namespace lvf {
-struct TfWork;
-struct LmCtl;
-struct Chain;
-struct StageClock;
-// one (v, ba, bg) block eliminated ahead of the dense factorisation: its 9 columns start at `col`, its `m` neighbour rows
-// (later-ordered (v, ba, bg) blocks, poses, the augmented row; ascending) sit at rows[row_off .. row_off + m)
-struct SpNode { int col, row_off, m, id; };
-constexpr int kSpMaxLevels = 12, kSpMaxRows = 768;
-struct SpLevels { int n; int first[kSpMaxLevels]; int count[kSpMaxLevels]; };
-// "Early" sparse levels (see Chain::early): the level reads its columns as  B (natural order, what the ImuError factors accumulated) +
-// LM damping + the updates of the levels below (all S holds there), instead of entries k_prepare assembled — so it does not have to wait
-// for k_prepare and can ride in an earlier launch.  B == nullptr: the classic form (S holds the assembled entries).
-// Ceres' Jacobi column scaling (Solver::Options::jacobi_scaling, a default the reference leaves on: backend.cpp:206-211; declared in
-// oracle/lm.h's header): s_j = 1 / (1 + sqrt(H0_jj)) with H0 = diag(J^T J) of the solve's FIRST linearisation, frozen for the solve; the LM
-// diagonal is clamped on the SCALED system, which in unscaled terms is D_jj = clamp(s_j^2 H_jj, 1e-6, 1e32) / s_j^2 (lm_damping).  h0 holds
-// H0 in the natural order [15 n_kf camera unknowns | n_lm inverse depths]; while *frozen == 0 (the first pass of a solve) the kernels that
-// form the damping store H_jj there, afterwards they read it (k_lm_decide raises the flag).
-struct JacobiDev { GP<double> h0; GP<const int> frozen; };
-struct SpSrc {
-  GP<const double> B; int ldB, dp; GP<const double> gc; GP<const double> radius; GP<const int> rows_nat;
-  // levels CHAINED inside one launch (the Schur complement's: it lasts long enough for three of them): the level waits until `wait_target`
-  // workgroups of the level below have arrived at *wait_counter, and arrives at *done_counter itself.  What it reads of the level
-  // below are RETURNING atomic adds into S (agent scope), read back with agent-scope atomic loads; the arrival is a RELEASE add, the
-  // waiting side follows its spin with an agent-scope ACQUIRE fence in every wave (`fenced`, default; LVF_CHAIN_FENCE=0: the relaxed
-  // round-3 form for A/B timing).  Producers carry lower workgroup numbers than their consumers, so they are normally dispatched
-  // first — nothing DEPENDS on that: a consumer that does not see its producers within `timeout_ticks` raises the hand-over flag
-  // (SC_FAIL >= kFailHandover), the decision ends the loop WITHOUT taking or counting the step (LVF_WHY_HANDOVER) and the host re-runs
-  // the iteration with every level in a launch of its own (lvf_problem::no_chain) — a scheduling delay never becomes a numerical outcome.
-  GP<int> wait_counter; int wait_target; GP<int> done_counter;
-  int fenced; unsigned timeout_ticks;      // wall_clock64() ticks (100 MHz) before the hand-over is given up
-  int strip_end;           // S rows / columns below it belong to sparse blocks (lvf_problem::off)
-  int rmw_read;            // diagnostic: chained reads by returning atomics instead of agent-scope loads
-  GP<unsigned long long> dbg; // LVF_SP_TIMING=1: eight wall_clock64() stamps per workgroup (tile 0 of every node), else null
-  int s_zero;              // the level has nothing below it (level 0, early form): its part of S is still all zeros, not read
-  JacobiDev jac{nullptr, nullptr};
-  // fused chain (AccSel): *sel != 0 -> B and gc are read from the second accumulator set
-  GP<const int> sel{nullptr}; GP<const double> B1{nullptr}, gc1{nullptr};
-};
-struct SpArgs {          // one sparse level
-  GP<const SpNode> nodes; int first, tiles; GP<const int> rows; GP<double> S; int ld; GP<double> W; int wstride; GP<double> Lout; GP<int> fail; int nblocks; GP<const int> done;
-  SpSrc src;
-};
+
 template <bool SEL = false>
 __device__ __forceinline__ void sp_ride(const int vb, const SpArgs& a);     // workgroup vb of the level (defined with k_sp_eliminate)
-// SC_FAIL codes (raised with atomicMax: the largest wins): 1 + kb = dense block step kb met a non-positive pivot, kFailSparse + id = sparse
-// block id did, kFailHandover + id = a chained level gave up waiting for the level below (NOT a property of the problem: see SpSrc)
-constexpr int kFailSparse = 100000, kFailHandover = 300000;
-// Test tap (lvf_problem_debug_override_reduced): a caller's reduced system S [d x d] / rhs [d] in the natural unknown order, written over the
-// assembled one before any elimination level starts
-struct ReducedOverride { int d = 0; DevBuf<double> S, rhs; };
-// (debug_taps.hip: the copy kernel lives in a translation unit of its own, so this file's device code is what it is without the tap)
-int launch_override_reduced(hipStream_t q, int d, int ld, int aug, const int* perm, const double* Sov, const double* rhs, double* S);
-}
-struct lvf_problem {
-  lvf_ctx* ctx = nullptr;
-  lvf_state* st = nullptr;
-  lvf_batch *tc = nullptr, *tf = nullptr, *po = nullptr, *imu = nullptr, *prior = nullptr;
-  int n_kf = 0, n_lm = 0, d = 0, dp = 0, ldE = 0, dpad = 0, nb = 0;
-  // layout of the factorised matrix S (see "elimination order" below): [sparse (v,ba,bg) blocks | dense (v,ba,bg) blocks | poses | rhs row | pad]
-  int ld = 0, off = 0, off_pose = 0, ndense = 0, aug = 0, sp_wstride = 0;
-  lvf::SpLevels sp_levels{};
-  std::vector<int> sp_tiles, sp_shmem;          // per level: workgroups per node, dynamic LDS bytes
-  std::vector<int> sp_item0, sp_items;          // per level: its slice of sp_rows
-  std::vector<int32_t> plan_key;                // (n_kf, IMU index pairs) the current plan was built for
-  lvf::DevBuf<lvf::SpNode> sp_nodes;
-  lvf::DevBuf<int> sp_rows, sp_rows_nat, sp_owner, perm, iperm;      // sp_rows_nat: the natural-order unknown of every entry of sp_rows (-2 = the right-hand-side row)
-  lvf::DevBuf<int> lm_kmin, lm_kmax, lm_order, lm_nactive;   // per-landmark keyframe track [kmin, kmax]; Schur row order; #rows with pose blocks
-  bool band_ready = false;
-  // compact landmark layout + slabs of the atomic-free TwoFrame linearisation (see TfCompact)
-  bool compact = false;
-  lvf::DevBuf<int> lm_eoff, n_slots, tf_slot, run_first;
-  lvf::DevBuf<double> slotB, slabP, slabQ, Ct, grt;
-  lvf::StageClock* clk = nullptr;     // lvf_problem_stage_times
-  bool accum_clean = false;           // B / gc / C / g_rho / cost stripes are zero (left so by the last iteration's cost + decision launch)
-  const double* chain_tcw = nullptr;      // the TwoCamera per-block weight array the current chain was built with
-  int band_rows = 64;           // landmark rows per slice of the band Schur complement (a batch uses more: fewer output atomics)
-  lvf::DevBuf<int4> band_work; lvf::DevBuf<int> n_band_work_dev; lvf::HostPin<int> h_n_band_work;
-  int n_band_work = 0, band_rows_built = 0;
-  bool band_pending = false; hipEvent_t ev_band = nullptr;      // the item count of the list is still on its way (awaited just before the Schur launch)
-  int band_epoch = 0;                 // bumped whenever the landmark bands change (a batch keeps its own, wider-slice work lists: lvf_problem_batch)
-  std::vector<lvf_problem_batch*> batches;      // the batches that borrow this problem (they are told when it is destroyed)
-  lvf::HostPin<int> h_run_first;
-  lvf::DevBuf<unsigned long long> dbg, dbg_lin, dbg_sp;
-  lvf::DevBuf<double> dbg_hist;                 // LVF_LM_HISTORY=1: the decisions of the last solve (lvf_problem_debug_history)
-  lvf::DevBuf<double> sp_sync;                  // arrival counters of sparse levels chained inside one launch (one 8-byte slot per level, an int in each; cleared with the accumulators)
-  lvf::DevBuf<double> sp_W, sp_L, Dinv;         // Dinv: L_kk^-T of every 64x64 diagonal block of the dense corner
-  // product form of the sparse back substitution (lvf::GRide): G [9 n_nodes][ldG], allocated by the chain that uses it; sp_gmap [n_nodes][ldG]:
-  // which of a node's own rows (index into sp_rows) a dense-corner / augmented column is, or -1
-  lvf::DevBuf<double> sp_G; lvf::DevBuf<int> sp_gmap; int ldG = 0;
-  lvf::DevBuf<double> sp_T;      // block form of the dense back substitution (lvf::TRide): nb x nb blocks of 64 x 64, block (k, j) used for k < j
-  lvf::DevBuf<double> Ldiag;                    // the factored diagonal blocks L_kk [nb][64][64] (NOT stored back into S: see chol_step_body)
-  std::vector<int> perm_h;
-  lvf::DevBuf<double> B, gc, C, gr, E, Cd, S, dxc, dxl, scal;
-  lvf::DevBuf<double> B1, gc1, C1, gr1, E1, slotB1;    // the second accumulator set of the fused chain (lvf::AccSel)
-  lvf::DevBuf<double> jh0;                      // Jacobi scaling of the running solve: diag(J^T J) of its first pass (JacobiDev)
-  lvf::DevBuf<double> poses2, vel2, ba2, bg2, invd2;   // candidate state x + dx
-  lvf::DevBuf<uint8_t> pose_const;
-  lvf::DevBuf<int> fail;
-  lvf::DevBuf<lvf::TfWork> tf_work;   // per-workgroup runs of same-k2 blocks (empty => generic atomic path)
-  lvf::HostPin<lvf::TfWork> h_tf_work;
-  std::vector<uint8_t> pose_const_h;
-  bool linearized = false;
-  bool acc1_ready = false;            // the fused chain's second accumulator set is allocated and cleared for the current configuration (ensure_acc1)
-  // TwoFrame blocks as the solver reads them: the batch's own arrays, or — when the blocks of a current-keyframe run come with their first
-  // keyframes in no order (landmark ids not in creation order) — copies sorted by (current, first) keyframe made at problem_configure, so
-  // that a wave's 64 blocks share a few first keyframes and their sums go through the group-wise reductions instead of 63 LDS atomics per
-  // block (the slowest workgroup of k_lin_visual: 18 -> 12 us).  The batch itself is never reordered (lvf_batch_evaluate keeps its order).
-  lvf::DevBuf<double2> tfs_fo, tfs_ob;
-  lvf::DevBuf<int> tfs_lm, tfs_k1, tfs_k2, tfs_perm;
-  lvf::HostPin<int> h_tfs_perm;     // pinned staging of the permutation (the upload is asynchronous)
-  bool tf_sorted_copy = false;
-  const double2* tf_fo() const { return tf_sorted_copy ? tfs_fo.p : (const double2*)tf->ob_a.p; }
-  const double2* tf_ob() const { return tf_sorted_copy ? tfs_ob.p : (const double2*)tf->ob_b.p; }
-  const int* tf_lm() const { return tf_sorted_copy ? tfs_lm.p : tf->idx_a.p; }
-  const int* tf_k1() const { return tf_sorted_copy ? tfs_k1.p : tf->idx_b.p; }
-  const int* tf_k2() const { return tf_sorted_copy ? tfs_k2.p : tf->idx_c.p; }
-  bool tf_unique_lk2 = false;   // no (landmark, current keyframe) pair occurs twice in the TwoFrame batch
-  bool tf_k1_first = false;     // every TwoFrame block's first keyframe precedes its current keyframe
-  double last_radius = 0;
-  // the device-resident LM loop
-  lvf::DevBuf<lvf::LmCtl> ctl;        // control block (radius, costs, accept / reject, termination) in HBM
-  lvf::LmCtl* rec = nullptr;          // host-visible mirror written by k_lm_decide (hipHostMalloc)
-  lvf::HostPin<lvf::LmCtl> h_ctl;     // pinned staging for uploads / read-backs of the control block
-  lvf::Chain* chain = nullptr;        // argument blocks of one iteration
-  bool chain_ready = false;
-  bool no_chain = false;              // a chained hand-over timed out: this problem's levels are launches of their own until kUnchainedSolves solves have gone by
-  int unchained_solves = 0;           // solves taken since no_chain was set (chaining is tried again after kUnchainedSolves of them: one scheduling blip
-                                      // under Relocator traffic — relocator.cpp:188 — must not cost a persistent window its chained launches for good)
-  int handover_retries = 0;           // iterations re-run because of that (reported in lvf_solver_summary::hand_over_retries)
-  int force_handover_timeouts = 0;    // test hook (lvf_problem_debug_force_handover_timeout): the next chain is built with an unreachable wait target
-  const void* chain_state[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};    // the state pointers the chain was built for
-  double huber = 1.0;
-  hipGraphExec_t graph_exec = nullptr;
-  std::unique_ptr<lvf::ReducedOverride> ov;     // test tap: non-null while a reduced system is overridden (enqueue_iteration)
-  bool step_ready = false;            // dxc / the fail flag hold the step of an iteration (lvf_problem_debug_download_step)
-  int last_solved = -1;               // LmCtl::solved of the last iteration (lvf_problem_debug_last_solved)
-  ~lvf_problem();
-};
 
-namespace lvf {
-
-constexpr int kT = 256;
 typedef double double4_t __attribute__((ext_vector_type(4)));
-// device scalar slots
-// Each sum slot is STRIPED over kStripes addresses (workgroup b adds into stripe b % kStripes, the host adds the stripes up): a
-// cost pass issues one atomic per wave, ~1100 of them at configs[3], and on ONE address they serialise in L2 (measured: the
-// residual-only TwoFrame pass spent 2/3 of its 16 us there).  SC_GMAX is a max (striped too; the decision takes the max over the stripes).
-constexpr int kStripes = 32;
-enum { SC_COST = 0, SC_COST_NEW = 1 * kStripes, SC_MODEL = 2 * kStripes, SC_DXNORM = 3 * kStripes, SC_XNORM = 4 * kStripes, SC_GMAX = 5 * kStripes,
-       SC_N = 6 * kStripes, SC_FAIL = SC_N /* int flag */, SC_TICKET = SC_N + 1 /* int: workgroups of the candidate-cost pass that are done */, SC_ALLOC = SC_N + 2 };
-static inline double stripe_sum(const double* h, int slot) { double s = 0.0; for (int k = 0; k < kStripes; ++k) s += h[slot + k]; return s; }
 
 // The LM loop's `done` flag gates every launch of an iteration.  Tested at the top of a kernel it is a dependent global round trip
 // (~0.5-1 us) in front of everything; issued FIRST and tested after the kernel's own first loads have been issued, its latency hides
@@ -186,36 +35,11 @@ __device__ __forceinline__ void block_add(double v, double* dst) {
   if ((threadIdx.x & 63) == 0 && v != 0.0) atomicAdd(dst + ((blockIdx.x + blockIdx.y) & (kStripes - 1)), v);
 }
 
-struct StateP { GP<const double> poses, vel, ba, bg, inv_depth, w_kf; };
 
-// The fused chain (LVF_FUSED_LIN, default on) linearises at the CANDIDATE inside the cost + decision pass, so a problem keeps two sets of what
-// a linearisation writes — B, gc, C, g_rho, the E rows and the TwoFrame slot records — and LmCtl::aset names the set that holds the
-// linearisation at the current state.  An argument block whose `sel` is set picks its set on device (set 1: the pointers here; set 0: the
-// block's own); sel == nullptr (today's chain, the taps, a batch) always means set 0.
-struct AccSel { GP<const int> sel; GP<double> B, gc, C, gr, E, slotB; };
 __device__ __forceinline__ int acc_set(const AccSel& a) { return a.sel ? *a.sel : 0; }
 // SEL = false (the batched table launches, which never run the fused chain): set 0, the selection compiled out
 template <bool SEL> __device__ __forceinline__ int acc_set_t(const AccSel& a) { return SEL ? acc_set(a) : 0; }
 
-// Device-resident control block of one window's Levenberg-Marquardt loop.  Everything that changes from one iteration to the next
-// lives here (trust-region radius, costs, accept / reject, termination), so the arguments of every kernel of an iteration are
-// constant across iterations: the host enqueues iteration after iteration without waiting, k_lm_decide closes each one on device
-// (what the reference's ceres::Solve does on the host between evaluations).
-struct LmCtl {
-  double radius, decrease;                         // trust region (in: start values; updated by every iteration)
-  double last_radius;                              // the radius the last iteration's step was computed with
-  double cost, initial_cost;                       // cost at the current state / at the first linearisation
-  double cost_before, cost_after, model, dxnorm, xnorm, gmax;   // scalars of the last iteration
-  double huber, function_tol, gradient_tol, parameter_tol, min_rel_decrease;
-  int max_iters;
-  int iter, successes, invalid_run;                // iterations taken / accepted steps / consecutive unsolvable steps
-  int accepted, solved;                            // of the last iteration
-  int done, termination;                           // done != 0: the remaining launches of this window return immediately
-  int why, rejected;                               // LVF_WHY_* reason of the termination ; rejected / invalid steps so far
-  int jfrozen;                                     // Jacobi scaling taken (JacobiDev): 0 until the solve's first pass has been decided on
-  int aset;                                        // fused chain: the accumulator set holding the linearisation at the state (AccSel)
-  int lin_pending;                                 // fused chain: that set's TwoFrame slabs are not yet reduced into B / gc (an accepted candidate pass)
-};
 
 // lower-triangle accumulation of a 6x6 block pair J_a^T J_b into B at (ra, rb) block offsets (ra >= rb required
 // for off-diagonal; for ra == rb only the lower half is written)
@@ -369,23 +193,6 @@ __global__ __launch_bounds__(kT) void k_lin_tf(int n, int n_kf, const double2* _
 //   * B[k1,k1], g[k1] and the cross block B[k2,k1] only depend on k1 <= n_kf: accumulated with ds_add_f64 in a
 //     [n_kf][63] LDS table and flushed once per workgroup (non-zero entries only),
 //   * only the landmark-indexed sums (C, g_rho, E rows) remain global atomics: 14 per block instead of 134.
-struct TfWork { int first, count, k2; };
-// Atomic-free outputs of the sorted TwoFrame linearisation ("compact" mode).  Measured on MI355X: the 8 landmark-indexed global f64
-// atomics per block were 18 of the 21 us a workgroup spent between loading its blocks and its reductions, and together with the
-// per-workgroup flush of the keyframe-indexed sums (~1 M atomics per linearisation at configs[3]) they are a chip-wide L2 bottleneck
-// (~30 atomics / ns) that a batch of windows hits W times over.  Instead:
-//   * the k2 columns of a landmark's (dense) E row have exactly one writer: plain stores.  The row is NOT cleared per linearisation: its
-//     non-zero pattern (the landmark's track) is fixed for a problem, so E is zeroed once per problem_configure and every entry inside
-//     the pattern is overwritten by every linearisation;
-//   * every block owns a SLOT s = eoff[l] + (k2 - k1 - 1) of its landmark's track and writes there, with plain 16-byte stores, one
-//     64-byte record: its contributions to the k1 columns of E (6), to C and to g_rho.  k_prepare reads a landmark's slots as one
-//     contiguous range, sums them and completes the row (k1 columns, g_rho column) and Cd;
-//   * every workgroup writes its LDS table of keyframe-indexed sums to its own slab (slabP[wg][k1][64], slabQ[wg][32]); k_tf_reduce adds
-//     the slabs of a run into B / gc, each entry of B having exactly one owner there.
-struct TfCompact { int on; GP<const int> slot; GP<double> slotB, slabP, slabQ; int staged; };
-constexpr int kSlabRow = 64, kSlabQ = 32;
-constexpr int kAccSlots = 63;   // 21 (B[k1,k1] lower) + 6 (g[k1]) + 36 (cross block, rows = k2 tangent, cols = k1 tangent)
-constexpr int kStageWave = 64 * 9 + 32;   // doubles of LDS staging per wave (segmented first-keyframe sums): 64 x (8 + 1 pad) values + 64 ints
 // DYN: the LDS tables are carved from the launch's dynamic LDS, sized by the window's n_kf (k_lin_visual: 32 KB at 50 keyframes instead of
 // 79 KB of static arrays sized for 64 — three workgroups per CU instead of two)
 template <bool DYN = false>
@@ -663,19 +470,6 @@ __device__ __forceinline__ void lin_tf_sorted_body(const int vb, const TfWork* _
 // ------------------------------------------------------------------------------------------------ candidate cost, visual factors
 // One launch for the residual-only passes of the three reprojection batches (the workgroups of the launch are split into a
 // TwoCamera, a TwoFrame and a PoseOnly segment): as three back-to-back launches of 4-9 us they were mostly launch boundaries.
-struct CostVisual {
-  int n_tc, n_tf, n_po, g_tc, g_tf;
-  GP<const double2> tc_lo, tc_ro; GP<const int> tc_lm, tc_kf; GP<const double> tc_w; CamD tc_left, tc_right;
-  GP<const double2> tf_fo, tf_ob; GP<const int> tf_lm, tf_k1, tf_k2; CamD tf_left, tf_right;
-  GP<const double2> po_ob; GP<const int> po_kf, po_pwi; GP<const double> po_pw; CamD po_cam;
-};
-struct ImuEvalArgs { int n; GP<const double> pre, sqrt_info; GP<const int> kf_i, kf_j; };      // ImuError factors evaluated inside a merged launch
-struct CostArgs {
-  CostVisual a; int n_kf; StateP s; double huber; GP<double> cost; int nblocks; GP<const int> done;
-  ImuEvalArgs imu; int g_imu;       // workgroups [0, g_imu) evaluate one ImuError factor each, the visual passes follow
-  int tiles;                        // tiles of kT blocks per visual workgroup (0 = 1)
-  ZeroList zero; int zero_wgs;      // workgroups [nblocks, nblocks + zero_wgs) of the merged cost + decision launch clear the accumulators for the NEXT linearisation
-};
 // the calling thread's share of the candidate cost (workgroup b of the pass)
 __device__ __forceinline__ double cost_visual_value(const int b, const CostArgs& A) {
   const CostVisual& a = A.a;
@@ -840,7 +634,6 @@ __global__ __launch_bounds__(kT) void k_lin_po(int n, int n_kf, const double2* _
 
 // ------------------------------------------------------------------------------------------------ IMU
 // consumes the materialised ImuError outputs (res[n][15], eight Jacobian blocks) of launch_imu; one wave per factor
-struct ImuJ { GP<const double> j[8]; };
 __global__ __launch_bounds__(64) void k_lin_imu(int n, int n_kf, const double* __restrict__ res, ImuJ J, const int* __restrict__ kf_i,
                                                 const int* __restrict__ kf_j, const double* __restrict__ poses,
                                                 const uint8_t* __restrict__ pose_const, double* __restrict__ B, int ld,
@@ -984,8 +777,6 @@ __device__ __forceinline__ void lin_imu_body4(const int vb, int n, int n_kf, con
 //   stage sqrt_info -> one lane forms the raw residual and the 15 x 32 pre-weighting Jacobian -> all lanes weight them ->
 //   pose columns to tangent coordinates -> J^T J / J^T r into B / gc, 1/2 |r|^2 into the cost.
 // LDS (doubles): sS 225 | sM 480 (later the local 15 x 30 Jacobian) | sJw 480 | sr0 16 | sr 16 | sidx 16  = kImuWaveLds.
-constexpr int kEndZeroWgs = 192;       // workgroups of the cost + decision launch that clear the accumulators
-constexpr int kImuWaveLds = 225 + 480 + 480 + 16 + 16 + 16 + 248 + 32 + 2;      // + the pre-integration's head (OFF_COV doubles) + the two keyframes' states
 __device__ __forceinline__ void lin_imu_eval_body(const int f, const ImuEvalArgs& I, int n_kf, const StateP& s, const uint8_t* __restrict__ pose_const,
                                                   double* __restrict__ B, int ld, double* __restrict__ gc, double* __restrict__ cost, unsigned long long* dbg) {
   // ONE factor per workgroup: the evaluation's serial part (one lane) is what it is, everything around it is spread over all kT threads
@@ -1071,23 +862,6 @@ __device__ __forceinline__ void lin_imu_eval_body(const int f, const ImuEvalArgs
   if (dbg) dbg[4] = wall_clock64();
 }
 
-struct LinVisual {
-  int n_tfw, g_tc;
-  // TwoFrame
-  GP<const TfWork> work; GP<const double2> tf_fo, tf_ob; GP<const int> tf_lm, tf_k1; CamD tf_left, tf_right; int unique_lk2; TfCompact cp;
-  // TwoCamera
-  int n_tc; GP<const double2> tc_lo, tc_ro; GP<const int> tc_lm, tc_kf; GP<const double> tc_w; CamD tc_left, tc_right;
-  // PoseOnly
-  int n_po, g_po; GP<const double2> po_ob; GP<const int> po_kf, po_pwi; GP<const double> po_pw; CamD po_cam;
-  // ImuError: evaluated inside the launch (imu.pre != nullptr) or ahead of it by k_imu<true> (imu_res / imu_J)
-  int n_imu; GP<const double> imu_res; ImuJ imu_J; GP<const int> imu_i, imu_j; ImuEvalArgs imu;
-};
-struct LinArgs {
-  LinVisual v; int n_kf; StateP s; double huber; GP<const uint8_t> pose_const; GP<double> B; int ld; GP<double> gc; GP<double> E; int ldE; GP<double> C, gr, cost;
-  int nblocks; GP<const int> done; GP<unsigned long long> dbg; int rows;
-  GP<double> scal_reset;      // early sparse levels: the per-step scalars and the fail flag are reset HERE (the levels start before k_prepare, which resets them otherwise)
-  AccSel acc;                 // the second accumulator set (the fused candidate pass writes the set that is not active)
-};
 __device__ __forceinline__ void reset_step_scalars(double* scal) {
   for (int k = SC_COST_NEW + threadIdx.x; k < SC_N; k += kT) scal[k] = 0.0;
   if (threadIdx.x == 0) { *reinterpret_cast<int*>(scal + SC_FAIL) = 0; *reinterpret_cast<int*>(scal + SC_TICKET) = 0; }
@@ -1135,14 +909,6 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(3))) void k_
 //   workgroups [0, n_kf)         keyframe k: B[k,k] (21) and g[k] (6) = sum of slabQ over run(k) (k as current keyframe)
 //                                                                      + sum of slabP[.][k][0..27) over every later workgroup (k as first keyframe)
 //   the rest                     one thread per (k2, k1 < k2, entry of the 6x6 cross block) = sum of slabP[.][k1][27..63) over run(k2)
-struct TfReduceArgs {
-  int n_kf, n_wg; GP<const int> run_first; GP<const double> slabP, slabQ; GP<double> B; int ld; GP<double> gc; int nblocks; GP<const int> done;
-  int own_blocks; SpArgs ride;       // workgroups [own_blocks, nblocks): a sparse level riding in this launch (early form)
-  // fused chain: B / gc of the active set (acc); `pending` (LmCtl::lin_pending) == 0: the active set was reduced by an earlier iteration (the
-  // last step was rejected) and this launch leaves it alone; workgroups [nblocks, nblocks + zero_wgs) clear the set that is NOT active
-  // (stand0 when set 1 is active, stand1 otherwise) for the candidate pass at the end of the iteration — never gated
-  AccSel acc; GP<const int> pending; ZeroList stand0, stand1; int zero_wgs;
-};
 template <bool SEL>
 __device__ __forceinline__ void tf_reduce_body(const int bx0, const TfReduceArgs& A) {
   if (bx0 >= A.nblocks) {
@@ -1301,7 +1067,6 @@ __global__ __launch_bounds__(64) void k_lin_prior(int n, const double* __restric
 }
 // The same with the evaluation inside (prior_eval.hpp): the block's residuals and ambient Jacobians never leave the thread — one launch
 // instead of k_pose_prior + k_lin_prior on the LM loop's path (a window with weak frames pays it every iteration), nothing materialised.
-struct PriorArgs { int n; GP<const int> kf_a, kf_b; GP<const double> target, weight, vv; };
 __global__ __launch_bounds__(64) void k_prior_lin(PriorArgs P, const double* __restrict__ poses, const uint8_t* __restrict__ pose_const,
                                                   double* __restrict__ B, int ld, double* __restrict__ gc, double* __restrict__ cost) {
   const int i = blockIdx.x * 64 + threadIdx.x;
@@ -1352,18 +1117,6 @@ __device__ __forceinline__ double lm_damping_own(double h, const JacobiDev& j, i
 //   blocks [nS_blocks, ...)    : Cd = C + clamp(C)/radius ; E[l][dp] = gr[l] (the extra column that makes the SYRK also
 //                                produce E^T Cd^-1 g_rho)
 //   block 0 / thread 0         : resets the per-step scalars (candidate cost, model change, norms) and the Cholesky fail flag
-struct PrepArgs {
-  int ld, dpad, jl0 /* = d: the first landmark slot of jac.h0 */; GP<const int> iperm; GP<const double> B, gc; GP<const double> radius; GP<double> S; unsigned nS_blocks; int n_lm, dp, ldE; GP<const double> C, gr;
-  GP<double> Cd, E, scal; int nblocks; GP<const int> done;
-  // atomic-free mode (slotB != nullptr): per-landmark totals from the slot records
-  GP<const int> eoff, kmin, kmax; GP<const double> slotB; GP<double> Ct, grt;
-  // early form (early != 0): S was cleared with the accumulators and sparse levels may already have added into the dense corner, so the
-  // corner's entries (rows / columns >= off) are ADDED, and the columns of the sparse blocks are left alone (the levels form them themselves)
-  int early, off;
-  int own_blocks; SpArgs ride;       // workgroups [own_blocks, nblocks): a sparse level riding in this launch
-  JacobiDev jac;
-  AccSel acc;                        // fused chain: B, gc, C, g_rho, the slot records and E of the active set
-};
 template <bool SEL>
 __device__ __forceinline__ void prepare_body(const unsigned bx0, const PrepArgs& A) {
   if (bx0 >= (unsigned)A.nblocks || (A.done && *A.done)) return;
@@ -1455,7 +1208,6 @@ __global__ __launch_bounds__(kT) void k_prepare_bt(const PrepArgs* __restrict__ 
 // T = Ea^T diag(1/Cd) Ea with Ea = [E | g_rho] (n_lm x ldE).  One wave per (16x16 output tile, K-chunk); tiles on or
 // below the diagonal only.  v_mfma_f64_16x16x4_f64: A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15],
 // D: col = lane&15, row = (lane>>4) + 4*reg.   S[i][j] -= T[i][j] (i,j < dp);  S[d][i] += T[dp][i].
-constexpr int kSchurChunk = 512;
 __global__ __launch_bounds__(64) void k_schur_syrk(int n_lm, int dp, int ldE, int ntile, const double* __restrict__ E,
                                                    const double* __restrict__ Cd, int d, int ldS, double* __restrict__ S) {
   // decode lower-triangular tile index
@@ -1490,7 +1242,6 @@ __global__ __launch_bounds__(64) void k_schur_syrk(int n_lm, int dp, int ldE, in
 // the current one feeds the matrix cores); every wave keeps up to kSchurTilesPerWave 16x16 accumulators in registers across
 // the whole slice and the workgroup touches S once at the end.  Versus one wave per (tile, 512-row chunk) with strided 8-byte
 // global operand loads: the same MFMA count, 1/8 of the atomics, and E is read once per tile group instead of once per tile.
-constexpr int kSchurGroups = 8, kSchurTilesPerWave = 8, kSchurRows = 16;
 __global__ __launch_bounds__(256) void k_schur_lds(int n_lm, int dp, int ldE, int ntile, int rows_per_slice, const double* __restrict__ E,
                                                    const double* __restrict__ Cd, int d, int ldS, double* __restrict__ S) {
   extern __shared__ double sh[];          // Es[kSchurRows][ldE] | icd[kSchurRows]
@@ -1572,11 +1323,6 @@ __global__ __launch_bounds__(256) void k_schur_lds(int n_lm, int dp, int ldE, in
 // those columns (plus the tile holding the g_rho column) and only forms the band's lower-triangular tiles.  At configs[3]
 // that is ~1/5 of the MFMAs and ~1/30 of the E bytes of the dense SYRK.  Correctness never depends on the ordering: the
 // band of each slice is computed from the actual kmin/kmax of its rows.
-constexpr int kBandTilesPerWave = 8;        // output tiles (16 x 16 accumulators) a wave of the band Schur complement carries.  (Measured round 4, same box: 16 — one
-// workgroup covers most slices' whole band, E read once instead of ~2x — needs > 256 VGPRs: 0.204 -> 0.254 ms / iteration spilling under the two-waves-per-SIMD
-// attribute below, 0.206 / 8 windows 0.375 -> 0.435 ms with one wave per SIMD; 4 — more, smaller workgroups — 8 windows 0.43 -> 0.59 ms.  The launch is bound by
-// how many workgroups overlap their fetch -> LDS -> matrix-core chains, not by E's bytes.)
-constexpr int kBandRows = 64, kBandRowsMax = 256, kBandTilesPerGroup = 4 * kBandTilesPerWave;     // rows per slice: 64 for one window, up to 256 in a batch (fewer output atomics)
 __global__ __launch_bounds__(kT) void k_lm_range(int n, const int* __restrict__ lm, const int* __restrict__ k1, const int* __restrict__ k2,
                                                  int* __restrict__ kmin, int* __restrict__ kmax) {
   const int i = blockIdx.x * kT + threadIdx.x;
@@ -1857,32 +1603,6 @@ __global__ __launch_bounds__(256) void k_schur_band(int dp, int ldE, const doubl
                                                     double* __restrict__ S) {
   schur_band_body(blockIdx.x, blockIdx.y, dp, ldE, E, Cd, order, n_active_p, kmin, kmax, d, ldS, S);
 }
-struct LmBand { GP<const int> order; GP<const int> n_active; GP<const int> kmin; GP<const int> kmax; };   // null order => dense SYRK
-static int launch_schur(hipStream_t q, int n_lm, int dp, int ldE, const double* E, const double* Cd, int d, int ldS, double* S, const LmBand& band) {
-  const int nt = ldE / 16, ntile = nt * (nt + 1) / 2;
-  if (band.order) {
-    const size_t shb = ((size_t)kSchurRows * (ldE + 16) + kSchurRows) * sizeof(double) + kBandRowsMax * sizeof(int);
-    if (shb <= 64 * 1024) {
-      hipLaunchKernelGGL(k_schur_band, dim3((n_lm + kBandRows - 1) / kBandRows, (ntile + kBandTilesPerGroup - 1) / kBandTilesPerGroup), dim3(256), shb, q,
-                         dp, ldE, E, Cd, band.order, band.n_active, band.kmin, band.kmax, d, ldS, S);
-      LVF_HIP(hipGetLastError());
-      return LVF_OK;
-    }
-  }
-  const bool lds_path = ldE <= 320 && ntile <= kSchurGroups * 4 * kSchurTilesPerWave;
-  if (lds_path) {
-    const int slices = std::max(1, std::min(32, (n_lm + 4 * kSchurRows - 1) / (4 * kSchurRows)));   // 16..128 measured: 32 is the optimum at 10 k rows
-    int rows_per_slice = (n_lm + slices - 1) / slices;
-    rows_per_slice = ((rows_per_slice + kSchurRows - 1) / kSchurRows) * kSchurRows;
-    const size_t shb = ((size_t)kSchurRows * ldE + kSchurRows) * sizeof(double);
-    hipLaunchKernelGGL(k_schur_lds, dim3(kSchurGroups, (n_lm + rows_per_slice - 1) / rows_per_slice), dim3(256), shb, q, n_lm, dp, ldE, ntile, rows_per_slice, E,
-                       Cd, d, ldS, S);
-  } else {
-    hipLaunchKernelGGL(k_schur_syrk, dim3(ntile, (n_lm + kSchurChunk - 1) / kSchurChunk), dim3(64), 0, q, n_lm, dp, ldE, ntile, E, Cd, d, ldS, S);
-  }
-  LVF_HIP(hipGetLastError());
-  return LVF_OK;
-}
 
 // ------------------------------------------------------------------------------------------------ blocked Cholesky (64)
 // Right-looking, block 64, ONE launch per block step (k_chol_step): every workgroup of the step's column re-factors the 64x64 diagonal
@@ -1891,7 +1611,6 @@ static int launch_schur(hipStream_t q, int n_lm, int dp, int ldE, const double* 
 // The sequential critical path is ~64 x (rsqrt + broadcast) per block; everything else is wide.  Two sweeps over the 64 pivots exist: the
 // 16-pivot sub-block sweep (sub_pivots, the default) and the pair-pivot sweep it replaced (factor_diag_wave / factor_panel_wave,
 // LVF_CHOL_SUBBLOCK=0); loads, the previous step's update, the stores and everything another launch reads are common to both.
-constexpr int kNB = 64, kLd = 65;
 
 __device__ __forceinline__ void load_row64(const double* __restrict__ g, double a[kNB]) {
   const double2* g2 = reinterpret_cast<const double2*>(g);
@@ -1950,7 +1669,6 @@ __device__ __forceinline__ void rank1_row_bcast(const int from, double a[16], do
   if (from <= 14) fmac_row_bcast<14>(a[14], lv, m);
   if (from <= 15) fmac_row_bcast<15>(a[15], lv, m);
 }
-constexpr int kPG = 2, kCT = 512, kGW = 16 / kPG;                    // pivots per group, threads, groups per wave
 struct FactorLds { double* Lcol; double* Xcol; double* Linv; };       // Lcol/Xcol: [64 columns][64 rows]
 
 // diagonal wave Q, steps s = kGW qj + i (i unrolled, qj a real loop: the code of one column group is reused four times).  In step s the
@@ -2098,11 +1816,6 @@ __device__ __forceinline__ void sub_pivots(double d[16], double b[16], bool& bad
 //       L_kk^-T for the back substitution.
 //   workgroups behind them     — the rest of step kb-1's trailing update, A[bi][bj] -= P_bi P_bj^T for kb < bj <= bi, which nothing in
 //       this launch reads (the next step does).
-struct CholArgs { GP<double> Sd; int ld, nb; GP<int> fail; GP<double> Dinv; GP<const int> done; GP<unsigned long long> dbg; int last_cols; GP<double> Ldiag; };   // dbg: LVF_CHOL_TIMING stamps; last_cols: real (un-padded) columns of the last block
-__host__ __device__ inline int chol_step_grid(int nb, int kb) {
-  const int below = nb - kb - 1;
-  return kb >= nb ? 0 : 2 + below + (kb > 0 ? below * (below + 1) / 2 : 0);
-}
 
 // staging of a 64x64 block at g (leading dimension ld) into LDS with row stride kLd by 256 threads (t = 0..255): all eight 16-byte
 // loads of a thread are in flight before the first LDS write (written as one loop the compiler waits for each load in turn)
@@ -2170,7 +1883,6 @@ __device__ __forceinline__ void chol_update_tile(double* S, int ld, int kp, int 
 // two 16x16 tiles per wave on the matrix cores).  Stored TRANSPOSED, block (k, j) at T + (k nb + j) 64^2, entry [r][c] = T_kj[c][r]: the
 // back substitution's wave `part` reads rows 8 part .. 8 part + 7, each one contiguous run of 64 doubles.
 // Riders wait for nothing and raise no flag; a poisoned factor sends its NaN through here into a step the failure flag rejects.
-struct TRide { int n; GP<double> T; };
 __device__ __forceinline__ void back_block_ride(const int vb, const CholArgs& A, const int kb, const TRide& R) {
   if (vb >= R.n || kb < 1 || kb + vb >= A.nb) return;
   if (A.done && *A.done) return;
@@ -2387,7 +2099,6 @@ __device__ __forceinline__ void chol_step_body(const int bx, const CholArgs& A, 
 // leave most of the chip idle), level n_levels - 1 - kb in launch kb, so the launch boundaries order the levels.  One workgroup per node, one
 // thread per column, no LDS and no barrier: the row list is ascending, i.e. the sparse neighbours come first, and `map` (host-built with the
 // plan) tells a column which of the node's own rows it is.
-struct GRide { int n, first; GP<const SpNode> nodes; GP<const int> rows; GP<const double> W; int wstride; GP<const double> Linv; GP<const int> map; GP<double> G; int ldG, off; GP<const int> done; };
 __device__ __forceinline__ void back_product_ride(const int vb, const GRide& R) {
   if (vb >= R.n) return;
   if (R.done && *R.done) return;
@@ -2443,7 +2154,6 @@ __global__ __launch_bounds__(kCT) void k_chol_step_pp(CholArgs a, int kb, GRide 
 }
 __global__ __launch_bounds__(kCT) void k_chol_step_pp_b(const CholArgs* __restrict__ t, int kb) { chol_step_body<false>(blockIdx.x, t[blockIdx.y], kb); }
 __global__ __launch_bounds__(kCT) void k_chol_step_pp_bt(const CholArgs* __restrict__ t, int kb) { chol_step_body<false>(blockIdx.y, t[blockIdx.x], kb); }
-static bool chol_subblock_on() { static const bool on = [] { const char* e = std::getenv("LVF_CHOL_SUBBLOCK"); return !(e && e[0] == '0'); }(); return on; }
 
 // ------------------------------------------------------------------------------------------------ elimination order
 // The (v, ba, bg) blocks only meet each other and the poses through ImuError factors, i.e. along the IMU chain: block k touches
@@ -2731,14 +2441,6 @@ __global__ __launch_bounds__(256) void k_sp_eliminate_b(const SpArgs* __restrict
 // The band-limited Schur complement and the FIRST sparse level in one launch: both only ADD (atomically) into entries of S the other
 // does not read — the Schur complement touches the pose corner and the pose part of the rhs row, level 0 reads its own (v,ba,bg)
 // columns — so they are independent; later levels depend on level 0 and stay launches of their own.
-struct SchurSp0Args {
-  int n_slices, n_groups, dp, ldE; GP<const double> E, Cd; GP<const int> order, n_active, kmin, kmax; int d_local, ldS; GP<double> S_pose;
-  SpArgs sp;             // the sparse level riding in the launch (sp.nblocks == 0: Schur complement only): level 0, or — early form — the first one left
-  SpArgs sp_b, sp_c;     // early form: the next two levels, chained behind it inside the launch (SpSrc::wait_counter)
-  int nblocks; GP<const int> done; GP<unsigned long long> dbg; int rows;
-  GP<const int4> work; int n_work;      // (slice, group, band lo | hi << 16, slice end) items; the sparse levels run in the first workgroups, the items behind
-  AccSel acc;                           // fused chain: E of the active set
-};
 template <bool SEL>
 __device__ __forceinline__ void schur_sp0_body(const int b, const SchurSp0Args& A) {
   if (b >= A.nblocks) return;
@@ -2765,14 +2467,6 @@ __device__ __forceinline__ void schur_sp0_body(const int b, const SchurSp0Args& 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_schur_sp0(SchurSp0Args a) { schur_sp0_body<true>(blockIdx.x, a); }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_schur_sp0_b(const SchurSp0Args* __restrict__ t) { schur_sp0_body<false>(blockIdx.x, t[blockIdx.y]); }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_schur_sp0_bt(const SchurSp0Args* __restrict__ t) { schur_sp0_body<false>(blockIdx.y, t[blockIdx.x]); }
-struct SpBack {                    // what the back substitution needs of the plan
-  SpLevels lv;
-  int item0[kSpMaxLevels], items[kSpMaxLevels];   // the level's slice of rows/owner/W
-  GP<const SpNode> nodes; GP<const int> rows; GP<const int> owner; GP<const double> W; GP<const double> Linv; GP<const int> perm;
-  int off, aug, d_total, total_items, n_nodes, max_count, linv_in_lds;
-  int prod_items;                  // > 0: LDS room for that many (row x 9) products => conflict-free two-stage sums; 0: LDS atomics
-  GP<unsigned long long> dbg;         // LVF_BACK_TIMING=1: wall_clock64() stamps (100 MHz) at the phase boundaries, else null
-};
 
 // workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt, i.e. it would wait for the global prefetches
 // that are meant to stay in flight across it
@@ -2794,16 +2488,6 @@ template <typename T>
 __device__ __forceinline__ T ld_off32(const T* base, unsigned byte_off) {     // wave-uniform base + 32-bit lane offset (saddr + voffset form)
   return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
 }
-constexpr int kBT = 512, kBParts = kBT / 64, kBackPre = 256 / kBParts, kBackInv = 64 / kBParts, kTailPre = 6;
-// pose_ready (merged back-substitution + step tail, k_backsolve_tail): once the dense corner is solved the POSE part of the step (natural
-// unknowns [0, n_pose)) is written out and *pose_ready is raised (release, agent scope) — what the landmark back-substitution waits for
-// T (block form, back_block_ride): the stored products T_kj of this iteration's factor, or null for the form that reads S and Dinv
-struct BackArgs { GP<const double> Sd; int ld, d; GP<const double> Dinv; GP<double> xout; SpBack sp; GP<const int> done; GP<const double> Ldiag; GP<int> pose_ready = nullptr; int n_pose = 0; int pose_fenced = 0;
-                  GP<const double> T = nullptr; };
-// block form: links j = nblk - 1 .. 1 whose products a thread holds in registers, eight doubles per block (k, j), k < j.  The dense-corner-only
-// body has the room for a corner of five blocks (ten products); beside the sparse levels' items they take the place of the gather operands
-// (three products: three blocks).  A corner with more blocks keeps the S / Dinv form (build_chain).
-constexpr int kBackTJ = 4, kBackTJLevels = 2;
 // LEVELS = false (the product form, k_backsolve_tail with Chain::back_product): the dense corner only.  The WHOLE dense-corner solution is
 // published — the plan may leave (v, ba, bg) blocks in the corner's padding, and the sibling workgroups' product with G reads them — and the
 // sparse items, the stored L_bb^-1 and the levels are neither requested nor run.
@@ -3089,7 +2773,6 @@ __global__ __launch_bounds__(kBT) void k_chol_backsolve_b(const BackArgs* __rest
 // into LDS, multiply-adds from registers, row16_sum and the stores; the rest of a longer band and any further pass are read as before.
 // Two passes of 32 landmarks over 224 workgroups hold 14 336 landmarks: the 10 000 of the headline window need nothing else.
 // (What is requested early is NOT __restrict__ then: LLVM would sink the requests past the wait to their uses, as in chol_backsolve_body.)
-constexpr int kLmEPre = 8;
 struct NoWait { __device__ __forceinline__ void operator()() const {} };
 template <bool R, typename T> struct RestrictIf { typedef T* __restrict__ type; };
 template <typename T> struct RestrictIf<false, T> { typedef T* type; };
@@ -3278,12 +2961,6 @@ __device__ __forceinline__ void apply_step_body(const int vb, int n_kf, int n_lm
 
 // landmark back-substitution and the camera-side step / model terms as ONE launch: workgroups [0, g_lm) walk the landmarks,
 // the rest apply dx to the keyframe states (independent of the landmark results)
-struct TailArgs {
-  int g_lm, n_lm, dp, ldE; GP<const double> E, C, Cd, gr, dxc; GP<double> dxl, scal; GP<const int> kmin, kmax; int n_kf; StateP s;
-  GP<double> poses2, vel2, ba2, bg2, invd2; int d, ld; GP<const double> B, gc; GP<const double> radius; int nblocks; GP<const int> done;
-  GP<const unsigned char> pose_const; JacobiDev jac;
-  AccSel acc;             // fused chain: E, B, gc of the active set (C, gr here are k_prepare's single totals Ct / grt: the chain needs compact mode)
-};
 template <bool SEL = true> __device__ __forceinline__ const double* tail_E(const TailArgs& A) { return acc_set_t<SEL>(A.acc) ? (const double*)A.acc.E : (const double*)A.E; }
 template <bool SEL = true> __device__ __forceinline__ const double* tail_B(const TailArgs& A) { return acc_set_t<SEL>(A.acc) ? (const double*)A.acc.B : (const double*)A.B; }
 template <bool SEL = true> __device__ __forceinline__ const double* tail_gc(const TailArgs& A) { return acc_set_t<SEL>(A.acc) ? (const double*)A.acc.gc : (const double*)A.gc; }
@@ -3310,9 +2987,6 @@ __global__ __launch_bounds__(kT) void k_step_tail_bt(const TailArgs* __restrict_
 // wait for the same flag as the landmark workgroups, take one product with their rows of G (formed under the dense factorisation:
 // back_product_ride) and apply the (v, ba, bg) part of the step for their keyframes.  The launch then ends at flag + max(landmark pass,
 // product) instead of flag + levels.
-struct BackTailArgs { BackArgs back; TailArgs tail; int g_lm; int fenced; unsigned timeout_ticks; GP<int> fail;
-                      int g_prod = 0, kpw = 0, ldG = 0; GP<const double> G = nullptr; GP<const int> iperm = nullptr;
-                      int early = 1; };      // early: the landmark and pose workgroups request their operands before the wait (LVF_BACK_EARLY=0: behind it)
 // the bounded wait of the consumers of pose_ready (SpSrc has the rules)
 __device__ __forceinline__ void wait_pose_ready(const BackTailArgs& a) {
   if (threadIdx.x == 0) {
@@ -3475,16 +3149,6 @@ __global__ __launch_bounds__(kBT) void k_backsolve_tail(BackTailArgs a) {
 // of kilobytes: the window's poses, velocities, biases and inverse depths) and the termination tests — what ceres::Solve's
 // TrustRegionMinimizer does on the host between evaluations (declared semantics: oracle/lm.h).  The scalars arrive as 32-way striped
 // sums (block_add); `rec` (optional, host-mapped) receives a copy of the control block so a waiting host sees progress without a copy.
-struct DecideArgs {
-  GP<const double> scal; GP<LmCtl> ctl; GP<LmCtl> rec; GP<int> ticket;
-  int n_kf, n_lm;
-  GP<double> poses, vel, ba, bg, invd;                 // the state
-  GP<const double> poses2, vel2, ba2, bg2, invd2;      // the candidate
-  GP<unsigned long long> dbg;                              // LVF_COST_TIMING=1: wall_clock64() stamps (100 MHz), else null
-  GP<double> hist;                                         // LVF_LM_HISTORY=1: eight doubles per closed pass (64 passes), else null
-  int fused;                                               // closes a fused candidate pass (k_lin_cost_decide): see lm_decide_body
-};
-constexpr int kDT = 256;
 // COHERENT: the sums are read past the caches (the caller is the last workgroup of the launch that produced part of them)
 template <bool COHERENT = false>
 __device__ __forceinline__ void lm_decide_body(const DecideArgs& A) {
@@ -3705,7 +3369,6 @@ __global__ __launch_bounds__(kT) void k_cost_decide_bt(const CostArgs* __restric
 // the candidate is not evaluated a second time — and a rejected step re-uses the linearisation at x it already has.  The workgroup's cost
 // parts meet in LDS and leave as ONE returning atomic before its ticket (cost_decide_body has the ordering argument); workgroups
 // [nblocks, nblocks + zero_wgs) clear S and the arrival counters for the next iteration (the accumulator sets: k_tf_reduce).
-struct FusedArgs { LinArgs lin; DecideArgs dec; GP<double> cost_new; int nblocks; GP<const int> done; ZeroList zero; int zero_wgs; };
 __device__ __forceinline__ void lin_cost_decide_body(const int b, const FusedArgs& A) {
   if (b >= A.nblocks) {
     if (b - A.nblocks < A.zero_wgs) zero_list_share(A.zero, b - A.nblocks, A.zero_wgs);
@@ -3737,2008 +3400,10 @@ __device__ __forceinline__ void lin_cost_decide_body(const int b, const FusedArg
 }
 __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(3))) void k_lin_cost_decide(FusedArgs a) { lin_cost_decide_body(blockIdx.x, a); }
 
-// ================================================================================================ host side
-static StateP state_ptrs(const lvf_state* st) { return StateP{st->poses.p, st->vel.p, st->ba.p, st->bg.p, st->inv_depth.p, st->w_visual.p}; }
-static inline int grid(int n) { return (n + kT - 1) / kT; }
-
-// The argument blocks of ONE LM iteration of a window.  Nothing in them changes from iteration to iteration (the trust-region radius,
-// the accept / reject state and the termination flag live in the device-resident LmCtl; an accepted candidate is COPIED into the state
-// buffers by k_lm_decide), so they are built once per problem_configure and
-//   * passed by value to the single-window launches, or
-//   * stored as one entry per window in device tables, every launch of the chain then covering a whole batch of windows (blockIdx.y).
-struct Chain {
-  bool fast = false;            // merged linearisation (sorted TwoFrame work list) available
-  bool batchable = false;       // every launch of the iteration has a table form (fast + band Schur merged with sparse level 0 + no priors)
-  bool has_imu = false, has_prior = false, imu_in_cost = false;
-  ZeroList zero_end{};
-  ZeroList zero{};              // everything a linearisation accumulates into (explicit k_zero_multi when the accumulators are not known clean)
-  ImuArgs imu_lin{}, imu_cost{};
-  LinArgs lin{}; size_t lin_lds = 0;
-  TfReduceArgs red{}; size_t red_lds = 0;     // compact mode: the slabs of the TwoFrame linearisation -> B, gc
-  PrepArgs prep{};              // classic form (stores the whole lower triangle); also what the parity taps use
-  // Early sparse levels.  The (v, ba, bg) columns only ever receive ImuError terms, the LM damping and the updates of lower levels, so a
-  // level can form its columns from B itself (SpSrc) as soon as the linearisation launch is over: level 0 rides in the k_tf_reduce
-  // launch, level 1 in k_prepare's, level 2 in the Schur complement's, and only what is left takes launches of its own (at 50 keyframes
-  // two instead of four).  For that S is cleared with the accumulators and k_prepare ADDS the dense corner (prep_early).
-  bool early = false;
-  PrepArgs prep_early{}; size_t prep_lds = 0;
-  int first_own_level = 0;      // sparse levels [first_own_level, n_levels) are launches of their own
-  bool merged_level0 = false;
-  SchurSp0Args ssp0{}; size_t ssp0_lds = 0;
-  int n_levels = 0; SpArgs sp[kSpMaxLevels]; int sp_lds[kSpMaxLevels] = {0};
-  CholArgs chol{};
-  BackArgs back{}; size_t back_lds = 0;
-  TailArgs tail{}; size_t tail_lds = 0;
-  bool back_tail_merged = false; BackTailArgs bt{}; size_t bt_lds = 0;      // k_backsolve_tail (single-window chain, chained levels allowed)
-  // the sparse back substitution as ONE product with G, formed by riders of the block-step launches (GRide; LVF_BACK_PRODUCT=0 turns it off)
-  bool back_product = false; GRide gride{};
-  // the dense back substitution on stored block products T_kj, formed by riders of the block-step launches (TRide; LVF_BACK_BLOCKS=0 turns it off)
-  bool back_blocks = false; TRide tride{};
-  CostArgs cost{};
-  DecideArgs dec{};
-  // the fused chain (AccSel; LVF_FUSED_LIN=0 turns it off): the second accumulator set's pointers and the standby clears (k_tf_reduce: stand0
-  // clears set 0, stand1 set 1) — both filled by ensure_acc1 — and the candidate pass
-  bool fused_ok = false;
-  AccSel acc{};
-  ZeroList stand0{}, stand1{};
-  FusedArgs fused{};
-};
-
-void stage_clock_free(StageClock* k);
-void batch_orphan(lvf_problem_batch* b, lvf_problem* dying);
-}  // namespace lvf
-lvf_problem::~lvf_problem() {
-  // a batch that still borrows this problem must never dereference it again: it is marked orphaned (its calls fail with LVF_ERR_STATE)
-  // and forgets every member, so destroying it later touches nothing
-  for (lvf_problem_batch* b : batches) lvf::batch_orphan(b, this);
-  delete chain;
-  lvf::stage_clock_free(clk);
-  if (rec && !lvf::HostPinPool::get().give(rec, lvf::Pool::bucket(sizeof(lvf::LmCtl)))) (void)hipHostFree(rec);
-  if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-  if (ev_band) (void)hipEventDestroy(ev_band);
-}
-namespace lvf {
-
-static void fill_cost_visual(const lvf_problem* p, CostVisual& a) {
-  a = CostVisual{};
-  if (p->tc && p->tc->n) {
-    a.n_tc = p->tc->n; a.tc_lo = (const double2*)p->tc->ob_a.p; a.tc_ro = (const double2*)p->tc->ob_b.p; a.tc_lm = p->tc->idx_a.p; a.tc_kf = p->tc->idx_b.p;
-    a.tc_w = p->tc->wblk.n ? p->tc->wblk.p : nullptr; a.tc_left = p->tc->cam_a; a.tc_right = p->tc->cam_b;
-  }
-  if (p->tf && p->tf->n) {
-    a.n_tf = p->tf->n; a.tf_fo = p->tf_fo(); a.tf_ob = p->tf_ob(); a.tf_lm = p->tf_lm(); a.tf_k1 = p->tf_k1();
-    a.tf_k2 = p->tf_k2(); a.tf_left = p->tf->cam_a; a.tf_right = p->tf->cam_b;
-  }
-  if (p->po && p->po->n) {
-    a.n_po = p->po->n; a.po_ob = (const double2*)p->po->ob_a.p; a.po_kf = p->po->idx_a.p; a.po_pwi = p->po->idx_b.p; a.po_pw = p->po->table.p; a.po_cam = p->po->cam_a;
-  }
-  a.g_tc = grid(a.n_tc); a.g_tf = grid(a.n_tf);
-}
-
-// a state-shaped VIEW of borrowed device pointers (for the launchers that take an lvf_state); never destroyed with live pointers
-struct StateView {
-  lvf_state v;
-  StateView(lvf_ctx* ctx, int n_kf, int n_lm, double* poses, double* vel, double* ba, double* bg, double* invd, double* wv) {
-    v.ctx = ctx; v.n_kf = n_kf; v.n_lm = n_lm;
-    v.poses.p = poses; v.vel.p = vel; v.ba.p = ba; v.bg.p = bg; v.inv_depth.p = invd; v.w_visual.p = wv;
-  }
-  ~StateView() { v.poses.p = v.vel.p = v.ba.p = v.bg.p = v.inv_depth.p = v.w_visual.p = nullptr; }
-};
-
-// accumulates 1/2 sum rho into *cost_slot at the given state (residual-only pass); not gated by the LM control block
-static int enqueue_cost(lvf_problem* p, const StateP& s, const lvf_state* imu_state_view, double huber, double* cost_slot) {
-  hipStream_t q = p->ctx->stream;
-  CostArgs c{};
-  fill_cost_visual(p, c.a);
-  c.n_kf = p->n_kf; c.s = s; c.huber = huber; c.cost = cost_slot; c.done = nullptr;
-  c.nblocks = c.a.g_tc + c.a.g_tf + grid(c.a.n_po);
-  if (c.nblocks > 0) hipLaunchKernelGGL(k_cost_visual, dim3(c.nblocks), dim3(kT), 0, q, c);
-  if (p->imu && p->imu->n) {
-    static_assert(kStripes == 32, "k_imu stripes its cost over 32 slots");
-    LVF_TRY(launch_imu(p->imu, imu_state_view, false, cost_slot));      // residuals and their cost in one launch
-  }
-  if (p->prior && p->prior->n) {
-    LVF_TRY(launch_pose_prior(p->prior, imu_state_view, false));
-    hipLaunchKernelGGL(k_cost_sq, dim3(grid(6 * p->prior->n)), dim3(kT), 0, q, 6 * p->prior->n, p->prior->res.p, cost_slot);
-  }
-  LVF_HIP(hipGetLastError());
-  return LVF_OK;
-}
-
-static void fill_back_args(lvf_problem* p, BackArgs& ba, size_t* lds_bytes) {
-  SpBack sb{};
-  sb.lv = p->sp_levels; sb.rows = p->sp_rows.p; sb.owner = p->sp_owner.p; sb.W = p->sp_W.p; sb.Linv = p->sp_L.p; sb.perm = p->perm.p;
-  sb.off = p->off; sb.aug = p->aug; sb.d_total = p->d;
-  sb.dbg = nullptr;
-  int max_count = 0;
-  for (int lv = 0; lv < p->sp_levels.n; ++lv) {
-    max_count = std::max(max_count, p->sp_levels.count[lv]);
-    sb.item0[lv] = p->sp_item0[lv]; sb.items[lv] = p->sp_items[lv];
-  }
-  const int n_nodes = p->sp_levels.n ? p->sp_levels.first[p->sp_levels.n - 1] + p->sp_levels.count[p->sp_levels.n - 1] : 0;
-  sb.total_items = p->sp_levels.n ? p->sp_item0[p->sp_levels.n - 1] + p->sp_items[p->sp_levels.n - 1] : 0;
-  sb.n_nodes = n_nodes; sb.max_count = max_count;
-  sb.nodes = p->sp_nodes.p;
-  static const bool big_lds = [] {        // up to 160 KB of LDS per workgroup on gfx950; the default cap for dynamic LDS is 64 KB
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_backsolve), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_backsolve_b), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) == hipSuccess;
-  }();
-  const size_t lds_cap = big_lds ? 156 * 1024 : 64 * 1024;
-  size_t doubles = (size_t)p->off + (size_t)((p->ndense + 63) / 64) * 64 + (size_t)(kBParts + 1) * kNB + 9 * (size_t)max_count + kBT + (size_t)n_nodes + 2;
-  sb.linv_in_lds = (doubles + 81 * (size_t)n_nodes) * sizeof(double) <= 48 * 1024 ? 1 : 0;
-  if (sb.linv_in_lds) doubles += 81 * (size_t)n_nodes;
-  int max_items = 0;
-  for (int lv = 0; lv < p->sp_levels.n; ++lv) max_items = std::max(max_items, p->sp_items[lv]);
-  sb.prod_items = ((doubles + 9 * (size_t)max_items) * sizeof(double) <= lds_cap) ? max_items : 0;
-  doubles += 9 * (size_t)sb.prod_items;
-  *lds_bytes = doubles * sizeof(double);
-  ba.Sd = p->S.p + (size_t)p->off * (p->ld + 1); ba.ld = p->ld; ba.d = p->ndense; ba.Dinv = p->Dinv.p; ba.Ldiag = p->Ldiag.p; ba.xout = p->dxc.p; ba.sp = sb;
-}
-
-// the work list of the band Schur complement for the current rows-per-slice setting; its length is part of the launch grid
-static inline int band_rows_clamped(int rows) { return std::min(kBandRowsMax, std::max(16, rows)); }
-// work list of p's band Schur complement for `rows` landmark rows per slice, into buffers of the caller's (the problem's own list, or a
-// batch's: a batch sums over wider slices and must not touch its members)
-// `defer`: do not wait for the item count — an event is recorded behind its copy and await_band_work() collects it right before the first
-// launch that needs it (the Schur complement's), by which time the linearisation launches enqueued in between have long kept the device busy
-static int build_band_work(lvf_problem* p, int rows_in, DevBuf<int4>& work, int* n_work, bool defer = false) {
-  hipStream_t q = p->ctx->stream;
-  const int rows = band_rows_clamped(rows_in);
-  const int n_slices = (p->n_lm + rows - 1) / rows;
-  const int nt = p->ldE / 16, groups_max = (nt * (nt + 1) / 2 + kBandTilesPerGroup - 1) / kBandTilesPerGroup;
-  LVF_TRY(work.ensure((size_t)n_slices * groups_max)); LVF_TRY(p->n_band_work_dev.ensure(1)); LVF_TRY(p->h_n_band_work.reserve(1));
-  LVF_HIP(hipMemsetAsync(p->n_band_work_dev.p, 0, sizeof(int), q));
-  hipLaunchKernelGGL(k_band_work, dim3(n_slices), dim3(64), 0, q, rows, p->dp, p->lm_nactive.p, p->lm_order.p, p->lm_kmin.p, p->lm_kmax.p, work.p, p->n_band_work_dev.p);
-  LVF_HIP(hipGetLastError());
-  LVF_HIP(hipMemcpyAsync(p->h_n_band_work.p, p->n_band_work_dev.p, sizeof(int), hipMemcpyDeviceToHost, q));
-  if (defer) {
-    if (!p->ev_band) LVF_HIP(hipEventCreateWithFlags(&p->ev_band, hipEventDisableTiming));
-    LVF_HIP(hipEventRecord(p->ev_band, q));
-    p->band_pending = true;
-    *n_work = 0;
-    return LVF_OK;
-  }
-  LVF_HIP(hipStreamSynchronize(q));
-  *n_work = p->h_n_band_work[0];
-  return LVF_OK;
-}
-static int ensure_band_work(lvf_problem* p) {
-  if (!p->band_ready || p->n_lm == 0 || p->band_rows_built == p->band_rows) return LVF_OK;
-  LVF_TRY(build_band_work(p, p->band_rows, p->band_work, &p->n_band_work, /*defer=*/true));
-  p->band_rows_built = p->band_rows;
-  return LVF_OK;
-}
-
-// (re)builds the argument blocks of an iteration from the problem's CURRENT buffers (call after problem_configure / set_pose_priors)
-static int build_chain(lvf_problem* p) {
-  if (!p->chain) p->chain = new Chain();
-  Chain& c = *p->chain;
-  c = Chain();
-  p->accum_clean = false;           // buffers may have been re-allocated
-  LVF_TRY(ensure_band_work(p));
-  LVF_TRY(p->ctl.ensure(1));
-  if (!p->rec) {
-    void* h = HostPinPool::get().take(Pool::bucket(sizeof(LmCtl)));       // (pinned blocks are recycled: lvf_internal.hpp)
-    if (!h) LVF_HIP(hipHostMalloc(&h, Pool::bucket(sizeof(LmCtl)), hipHostMallocDefault));
-    p->rec = static_cast<LmCtl*>(h);
-    std::memset(p->rec, 0, sizeof(LmCtl));
-  }
-  LmCtl* ctl = p->ctl.p;
-  const int* done = &ctl->done;
-  const double* radius = &ctl->radius;
-  LVF_TRY(p->jh0.ensure((size_t)p->d + p->n_lm + 1));
-  const JacobiDev jac{p->jh0.p, &ctl->jfrozen};
-  const StateP s = state_ptrs(p->st);
-  const StateP s2{p->poses2.p, p->vel2.p, p->ba2.p, p->bg2.p, p->invd2.p, p->st->w_visual.p};
-  double* cost = p->scal.p + SC_COST;
-  c.fast = p->tf && p->tf->n && p->tf_work.n && p->n_kf <= kMaxStagedKf;
-  c.has_imu = p->imu && p->imu->n;
-  c.has_prior = p->prior && p->prior->n;
-  const size_t schur_lds = p->n_lm ? ((size_t)kSchurRows * (p->ldE + 16) + kSchurRows) * sizeof(double) + kBandRowsMax * sizeof(int) : 0;
-  const bool schur_merged = p->n_lm && p->band_ready && schur_lds <= 64 * 1024 && p->sp_levels.n > 0 && (size_t)p->sp_shmem[0] <= 64 * 1024;
-  {
-    // LVF_EARLY_LEVELS=0: the classic order (A/B measurements); LVF_POISON_S fills S with NaN before the assembly, which only the classic form survives
-    static const bool early_on = [] { const char* e = std::getenv("LVF_EARLY_LEVELS"); return !(e && e[0] == '0') && std::getenv("LVF_POISON_S") == nullptr; }();
-    bool fits = true;
-    for (int lv = 0; lv < std::min(3, p->sp_levels.n); ++lv) fits = fits && (size_t)p->sp_shmem[lv] <= 64 * 1024;
-    c.early = early_on && c.fast && c.has_imu && schur_merged && fits && p->sp_levels.n >= 2;      // (one level: it already hides in the Schur launch)
-  }
-  // the merged back substitution + step tail (k_backsolve_tail) hands the pose increments over inside a launch: allowed where in-launch
-  // hand-overs are allowed at all (a problem whose hand-over timed out keeps its launches apart: lvf_problem::no_chain); its flag lives in the
-  // arrival-counter block, which is then cleared with the accumulators whether or not sparse levels are chained
-  static const bool bt_merge_on = [] { const char* e = std::getenv("LVF_BACK_TAIL_MERGE"); return !(e && e[0] == '0'); }();
-  static const bool bt_chain_on = [] { const char* e = std::getenv("LVF_CHAIN_LEVELS"); return !(e && std::atoi(e) <= 0); }();
-  const bool bt_wanted = bt_merge_on && bt_chain_on && !p->no_chain && p->n_lm > 0;
-  {
-    int k = 0;
-    static const bool tri_on = [] { const char* e = std::getenv("LVF_ZERO_TRI"); return !(e && e[0] == '0'); }();
-    bool overflow = false;
-    auto add = [&](double* ptr, size_t n, int tri = 0) {
-      if (!(ptr && n)) return;
-      if (k >= kZeroListMax) { overflow = true; return; }      // (the struct travels by value: never write past its arrays)
-      c.zero.p[k] = ptr; c.zero.n[k] = n; c.zero.tri[k] = (tri_on && tri % 2 == 0) ? tri : 0; ++k;
-    };
-    add(p->B.p, (size_t)p->dpad * p->dpad, p->dpad); add(p->gc.p, p->dpad);
-    if (p->n_lm) { if (!p->compact) add(p->E.p, (size_t)p->n_lm * p->ldE); add(p->C.p, p->n_lm); add(p->gr.p, p->n_lm); }
-    if (c.early) add(p->S.p, (size_t)p->ld * p->ld, p->ld);      // early sparse levels add into S before k_prepare does
-    if (c.early || bt_wanted) add(p->sp_sync.p, kSpMaxLevels);     // the arrival counters of chained levels / the pose hand-over flag
-    c.zero_end = c.zero; c.zero_end.count = k;         // cleared at the END of an iteration, beside the cost pass (the scalars: by the decision itself)
-    add(p->scal.p, SC_N);
-    c.zero.count = k;
-    LVF_REQUIRE(!overflow, "build_chain: more than %d accumulator arrays (raise kZeroListMax)", kZeroListMax);
-  }
-  if (c.has_imu) {
-    fill_imu_args(p->imu, s.poses, s.vel, s.ba, s.bg, nullptr, nullptr, done, &c.imu_lin);
-    fill_imu_args(p->imu, s2.poses, s2.vel, s2.ba, s2.bg, p->scal.p + SC_COST_NEW, nullptr, done, &c.imu_cost);
-  }
-  if (c.fast) {
-    LinVisual& a = c.lin.v;
-    a = LinVisual{};
-    a.n_tfw = (int)p->tf_work.n; a.work = p->tf_work.p; a.tf_fo = p->tf_fo(); a.tf_ob = p->tf_ob();
-    a.tf_lm = p->tf_lm(); a.tf_k1 = p->tf_k1(); a.tf_left = p->tf->cam_a; a.tf_right = p->tf->cam_b; a.unique_lk2 = p->tf_unique_lk2 ? 1 : 0;
-    if (p->tc && p->tc->n) {
-      a.n_tc = p->tc->n; a.tc_lo = (const double2*)p->tc->ob_a.p; a.tc_ro = (const double2*)p->tc->ob_b.p; a.tc_lm = p->tc->idx_a.p; a.tc_kf = p->tc->idx_b.p;
-      a.tc_w = p->tc->wblk.n ? p->tc->wblk.p : nullptr; a.tc_left = p->tc->cam_a; a.tc_right = p->tc->cam_b;
-    }
-    if (p->po && p->po->n) {
-      a.n_po = p->po->n; a.po_ob = (const double2*)p->po->ob_a.p; a.po_kf = p->po->idx_a.p; a.po_pwi = p->po->idx_b.p; a.po_pw = p->po->table.p; a.po_cam = p->po->cam_a;
-    }
-    a.g_tc = grid(a.n_tc); a.g_po = grid(a.n_po);
-    if (c.has_imu) {
-      a.n_imu = p->imu->n; a.imu_res = p->imu->res.p; a.imu_i = p->imu->idx_a.p; a.imu_j = p->imu->idx_b.p;
-      for (int k = 0; k < 8; ++k) a.imu_J.j[k] = p->imu->jac[k].p;
-      a.imu = ImuEvalArgs{p->imu->n, p->imu->pre.p, p->imu->sqrt_info.p, p->imu->idx_a.p, p->imu->idx_b.p};
-    }
-    static const int staged_on = [] { const char* e = std::getenv("LVF_STAGED"); return (e && e[0] == '0') ? 0 : 1; }();
-    a.cp = TfCompact{0, nullptr, nullptr, nullptr, nullptr, staged_on};
-    if (p->compact) {
-      a.cp = TfCompact{1, p->tf_slot.p, p->slotB.p, p->slabP.p, p->slabQ.p, staged_on};
-      TfReduceArgs& r = c.red;
-      r.n_kf = p->n_kf; r.n_wg = a.n_tfw; r.run_first = p->run_first.p; r.slabP = p->slabP.p; r.slabQ = p->slabQ.p; r.B = p->B.p; r.ld = p->dpad; r.gc = p->gc.p;
-      r.nblocks = p->n_kf * ((a.n_tfw + 63) / 64) + grid(p->n_kf * (p->n_kf - 1) / 2 * 36); r.done = done;
-      r.own_blocks = r.nblocks; r.ride = SpArgs{}; r.ride.nblocks = 0;
-    }
-    c.lin.n_kf = p->n_kf; c.lin.s = s; c.lin.huber = 0.0; c.lin.pose_const = p->pose_const.p; c.lin.B = p->B.p; c.lin.ld = p->dpad; c.lin.gc = p->gc.p; c.lin.E = p->E.p;
-    c.lin.ldE = p->ldE; c.lin.C = p->C.p; c.lin.gr = p->gr.p; c.lin.cost = cost; c.lin.done = done; c.lin.dbg = nullptr;
-    c.lin.scal_reset = c.early ? p->scal.p : nullptr;
-    c.lin.nblocks = a.n_tfw + a.g_tc + a.g_po + (a.imu.pre ? a.n_imu : (a.n_imu + 3) / 4);
-    c.lin_lds = std::max((size_t)(sizeof(PoseD) / 8 + kAccSlots) * p->n_kf + 32 + 4 * (size_t)kStageWave, (size_t)std::max(kImuWaveLds, 1864 + 64)) * sizeof(double);
-  }
-  // damped system
-  {
-    PrepArgs& a = c.prep;
-    a.ld = p->ld; a.dpad = p->dpad; a.iperm = p->iperm.p; a.B = p->B.p; a.gc = p->gc.p; a.radius = radius; a.S = p->S.p; a.jac = jac; a.jl0 = p->d;
-    // (the lower triangle, folded: prepare_body)
-    a.nS_blocks = (unsigned)(((size_t)((p->ld + 1) / 2) * (p->ld + 1) + kT - 1) / kT); a.n_lm = p->n_lm; a.dp = p->dp; a.ldE = p->ldE; a.C = p->C.p; a.gr = p->gr.p; a.Cd = p->Cd.p; a.E = p->E.p;
-    a.eoff = p->lm_eoff.p; a.kmin = p->lm_kmin.p; a.kmax = p->lm_kmax.p; a.slotB = p->compact ? p->slotB.p : nullptr; a.Ct = p->Ct.p; a.grt = p->grt.p;
-    a.scal = p->scal.p; a.nblocks = (int)a.nS_blocks + (p->n_lm ? grid(p->compact ? 8 * p->n_lm : p->n_lm) : 0); a.done = done;
-    a.early = 0; a.off = p->off; a.own_blocks = a.nblocks; a.ride = SpArgs{}; a.ride.nblocks = 0;
-    PrepArgs& e = c.prep_early;
-    e = a;
-    const int nn = p->ld - p->off;
-    e.early = 1; e.scal = nullptr;                      // (the scalars are reset by the linearisation launch: LinArgs::scal_reset)
-    e.nS_blocks = (unsigned)(((size_t)((nn + 1) / 2) * (nn + 1) + kT - 1) / kT);
-    e.nblocks = e.own_blocks = (int)e.nS_blocks + (p->n_lm ? grid(p->compact ? 8 * p->n_lm : p->n_lm) : 0);
-  }
-  int* fail = reinterpret_cast<int*>(p->scal.p + SC_FAIL);
-  c.n_levels = p->sp_levels.n;
-  for (int lv = 0; lv < p->sp_levels.n; ++lv) {
-    SpArgs& a = c.sp[lv];
-    a.nodes = p->sp_nodes.p; a.first = p->sp_levels.first[lv]; a.tiles = p->sp_tiles[lv]; a.rows = p->sp_rows.p; a.S = p->S.p; a.ld = p->ld; a.W = p->sp_W.p;
-    a.wstride = p->sp_wstride; a.Lout = p->sp_L.p; a.fail = fail; a.nblocks = p->sp_levels.count[lv] * p->sp_tiles[lv]; a.done = done;
-    // (0.5 ms at 100 MHz before a chained level gives up on the level below — a hand-over normally takes microseconds, and a retry costs one iteration of 0.2 ms: round 4 waited 2 ms, ten iterations of latency on a shared GPU; LVF_CHAIN_TIMEOUT_US overrides; LVF_CHAIN_FENCE=0: relaxed hand-over, A/B only)
-    static const unsigned chain_timeout = [] { const char* e = std::getenv("LVF_CHAIN_TIMEOUT_US"); return e ? (unsigned)std::max(1, std::atoi(e)) * 100u : 50000u; }();
-    static const int chain_fenced = [] { const char* e = std::getenv("LVF_CHAIN_FENCE"); return (e && e[0] == '0') ? 0 : 1; }();
-    a.src = c.early ? SpSrc{p->B.p, p->dpad, p->dp, p->gc.p, radius, p->sp_rows_nat.p, nullptr, 0, nullptr, chain_fenced, chain_timeout, p->off, std::getenv("LVF_CHAIN_RMW_READ") ? 1 : 0, nullptr, lv == 0 ? 1 : 0}
-                    : SpSrc{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, chain_fenced, chain_timeout, p->off, 0, nullptr, 0};
-    a.src.jac = jac;
-    c.sp_lds[lv] = p->sp_shmem[lv];
-  }
-  c.merged_level0 = false;
-  if (p->n_lm) {
-    const int nt = p->ldE / 16, ntile = nt * (nt + 1) / 2;
-    const size_t shb = schur_lds;
-    // early form: the levels are dealt to the launches that exist anyway, in order
-    int next_level = 0;
-    // Where the levels go (measured, MI355X): the Schur launch hides three (one riding, two chained behind it); a level riding in
-    // k_tf_reduce's launch costs ~0 us, in k_prepare's ~2 us, a launch of its own 7.6 us.  So the LAST three levels go to the Schur launch
-    // and only what is left over rides in the two launches ahead (16 / 20 keyframes, three levels: 0.111 / 0.125 -> 0.098 / 0.118 ms
-    // with the chain alone, 0.103 / 0.123 with riders in front of it).  LVF_RIDE_TF / LVF_RIDE_PREP = 0 | 1 override, LVF_CHAIN_LEVELS = 0..2.
-    static const int ride_tf_env = [] { const char* e = std::getenv("LVF_RIDE_TF"); return e ? std::atoi(e) : -1; }();
-    static const int ride_prep_env = [] { const char* e = std::getenv("LVF_RIDE_PREP"); return e ? std::atoi(e) : -1; }();
-    static const int chain_n_env = [] { const char* e = std::getenv("LVF_CHAIN_LEVELS"); return e ? std::max(0, std::min(2, std::atoi(e))) : 2; }();
-    const int chain_n = p->no_chain ? 0 : chain_n_env;      // (a hand-over that timed out once: every level in a launch of its own from then on)
-    const int excess = std::max(0, c.n_levels - (1 + chain_n));
-    const bool ride_tf = ride_tf_env >= 0 ? ride_tf_env != 0 : (p->compact && excess >= 1);
-    const bool ride_prep = ride_prep_env >= 0 ? ride_prep_env != 0 : (excess >= 2 || (excess >= 1 && !(ride_tf && p->compact)));
-    if (c.early) {
-      if (!ride_tf) {}
-      else if (p->compact && next_level < c.n_levels) { c.red.ride = c.sp[next_level]; c.red.nblocks = c.red.own_blocks + c.red.ride.nblocks; c.red_lds = (size_t)c.sp_lds[next_level]; ++next_level; }
-      if (ride_prep && next_level < c.n_levels) { PrepArgs& e = c.prep_early; e.ride = c.sp[next_level]; e.nblocks = e.own_blocks + e.ride.nblocks; c.prep_lds = (size_t)c.sp_lds[next_level]; ++next_level; }
-    }
-    if (schur_merged) {
-      SchurSp0Args& a = c.ssp0;
-      a.rows = band_rows_clamped(p->band_rows);
-      a.n_slices = (p->n_lm + a.rows - 1) / a.rows; a.n_groups = (ntile + kBandTilesPerGroup - 1) / kBandTilesPerGroup;
-      a.dp = p->dp; a.ldE = p->ldE; a.E = p->E.p; a.Cd = p->Cd.p; a.order = p->lm_order.p;
-      a.dbg = nullptr; a.n_active = p->lm_nactive.p; a.kmin = p->lm_kmin.p; a.kmax = p->lm_kmax.p;
-      a.d_local = p->dp; a.ldS = p->ld; a.S_pose = p->S.p + (size_t)p->off_pose * (p->ld + 1);
-      const int ride = c.early ? next_level : 0;       // classic: level 0 rides here
-      a.sp = SpArgs{}; a.sp.nblocks = 0; a.sp_b = a.sp; a.sp_c = a.sp;
-      c.ssp0_lds = shb;
-      next_level = ride;
-      if (ride < c.n_levels) { a.sp = c.sp[ride]; c.ssp0_lds = std::max(c.ssp0_lds, (size_t)p->sp_shmem[ride]); next_level = ride + 1; }
-      // the Schur complement lasts ~20 us at this size, a level ~5: the next two levels wait for their predecessor INSIDE the launch
-      if (c.early && chain_n > 0) {
-        int* cnt = reinterpret_cast<int*>(p->sp_sync.p);
-        SpArgs* slot[2] = {&a.sp_b, &a.sp_c};
-        SpArgs* prev = &a.sp;
-        for (int k = 0; k < std::min(2, chain_n) && next_level < c.n_levels && (size_t)p->sp_shmem[next_level] <= 64 * 1024; ++k) {
-          *slot[k] = c.sp[next_level];
-          prev->src.done_counter = cnt + 2 * (next_level - 1);
-          slot[k]->src.wait_counter = cnt + 2 * (next_level - 1); slot[k]->src.wait_target = prev->nblocks;
-          if (p->force_handover_timeouts > 0 && k == 0) { slot[k]->src.wait_target = prev->nblocks + 1; slot[k]->src.timeout_ticks = 2000u; }      // test hook: a producer that never arrives (20 us)
-          c.ssp0_lds = std::max(c.ssp0_lds, (size_t)p->sp_shmem[next_level]);
-          prev = slot[k];
-          ++next_level;
-        }
-      }
-      a.work = p->band_work.p; a.n_work = p->n_band_work;
-      a.nblocks = a.n_work + a.sp.nblocks + a.sp_b.nblocks + a.sp_c.nblocks; a.done = done;
-      c.merged_level0 = true;
-      c.first_own_level = next_level;
-    }
-  }
-  c.chol.Sd = p->S.p + (size_t)p->off * (p->ld + 1); c.chol.ld = p->ld; c.chol.nb = p->nb; c.chol.fail = fail; c.chol.Dinv = p->Dinv.p; c.chol.Ldiag = p->Ldiag.p; c.chol.done = done;
-  c.chol.last_cols = p->ndense + 1 - kNB * (p->nb - 1);       // (the right-hand-side row is the last real one)
-  fill_back_args(p, c.back, &c.back_lds);
-  c.back.done = done;
-  {
-    TailArgs& a = c.tail;
-    // (640 workgroups take the 10 000 landmarks of the BASELINE window in one pass of 16 per workgroup; measured 1-2 % of an iteration over a cap of 256)
-    static const int tail_cap = [] { const char* e = std::getenv("LVF_TAIL_WGS"); return e ? std::atoi(e) : 640; }();
-    a.g_lm = p->n_lm ? std::min(tail_cap, (p->n_lm + kT / 16 - 1) / (kT / 16)) : 0;
-    a.n_lm = p->n_lm; a.dp = p->dp; a.ldE = p->ldE; a.E = p->E.p; a.C = p->compact ? p->Ct.p : p->C.p; a.Cd = p->Cd.p;
-    a.gr = p->compact ? p->grt.p : p->gr.p; a.dxc = p->dxc.p; a.dxl = p->dxl.p; a.scal = p->scal.p;
-    a.kmin = p->band_ready ? p->lm_kmin.p : nullptr; a.kmax = p->lm_kmax.p; a.n_kf = p->n_kf; a.s = s; a.poses2 = p->poses2.p; a.vel2 = p->vel2.p; a.ba2 = p->ba2.p;
-    a.bg2 = p->bg2.p; a.invd2 = p->invd2.p; a.d = p->d; a.ld = p->dpad; a.B = p->B.p; a.gc = p->gc.p; a.radius = radius; a.nblocks = a.g_lm + grid(p->d); a.done = done; a.pose_const = p->pose_const.p; a.jac = jac;
-    c.tail_lds = (size_t)p->ldE * sizeof(double);
-  }
-  {
-    static const unsigned bt_timeout = [] { const char* e = std::getenv("LVF_CHAIN_TIMEOUT_US"); return e ? (unsigned)std::max(1, std::atoi(e)) * 100u : 50000u; }();
-    static const int bt_fenced = [] { const char* e = std::getenv("LVF_CHAIN_FENCE"); return e ? std::atoi(e) : 1; }();
-    static const bool bt_big_lds = hipFuncSetAttribute(reinterpret_cast<const void*>(k_backsolve_tail), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) == hipSuccess;
-    c.back_tail_merged = bt_wanted && c.tail.g_lm > 0;
-    if (c.back_tail_merged) {
-      BackTailArgs& m = c.bt;
-      m.back = c.back; m.tail = c.tail;
-      m.back.pose_ready = reinterpret_cast<int*>(p->sp_sync.p) + 2 * kSpMaxLevels - 2;      // (the last int pair of the arrival-counter block: the levels use pairs 0 .. n_levels - 2)
-      m.back.n_pose = p->dp;
-      // (one round of workgroups: the launch's register and LDS footprint is the back substitution's, so about one workgroup fits a CU, and a
-      // landmark workgroup that has to wait for a CU starts after the others are done)
-      static const int bt_wgs = [] { const char* e = std::getenv("LVF_BACK_TAIL_WGS"); return e ? std::max(1, std::atoi(e)) : 224; }();
-      m.g_lm = std::min(bt_wgs, (p->n_lm + kBT / 16 - 1) / (kBT / 16));
-      m.fenced = bt_fenced == 2; m.back.pose_fenced = bt_fenced == 2; m.timeout_ticks = bt_timeout; m.fail = fail;
-      static const int bt_early = [] { const char* e = std::getenv("LVF_BACK_EARLY"); return (e && e[0] == '0') ? 0 : 1; }();
-      m.early = bt_early;
-      if (p->force_handover_timeouts > 1) { m.back.pose_ready = reinterpret_cast<int*>(p->sp_sync.p) + 2 * kSpMaxLevels - 4; m.timeout_ticks = 2000u; }      // test hook (n >= 2): a flag nobody raises
-      c.bt_lds = std::max(c.back_lds, c.tail_lds);
-      if (c.bt_lds > 64 * 1024 && !bt_big_lds) c.back_tail_merged = false;
-    }
-    // The product form: on where the levels can be dealt one to a block-step launch (n_levels <= nb; level n_levels - 1 - kb rides in launch
-    // kb) and the merged launch is in use.  Its G workgroups must fit the chip in ONE round beside workgroup 0, the pose workgroup and the
-    // landmark workgroups (about one workgroup of this launch fits a compute unit; a workgroup that has to wait for one starts after the
-    // others are done), each owns whole keyframes, one thread per unknown.
-    static const bool prod_on = [] { const char* e = std::getenv("LVF_BACK_PRODUCT"); return !(e && e[0] == '0'); }();
-    c.back_product = false; c.gride = GRide{}; c.gride.n = 0;
-    if (prod_on && c.back_tail_merged && c.n_levels >= 1 && c.n_levels <= p->nb && p->ldG > 0) {
-      static const int n_cu = [] { int dev = 0, n = 0; return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }();
-      const int room = n_cu - 2 - c.bt.g_lm;
-      const int kpw = room >= 1 ? (p->n_kf + std::min(room, p->n_kf) - 1) / std::min(room, p->n_kf) : 0;
-      const int n_nodes = p->sp_levels.first[c.n_levels - 1] + p->sp_levels.count[c.n_levels - 1];
-      if (kpw >= 1 && 9 * kpw <= kBT) {
-        LVF_TRY(p->sp_G.ensure((size_t)9 * n_nodes * p->ldG));
-        BackTailArgs& m = c.bt;
-        m.kpw = kpw; m.g_prod = (p->n_kf + kpw - 1) / kpw; m.ldG = p->ldG; m.G = p->sp_G.p; m.iperm = p->iperm.p;
-        c.bt_lds = std::max(c.bt_lds, (size_t)(p->ldG + 9 * kpw) * sizeof(double));
-        c.gride = GRide{0, 0, p->sp_nodes.p, p->sp_rows.p, p->sp_W.p, p->sp_wstride, p->sp_L.p, p->sp_gmap.p, p->sp_G.p, p->ldG, p->off, done};
-        c.back_product = true;
-      }
-    }
-    // The block form: on for every single-window chain of two or more blocks (the riders go with k_chol_step / k_chol_step_pp whether or not
-    // the G product is on) whose link products fit the registers of the body that will run — five blocks for the dense-corner-only body of the
-    // product form, three beside the sparse levels' items.  Off where the augmented row sits alone in the last factor block (d a multiple of
-    // 64: the first solved block would take its right-hand side from a panel, not from Ldiag — a corner the plan's cost steers away from, it
-    // pays a block step for one row) and in the chain-free re-run after a hand-over time-out; those read S and Dinv as before.
-    static const bool blocks_on = [] { const char* e = std::getenv("LVF_BACK_BLOCKS"); return !(e && e[0] == '0'); }();
-    c.back_blocks = false; c.tride = TRide{0, nullptr};
-    if (blocks_on && !p->no_chain && p->nb >= 2 && p->ndense % kNB != 0 && p->nb - 1 <= (c.back_product ? kBackTJ : kBackTJLevels)) {
-      LVF_TRY(p->sp_T.ensure((size_t)p->nb * p->nb * kNB * kNB));
-      c.tride = TRide{0, p->sp_T.p};
-      c.back_blocks = true;
-    }
-    static const bool chain_info = std::getenv("LVF_CHAIN_INFO") != nullptr;
-    if (chain_info) std::fprintf(stderr, "chain: n_kf %d n_lm %d fast %d has_imu %d early %d compact %d levels %d no_chain %d merged_level0 %d back_tail_merged %d (g_lm %d, lds %zu) back_product %d (nb %d, %d G workgroups of %d keyframes)\n", p->n_kf, p->n_lm, (int)c.fast, (int)c.has_imu,
-                                 (int)c.early, (int)p->compact, c.n_levels, (int)p->no_chain, (int)c.merged_level0, (int)c.back_tail_merged, c.bt.g_lm, c.bt_lds,
-                                 (int)c.back_product, p->nb, c.bt.g_prod, c.bt.kpw);
-    if (chain_info) std::fprintf(stderr, "chain: back_blocks %d\n", (int)c.back_blocks);
-  }
-  fill_cost_visual(p, c.cost.a);
-  c.cost.n_kf = p->n_kf; c.cost.s = s2; c.cost.huber = 0.0; c.cost.cost = p->scal.p + SC_COST_NEW; c.cost.done = done;
-  c.cost.nblocks = c.cost.a.g_tc + c.cost.a.g_tf + grid(c.cost.a.n_po);
-  {
-    // two tiles of kT blocks per workgroup: half as many workgroups to dispatch ahead of the decision (measured -1 % of an iteration; three: same)
-    static const int cost_tiles = [] { const char* e = std::getenv("LVF_COST_TILES"); return e ? std::atoi(e) : 2; }();
-    if (cost_tiles > 1) {
-      CostArgs& k = c.cost;
-      const int per = kT * cost_tiles;
-      k.tiles = cost_tiles;
-      k.a.g_tc = (k.a.n_tc + per - 1) / per; k.a.g_tf = (k.a.n_tf + per - 1) / per;
-      k.nblocks = k.a.g_tc + k.a.g_tf + (k.a.n_po + per - 1) / per;
-    }
-  }
-  c.cost.g_imu = 0; c.cost.imu = ImuEvalArgs{};
-  c.imu_in_cost = c.fast && c.has_imu && c.cost.nblocks > 0;         // the IMU cost rides in the merged cost + decision launch
-  if (c.imu_in_cost) { c.cost.imu = ImuEvalArgs{p->imu->n, p->imu->pre.p, p->imu->sqrt_info.p, p->imu->idx_a.p, p->imu->idx_b.p}; c.cost.g_imu = p->imu->n; c.cost.nblocks += p->imu->n; }
-  c.cost.zero = c.zero_end; c.cost.zero_wgs = c.fast ? kEndZeroWgs : 0;
-  {
-    DecideArgs& a = c.dec;
-    a.scal = p->scal.p; a.ctl = ctl; a.rec = p->rec; a.ticket = reinterpret_cast<int*>(p->scal.p + SC_TICKET); a.n_kf = p->n_kf; a.n_lm = p->n_lm;
-    a.poses = p->st->poses.p; a.vel = p->st->vel.p; a.ba = p->st->ba.p; a.bg = p->st->bg.p; a.invd = p->st->inv_depth.p;
-    a.poses2 = p->poses2.p; a.vel2 = p->vel2.p; a.ba2 = p->ba2.p; a.bg2 = p->bg2.p; a.invd2 = p->invd2.p;
-    static const bool lm_history = std::getenv("LVF_LM_HISTORY") != nullptr;
-    a.hist = nullptr;
-    if (lm_history) { LVF_TRY(p->dbg_hist.ensure(8 * 64)); a.hist = p->dbg_hist.p; }
-  }
-  {
-    // the fused chain: the compact single-window chain with every reader of the accumulators selecting its set on device (problems with
-    // pose priors keep today's chain: their prior terms have no candidate linearisation)
-    static const bool fused_on = [] { const char* e = std::getenv("LVF_FUSED_LIN"); return !(e && e[0] == '0'); }();
-    c.fused_ok = fused_on && c.fast && p->compact && !c.has_prior && c.merged_level0 && p->n_lm > 0 && c.lin.nblocks > 0 && c.cost.nblocks > 0 &&
-                 (!c.has_imu || (c.imu_in_cost && c.lin.v.imu.pre));
-    p->acc1_ready = false;            // the second set is allocated and cleared by the first fused solve (ensure_acc1)
-    if (c.fused_ok) {
-      // what the candidate pass clears for the next iteration: zero_end less the accumulator sets (S, the arrival counters)
-      ZeroList fz{};
-      for (int k = 0; k < c.zero_end.count; ++k) {
-        double* q0 = c.zero_end.p[k];
-        if (q0 == p->B.p || q0 == p->gc.p || q0 == p->C.p || q0 == p->gr.p) continue;
-        fz.p[fz.count] = q0; fz.n[fz.count] = c.zero_end.n[k]; fz.tri[fz.count] = c.zero_end.tri[k]; ++fz.count;
-      }
-      FusedArgs& f = c.fused;
-      f.lin = c.lin; f.lin.s = s2; f.lin.cost = nullptr; f.lin.scal_reset = nullptr; f.lin.dbg = nullptr;
-      f.dec = c.dec; f.dec.fused = 1;
-      f.cost_new = p->scal.p + SC_COST_NEW; f.nblocks = c.lin.nblocks; f.done = done; f.zero = fz; f.zero_wgs = kEndZeroWgs;
-    }
-  }
-  c.batchable = c.fast && p->compact && c.has_imu && !c.has_prior && c.merged_level0 && c.lin.nblocks > 0 && c.cost.nblocks > 0;
-  { const StateP sp = state_ptrs(p->st); std::memcpy(p->chain_state, &sp, sizeof(sp)); }
-  p->chain_tcw = p->tc && p->tc->wblk.n ? p->tc->wblk.p : nullptr;
-  p->chain_ready = true;
-  return LVF_OK;
-}
-static bool chain_stale(const lvf_problem* p) {
-  if (!p->chain_ready || !p->chain) return true;
-  const StateP s = state_ptrs(p->st);
-  static_assert(sizeof(StateP) == sizeof(p->chain_state), "StateP is six pointers");
-  if (std::memcmp(&s, p->chain_state, sizeof(StateP)) != 0) return true;      // the state's buffers were re-allocated (window grew)
-  // lvf_two_camera_set_block_weights after the problem was created: the argument blocks hold the old weight pointer (or none)
-  const double* w = p->tc && p->tc->wblk.n ? p->tc->wblk.p : nullptr;
-  return w != p->chain_tcw;
-}
-// The second accumulator set, allocated and cleared on the first fused solve after a configure (a problem that is only ever solved in a batch,
-// or one iteration at a time, never holds it).  E's and the slot records' zeros outside what a linearisation writes are set here, as for
-// set 0 in problem_configure; B, gc, C and g_rho need nothing: the first k_tf_reduce of every fused solve clears the standby set, which is
-// set 1 then (LmCtl::aset starts every solve at 0).
-static int ensure_acc1(lvf_problem* p) {
-  Chain& c = *p->chain;
-  if (!c.fused_ok || p->acc1_ready) return LVF_OK;
-  hipStream_t q = p->ctx->stream;
-  LVF_TRY(p->B1.ensure(p->B.n)); LVF_TRY(p->gc1.ensure(p->gc.n)); LVF_TRY(p->C1.ensure(p->C.n)); LVF_TRY(p->gr1.ensure(p->gr.n));
-  LVF_TRY(p->E1.ensure(p->E.n)); LVF_TRY(p->slotB1.ensure(p->slotB.n));
-  LVF_HIP(hipMemsetAsync(p->E1.p, 0, p->E1.n * 8, q));
-  hipLaunchKernelGGL(k_tf_slots_zero, dim3(256), dim3(kT), 0, q, 0, 0, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
-                     (int*)nullptr, p->n_slots.p, p->slotB1.p);
-  LVF_HIP(hipGetLastError());
-  c.acc = AccSel{&p->ctl.p->aset, p->B1.p, p->gc1.p, p->C1.p, p->gr1.p, p->E1.p, p->slotB1.p};
-  // the standby lists: one set's B, gc, C, g_rho (as zero_end clears set 0's)
-  c.stand0 = ZeroList{}; c.stand1 = ZeroList{};
-  for (int k = 0; k < c.zero_end.count; ++k) {
-    double* q0 = c.zero_end.p[k];
-    double* q1 = q0 == p->B.p ? p->B1.p : q0 == p->gc.p ? p->gc1.p : q0 == p->C.p ? p->C1.p : q0 == p->gr.p ? p->gr1.p : nullptr;
-    if (!q1) continue;
-    c.stand0.p[c.stand0.count] = q0; c.stand0.n[c.stand0.count] = c.zero_end.n[k]; c.stand0.tri[c.stand0.count] = c.zero_end.tri[k]; ++c.stand0.count;
-    c.stand1.p[c.stand1.count] = q1; c.stand1.n[c.stand1.count] = c.zero_end.n[k]; c.stand1.tri[c.stand1.count] = c.zero_end.tri[k]; ++c.stand1.count;
-  }
-  c.fused.lin.acc = c.acc;
-  p->acc1_ready = true;
-  return LVF_OK;
-}
-
-// the linearisation at the current state: cost, B, gc, E, C, gr.  `gated`: skipped on device once the LM loop has finished
-// HIP events between the stages of one LM iteration (lvf_problem_stage_times): event 0 before the first launch, event k + 1 after stage k
-enum { ST_IMU_LIN = 0, ST_LIN_VISUAL, ST_TF_REDUCE, ST_PREPARE, ST_SCHUR_SP0, ST_SP_LEVELS, ST_CHOL, ST_BACKSOLVE, ST_STEP_TAIL, ST_COST, ST_DECIDE, ST_FUSED, ST_N };
-static const char* const kStageNames[ST_N] = {"k_zero_multi (only when the accumulators are not known clean)", "k_lin_visual", "k_tf_reduce (+ sparse level 0)", "k_prepare (+ sparse level 1)", "k_schur_sp0 (+ a sparse level)", "k_sp_eliminate (the levels left)",
-                                             "k_chol_step (all block steps)", "k_chol_backsolve", "k_step_tail", "k_cost_decide (candidate cost incl. the ImuError factors; its last workgroup closes the iteration; + prior passes)", "k_lm_decide (windows without visual blocks)",
-                                             "k_lin_cost_decide (fused chain: linearisation at the candidate + its cost; its last workgroup closes the iteration)"};
-// (one event set per timed iteration: the iterations are enqueued back to back and waited for ONCE, so every stage — the first one of an
-// iteration included — starts behind a busy queue like in the device loop; with a wait per iteration the first stage absorbed the idle
-// queue's start-up, ~6 us of k_lin_visual's figure)
-constexpr int kClockReps = 16, kClockLaunches = 48;
-// Two sources per timed iteration: ev[] — events between the STAGES on the stream (a span: kernels + the gaps between them + the marker's own
-// cost) — and kstart[] / kstop[] — a start / stop event pair recorded WITH every kernel launch of the fast chain (hipExtLaunchKernelGGL: the
-// dispatch packet's own timestamps, i.e. what rocprofv3 --kernel-trace reports as the kernel's duration).  Stage times are the sums of the
-// second kind, so bench.py's roofline entries follow profiles/ for short stages too (the event-pair subtraction left k_lin_visual 18 % high).
-struct StageClock {
-  hipEvent_t ev[kClockReps][ST_N + 1]; int launches[ST_N]; bool on = false; int rep = 0;
-  hipEvent_t kstart[kClockReps][kClockLaunches], kstop[kClockReps][kClockLaunches]; int kstage[kClockLaunches]; int nk = 0; bool kernel_events = false;
-};
-void stage_clock_free(StageClock* k) {
-  if (!k) return;
-  for (auto& r : k->ev) for (auto& e : r) (void)hipEventDestroy(e);
-  if (k->kernel_events) { for (auto& r : k->kstart) for (auto& e : r) (void)hipEventDestroy(e); for (auto& r : k->kstop) for (auto& e : r) (void)hipEventDestroy(e); }
-  delete k;
-}
-// a launch of the iteration's fast chain: plain, or — while lvf_problem_stage_times is recording — with its own start / stop events
-#define LVF_CHAIN_LAUNCH(p_, stage_, kernel_, grid_, block_, lds_, q_, ...)                                                          \
-  do {                                                                                                                              \
-    StageClock* k__ = (p_)->clk;                                                                                                    \
-    if (k__ && k__->on && k__->kernel_events && k__->nk < kClockLaunches) {                                                         \
-      const int i__ = k__->nk++;                                                                                                    \
-      k__->kstage[i__] = (stage_);                                                                                                  \
-      hipExtLaunchKernelGGL(kernel_, grid_, block_, lds_, q_, k__->kstart[k__->rep][i__], k__->kstop[k__->rep][i__], 0, __VA_ARGS__); \
-    } else hipLaunchKernelGGL(kernel_, grid_, block_, lds_, q_, __VA_ARGS__);                                                       \
-  } while (0)
-static inline void stage_mark(lvf_problem* p, int stage_done, int launches) {
-  StageClock* k = p->clk;
-  if (!k || !k->on) return;
-  (void)hipEventRecord(k->ev[k->rep][stage_done + 1], p->ctx->stream);
-  k->launches[stage_done] = launches;
-}
-
-// a sparse level of the fused chain reads B / gc of the active accumulator set (early form only: the classic form does not read them)
-static inline void acc_patch(SpArgs& a, const AccSel* acc) {
-  if (acc && a.src.B) { a.src.sel = acc->sel; a.src.B1 = (const double*)(double*)acc->B; a.src.gc1 = (const double*)(double*)acc->gc; }
-}
-
-// `iteration`: the launches belong to a full LM iteration (enqueue_iteration) — only then do the early sparse levels ride along and are the
-// per-step scalars reset here; a stand-alone linearisation (gradient / cost taps) leaves S and the control block alone
-// `acc` (fused chain): every launch selects its accumulator set on device; `lin` == false: the active set already holds the linearisation
-// (the last iteration's candidate pass), only k_tf_reduce runs
-static int enqueue_linearize(lvf_problem* p, double huber, bool gated, bool iteration = false, const AccSel* acc = nullptr, bool lin = true) {
-  hipStream_t q = p->ctx->stream;
-  if (chain_stale(p)) LVF_TRY(build_chain(p));
-  const Chain& c = *p->chain;
-  const StateP s = state_ptrs(p->st);
-  double* cost = p->scal.p + SC_COST;
-  bool imu_done = false;
-  // the accumulators are cleared at the END of every iteration (extra workgroups of the cost + decision launch); a launch of its own is
-  // only needed when they are not known to be clean (first linearisation after a configure, stand-alone gradient / reduced-system taps)
-  const bool clean = !lin || (c.fast && p->accum_clean);
-  p->accum_clean = false;
-  if (p->clk && p->clk->on) (void)hipEventRecord(p->clk->ev[p->clk->rep][0], q);
-  if (!clean) LVF_CHAIN_LAUNCH(p, ST_IMU_LIN, k_zero_multi, dim3(512, c.zero.count), dim3(kT), 0, q, c.zero);
-  if (c.fast) {
-    imu_done = true;                           // the ImuError factors are evaluated inside the merged launch below
-    stage_mark(p, ST_IMU_LIN, clean ? 0 : 1);
-    LinArgs la = c.lin;
-    la.huber = huber;
-    if (!gated) la.done = nullptr;
-    if (!iteration) la.scal_reset = nullptr;
-    static const bool lin_timing = std::getenv("LVF_LIN_TIMING") != nullptr;
-    if (lin_timing) { LVF_TRY(p->dbg_lin.ensure((size_t)la.v.n_tfw * 24 + 8)); la.dbg = p->dbg_lin.p; }
-    static const size_t lds_pad = [] { const char* e = std::getenv("LVF_LIN_LDS_PAD"); return e ? (size_t)std::atoi(e) : (size_t)0; }();      // experiment: fewer workgroups per CU
-    if (lin) LVF_CHAIN_LAUNCH(p, ST_LIN_VISUAL, k_lin_visual, dim3(la.nblocks), dim3(kT), c.lin_lds + lds_pad, q, la);      // (into set 0: a pass starts with LmCtl::aset = 0)
-    stage_mark(p, ST_LIN_VISUAL, lin ? 1 : 0);
-    if (p->compact) {
-      TfReduceArgs ra = c.red;
-      if (!gated) ra.done = nullptr;
-      if (!iteration) { ra.nblocks = ra.own_blocks; ra.ride.nblocks = 0; }
-      int zero_wgs = 0;
-      if (acc) {
-        ra.acc = *acc; acc_patch(ra.ride, acc);
-        ra.pending = lin ? nullptr : &p->ctl.p->lin_pending;
-        ra.stand0 = c.stand0; ra.stand1 = c.stand1; ra.zero_wgs = zero_wgs = kEndZeroWgs;
-      }
-      LVF_CHAIN_LAUNCH(p, ST_TF_REDUCE, k_tf_reduce, dim3(ra.nblocks + zero_wgs), dim3(kT), ra.ride.nblocks > 0 ? c.red_lds : 0, q, ra);
-    }
-    stage_mark(p, ST_TF_REDUCE, p->compact ? 1 : 0);
-    if (lin_timing) {
-      std::vector<unsigned long long> t((size_t)la.v.n_tfw * 8);
-      LVF_HIP(hipStreamSynchronize(q));
-      LVF_HIP(hipMemcpy(t.data(), p->dbg_lin.p, t.size() * 8, hipMemcpyDeviceToHost));
-      double ph[5] = {0, 0, 0, 0, 0}; unsigned long long first = ~0ull, last = 0, last_start = 0;
-      for (int w = 0; w < la.v.n_tfw; ++w) {
-        for (int k = 0; k < 5; ++k) ph[k] += (double)(t[(size_t)w * 8 + k + 1] - t[(size_t)w * 8 + k]) * 0.01;
-        first = std::min(first, t[(size_t)w * 8]); last = std::max(last, t[(size_t)w * 8 + 5]); last_start = std::max(last_start, t[(size_t)w * 8]);
-      }
-      {
-        double mx[5] = {0, 0, 0, 0, 0}; int slow = 0; double slow_t = 0;
-        for (int w = 0; w < la.v.n_tfw; ++w) {
-          for (int k = 0; k < 5; ++k) mx[k] = std::max(mx[k], (double)(t[(size_t)w * 8 + k + 1] - t[(size_t)w * 8 + k]) * 0.01);
-          const double tot = (double)(t[(size_t)w * 8 + 5] - t[(size_t)w * 8]) * 0.01;
-          if (tot > slow_t) { slow_t = tot; slow = w; }
-        }
-        std::vector<TfWork> hw((size_t)la.v.n_tfw);
-        LVF_HIP(hipMemcpy(hw.data(), la.v.work, hw.size() * sizeof(TfWork), hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "lin_tf: per-phase MAX over the workgroups (us): %.2f | %.2f | %.2f | %.2f | %.2f ; slowest workgroup %d (k2 = %d, %d blocks): %.2f us =", mx[0], mx[1], mx[2], mx[3], mx[4], slow, hw[slow].k2, hw[slow].count, slow_t);
-        for (int k = 0; k < 5; ++k) std::fprintf(stderr, " %.2f", (double)(t[(size_t)slow * 8 + k + 1] - t[(size_t)slow * 8 + k]) * 0.01);
-        // histogram of workgroup durations by current keyframe decile
-        {
-          unsigned long long u[16];
-          LVF_HIP(hipMemcpy(u, p->dbg_lin.p + (size_t)la.v.n_tfw * 8 + 8 + (size_t)slow * 16, sizeof(u), hipMemcpyDeviceToHost));
-          std::fprintf(stderr, " ; its waves (eval us, k1-sum us, groups):");
-          for (int wv = 0; wv < 4; ++wv) std::fprintf(stderr, " [%.2f %.2f %llu]", (double)(u[4 * wv + 1] - u[4 * wv]) * 0.01, (double)(u[4 * wv + 2] - u[4 * wv + 1]) * 0.01, u[4 * wv + 3]);
-        }
-        std::fprintf(stderr, " ; mean duration by k2 decile:");
-        const int nk = la.n_kf;
-        for (int dcl = 0; dcl < 5; ++dcl) {
-          double sum = 0; int cnt = 0;
-          for (int w = 0; w < la.v.n_tfw; ++w) if (hw[w].k2 * 5 / std::max(nk, 1) == dcl) { sum += (double)(t[(size_t)w * 8 + 5] - t[(size_t)w * 8]) * 0.01; ++cnt; }
-          std::fprintf(stderr, " %.1f(%d)", cnt ? sum / cnt : 0.0, cnt);
-        }
-        std::fprintf(stderr, "\n");
-      }
-      std::fprintf(stderr, "lin_tf: the TwoFrame workgroups START within %.2f us of each other; starts of workgroups 0, 1/4, 1/2, 3/4, last (us after the first): %.2f %.2f %.2f %.2f %.2f\n", (double)(last_start - first) * 0.01,
-                   (double)(t[0] - first) * 0.01, (double)(t[(size_t)(la.v.n_tfw / 4) * 8] - first) * 0.01, (double)(t[(size_t)(la.v.n_tfw / 2) * 8] - first) * 0.01,
-                   (double)(t[(size_t)(3 * la.v.n_tfw / 4) * 8] - first) * 0.01, (double)(t[(size_t)(la.v.n_tfw - 1) * 8] - first) * 0.01);
-      std::fprintf(stderr, "lin_tf phases (us, mean over %d workgroups): stage %.2f | eval+landmark atomics %.2f | k1 sums %.2f | k2 sums %.2f | flush %.2f ; first start -> last end %.2f\n",
-                   la.v.n_tfw, ph[0] / la.v.n_tfw, ph[1] / la.v.n_tfw, ph[2] / la.v.n_tfw, ph[3] / la.v.n_tfw, ph[4] / la.v.n_tfw, (double)(last - first) * 0.01);
-      if (la.v.imu.pre) {
-        unsigned long long u[5];
-        LVF_HIP(hipMemcpy(u, p->dbg_lin.p + (size_t)la.v.n_tfw * 8, sizeof(u), hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "lin_imu phases of factor 0 (us): stage %.2f | raw residual + pre-weighting Jacobian (one lane) %.2f | weight + to tangent %.2f | J^T J, J^T r %.2f ; start %.2f after the first TwoFrame workgroup, end %.2f before the last one's end\n",
-                     (double)(u[1] - u[0]) * 0.01, (double)(u[2] - u[1]) * 0.01, (double)(u[3] - u[2]) * 0.01, (double)(u[4] - u[3]) * 0.01, ((double)u[0] - (double)first) * 0.01, ((double)last - (double)u[4]) * 0.01);
-      }
-    }
-  } else {
-    if (p->tc && p->tc->n)
-      hipLaunchKernelGGL(k_lin_tc<false>, dim3(grid(p->tc->n)), dim3(kT), 0, q, p->tc->n, (const double2*)p->tc->ob_a.p, (const double2*)p->tc->ob_b.p,
-                         p->tc->idx_a.p, p->tc->idx_b.p, p->tc->wblk.n ? p->tc->wblk.p : (const double*)nullptr, s, p->tc->cam_a, p->tc->cam_b, huber, p->C.p, p->gr.p, cost);
-    if (p->tf && p->tf->n)
-      hipLaunchKernelGGL(k_lin_tf<false>, dim3(grid(p->tf->n)), dim3(kT), 0, q, p->tf->n, p->n_kf, (const double2*)p->tf->ob_a.p, (const double2*)p->tf->ob_b.p,
-                         p->tf->idx_a.p, p->tf->idx_b.p, p->tf->idx_c.p, s, p->tf->cam_a, p->tf->cam_b, huber, p->pose_const.p, p->B.p, p->dpad,
-                         p->gc.p, p->E.p, p->ldE, p->C.p, p->gr.p, cost);
-    if (p->po && p->po->n)
-      hipLaunchKernelGGL(k_lin_po<false>, dim3(grid(p->po->n)), dim3(kT), 0, q, p->po->n, p->n_kf, (const double2*)p->po->ob_a.p, p->po->idx_a.p,
-                         p->po->idx_b.p, p->po->table.p, s, p->po->cam_a, huber, p->pose_const.p, p->B.p, p->dpad, p->gc.p, cost);
-  }
-  if (c.has_imu && !imu_done) {
-    LVF_TRY(launch_imu(p->imu, p->st, true));
-    ImuJ J;
-    for (int k = 0; k < 8; ++k) J.j[k] = p->imu->jac[k].p;
-    hipLaunchKernelGGL(k_lin_imu, dim3(p->imu->n), dim3(64), 0, q, p->imu->n, p->n_kf, p->imu->res.p, J, p->imu->idx_a.p, p->imu->idx_b.p,
-                       p->st->poses.p, p->pose_const.p, p->B.p, p->dpad, p->gc.p, cost);
-  }
-  if (c.has_prior) {
-    const lvf_batch* pb = p->prior;
-    const PriorArgs P{pb->n, pb->idx_a.p, pb->idx_b.p, pb->table.p, pb->ob_a.p, pb->ob_b.p};
-    hipLaunchKernelGGL(k_prior_lin, dim3((pb->n + 63) / 64), dim3(64), 0, q, P, p->st->poses.p, p->pose_const.p, p->B.p, p->dpad, p->gc.p, cost);
-  }
-  LVF_HIP(hipGetLastError());
-  p->linearized = true;
-  return LVF_OK;
-}
-
-// the deferred item count of the band work list (build_band_work) -> the Schur launch's arguments
-static int await_band_work(lvf_problem* p) {
-  if (!p->band_pending) return LVF_OK;
-  LVF_HIP(hipEventSynchronize(p->ev_band));
-  p->band_pending = false;
-  p->n_band_work = p->h_n_band_work[0];
-  if (p->chain && p->chain->merged_level0) {
-    SchurSp0Args& a = p->chain->ssp0;
-    a.n_work = p->n_band_work;
-    a.nblocks = a.n_work + a.sp.nblocks + a.sp_b.nblocks + a.sp_c.nblocks;
-  }
-  return LVF_OK;
-}
-
-// S (elimination order) = B + D - E^T Cd^-1 E, rhs row = -(gc - E^T Cd^-1 g_rho); radius read from `radius_dev`
-static int enqueue_reduced_system(lvf_problem* p, const double* radius_dev, bool reset_scalars, bool gated, bool* level0_done, const AccSel* acc = nullptr) {
-  hipStream_t q = p->ctx->stream;
-  const Chain& c = *p->chain;
-  // the parity tap (level0_done == nullptr: the damped system alone, nothing eliminated) always takes the classic assembly
-  const bool early = c.early && level0_done != nullptr;
-  PrepArgs pa = early ? c.prep_early : c.prep;
-  if (acc) { pa.acc = *acc; acc_patch(pa.ride, acc); }
-  pa.radius = radius_dev;
-  if (!reset_scalars) pa.scal = nullptr;
-  if (!gated) pa.done = nullptr;
-  // LVF_POISON_S=1 (diagnostic): every byte of S is 0xff (NaN) before the assembly, so whatever the assembly does not write — the upper
-  // triangle — stays NaN; results must not change (tests/test_gpu_solver.py runs the parity cases this way too)
-  static const bool poison = std::getenv("LVF_POISON_S") != nullptr;
-  if (poison) LVF_HIP(hipMemsetAsync(p->S.p, 0xff, (size_t)p->ld * p->ld * 8, q));
-  LVF_CHAIN_LAUNCH(p, ST_PREPARE, k_prepare, dim3(pa.nblocks), dim3(kT), pa.ride.nblocks > 0 ? c.prep_lds : 0, q, pa);
-  stage_mark(p, ST_PREPARE, 1);
-  if (!early && c.early) p->accum_clean = false;       // the tap wrote S: the next iteration must clear it
-  if (level0_done) *level0_done = false;
-  if (p->n_lm) {
-    LVF_TRY(await_band_work(p));                       // (patches c.ssp0: `c` refers to the problem's chain)
-    if (c.merged_level0) {
-      SchurSp0Args sa = c.ssp0;
-      if (acc) { sa.acc = *acc; acc_patch(sa.sp, acc); acc_patch(sa.sp_b, acc); acc_patch(sa.sp_c, acc); }
-      if (!gated) sa.done = nullptr;
-      if (!level0_done) { sa.nblocks = sa.n_work; sa.sp.nblocks = 0; sa.sp_b.nblocks = 0; sa.sp_c.nblocks = 0; }       // the Schur complement alone (parity tap)
-      static const bool schur_timing = std::getenv("LVF_SCHUR_TIMING") != nullptr;
-      const int ns = sa.n_work;
-      if (schur_timing) { LVF_TRY(p->dbg_lin.ensure((size_t)ns * 8 + 8)); LVF_HIP(hipMemsetAsync(p->dbg_lin.p, 0, (size_t)ns * 64, q)); sa.dbg = p->dbg_lin.p; }
-      if (sa.nblocks > 0) LVF_CHAIN_LAUNCH(p, ST_SCHUR_SP0, k_schur_sp0, dim3(sa.nblocks), dim3(256), c.ssp0_lds, q, sa);
-      stage_mark(p, ST_SCHUR_SP0, 1);
-      if (schur_timing) {
-        std::vector<unsigned long long> t((size_t)ns * 8);
-        LVF_HIP(hipStreamSynchronize(q));
-        LVF_HIP(hipMemcpy(t.data(), p->dbg_lin.p, t.size() * 8, hipMemcpyDeviceToHost));
-        double ph[3] = {0, 0, 0}; int cnt = 0; unsigned long long first = ~0ull, last = 0;
-        for (int w = 0; w < ns; ++w) {
-          if (!t[(size_t)w * 8 + 3]) continue;
-          ++cnt;
-          for (int k = 0; k < 3; ++k) ph[k] += (double)(t[(size_t)w * 8 + k + 1] - t[(size_t)w * 8 + k]) * 0.01;
-          first = std::min(first, t[(size_t)w * 8]); last = std::max(last, t[(size_t)w * 8 + 3]);
-        }
-        std::fprintf(stderr, "schur band phases (us, mean over %d of %d workgroups): setup + first fetch issue %.2f | chunks (stage + mfma) %.2f | output atomics %.2f ; first start -> last end %.2f\n",
-                     cnt, ns, ph[0] / std::max(cnt, 1), ph[1] / std::max(cnt, 1), ph[2] / std::max(cnt, 1), (double)(last - first) * 0.01);
-      }
-      if (level0_done) *level0_done = true;
-    } else {
-      double* S_pose = p->S.p + (size_t)p->off_pose * (p->ld + 1);
-      const LmBand band{p->band_ready ? p->lm_order.p : nullptr, p->lm_nactive.p, p->lm_kmin.p, p->lm_kmax.p};
-      LVF_TRY(launch_schur(q, p->n_lm, p->dp, p->ldE, p->E.p, p->Cd.p, p->dp, p->ld, S_pose, band));
-    }
-  }
-  LVF_HIP(hipGetLastError());
-  return LVF_OK;
-}
-
-// one complete LM iteration of one window on its stream, closed on device by k_lm_decide; nothing is waited for
-// `fused` (Chain::fused_ok, a device-loop solve only): kFusedOn = every launch selects its accumulator set on device; kFusedNoLin = the iteration
-// starts at k_tf_reduce (the last one's candidate pass linearised); kFusedTail = it ends with the candidate pass k_lin_cost_decide
-enum { kFusedOn = 1, kFusedNoLin = 2, kFusedTail = 4 };
-static int enqueue_iteration(lvf_problem* p, bool end_zero, int fused = 0) {
-  hipStream_t q = p->ctx->stream;
-  if (chain_stale(p)) LVF_TRY(build_chain(p));
-  const Chain& c = *p->chain;
-  const ReducedOverride* ov = p->ov.get();    // test tap (null in production)
-  if (ov) LVF_REQUIRE(ov->d == p->d, "the overridden reduced system has %d unknowns, the problem now has %d: clear or set it again", ov->d, p->d);      // (before any launch)
-  if (!c.fused_ok || !p->acc1_ready || ov) fused = 0;
-  const AccSel* acc = (fused & kFusedOn) ? &c.acc : nullptr;
-  static const bool sp_timing = std::getenv("LVF_SP_TIMING") != nullptr;
-  if (sp_timing && c.early) {
-    // diagnostic: the levels' stamps (the chain is rebuilt with the debug pointer in every level's arguments; printed by the next call)
-    const int n_nodes = p->sp_levels.n ? p->sp_levels.first[p->sp_levels.n - 1] + p->sp_levels.count[p->sp_levels.n - 1] : 0;
-    if (p->dbg_sp.n == 0) {
-      LVF_TRY(p->dbg_sp.ensure((size_t)n_nodes * 8 + 8)); p->dbg_sp.n = (size_t)n_nodes * 8;
-      LVF_HIP(hipMemsetAsync(p->dbg_sp.p, 0, (size_t)n_nodes * 64, q));
-      Chain& cw = *p->chain;
-      for (int lv = 0; lv < cw.n_levels; ++lv) cw.sp[lv].src.dbg = p->dbg_sp.p;
-      cw.red.ride.src.dbg = p->dbg_sp.p; cw.prep_early.ride.src.dbg = p->dbg_sp.p; cw.ssp0.sp.src.dbg = p->dbg_sp.p; cw.ssp0.sp_b.src.dbg = p->dbg_sp.p; cw.ssp0.sp_c.src.dbg = p->dbg_sp.p;
-    } else {
-      std::vector<unsigned long long> t((size_t)n_nodes * 8);
-      LVF_HIP(hipStreamSynchronize(q));
-      LVF_HIP(hipMemcpy(t.data(), p->dbg_sp.p, t.size() * 8, hipMemcpyDeviceToHost));
-      for (int lv = 0; lv < p->sp_levels.n; ++lv) {
-        const int f0 = p->sp_levels.first[lv], cnt = p->sp_levels.count[lv];
-        double ph[7] = {0, 0, 0, 0, 0, 0, 0}; unsigned long long first = ~0ull, last = 0;
-        for (int k = f0; k < f0 + cnt; ++k) {
-          for (int j = 0; j < 7; ++j) ph[j] += (double)(t[(size_t)k * 8 + j + 1] - t[(size_t)k * 8 + j]) * 0.01 / cnt;
-          first = std::min(first, t[(size_t)k * 8]); last = std::max(last, t[(size_t)k * 8 + 7]);
-        }
-        std::fprintf(stderr, "sparse level %d (%d blocks, us): requests by address %.2f | wait for the level below %.2f | S entries %.2f | factor %.2f | W + first adds (returning) %.2f | arrive %.2f | rest of the adds %.2f ; start %.2f after level 0's first start, span %.2f\n",
-                     lv, cnt, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6], (double)(first - t[0]) * 0.01, (double)(last - first) * 0.01);
-      }
-    }
-  }
-  // With an override the damped system is assembled the classic way (no level rides in the launches ahead: they would read B), the caller's
-  // entries go over it, and every level is a launch of its own reading S alone; from the block steps on the chain is production's.
-  // (iteration = false also takes the reset of the per-step scalars and of SC_FAIL out of the linearisation launch: the classic k_prepare
-  // below does it, as in the chain without early levels, so a flag raised by one iteration never reaches the next.)
-  LVF_TRY(enqueue_linearize(p, p->huber, true, !ov, acc, !(fused & kFusedNoLin)));
-  bool level0_done = false;
-  LVF_TRY(enqueue_reduced_system(p, &p->ctl.p->radius, true, true, ov ? nullptr : &level0_done, acc));
-  if (ov) {
-    // (a plain launch: a test-only copy is no stage of lvf_problem_stage_times.  Not gated by the loop's `done` flag either — after the end of a
-    // solve it only rewrites S, which nothing reads any more)
-    LVF_TRY(launch_override_reduced(q, p->d, p->ld, p->aug, p->perm.p, ov->S.p, ov->rhs.p, p->S.p));
-  }
-  const int own0 = level0_done ? c.first_own_level : 0;      // (levels below rode in the launches above)
-  for (int lv = own0; lv < c.n_levels; ++lv) {
-    SpArgs la = c.sp[lv];
-    acc_patch(la, acc);
-    if (ov) { SpSrc& sr = la.src; sr.B = nullptr; sr.ldB = 0; sr.dp = 0; sr.gc = nullptr; sr.radius = nullptr; sr.rows_nat = nullptr; sr.s_zero = 0; }      // the classic form
-    LVF_CHAIN_LAUNCH(p, ST_SP_LEVELS, k_sp_eliminate, dim3(la.nblocks), dim3(256), c.sp_lds[lv], q, la);
-  }
-  stage_mark(p, ST_SP_LEVELS, std::max(0, c.n_levels - own0));
-  for (int kb = 0; kb < p->nb; ++kb) {
-    CholArgs cha = c.chol;
-    static const bool chol_timing = std::getenv("LVF_CHOL_TIMING") != nullptr;
-    if (chol_timing) { LVF_TRY(p->dbg.ensure(128)); cha.dbg = p->dbg.p; }      // [0, 64): phases of 8 block steps; [64, 128): their sub-block stages
-    GRide gr = c.gride;                                   // the riders that form G: the top level first, one level per launch
-    const int glv = c.n_levels - 1 - kb;
-    if (c.back_product && glv >= 0) { gr.first = p->sp_levels.first[glv]; gr.n = p->sp_levels.count[glv]; } else gr.n = 0;
-    TRide tr = c.tride;                                   // the riders that form T_kj, k = kb - 1: both factors are final since launch kb - 1
-    tr.n = (c.back_blocks && kb >= 1) ? p->nb - kb : 0;
-    if (chol_subblock_on()) LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step, dim3(chol_step_grid(p->nb, kb) + gr.n + tr.n), dim3(kCT), 0, q, cha, kb, gr, tr);
-    else LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step_pp, dim3(chol_step_grid(p->nb, kb) + gr.n + tr.n), dim3(kCT), 0, q, cha, kb, gr, tr);
-  }
-  {
-    BackArgs ba = c.back;
-    static const bool back_timing = std::getenv("LVF_BACK_TIMING") != nullptr;
-    if (back_timing) { LVF_TRY(p->dbg.ensure(64)); ba.sp.dbg = p->dbg.p; }
-    if (c.back_blocks) ba.T = p->sp_T.p;
-    stage_mark(p, ST_CHOL, p->nb);
-    if (c.back_tail_merged) {
-      BackTailArgs bt = c.bt;
-      if (back_timing) bt.back.sp.dbg = p->dbg.p;
-      bt.back.T = ba.T;
-      if (acc) bt.tail.acc = *acc;
-      LVF_CHAIN_LAUNCH(p, ST_BACKSOLVE, k_backsolve_tail, dim3(2 + c.bt.g_lm + c.bt.g_prod), dim3(kBT), c.bt_lds, q, bt);
-      stage_mark(p, ST_BACKSOLVE, 1);
-      stage_mark(p, ST_STEP_TAIL, 0);
-    } else {
-      LVF_CHAIN_LAUNCH(p, ST_BACKSOLVE, k_chol_backsolve, dim3(1), dim3(kBT), c.back_lds, q, ba);
-      stage_mark(p, ST_BACKSOLVE, 1);
-      TailArgs ta = c.tail;
-      if (acc) ta.acc = *acc;
-      LVF_CHAIN_LAUNCH(p, ST_STEP_TAIL, k_step_tail, dim3(ta.nblocks), dim3(kT), c.tail_lds, q, ta);
-      stage_mark(p, ST_STEP_TAIL, 1);
-    }
-  }
-  if (fused & kFusedTail) {
-    // the candidate pass linearises x + dx into the standby set and closes the iteration (k_lin_cost_decide)
-    FusedArgs fa = c.fused;
-    fa.lin.huber = p->huber;
-    LVF_CHAIN_LAUNCH(p, ST_FUSED, k_lin_cost_decide, dim3(fa.nblocks + fa.zero_wgs), dim3(kT), c.lin_lds, q, fa);
-    stage_mark(p, ST_COST, 0);
-    stage_mark(p, ST_FUSED, 1);
-    p->accum_clean = false;
-    p->linearized = false;
-    LVF_HIP(hipGetLastError());
-    return LVF_OK;
-  }
-  // candidate cost: the small passes first, then the visual pass whose last workgroup closes the iteration
-  CostArgs ca = c.cost;
-  ca.huber = p->huber;
-  if (c.has_imu && !c.imu_in_cost) LVF_TRY(launch_imu_args(q, c.imu_cost, false));
-  if (c.has_prior) {
-    const lvf_batch* pb = p->prior;
-    const PriorArgs P{pb->n, pb->idx_a.p, pb->idx_b.p, pb->table.p, pb->ob_a.p, pb->ob_b.p};
-    hipLaunchKernelGGL(k_prior_cost, dim3((pb->n + 63) / 64), dim3(64), 0, q, P, p->poses2.p, p->scal.p + SC_COST_NEW);
-  }
-  if (ca.nblocks > 0) {
-    if (!end_zero) ca.zero_wgs = 0;
-    DecideArgs da = c.dec;
-    static const bool cost_timing = std::getenv("LVF_COST_TIMING") != nullptr;
-    if (cost_timing) { LVF_TRY(p->dbg.ensure(64)); da.dbg = p->dbg.p; }
-    LVF_CHAIN_LAUNCH(p, ST_COST, k_cost_decide, dim3(ca.nblocks + ca.zero_wgs), dim3(kT), 0, q, ca, da, end_zero ? 1 : 0);
-    p->accum_clean = ca.zero_wgs > 0;
-    if (p->accum_clean) p->linearized = false;         // the normal equations of this iteration are gone: no reduced-system tap
-    stage_mark(p, ST_COST, 1 + (c.has_imu && !c.imu_in_cost ? 1 : 0) + (c.has_prior ? 1 : 0));
-  } else {
-    stage_mark(p, ST_COST, (c.has_imu ? 1 : 0) + (c.has_prior ? 1 : 0));
-    LVF_CHAIN_LAUNCH(p, ST_DECIDE, k_lm_decide, dim3(1), dim3(kDT), 0, q, c.dec);
-    stage_mark(p, ST_DECIDE, 1);
-  }
-  LVF_HIP(hipGetLastError());
-  return LVF_OK;
-}
-
-static void ctl_from_options(const lvf_solver_options* o, double radius, double decrease, int max_iters, bool with_tolerances, LmCtl* c) {
-  std::memset(c, 0, sizeof(*c));
-  c->radius = radius; c->decrease = decrease; c->last_radius = radius;
-  c->huber = o->huber_a; c->min_rel_decrease = o->min_relative_decrease;
-  c->function_tol = with_tolerances ? o->function_tolerance : -1.0;
-  c->gradient_tol = with_tolerances ? o->gradient_tolerance : -1.0;
-  c->parameter_tol = with_tolerances ? o->parameter_tolerance : -1.0;
-  c->max_iters = max_iters;
-  c->termination = 1; c->why = LVF_WHY_MAX_ITERATIONS;
-}
-static int upload_ctl(lvf_problem* p, const LmCtl& c) {
-  if (chain_stale(p)) LVF_TRY(build_chain(p));
-  *p->rec = c;                               // the host-visible mirror starts from the same values
-  LVF_TRY(p->h_ctl.reserve(1));
-  p->h_ctl[0] = c;
-  LVF_HIP(hipMemcpyAsync(p->ctl.p, p->h_ctl.p, sizeof(LmCtl), hipMemcpyHostToDevice, p->ctx->stream));
-  return LVF_OK;
-}
-static int download_ctl(lvf_problem* p, LmCtl* out) {
-  hipStream_t q = p->ctx->stream;
-  LVF_TRY(p->h_ctl.reserve(2));
-  LVF_HIP(hipMemcpyAsync(&p->h_ctl[1], p->ctl.p, sizeof(LmCtl), hipMemcpyDeviceToHost, q));
-  LVF_HIP(hipStreamSynchronize(q));
-  *out = p->h_ctl[1];
-  return LVF_OK;
-}
-
-// The loop ended because a chained sparse level timed out waiting for the level below (LVF_WHY_HANDOVER; the step was neither taken nor
-// counted).  The problem gives up chaining for good (its levels become launches of their own: the LVF_CHAIN_LEVELS=0 form), the control
-// block is re-armed as the aborted iteration found it and the caller enqueues again.  Returns false when there is nothing to retry.
-static bool handover_pending(const lvf_problem* p, const LmCtl& c) { return c.done && c.why == LVF_WHY_HANDOVER && !p->no_chain; }
-static int rearm_after_handover(lvf_problem* p, LmCtl* c) {
-  p->no_chain = true; p->unchained_solves = 0; p->chain_ready = false; p->handover_retries += 1;
-  if (p->force_handover_timeouts > 0) p->force_handover_timeouts -= 1;
-  c->done = 0; c->termination = 1; c->why = LVF_WHY_MAX_ITERATIONS;
-  c->aset = 0; c->lin_pending = 0;           // (the re-run linearises into set 0 with today's chain)
-  p->accum_clean = false;                    // (the aborted iteration's partial sums: cleared by an explicit launch before the re-run)
-  return upload_ctl(p, *c);                  // rebuilds the chain
-}
-
-struct IterOut { double cost_before, cost_after, model, dxnorm, xnorm, gmax; bool accepted, solved; };
-
-// exactly one LM iteration from the current state (no tolerance tests): the per-iteration parity point
-static int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* radius, double* decrease, IterOut* out) {
-  LmCtl c;
-  ctl_from_options(o, *radius, *decrease, 1, false, &c);
-  p->huber = o->huber_a;
-  LVF_TRY(upload_ctl(p, c));
-  LVF_TRY(enqueue_iteration(p, false));
-  LVF_TRY(download_ctl(p, &c));
-  if (handover_pending(p, c)) {              // a chained hand-over timed out: the same iteration again, un-chained
-    LVF_TRY(rearm_after_handover(p, &c));
-    LVF_TRY(enqueue_iteration(p, false));
-    LVF_TRY(download_ctl(p, &c));
-  }
-  if (p->dbg.p && std::getenv("LVF_CHOL_TIMING")) {
-    unsigned long long t[128];
-    LVF_HIP(hipMemcpy(t, p->dbg.p, sizeof(t), hipMemcpyDeviceToHost));
-    for (int kb = 0; kb < p->nb && kb < 8; ++kb) {
-      const unsigned long long* u = t + 8 * kb;
-      if (chol_subblock_on() && kb + 2 < p->nb + 1) {      // a full block: per stage, sweep + exchange | tile products (seen by wave 0 of workgroup 1)
-        const unsigned long long* v = t + 64 + 8 * kb;
-        std::fprintf(stderr, "chol step %d stages (us): %.2f | %.2f ; %.2f | %.2f ; %.2f | %.2f ; %.2f\n", kb, (double)(v[0] - u[3]) * 0.01, (double)(v[1] - v[0]) * 0.01,
-                     (double)(v[2] - v[1]) * 0.01, (double)(v[3] - v[2]) * 0.01, (double)(v[4] - v[3]) * 0.01, (double)(v[5] - v[4]) * 0.01, (double)(v[6] - v[5]) * 0.01);
-      }
-      if (kb == 0) std::fprintf(stderr, "chol step 0 (us): loads %.2f | factor %.2f (%llu shader clocks) | store %.2f\n", (double)(u[3] - u[0]) * 0.01, (double)(u[4] - u[3]) * 0.01, u[7] - u[6], (double)(u[5] - u[4]) * 0.01);
-      else if (kb + 2 < p->nb + 1) std::fprintf(stderr, "chol step %d (us): stage %.2f | mfma %.2f | relayout %.2f | factor %.2f | store %.2f ; since previous step's end %.2f\n", kb, (double)(u[1] - u[0]) * 0.01,
-                        (double)(u[2] - u[1]) * 0.01, (double)(u[3] - u[2]) * 0.01, (double)(u[4] - u[3]) * 0.01, (double)(u[5] - u[4]) * 0.01, (double)(u[0] - u[-3]) * 0.01);
-    }
-  }
-  if (p->dbg.p && std::getenv("LVF_COST_TIMING")) {
-    unsigned long long t[64];
-    LVF_HIP(hipMemcpy(t, p->dbg.p, sizeof(t), hipMemcpyDeviceToHost));
-    auto us = [&](int a, int b) { return ((double)t[b] - (double)t[a]) * 0.01; };
-    std::fprintf(stderr, "cost+decide (us): imu wg0 stage %.2f | raw (one lane) %.2f | weight+sum %.2f ; first visual wg %.2f (starts %.2f after imu wg0) ; decision starts %.2f after imu wg0's start: sums %.2f | logic %.2f | commit %.2f | record %.2f\n",
-                 us(8, 9), us(9, 10), us(10, 11), us(12, 13), us(8, 12), us(8, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5));
-  }
-  if (p->dbg.p && std::getenv("LVF_BACK_TIMING")) {
-    unsigned long long t[64];
-    LVF_HIP(hipMemcpy(t, p->dbg.p, sizeof(t), hipMemcpyDeviceToHost));
-    std::fprintf(stderr, "backsolve phases (us):");
-    for (unsigned long long k = 1; k < t[63] && k < 55; ++k) std::fprintf(stderr, " %.2f", (double)(t[k] - t[k - 1]) * 0.01);
-    if (p->chain && p->chain->back_tail_merged)
-      std::fprintf(stderr, " | merged launch, us after workgroup 0's start: step applied %.2f ; first landmark workgroup starts %.2f, sees the poses %.2f, done %.2f ; last one starts %.2f, sees %.2f, done %.2f",
-                   (double)(t[55] - t[0]) * 0.01, (double)(t[56] - t[0]) * 0.01, (double)(t[57] - t[0]) * 0.01, (double)(t[58] - t[0]) * 0.01, (double)(t[59] - t[0]) * 0.01,
-                   (double)(t[60] - t[0]) * 0.01, (double)(t[61] - t[0]) * 0.01);
-    if (p->chain && p->chain->back_tail_merged) std::fprintf(stderr, " ; pose workgroup done %.2f", (double)(t[62] - t[0]) * 0.01);
-    if (p->chain && p->chain->back_product)
-      std::fprintf(stderr, " | product form (\"step applied\" = workgroup 0 done): first G workgroup starts %.2f, sees the flag %.2f, has the dense solution %.2f, its rows %.2f, applied %.2f",
-                   (double)(t[40] - t[0]) * 0.01, (double)(t[41] - t[0]) * 0.01, (double)(t[42] - t[0]) * 0.01, (double)(t[43] - t[0]) * 0.01, (double)(t[44] - t[0]) * 0.01);
-    std::fprintf(stderr, "\n");
-  }
-  out->cost_before = c.cost_before; out->cost_after = c.cost_after; out->model = c.model; out->dxnorm = c.dxnorm; out->xnorm = c.xnorm; out->gmax = c.gmax;
-  out->solved = c.solved != 0; out->accepted = c.accepted != 0;
-  p->last_radius = c.last_radius;
-  p->step_ready = true; p->last_solved = c.solved;
-  *radius = c.radius; *decrease = c.decrease;
-  return LVF_OK;
-}
-
-// waits until the host-visible mirror shows at least `iter` closed iterations (or the loop finished); falls back to a stream
-// synchronisation when the mirror does not move (e.g. device writes to host memory only becoming visible at kernel boundaries)
-static int wait_for_iteration(lvf_problem* p, int iter) {
-  const volatile LmCtl* r = p->rec;
-  const auto t0 = std::chrono::steady_clock::now();
-  while (r->iter < iter && !r->done) {
-    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.05) {
-      LmCtl c;
-      LVF_TRY(download_ctl(p, &c));          // synchronises the stream
-      *p->rec = c;
-      break;
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
-  return LVF_OK;
-}
-
-// Elimination plan (host, <= a few hundred nodes): which (v, ba, bg) blocks are factorised sparsely, in which level, with which
-// neighbour rows; the S row of every unknown.  Rebuilt only when (n_kf, IMU index pairs) change.  LVF_SPARSE_VB=0 keeps every
-// block in the dense corner (the round-1 layout, poses last) for A/B measurements.
-static int build_elimination_plan(lvf_problem* p) {
-  const int n = p->n_kf;
-  std::vector<int32_t> key;
-  key.push_back(n);
-  const lvf_batch* imu = p->imu;
-  const bool have_idx = imu && imu->n > 0 && (int)imu->host_kf1.size() == imu->n && (int)imu->host_kf2.size() == imu->n;
-  if (imu && imu->n > 0) {
-    key.push_back(have_idx ? 1 : 0);
-    if (have_idx) { key.insert(key.end(), imu->host_kf1.begin(), imu->host_kf1.end()); key.insert(key.end(), imu->host_kf2.begin(), imu->host_kf2.end()); }
-  }
-  if (key == p->plan_key && p->ld > 0) return LVF_OK;
-  static const bool sparse_on = [] { const char* e = std::getenv("LVF_SPARSE_VB"); return !(e && e[0] == '0'); }();
-  std::vector<std::vector<char>> va(n, std::vector<char>(n, 0)), pa(n, std::vector<char>(n, 0));
-  bool sparse = sparse_on && (!imu || imu->n == 0 || have_idx);
-  if (have_idx)
-    for (int f = 0; f < imu->n; ++f) {
-      const int i = imu->host_kf1[f], j = imu->host_kf2[f];
-      if (i < 0 || j < 0 || i >= n || j >= n || i == j) continue;
-      va[i][j] = va[j][i] = 1;
-      pa[i][i] = pa[i][j] = pa[j][i] = pa[j][j] = 1;
-    }
-  struct NodeInfo { int kf; std::vector<int> vb, pose; };
-  std::vector<NodeInfo> nodes;
-  std::vector<char> alive(n, 1);
-  SpLevels lv{};
-  // How many levels to eliminate sparsely.  Whatever is left rides in the dense corner, which is factorised in 64-column block steps:
-  // a level beyond the first (level 0 rides in the Schur launch) costs a launch (~8.5 us), a block step ~18 us.  A dry run of the greedy
-  // level construction gives the number of blocks left after each level; the cut-off minimises 8.5 (levels - 1) + 18 block steps (measured launch costs, us).
-  // (At 50 keyframes: 5 levels and one block in the corner's padding instead of 6 levels; at 5: level 0 only.)
-  int max_levels = kSpMaxLevels;
-  if (sparse) {
-    std::vector<std::vector<char>> va2 = va;
-    std::vector<char> alive2(n, 1);
-    std::vector<int> left_after;                      // blocks left after level l
-    for (int l = 0; l < kSpMaxLevels; ++l) {
-      std::vector<char> blocked(n, 0);
-      std::vector<int> chosen;
-      for (int k = 0; k < n; ++k) {
-        if (!alive2[k] || blocked[k]) continue;
-        chosen.push_back(k);
-        for (int u = 0; u < n; ++u) if (va2[k][u]) blocked[u] = 1;
-      }
-      if (chosen.empty()) break;
-      for (int b : chosen) {
-        std::vector<int> nb_;
-        for (int u = 0; u < n; ++u) if (va2[b][u] && alive2[u]) nb_.push_back(u);
-        for (int u : nb_) { for (int w : nb_) if (w != u) va2[u][w] = 1; va2[u][b] = 0; }
-        alive2[b] = 0;
-      }
-      int left = 0;
-      for (int k = 0; k < n; ++k) left += alive2[k] ? 1 : 0;
-      left_after.push_back(left);
-    }
-    double best = 1e300;
-    for (size_t l = 0; l < left_after.size(); ++l) {
-      const int steps = (9 * left_after[l] + p->dp + 1 + 63) / 64;
-      const double cost = 8.5 * (double)l + 18.0 * steps;
-      if (cost < best - 1e-9) { best = cost; max_levels = (int)l + 1; }
-    }
-    static const int force_levels = [] { const char* e = std::getenv("LVF_FORCE_LEVELS"); return e ? std::atoi(e) : 0; }();      // experiment
-    if (force_levels > 0) max_levels = std::min((int)left_after.size(), force_levels);
-  }
-  while (sparse && lv.n < std::min(max_levels, kSpMaxLevels)) {
-    std::vector<char> blocked(n, 0);
-    std::vector<int> chosen;
-    for (int k = 0; k < n; ++k) {
-      if (!alive[k] || blocked[k]) continue;
-      int m = 1;
-      for (int u = 0; u < n; ++u) m += 9 * (va[k][u] && alive[u]) + 6 * pa[k][u];
-      if (m > kSpMaxRows) continue;
-      chosen.push_back(k);
-      for (int u = 0; u < n; ++u) if (va[k][u]) blocked[u] = 1;
-    }
-    if (chosen.empty()) break;
-    lv.first[lv.n] = (int)nodes.size(); lv.count[lv.n] = (int)chosen.size(); ++lv.n;
-    for (int b : chosen) {
-      NodeInfo ni; ni.kf = b;
-      for (int u = 0; u < n; ++u) { if (va[b][u] && alive[u]) ni.vb.push_back(u); if (pa[b][u]) ni.pose.push_back(u); }
-      nodes.push_back(std::move(ni));
-    }
-    for (size_t ci = 0; ci < chosen.size(); ++ci) {   // fill-in among the neighbours of an eliminated block
-      const int b = chosen[ci];
-      const NodeInfo& ni = nodes[lv.first[lv.n - 1] + (int)ci];
-      for (int u : ni.vb) {
-        for (int w : ni.vb) if (w != u) va[u][w] = 1;
-        for (int k : ni.pose) pa[u][k] = 1;
-        va[u][b] = 0;
-      }
-      alive[b] = 0;
-    }
-  }
-  // S rows
-  const int ns = (int)nodes.size();
-  std::vector<int> vbcol(n, -1);
-  for (int s_ = 0; s_ < ns; ++s_) vbcol[nodes[s_].kf] = 9 * s_;
-  p->off = (9 * ns + 1) & ~1;
-  int ndv = 0;
-  for (int k = 0; k < n; ++k) if (alive[k]) vbcol[k] = p->off + 9 * ndv++;
-  p->off_pose = p->off + 9 * ndv;
-  p->ndense = 9 * ndv + p->dp;
-  p->aug = p->off + p->ndense;
-  p->nb = (p->ndense + 1 + 63) / 64;
-  p->ld = p->off + 64 * p->nb;
-  p->perm_h.assign(p->d, 0);
-  std::vector<int> iperm(p->ld, -1);
-  for (int i = 0; i < p->dp; ++i) p->perm_h[i] = p->off_pose + i;
-  for (int k = 0; k < n; ++k) for (int c = 0; c < 9; ++c) p->perm_h[p->dp + 9 * k + c] = vbcol[k] + c;
-  for (int i = 0; i < p->d; ++i) iperm[p->perm_h[i]] = i;
-  iperm[p->aug] = -2;
-  // device tables
-  std::vector<SpNode> dn(ns);
-  std::vector<int> rows, owner, rows_nat;
-  p->sp_tiles.assign(lv.n, 1); p->sp_shmem.assign(lv.n, 0); p->sp_item0.assign(lv.n, 0); p->sp_items.assign(lv.n, 0);
-  for (int l = 0; l < lv.n; ++l) {
-    int mmax = 0;
-    for (int s_ = lv.first[l]; s_ < lv.first[l] + lv.count[l]; ++s_) {
-      const NodeInfo& ni = nodes[s_];
-      dn[s_].col = 9 * s_; dn[s_].row_off = (int)rows.size(); dn[s_].id = ni.kf;
-      std::vector<int> r;
-      for (int u : ni.vb) for (int c = 0; c < 9; ++c) r.push_back(vbcol[u] + c);
-      for (int k : ni.pose) for (int c = 0; c < 6; ++c) r.push_back(p->off_pose + 6 * k + c);
-      r.push_back(p->aug);
-      std::sort(r.begin(), r.end());
-      dn[s_].m = (int)r.size();
-      mmax = std::max(mmax, dn[s_].m);
-      rows.insert(rows.end(), r.begin(), r.end());
-      owner.insert(owner.end(), r.size(), s_);
-    }
-    p->sp_item0[l] = dn[lv.first[l]].row_off; p->sp_items[l] = (int)rows.size() - p->sp_item0[l];
-    const int P = mmax * (mmax + 1) / 2;
-    p->sp_tiles[l] = std::max(1, std::min(32, (P + 2047) / 2048));
-    p->sp_shmem[l] = (9 * mmax + 81 + 9) * 8 + 2 * 4 * mmax + 16;
-  }
-  p->sp_levels = lv;
-  hipStream_t q = p->ctx->stream;
-  LVF_TRY(p->perm.assign(p->perm_h.data(), p->perm_h.size(), q)); LVF_TRY(p->iperm.assign(iperm.data(), iperm.size(), q));
-  p->ldG = 0;
-  if (ns) {
-    rows_nat.resize(rows.size());
-    for (size_t i = 0; i < rows.size(); ++i) rows_nat[i] = iperm[rows[i]];
-    LVF_TRY(p->sp_rows_nat.assign(rows_nat.data(), rows_nat.size(), q));
-    LVF_TRY(p->sp_nodes.assign(dn.data(), dn.size(), q)); LVF_TRY(p->sp_rows.assign(rows.data(), rows.size(), q)); LVF_TRY(p->sp_owner.assign(owner.data(), owner.size(), q));
-    LVF_TRY(p->sp_W.ensure(rows.size() * 9)); LVF_TRY(p->sp_L.ensure((size_t)ns * 81));
-    p->sp_wstride = (int)rows.size();
-    p->ldG = ((p->ndense + 1 + 15) / 16) * 16;
-    std::vector<int> gmap((size_t)ns * p->ldG, -1);
-    for (int s_ = 0; s_ < ns; ++s_)
-      for (int r = 0; r < dn[s_].m; ++r) { const int R = rows[dn[s_].row_off + r]; if (R >= p->off) gmap[(size_t)s_ * p->ldG + (R - p->off)] = dn[s_].row_off + r; }
-    LVF_TRY(p->sp_gmap.assign(gmap.data(), gmap.size(), q));
-    LVF_HIP(hipStreamSynchronize(q));    // (gmap goes out of scope with this block)
-  }
-  LVF_HIP(hipStreamSynchronize(q));      // the host vectors above go out of scope
-  p->plan_key = std::move(key);
-  return LVF_OK;
-}
-
-int problem_configure(lvf_problem* p) {
-  static const bool cfg_timing = std::getenv("LVF_CONFIGURE_TIMING") != nullptr;
-  const auto cfg_t0 = std::chrono::steady_clock::now();
-  auto cfg_mark = [&](const char* what) {
-    if (cfg_timing) std::fprintf(stderr, "  problem_configure: %s at %.3f ms\n", what, 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - cfg_t0).count());
-  };
-  lvf_state* st = p->st;
-  lvf_ctx* ctx = p->ctx;
-  p->n_kf = st->n_kf; p->n_lm = st->n_lm;
-  p->d = 15 * p->n_kf; p->dp = 6 * p->n_kf;
-  p->ldE = ((p->dp + 1 + 15) / 16) * 16;
-  p->dpad = ((p->d + 1 + 63) / 64) * 64;
-  LVF_TRY(build_elimination_plan(p));                 // sets ld, off, off_pose, ndense, aug, nb and the sparse levels
-  cfg_mark("elimination plan");
-  const size_t nS = (size_t)p->dpad * p->dpad;
-  LVF_TRY(p->Dinv.ensure((size_t)p->nb * kNB * kNB)); LVF_TRY(p->Ldiag.ensure((size_t)p->nb * kNB * kNB));
-  LVF_TRY(p->B.ensure(nS)); LVF_TRY(p->S.ensure((size_t)p->ld * p->ld)); LVF_TRY(p->gc.ensure(p->dpad)); LVF_TRY(p->dxc.ensure(p->dpad));
-  LVF_TRY(p->C.ensure(p->n_lm)); LVF_TRY(p->gr.ensure(p->n_lm)); LVF_TRY(p->Cd.ensure(p->n_lm)); LVF_TRY(p->dxl.ensure(p->n_lm));
-  LVF_TRY(p->scal.ensure(SC_ALLOC)); LVF_TRY(p->sp_sync.ensure(kSpMaxLevels));
-  // candidate state x + dx (an accepted candidate is copied into the state by k_lm_decide)
-  LVF_TRY(p->poses2.ensure(std::max(st->poses.cap, (size_t)7 * p->n_kf))); LVF_TRY(p->vel2.ensure(std::max(st->vel.cap, (size_t)3 * p->n_kf)));
-  LVF_TRY(p->ba2.ensure(std::max(st->ba.cap, (size_t)3 * p->n_kf))); LVF_TRY(p->bg2.ensure(std::max(st->bg.cap, (size_t)3 * p->n_kf)));
-  LVF_TRY(p->invd2.ensure(std::max(st->inv_depth.cap, (size_t)p->n_lm)));
-  LVF_TRY(p->pose_const.ensure((size_t)p->n_kf + 8)); LVF_TRY(p->fail.ensure(1));      // (+8: cleared in 8-byte words)
-  p->pose_const_h.assign(p->n_kf, 0);
-  cfg_mark("buffers");
-  p->tf_work.n = 0;
-  p->tf_unique_lk2 = false; p->tf_k1_first = false; p->compact = false; p->tf_sorted_copy = false;
-  lvf_batch* two_frame = p->tf;
-  if (two_frame && two_frame->n && two_frame->sorted_by_kf && !two_frame->kf2_counts.empty() && two_frame->unique_lk2_known) {
-    // the creator (the persistent window) vouches for the shape: sorted by current keyframe, k1 < k2, one block per (landmark, keyframe)
-    size_t total = 0, nw = 0;
-    for (int32_t c : two_frame->kf2_counts) { total += (size_t)c; nw += ((size_t)c + kT - 1) / kT; }
-    if (total != (size_t)two_frame->n) { set_error("two-frame batch: per-keyframe counts do not add up to the number of blocks"); return LVF_ERR_INVALID; }
-    LVF_TRY(p->h_tf_work.reserve(nw + 1));
-    nw = 0;
-    int at = 0;
-    for (size_t k = 0; k < two_frame->kf2_counts.size(); ++k)
-      for (int left = two_frame->kf2_counts[k]; left > 0; left -= kT) { const int c = std::min(left, kT); p->h_tf_work[nw++] = TfWork{at, c, (int)k}; at += c; }
-    LVF_TRY(p->tf_work.assign(p->h_tf_work.p, nw, ctx->stream));
-    p->tf_k1_first = true; p->tf_unique_lk2 = true;
-  } else if (two_frame && two_frame->n && two_frame->sorted_by_kf && !two_frame->host_kf2.empty()) {
-    // work list for the sorted fast path: runs of <= kT blocks sharing one current keyframe; k1 == k2 disables it.
-    // ONE pass over the blocks gathers everything the host has to know about them (the list is 72 k entries at configs[3] and this
-    // function is on adapt::Solve's path: seven separate passes were 0.45 ms of it):
-    //   * k1 != k2 everywhere, k1 < k2 everywhere;
-    //   * the current-keyframe runs (their starts) and, per run, how many blocks have which first keyframe (for the counting sort below);
-    //   * how often the first keyframe steps DOWN inside a run (ids in creation order: almost never);
-    //   * one block per (landmark, current keyframe) and ONE first keyframe per landmark, with two per-landmark tables: `seen_run[l]` =
-    //     the last run landmark l appeared in (a repeat inside one run is a duplicate pair), `first_kf[l]` = its first keyframe.  The plain
-    //     stores into E[l][k2 columns] must never meet the adds into E[l][k1 columns]; BuildProblem's blocks always satisfy this, a
-    //     hand-made batch may not.
-    const std::vector<int32_t>& k2 = two_frame->host_kf2; const std::vector<int32_t>& k1 = two_frame->host_kf1;
-    const std::vector<int32_t>& lmh = two_frame->host_lm;
-    const int n = two_frame->n, nkf = p->n_kf;
-    static const bool k1sort_on = [] { const char* e = std::getenv("LVF_TF_K1SORT"); return !(e && e[0] == '0'); }();
-    const bool want_hist = k1sort_on && nkf <= 256;
-    bool ok = true, k1_first = true;
-    bool uniq = two_frame->unique_lk2_known || lmh.size() == (size_t)n;
-    const bool check_uniq = uniq && !two_frame->unique_lk2_known;
-    const int32_t nl = (int32_t)p->n_lm;
-    std::vector<int32_t> seen_run, first_kf;
-    if (check_uniq) { seen_run.assign((size_t)nl, -1); first_kf.assign((size_t)nl, -1); }
-    std::vector<int32_t> run_start;                 // first block of every current-keyframe run (+ n at the end)
-    std::vector<int32_t> hist;                      // [run][first keyframe] block counts
-    run_start.reserve((size_t)nkf + 2);
-    if (want_hist) hist.reserve((size_t)(nkf + 1) * nkf);
-    int descents = 0, cur = INT32_MIN, run = -1;
-    int32_t* hrow = nullptr;
-    for (int i = 0; i < n; ++i) {
-      const int a = k1[i], c2 = k2[i];
-      ok = ok && a != c2; k1_first = k1_first && a < c2;
-      if (c2 != cur) {
-        cur = c2; ++run; run_start.push_back(i);
-        if (want_hist) { hist.resize(hist.size() + (size_t)nkf, 0); hrow = hist.data() + (size_t)run * nkf; }
-      } else descents += a < k1[i - 1] ? 1 : 0;
-      if (want_hist) ++hrow[std::min(std::max(a, 0), nkf - 1)];
-      if (check_uniq && uniq) {
-        const int32_t l = lmh[i];
-        if (l < 0 || l >= nl) uniq = false;
-        else {
-          if (seen_run[l] == run) uniq = false;
-          seen_run[l] = run;
-          if (first_kf[l] < 0) first_kf[l] = a; else if (first_kf[l] != a) uniq = false;
-        }
-      }
-    }
-    run_start.push_back(n);
-    p->tf_k1_first = ok && k1_first;
-    if (ok) {
-      // built straight into pinned staging owned by the problem: the upload is a real asynchronous copy and this function does not
-      // have to wait for the stream before returning
-      size_t nw = 0;
-      for (size_t r = 0; r + 1 < run_start.size(); ++r) nw += (size_t)(run_start[r + 1] - run_start[r] + kT - 1) / kT;
-      LVF_TRY(p->h_tf_work.reserve(nw + 1));
-      nw = 0;
-      for (size_t r = 0; r + 1 < run_start.size(); ++r)
-        for (int i = run_start[r]; i < run_start[r + 1]; i += kT) p->h_tf_work[nw++] = TfWork{i, std::min(kT, run_start[r + 1] - i), k2[run_start[r]]};
-      LVF_TRY(p->tf_work.assign(p->h_tf_work.p, nw, ctx->stream));
-      // first keyframes out of order inside the runs (more than one block in eight steps DOWN): sorted copies for the linearisation.
-      // BuildProblem's own order (landmark ids in creation order) passes untouched.
-      if (want_hist && (size_t)descents * 8 > (size_t)n) {
-        LVF_TRY(p->h_tfs_perm.reserve((size_t)n));
-        int* perm = p->h_tfs_perm.p;
-        for (size_t r = 0; r + 1 < run_start.size(); ++r) {     // counting sort of each run by first keyframe (stable): the histogram is there
-          int32_t* cnt = hist.data() + r * (size_t)nkf;
-          int32_t at = run_start[r];
-          for (int k = 0; k < nkf; ++k) { const int32_t c = cnt[k]; cnt[k] = at; at += c; }
-          for (int t = run_start[r]; t < run_start[r + 1]; ++t) perm[cnt[std::min(std::max(k1[t], 0), nkf - 1)]++] = t;
-        }
-        LVF_TRY(p->tfs_perm.assign(perm, (size_t)n, ctx->stream));
-        LVF_TRY(p->tfs_fo.ensure(n)); LVF_TRY(p->tfs_ob.ensure(n)); LVF_TRY(p->tfs_lm.ensure(n)); LVF_TRY(p->tfs_k1.ensure(n)); LVF_TRY(p->tfs_k2.ensure(n));
-        hipLaunchKernelGGL(k_tf_gather, dim3(grid(n)), dim3(kT), 0, ctx->stream, n, p->tfs_perm.p, (const double2*)two_frame->ob_a.p, (const double2*)two_frame->ob_b.p,
-                           two_frame->idx_a.p, two_frame->idx_b.p, two_frame->idx_c.p, p->tfs_fo.p, p->tfs_ob.p, p->tfs_lm.p, p->tfs_k1.p, p->tfs_k2.p);
-        LVF_HIP(hipGetLastError());
-        p->tf_sorted_copy = true;
-      }
-      p->tf_unique_lk2 = uniq;
-    }
-  }
-  cfg_mark("TwoFrame work list + shape checks");
-  // landmark tracks -> band-limited Schur (device side: the TwoFrame indices already live there)
-  p->band_ready = false;
-  static const bool band_on = [] { const char* e = std::getenv("LVF_SCHUR_BAND"); return !(e && e[0] == '0'); }();
-  const bool band_ok = band_on && p->n_lm > 0 && (size_t)(4 * p->n_kf + 1) * sizeof(int) <= 48 * 1024;
-  // compact landmark layout + slabs (atomic-free TwoFrame linearisation): needs the sorted work list, one block per (landmark,
-  // keyframe), the landmark's first keyframe ahead of its observations, and the merged band-Schur launch
-  static const bool compact_on = [] { const char* e = std::getenv("LVF_COMPACT"); return !(e && e[0] == '0'); }();
-  const size_t shb = ((size_t)kSchurRows * (p->ldE + 16) + kSchurRows) * sizeof(double) + kBandRowsMax * sizeof(int);
-  const bool merged = shb <= 64 * 1024 && p->sp_levels.n > 0 && (size_t)p->sp_shmem[0] <= 64 * 1024;
-  const bool want_compact = band_ok && compact_on && merged && p->dp <= 320 && two_frame && two_frame->n && p->tf_work.n && p->n_kf <= kMaxStagedKf && p->tf_unique_lk2 && p->tf_k1_first;
-  LVF_TRY(p->E.ensure((size_t)p->n_lm * p->ldE));
-  if (band_ok) { LVF_TRY(p->lm_kmin.ensure(p->n_lm)); LVF_TRY(p->lm_kmax.ensure(p->n_lm)); LVF_TRY(p->lm_order.ensure(p->n_lm)); LVF_TRY(p->lm_nactive.ensure(1)); }
-  // atomic-free mode: E's non-zero pattern is fixed for the problem and fully overwritten by every linearisation — cleared once, here;
-  // one launch for the clears AND the landmark tracks' initial values (a persistent window reconfigures every tick)
-  {
-    ZeroList z{};
-    if (want_compact && p->n_lm) { z.p[z.count] = p->E.p; z.n[z.count] = (unsigned long long)p->n_lm * p->ldE; ++z.count; }
-    z.p[z.count] = reinterpret_cast<double*>(p->pose_const.p); z.n[z.count] = (unsigned long long)(p->n_kf + 7) / 8; ++z.count;      // (the buffer's capacity is padded)
-    z.p[z.count] = p->dxc.p; z.n[z.count] = (unsigned long long)p->dpad; ++z.count;
-    hipLaunchKernelGGL(k_zero_multi_ranges, dim3(512, z.count + (band_ok ? 1 : 0)), dim3(kT), 0, ctx->stream, z, p->n_lm, band_ok ? p->lm_kmin.p : nullptr, band_ok ? p->lm_kmax.p : nullptr);
-    LVF_HIP(hipGetLastError());
-  }
-  if (band_ok) {
-    hipStream_t q = ctx->stream;
-    if (two_frame && two_frame->n)
-      hipLaunchKernelGGL(k_lm_range, dim3(grid(two_frame->n)), dim3(kT), 0, q, two_frame->n, two_frame->idx_a.p, two_frame->idx_b.p, two_frame->idx_c.p,
-                         p->lm_kmin.p, p->lm_kmax.p);
-    if (want_compact) {
-      LVF_TRY(p->lm_eoff.ensure(p->n_lm)); LVF_TRY(p->n_slots.ensure(1));
-      // (the slot offsets ride beside the sort: two independent one-workgroup chains, one launch)
-      hipLaunchKernelGGL(k_lm_sort_offsets, dim3(2), dim3(1024), (size_t)(4 * p->n_kf + 1) * sizeof(int), q, p->n_lm, p->n_kf, p->lm_kmin.p, p->lm_kmax.p, p->lm_order.p,
-                         p->lm_nactive.p, p->lm_eoff.p, p->n_slots.p);
-    } else
-    hipLaunchKernelGGL(k_lm_sort, dim3(1), dim3(1024), (size_t)(4 * p->n_kf + 1) * sizeof(int), q, p->n_lm, p->n_kf, p->lm_kmin.p, p->lm_kmax.p, p->lm_order.p,
-                       p->lm_nactive.p);
-    LVF_HIP(hipGetLastError());
-    p->band_ready = true;
-    p->band_rows_built = 0;         // the bands changed: the work list is rebuilt with the next chain
-    p->band_epoch += 1;
-    if (want_compact) {
-      const size_t cap_slots = (size_t)p->n_lm * (size_t)std::max(p->n_kf - 1, 1);      // worst case: every landmark seen by every later keyframe
-      const int n_wg = (int)p->tf_work.n;
-      LVF_TRY(p->tf_slot.ensure(two_frame->n));
-      LVF_TRY(p->slotB.ensure(cap_slots * 8));
-      LVF_TRY(p->Ct.ensure(p->n_lm)); LVF_TRY(p->grt.ensure(p->n_lm));
-      LVF_TRY(p->slabP.ensure((size_t)n_wg * p->n_kf * kSlabRow)); LVF_TRY(p->slabQ.ensure((size_t)n_wg * kSlabQ));
-      {
-        const int g_slots = grid(two_frame->n);
-        hipLaunchKernelGGL(k_tf_slots_zero, dim3(g_slots + 256), dim3(kT), 0, q, two_frame->n, g_slots, p->tf_lm(), p->tf_k2(), p->lm_kmin.p, p->lm_eoff.p, p->tf_slot.p,
-                           p->n_slots.p, p->slotB.p);
-      }
-      LVF_HIP(hipGetLastError());
-      // run_first[k] = first workgroup of current keyframe k's run (the work list is sorted by k2); run_first[n_kf] = n_wg
-      LVF_TRY(p->h_run_first.reserve((size_t)p->n_kf + 1));
-      {
-        int w = 0;
-        for (int k = 0; k <= p->n_kf; ++k) {
-          while (w < n_wg && p->h_tf_work[w].k2 < k) ++w;
-          p->h_run_first[k] = w;
-        }
-      }
-      LVF_TRY(p->run_first.assign(p->h_run_first.p, (size_t)p->n_kf + 1, q));
-      p->compact = true;
-    }
-  }
-  cfg_mark("device-side layout launches + E");
-  // no stream wait here: every host source above is pinned and owned by the problem (or was waited for by the plan builder)
-  p->linearized = false;
-  p->chain_ready = false;
-  p->step_ready = false;
-  return LVF_OK;
-}
+// the instantiations the host side launches (enqueue_linearize in solver_chain.hip: a window without a sorted TwoFrame work list)
+template __global__ void k_lin_tc<false>(int, const double2*, const double2*, const int*, const int*, const double*, StateP, CamD, CamD, double, double*, double*, double*);
+template __global__ void k_lin_tf<false>(int, int, const double2*, const double2*, const int*, const int*, const int*, StateP, CamD, CamD, double, const uint8_t*, double*, int,
+                                         double*, double*, int, double*, double*, double*);
+template __global__ void k_lin_po<false>(int, int, const double2*, const int*, const int*, const double*, StateP, CamD, double, const uint8_t*, double*, int, double*, double*);
 
 }  // namespace lvf
-
-using namespace lvf;
-
-// ------------------------------------------------------------------------------------------------ a batch of windows
-// W independent windows advanced by ONE chain of launches per LM iteration: every kernel of the iteration takes blockIdx.y = window and
-// reads that window's argument block from a device table.  A single window's iteration is a chain of ~23 small launches that leaves
-// most of the 256 CUs idle (sequential pivots, 2 + k workgroups per panel step); a batch fills the same launches W times over — the
-// shape of every independent-window client of the reference: RL environments (src/lvio_fusion/src/environment.cpp:18-115), loop-closure
-// candidates (relocator.cpp:196-206), per-submap replays, and what ONE GPU of the 8-GPU sharding works on.
-struct lvf_problem_batch {
-  lvf_ctx* ctx = nullptr;
-  std::vector<lvf_problem*> probs;
-  bool tables = false;               // every member is batchable: table launches; otherwise the windows' own chains run back to back
-  int W = 0, max_levels = 0, max_nb = 0;
-  // per-stage argument tables [W] (device) and the launch shapes (max over the windows)
-  lvf::DevBuf<lvf::ImuArgs> imu_lin, imu_cost; int g_imu_lin = 0, g_imu_cost = 0;
-  lvf::DevBuf<lvf::LinArgs> lin; int g_lin = 0; size_t lds_lin = 0;
-  lvf::DevBuf<lvf::TfReduceArgs> red; int g_red = 0; size_t lds_red = 0;
-  lvf::DevBuf<lvf::PrepArgs> prep; int g_prep = 0; size_t lds_prep = 0;
-  int first_own_level = 0;           // min over the windows: the first sparse level that is a launch of its own
-  lvf::DevBuf<lvf::SchurSp0Args> ssp0; int g_ssp0 = 0; size_t lds_ssp0 = 0;
-  lvf::DevBuf<lvf::SpArgs> sp[lvf::kSpMaxLevels]; int g_sp[lvf::kSpMaxLevels] = {0}; int lds_sp[lvf::kSpMaxLevels] = {0};
-  lvf::DevBuf<lvf::CholArgs> chol;
-  lvf::DevBuf<lvf::BackArgs> back; size_t lds_back = 0;
-  lvf::DevBuf<lvf::TailArgs> tail; int g_tail = 0; size_t lds_tail = 0;
-  lvf::DevBuf<lvf::CostArgs> cost; int g_cost = 0;
-  lvf::DevBuf<lvf::DecideArgs> dec;
-  lvf::DevBuf<lvf::ZeroList> zero;   // every window's full accumulator list (cleared in one launch when a window is not known clean)
-  double huber_built = -1.0;
-  // A batch of more than one window sums its Schur complements over wider landmark slices (fewer output atomics: LVF_BATCH_BAND_ROWS,
-  // default 128).  The work lists for that width belong to the BATCH — a member's own list, slice width and chain are never touched, so a
-  // window solved alone, then in a batch, then alone again runs the same arithmetic the first and the third time.
-  std::vector<std::unique_ptr<lvf::DevBuf<int4>>> band_work; std::vector<int> n_band_work, band_epoch;
-  bool orphaned = false;             // a member was destroyed before the batch: every later call fails with LVF_ERR_STATE
-};
-
-namespace lvf {
-
-void batch_orphan(lvf_problem_batch* b, lvf_problem* dying) {
-  b->orphaned = true;
-  for (lvf_problem* p : b->probs)
-    if (p != dying) p->batches.erase(std::remove(p->batches.begin(), p->batches.end(), b), p->batches.end());
-  b->probs.clear();
-}
-
-template <typename T>
-static int upload_table(DevBuf<T>& dst, const std::vector<T>& src, hipStream_t q) {
-  LVF_TRY(dst.ensure(src.size()));
-  // pageable source: the runtime stages the copy before returning, so `src` may go out of scope
-  if (!src.empty()) LVF_HIP(hipMemcpyAsync(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, q));
-  return LVF_OK;
-}
-
-static int batch_build_tables(lvf_problem_batch* b, double huber) {
-  hipStream_t q = b->ctx->stream;
-  const int W = b->W;
-  bool all = true;
-  static const int batch_rows = [] { const char* e = std::getenv("LVF_BATCH_BAND_ROWS"); return e ? std::atoi(e) : 128; }();
-  if (b->orphaned) { set_error("lvf_problem_batch: a member problem was destroyed before the batch"); return LVF_ERR_STATE; }
-  for (size_t w = 0; w < b->probs.size(); ++w)
-    if (b->probs[w]->ov) { set_error("lvf_problem_batch: window %d has an overridden reduced system (lvf_problem_debug_override_reduced): the batched chains have no such tap", (int)w); return LVF_ERR_STATE; }
-  for (lvf_problem* p : b->probs) {
-    if (chain_stale(p)) LVF_TRY(build_chain(p));
-    LVF_TRY(await_band_work(p));             // (the member's own list: its count shares the pinned slot build_band_work reads below)
-    all = all && p->chain->batchable;
-  }
-  b->tables = all;
-  if (!all) return LVF_OK;
-  const bool wide = W > 1 && batch_rows != 64;
-  if (wide) {
-    b->band_work.resize(W); b->n_band_work.resize(W, 0); b->band_epoch.resize(W, -1);
-    for (int w = 0; w < W; ++w) {
-      lvf_problem* p = b->probs[w];
-      if (!b->band_work[w]) b->band_work[w].reset(new DevBuf<int4>());
-      if (b->band_epoch[w] == p->band_epoch) continue;
-      LVF_TRY(build_band_work(p, batch_rows, *b->band_work[w], &b->n_band_work[w]));
-      b->band_epoch[w] = p->band_epoch;
-    }
-  }
-  std::vector<ImuArgs> il(W), ic(W); std::vector<LinArgs> li(W); std::vector<TfReduceArgs> rd(W); std::vector<PrepArgs> pr(W); std::vector<SchurSp0Args> ss(W);
-  std::vector<CholArgs> ch(W); std::vector<BackArgs> bk(W); std::vector<TailArgs> tl(W); std::vector<CostArgs> co(W); std::vector<DecideArgs> de(W); std::vector<ZeroList> zl(W);
-  b->max_levels = 0; b->max_nb = 0;
-  b->g_red = 0; b->lds_red = 0; b->lds_prep = 0; b->first_own_level = kSpMaxLevels;
-  b->g_imu_lin = b->g_imu_cost = b->g_lin = b->g_prep = b->g_ssp0 = b->g_tail = b->g_cost = 0; b->lds_ssp0 = b->lds_back = b->lds_tail = b->lds_lin = 0;
-  for (int w = 0; w < W; ++w) {
-    const lvf_problem* p = b->probs[w];
-    const Chain& c = *p->chain;
-    il[w] = c.imu_lin; ic[w] = c.imu_cost; li[w] = c.lin; li[w].huber = huber; rd[w] = c.red; if (!p->compact) rd[w].nblocks = 0;
-    b->g_red = std::max(b->g_red, rd[w].nblocks); pr[w] = c.early ? c.prep_early : c.prep; ss[w] = c.ssp0; ch[w] = c.chol; bk[w] = c.back; tl[w] = c.tail;
-    if (wide) {                                          // the batch's own slice width and work list (the member's chain keeps its own)
-      SchurSp0Args& a = ss[w];
-      a.rows = band_rows_clamped(batch_rows); a.n_slices = (p->n_lm + a.rows - 1) / a.rows;
-      a.work = b->band_work[w]->p; a.n_work = b->n_band_work[w];
-      a.nblocks = a.n_work + a.sp.nblocks + a.sp_b.nblocks + a.sp_c.nblocks;
-    }
-    if (rd[w].nblocks > rd[w].own_blocks) b->lds_red = std::max(b->lds_red, c.red_lds);
-    if (pr[w].nblocks > pr[w].own_blocks) b->lds_prep = std::max(b->lds_prep, c.prep_lds);
-    b->first_own_level = std::min(b->first_own_level, c.first_own_level);
-    co[w] = c.cost; co[w].huber = huber; de[w] = c.dec; zl[w] = c.zero;
-    if (W >= 4) {                                        // fatter cost / zeroing workgroups in a batch (see cost_visual_value)
-      CostArgs& k = co[w];
-      const int t = 4, per = kT * t;
-      k.tiles = t;
-      k.a.g_tc = (k.a.n_tc + per - 1) / per; k.a.g_tf = (k.a.n_tf + per - 1) / per;
-      k.nblocks = k.g_imu + k.a.g_tc + k.a.g_tf + (k.a.n_po + per - 1) / per;
-      k.zero_wgs = std::min(k.zero_wgs, 48);
-      TailArgs& ta = tl[w];                              // ... and fewer landmark workgroups per window (64 windows: 203 -> 170 us with 256 instead of 640)
-      const int g2 = std::min(ta.g_lm, 256);
-      ta.nblocks -= ta.g_lm - g2; ta.g_lm = g2;
-    }
-    b->g_imu_lin = std::max(b->g_imu_lin, c.imu_lin.n + c.imu_lin.zero_wgs); b->g_imu_cost = std::max(b->g_imu_cost, c.imu_cost.n + c.imu_cost.zero_wgs);
-    b->g_lin = std::max(b->g_lin, c.lin.nblocks); b->lds_lin = std::max(b->lds_lin, c.lin_lds); b->g_prep = std::max(b->g_prep, pr[w].nblocks); b->g_ssp0 = std::max(b->g_ssp0, ss[w].nblocks);
-    b->lds_ssp0 = std::max(b->lds_ssp0, c.ssp0_lds); b->lds_back = std::max(b->lds_back, c.back_lds); b->g_tail = std::max(b->g_tail, tl[w].nblocks);
-    b->lds_tail = std::max(b->lds_tail, c.tail_lds); b->g_cost = std::max(b->g_cost, co[w].nblocks + co[w].zero_wgs);
-    b->max_levels = std::max(b->max_levels, c.n_levels); b->max_nb = std::max(b->max_nb, p->nb);
-  }
-  LVF_TRY(upload_table(b->imu_lin, il, q)); LVF_TRY(upload_table(b->imu_cost, ic, q)); LVF_TRY(upload_table(b->lin, li, q)); LVF_TRY(upload_table(b->red, rd, q)); LVF_TRY(upload_table(b->prep, pr, q));
-  LVF_TRY(upload_table(b->ssp0, ss, q)); LVF_TRY(upload_table(b->chol, ch, q)); LVF_TRY(upload_table(b->back, bk, q)); LVF_TRY(upload_table(b->tail, tl, q));
-  LVF_TRY(upload_table(b->cost, co, q)); LVF_TRY(upload_table(b->dec, de, q)); LVF_TRY(upload_table(b->zero, zl, q));
-  for (int lv = b->first_own_level; lv < b->max_levels; ++lv) {        // (the levels below ride in the launches ahead: Chain::first_own_level)
-    std::vector<SpArgs> sp(W);
-    b->g_sp[lv] = 0; b->lds_sp[lv] = 0;
-    for (int w = 0; w < W; ++w) {
-      const Chain& c = *b->probs[w]->chain;
-      if (lv >= c.first_own_level && lv < c.n_levels) { sp[w] = c.sp[lv]; b->g_sp[lv] = std::max(b->g_sp[lv], c.sp[lv].nblocks); b->lds_sp[lv] = std::max(b->lds_sp[lv], c.sp_lds[lv]); }
-      else { sp[w] = SpArgs{}; sp[w].nblocks = 0; }
-    }
-    LVF_TRY(upload_table(b->sp[lv], sp, q));
-  }
-  b->huber_built = huber;
-  return LVF_OK;
-}
-
-// one LM iteration of every window of the batch; nothing is waited for
-static int batch_enqueue_iteration(lvf_problem_batch* b, bool end_zero) {
-  hipStream_t q = b->ctx->stream;
-  if (!b->tables) {
-    for (lvf_problem* p : b->probs) LVF_TRY(enqueue_iteration(p, end_zero));
-    return LVF_OK;
-  }
-  const unsigned W = (unsigned)b->W;
-  bool clean = true;
-  for (lvf_problem* p : b->probs) { clean = clean && p->accum_clean; p->accum_clean = false; }
-  if (!clean) hipLaunchKernelGGL(k_zero_table, dim3(512, W), dim3(kT), 0, q, b->zero.p);
-  // LVF_BATCH_TRANSPOSE (bit mask, default 127: all; measured 8 windows 20.7k -> 22.1k it/s, 32 windows 28.9k -> 29.9k): which of lin (1), tf_reduce (2), prepare (4), Schur (8), block steps (16), tail (32), cost (64) are launched with blockIdx.x = window
-  static const int tr = [] { const char* e = std::getenv("LVF_BATCH_TRANSPOSE"); return e ? std::atoi(e) : 127; }();
-  const bool fits_y = std::max(std::max(b->g_lin, b->g_red), std::max(b->g_prep, b->g_ssp0)) <= 65535;
-  if ((tr & 1) && fits_y) hipLaunchKernelGGL(k_lin_visual_bt, dim3(W, b->g_lin), dim3(kT), b->lds_lin, q, b->lin.p);
-  else hipLaunchKernelGGL(k_lin_visual_b, dim3(b->g_lin, W), dim3(kT), b->lds_lin, q, b->lin.p);
-  if (b->g_red > 0) {
-    if ((tr & 2) && fits_y) hipLaunchKernelGGL(k_tf_reduce_bt, dim3(W, b->g_red), dim3(kT), b->lds_red, q, b->red.p);
-    else hipLaunchKernelGGL(k_tf_reduce_b, dim3(b->g_red, W), dim3(kT), b->lds_red, q, b->red.p);
-  }
-  if ((tr & 4) && fits_y) hipLaunchKernelGGL(k_prepare_bt, dim3(W, b->g_prep), dim3(kT), b->lds_prep, q, b->prep.p);
-  else hipLaunchKernelGGL(k_prepare_b, dim3(b->g_prep, W), dim3(kT), b->lds_prep, q, b->prep.p);
-  if ((tr & 8) && fits_y) hipLaunchKernelGGL(k_schur_sp0_bt, dim3(W, b->g_ssp0), dim3(256), b->lds_ssp0, q, b->ssp0.p);
-  else hipLaunchKernelGGL(k_schur_sp0_b, dim3(b->g_ssp0, W), dim3(256), b->lds_ssp0, q, b->ssp0.p);
-  for (int lv = b->first_own_level; lv < b->max_levels; ++lv)
-    if (b->g_sp[lv] > 0) hipLaunchKernelGGL(k_sp_eliminate_b, dim3(b->g_sp[lv], W), dim3(256), b->lds_sp[lv], q, b->sp[lv].p);
-  for (int kb = 0; kb < b->max_nb; ++kb) {
-    if (tr & 16) hipLaunchKernelGGL(chol_subblock_on() ? k_chol_step_bt : k_chol_step_pp_bt, dim3(W, chol_step_grid(b->max_nb, kb)), dim3(kCT), 0, q, b->chol.p, kb);
-    else hipLaunchKernelGGL(chol_subblock_on() ? k_chol_step_b : k_chol_step_pp_b, dim3(chol_step_grid(b->max_nb, kb), W), dim3(kCT), 0, q, b->chol.p, kb);
-  }
-  hipLaunchKernelGGL(k_chol_backsolve_b, dim3(1, W), dim3(kBT), b->lds_back, q, b->back.p);
-  if ((tr & 32) && b->g_tail <= 65535) hipLaunchKernelGGL(k_step_tail_bt, dim3(W, b->g_tail), dim3(kT), b->lds_tail, q, b->tail.p);
-  else hipLaunchKernelGGL(k_step_tail_b, dim3(b->g_tail, W), dim3(kT), b->lds_tail, q, b->tail.p);
-  // (batchable windows always have visual blocks)
-  if ((tr & 64) && b->g_cost <= 65535) hipLaunchKernelGGL(k_cost_decide_bt, dim3(W, b->g_cost), dim3(kT), 0, q, b->cost.p, b->dec.p, end_zero ? 1 : 0);
-  else hipLaunchKernelGGL(k_cost_decide_b, dim3(b->g_cost, W), dim3(kT), 0, q, b->cost.p, b->dec.p, end_zero ? 1 : 0);
-  LVF_HIP(hipGetLastError());
-  for (lvf_problem* p : b->probs) { p->linearized = !end_zero; p->accum_clean = end_zero; }     // (batchable windows: the cost + decision launch clears them)
-  return LVF_OK;
-}
-
-}  // namespace lvf
-
-extern "C" {
-
-void lvf_solver_options_default(lvf_solver_options* o) {
-  if (!o) return;
-  o->max_num_iterations = 50; o->max_solver_time_in_seconds = 0.0; o->huber_a = 1.0;
-  o->initial_trust_region_radius = 1e4; o->function_tolerance = 1e-6; o->gradient_tolerance = 1e-10;
-  o->parameter_tolerance = 1e-8; o->min_relative_decrease = 1e-3;
-}
-
-int lvf_problem_create(lvf_ctx* ctx, lvf_state* st, lvf_batch* two_camera, lvf_batch* two_frame, lvf_batch* pose_only,
-                       lvf_batch* imu, lvf_problem** out) {
-  LVF_REQUIRE(ctx && st && out, "lvf_problem_create: null argument");
-  LVF_REQUIRE(st->ctx == ctx, "lvf_problem_create: state belongs to another context");
-  LVF_REQUIRE(!two_camera || two_camera->kind == LVF_K_TWO_CAMERA, "two_camera batch has the wrong kind");
-  LVF_REQUIRE(!two_frame || two_frame->kind == LVF_K_TWO_FRAME, "two_frame batch has the wrong kind");
-  LVF_REQUIRE(!pose_only || pose_only->kind == LVF_K_POSE_ONLY, "pose_only batch has the wrong kind");
-  LVF_REQUIRE(!imu || imu->kind == LVF_K_IMU, "imu batch has the wrong kind");
-  for (lvf_batch* b : {two_camera, two_frame, pose_only, imu})
-    if (b) {
-      LVF_REQUIRE(b->ctx == ctx, "batch belongs to another context");
-      LVF_REQUIRE(b->min_n_kf <= st->n_kf && b->min_n_lm <= st->n_lm, "batch indices exceed the state (n_kf=%d n_lm=%d)", st->n_kf, st->n_lm);
-    }
-  LVF_REQUIRE(st->n_kf > 0, "lvf_problem_create: empty window");
-  LVF_TRY(lvf::enter(ctx));
-  auto* p = new lvf_problem();
-  p->ctx = ctx; p->st = st; p->tc = two_camera; p->tf = two_frame; p->po = pose_only; p->imu = imu;
-  const int rc = problem_configure(p);
-  if (rc != LVF_OK) { delete p; return rc; }
-  *out = p;
-  return LVF_OK;
-}
-int lvf_problem_destroy(lvf_problem* p) { delete p; return LVF_OK; }
-
-int lvf_problem_set_pose_priors(lvf_problem* p, lvf_batch* pose_priors) {
-  LVF_REQUIRE(p, "lvf_problem_set_pose_priors: null problem");
-  if (pose_priors) {
-    LVF_REQUIRE(pose_priors->kind == LVF_K_POSE_PRIOR, "pose_priors batch has the wrong kind");
-    LVF_REQUIRE(pose_priors->ctx == p->ctx, "batch belongs to another context");
-    LVF_REQUIRE(pose_priors->min_n_kf <= p->n_kf, "pose-prior batch references keyframe %d but the window has %d", pose_priors->min_n_kf - 1, p->n_kf);
-  }
-  p->prior = pose_priors;
-  p->linearized = false;
-  p->chain_ready = false;
-  return LVF_OK;
-}
-
-int lvf_problem_set_vbb_constant(lvf_problem* p, int kf, int v_constant, int ba_constant, int bg_constant) {
-  LVF_REQUIRE(p, "null problem");
-  LVF_REQUIRE(kf >= 0 && kf < p->n_kf, "keyframe %d out of range", kf);
-  p->pose_const_h[kf] = (uint8_t)((p->pose_const_h[kf] & 1) | (v_constant ? 2 : 0) | (ba_constant ? 4 : 0) | (bg_constant ? 8 : 0));
-  LVF_HIP(hipMemcpyAsync(p->pose_const.p, p->pose_const_h.data(), p->n_kf, hipMemcpyHostToDevice, p->ctx->stream));
-  LVF_HIP(hipStreamSynchronize(p->ctx->stream));
-  return LVF_OK;
-}
-
-int lvf_problem_set_pose_constant(lvf_problem* p, int kf, int is_constant) {
-  LVF_REQUIRE(p, "null problem");
-  LVF_REQUIRE(kf >= 0 && kf < p->n_kf, "keyframe %d out of range", kf);
-  p->pose_const_h[kf] = (uint8_t)((p->pose_const_h[kf] & ~1) | (is_constant ? 1 : 0));
-  LVF_HIP(hipMemcpyAsync(p->pose_const.p, p->pose_const_h.data(), p->n_kf, hipMemcpyHostToDevice, p->ctx->stream));
-  LVF_HIP(hipStreamSynchronize(p->ctx->stream));
-  return LVF_OK;
-}
-
-int lvf_problem_cost(lvf_problem* p, const lvf_solver_options* o, double* cost) {
-  LVF_REQUIRE(p && o && cost, "lvf_problem_cost: null argument");
-  LVF_TRY(lvf::enter(p->ctx));
-  hipStream_t q = p->ctx->stream;
-  LVF_HIP(hipMemsetAsync(p->scal.p, 0, SC_N * 8, q));
-  LVF_TRY(enqueue_cost(p, state_ptrs(p->st), p->st, o->huber_a, p->scal.p + SC_COST));
-  double hc[kStripes];
-  LVF_HIP(hipMemcpyAsync(hc, p->scal.p + SC_COST, sizeof(hc), hipMemcpyDeviceToHost, q));
-  // the stripes go back to zero: a following linearisation that trusts `accum_clean` (after a device-loop solve nothing else clears
-  // SC_COST) adds its cost into them — solve -> cost -> solve would otherwise start from a doubled cost_before
-  LVF_HIP(hipMemsetAsync(p->scal.p + SC_COST, 0, kStripes * 8, q));
-  LVF_HIP(hipStreamSynchronize(q));
-  *cost = stripe_sum(hc, 0);
-  return LVF_OK;
-}
-
-// Problem::Evaluate's gradient: J^T r with the loss function's Corrector applied and pose blocks in tangent coordinates, at the current
-// state — exactly what the linearisation accumulates.  gc [15 n_kf] in the reduced-system order (6 x n_kf pose tangents | 9 x n_kf (v, ba, bg)),
-// gl [n_lm] (may be NULL) the inverse-depth entries.
-int lvf_problem_stage_count(void) { return ST_N; }
-const char* lvf_problem_stage_name(int stage) { return stage >= 0 && stage < ST_N ? kStageNames[stage] : ""; }
-
-// `reps` LM iterations from the problem's current state (they ARE iterations: accepted steps move the state), HIP events on the
-// library's stream between the stages; us[k] = average duration of stage k, launches[k] = kernel launches it consists of.
-int lvf_problem_stage_times2(lvf_problem* p, const lvf_solver_options* o, double radius, int reps, double* us, double* spans_us, int* launches) {
-  LVF_REQUIRE(p && o && us && reps > 0, "lvf_problem_stage_times: bad argument");
-  LVF_TRY(lvf::enter(p->ctx));
-  hipStream_t q = p->ctx->stream;
-  if (!p->clk) {
-    p->clk = new StageClock();
-    for (auto& r : p->clk->ev) for (auto& e : r) LVF_HIP(hipEventCreate(&e));
-    for (auto& r : p->clk->kstart) for (auto& e : r) LVF_HIP(hipEventCreate(&e));
-    for (auto& r : p->clk->kstop) for (auto& e : r) LVF_HIP(hipEventCreate(&e));
-    p->clk->kernel_events = true;
-  }
-  StageClock& k = *p->clk;
-  for (int i = 0; i < ST_N; ++i) { us[i] = 0.0; k.launches[i] = 0; }
-  std::vector<double> span(ST_N, 0.0), kern(ST_N, 0.0);
-  std::vector<int> kcount(ST_N, 0);
-  reps = std::min(reps, kClockReps);
-  LmCtl c;
-  ctl_from_options(o, radius, 2.0, reps + 2, false, &c);
-  p->huber = o->huber_a;
-  LVF_TRY(upload_ctl(p, c));
-  // the device loop's chain: with the fused chain every timed iteration starts at k_tf_reduce and ends with the candidate pass
-  const bool fz = p->chain->fused_ok && !p->no_chain;
-  if (fz) LVF_TRY(ensure_acc1(p));
-  LVF_TRY(enqueue_iteration(p, true, fz ? kFusedOn | kFusedTail : 0));             // (un-timed: the timed iterations queue up behind it)
-  int nk = 0;
-  for (int r = 0; r < reps; ++r) {
-    k.on = true; k.rep = r; k.nk = 0;
-    const int rc = enqueue_iteration(p, true, fz ? kFusedOn | kFusedNoLin | kFusedTail : 0);
-    k.on = false;
-    nk = k.nk;
-    LVF_TRY(rc);
-  }
-  if (fz) LVF_TRY(enqueue_iteration(p, true, kFusedOn | kFusedNoLin));          // (un-timed: the plain cost pass leaves both accumulator sets clean)
-  LVF_HIP(hipStreamSynchronize(q));
-  for (int r = 0; r < reps; ++r) {
-    for (int i = 0; i < ST_N; ++i) {
-      if (k.launches[i] == 0) continue;
-      int prev = i;                                   // the event after the closest earlier stage that launched something (or event 0)
-      while (prev > 0 && k.launches[prev - 1] == 0) --prev;
-      float ms = 0.f;
-      LVF_HIP(hipEventElapsedTime(&ms, k.ev[r][prev], k.ev[r][i + 1]));
-      span[i] += 1e3 * (double)ms / reps;
-    }
-    for (int j = 0; j < nk; ++j) {                    // the kernels' own durations (dispatch timestamps)
-      float ms = 0.f;
-      LVF_HIP(hipEventElapsedTime(&ms, k.kstart[r][j], k.kstop[r][j]));
-      kern[k.kstage[j]] += 1e3 * (double)ms / reps;
-      if (r == 0) kcount[k.kstage[j]] += 1;
-    }
-  }
-  // a stage whose launches all carried their own events reports the sum of the kernel durations; others (generic paths: stand-alone IMU /
-  // prior passes) keep the between-stage span
-  for (int i = 0; i < ST_N; ++i) us[i] = (k.launches[i] > 0 && kcount[i] == k.launches[i]) ? kern[i] : span[i];
-  if (spans_us) for (int i = 0; i < ST_N; ++i) spans_us[i] = span[i];
-  if (launches) for (int i = 0; i < ST_N; ++i) launches[i] = k.launches[i];
-  return LVF_OK;
-}
-int lvf_problem_stage_times(lvf_problem* p, const lvf_solver_options* o, double radius, int reps, double* us, int* launches) {
-  return lvf_problem_stage_times2(p, o, radius, reps, us, nullptr, launches);
-}
-
-int lvf_problem_gradient(lvf_problem* p, const lvf_solver_options* o, double* gc, double* gl) {
-  LVF_REQUIRE(p && o && gc, "lvf_problem_gradient: null argument");
-  LVF_TRY(lvf::enter(p->ctx));
-  hipStream_t q = p->ctx->stream;
-  LVF_TRY(enqueue_linearize(p, o->huber_a, false));
-  const double* gr = p->gr.p;
-  if (gl && p->n_lm && p->compact) {
-    // atomic-free linearisation: a landmark's gradient entry is completed from its slot records by k_prepare (grt = gr + the slots)
-    LmCtl c;
-    ctl_from_options(o, o->initial_trust_region_radius, 2.0, 1, false, &c);
-    LVF_TRY(upload_ctl(p, c));
-    PrepArgs pa = p->chain->prep;
-    pa.radius = &p->ctl.p->radius; pa.scal = nullptr; pa.done = nullptr;
-    hipLaunchKernelGGL(k_prepare, dim3(pa.nblocks), dim3(kT), 0, q, pa);
-    LVF_HIP(hipGetLastError());
-    gr = p->grt.p;
-  }
-  LVF_HIP(hipMemcpyAsync(gc, p->gc.p, (size_t)p->d * 8, hipMemcpyDeviceToHost, q));
-  if (gl && p->n_lm) LVF_HIP(hipMemcpyAsync(gl, gr, (size_t)p->n_lm * 8, hipMemcpyDeviceToHost, q));
-  LVF_HIP(hipStreamSynchronize(q));
-  return LVF_OK;
-}
-
-int lvf_problem_lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* radius, double* decrease_factor,
-                             double* cost_before, double* cost_after, int* accepted) {
-  LVF_REQUIRE(p && o && radius && decrease_factor, "lvf_problem_lm_iteration: null argument");
-  LVF_REQUIRE(*radius > 0.0 && *decrease_factor > 0.0, "radius and decrease_factor must be positive");
-  LVF_TRY(lvf::enter(p->ctx));
-  IterOut it;
-  LVF_TRY(lm_iteration(p, o, radius, decrease_factor, &it));
-  if (cost_before) *cost_before = it.cost_before;
-  if (cost_after) *cost_after = it.cost_after;
-  if (accepted) *accepted = it.accepted ? 1 : 0;
-  return LVF_OK;
-}
-
-static void summary_from_ctl(const lvf_problem* p, const LmCtl& c, lvf_solver_summary* s) {
-  std::memset(s, 0, sizeof(*s));
-  s->num_residual_blocks = (p->tc ? p->tc->n : 0) + (p->tf ? p->tf->n : 0) + (p->po ? p->po->n : 0) + (p->imu ? p->imu->n : 0) + (p->prior ? p->prior->n : 0);
-  s->initial_cost = c.initial_cost; s->final_cost = c.cost; s->num_iterations = c.iter; s->num_successful_steps = c.successes; s->termination = c.termination;
-  s->num_unsuccessful_steps = c.rejected; s->termination_reason = c.why; s->hand_over_retries = p->handover_retries;
-}
-
-
-// The device LM loop: iterations are enqueued back to back, each closed on device (k_lm_decide); the host only watches a mirror of the
-// control block to stop enqueueing once the loop has finished (an iteration enqueued after the end costs ~20 empty launches).
-int lvf_problem_solve(lvf_problem* p, const lvf_solver_options* o, lvf_solver_summary* summary) { return lvf_problem_solve_then(p, o, summary, nullptr, nullptr); }
-
-// lvf_problem_solve with a caller's launches enqueued BEHIND the last iteration and AHEAD of the wait that ends the solve (`tail(user)`,
-// called once per pass of the hand-over retry loop, i.e. once in practice): the persistent window packs and copies its state back in
-// the same stream wait instead of a second one (window.hip).
-int lvf_problem_solve_then(lvf_problem* p, const lvf_solver_options* o, lvf_solver_summary* summary, int (*tail)(void*), void* user) {
-  LVF_REQUIRE(p && o && summary, "lvf_problem_solve: null argument");
-  LVF_TRY(lvf::enter(p->ctx));
-  LmCtl c;
-  ctl_from_options(o, o->initial_trust_region_radius, 2.0, o->max_num_iterations, true, &c);
-  p->huber = o->huber_a;
-  if (o->max_num_iterations <= 0) {          // nothing to iterate: report the cost at the start
-    double cost = 0.0;
-    LVF_TRY(lvf_problem_cost(p, o, &cost));
-    c.initial_cost = c.cost = cost;
-    summary_from_ctl(p, c, summary);
-    if (tail) LVF_TRY(tail(user));
-    return LVF_OK;
-  }
-  // a problem that lost its chained launches to a hand-over time-out gets them back after kUnchainedSolves solves (a time-out then simply sets it again)
-  constexpr int kUnchainedSolves = 32;
-  if (p->no_chain && ++p->unchained_solves > kUnchainedSolves && p->force_handover_timeouts == 0) { p->no_chain = false; p->unchained_solves = 0; p->chain_ready = false; }
-  LVF_TRY(upload_ctl(p, c));
-  const auto wall0 = std::chrono::steady_clock::now();
-  bool timed_out = false;
-  for (int first = 0;;) {
-    // the fused chain (Chain::fused_ok): the pass's first iteration linearises at the state as today, every later one starts from the
-    // linearisation the previous iteration's candidate pass made, and the last one enqueued for the solve ends with the plain cost pass (a
-    // re-run after a hand-over time-out takes today's chain: no_chain)
-    const bool fz = p->chain->fused_ok && !p->no_chain && !p->ov && o->max_num_iterations - first >= 2;
-    if (fz) LVF_TRY(ensure_acc1(p));
-    bool fused_tail = false;
-    for (int it = first; it < o->max_num_iterations; ++it) {
-      const int f = fz ? kFusedOn | (it > first ? kFusedNoLin : 0) | (it + 1 < o->max_num_iterations ? kFusedTail : 0) : 0;
-      LVF_TRY(enqueue_iteration(p, true, f));
-      fused_tail = (f & kFusedTail) != 0;
-      if (it >= first + 1) LVF_TRY(wait_for_iteration(p, it));          // iteration it-1 is closed; iteration `it` keeps the device busy meanwhile
-      if (p->rec->done) break;
-      if (o->max_solver_time_in_seconds > 0.0 &&
-          std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() >= o->max_solver_time_in_seconds) { timed_out = true; break; }
-    }
-    if (fused_tail) {
-      // the loop ended before the last iteration: the active set was not cleared by a plain cost pass — both sets are, here, with the cost stripes
-      const Chain& ch = *p->chain;
-      ZeroList z = ch.stand0;
-      for (int k = 0; k < ch.stand1.count && z.count < kZeroListMax; ++k) { z.p[z.count] = ch.stand1.p[k]; z.n[z.count] = ch.stand1.n[k]; z.tri[z.count] = ch.stand1.tri[k]; ++z.count; }
-      hipLaunchKernelGGL(k_zero_multi, dim3(512, z.count), dim3(kT), 0, p->ctx->stream, z);
-      LVF_HIP(hipGetLastError());
-      LVF_HIP(hipMemsetAsync(p->scal.p + SC_COST, 0, kStripes * 8, p->ctx->stream));
-      p->accum_clean = ch.stand0.count + ch.stand1.count <= kZeroListMax;
-    }
-    // the caller's launches ride behind the last iteration — unless the host already KNOWS this pass ended in a hand-over time-out (the mirror
-    // carries `why`): the state is not final then, the re-run's pass enqueues them.  (A time-out in the very last iteration enqueued is only
-    // seen after the wait: the tail then runs twice, the second time on the final state.)
-    const bool known_handover = p->rec->done && p->rec->why == LVF_WHY_HANDOVER && !p->no_chain;
-    if (tail && !known_handover) LVF_TRY(tail(user));
-    LVF_TRY(download_ctl(p, &c));
-    if (!handover_pending(p, c)) break;
-    LVF_TRY(rearm_after_handover(p, &c));     // a chained hand-over timed out: the loop goes on from the same point, un-chained
-    first = c.iter;
-  }
-  p->last_radius = c.last_radius;
-  p->step_ready = true; p->last_solved = c.solved;
-  summary_from_ctl(p, c, summary);
-  if (timed_out && !c.done) summary->termination_reason = LVF_WHY_TIME;
-  return LVF_OK;
-}
-
-int lvf_problem_reduced_dim(lvf_problem* p) { return p ? p->d : -1; }
-
-// the DAMPED reduced system of the last lm_iteration, rebuilt (the factorisation overwrote S): S [d x d] symmetric, rhs [d]
-int lvf_problem_download_reduced(lvf_problem* p, double* S, double* rhs) {
-  LVF_REQUIRE(p && S && rhs, "lvf_problem_download_reduced: null argument");
-  if (!p->linearized || !p->chain_ready) { set_error("no linearisation yet"); return LVF_ERR_STATE; }
-  LVF_TRY(lvf::enter(p->ctx));
-  hipStream_t q = p->ctx->stream;
-  const size_t nS = (size_t)p->ld * p->ld;
-  LVF_TRY(enqueue_reduced_system(p, &p->ctl.p->last_radius, false, false, nullptr));
-  std::vector<double> h(nS);
-  LVF_HIP(hipMemcpyAsync(h.data(), p->S.p, nS * 8, hipMemcpyDeviceToHost, q));
-  LVF_HIP(hipStreamSynchronize(q));
-  const int d = p->d, ld = p->ld;
-  const std::vector<int>& pm = p->perm_h;          // natural unknown -> S row
-  for (int i = 0; i < d; ++i)
-    for (int j = 0; j <= i; ++j) {
-      const double v = h[(size_t)std::max(pm[i], pm[j]) * ld + std::min(pm[i], pm[j])];
-      S[(size_t)i * d + j] = v; S[(size_t)j * d + i] = v;
-    }
-  for (int j = 0; j < d; ++j) rhs[j] = h[(size_t)p->aug * ld + pm[j]];
-  return LVF_OK;
-}
-
-// test tap (see lvf.h): the caller's reduced system replaces the assembled one in every iteration of this problem; both NULL clears it
-int lvf_problem_debug_override_reduced(lvf_problem* p, const double* S, const double* rhs) {
-  LVF_REQUIRE(p, "lvf_problem_debug_override_reduced: null problem");
-  LVF_REQUIRE((S == nullptr) == (rhs == nullptr), "lvf_problem_debug_override_reduced: S and rhs must both be given, or both be NULL (clear)");
-  LVF_TRY(lvf::enter(p->ctx));
-  hipStream_t q = p->ctx->stream;
-  if (!S) {
-    LVF_HIP(hipStreamSynchronize(q));          // (launches that read the copies may still be in flight)
-    p->ov.reset();
-    return LVF_OK;
-  }
-  LVF_REQUIRE(p->d > 0, "lvf_problem_debug_override_reduced: the problem has no unknowns");
-  std::unique_ptr<ReducedOverride> ov(new ReducedOverride());
-  ov->d = p->d;
-  LVF_TRY(ov->S.upload(S, (size_t)p->d * p->d, q));
-  LVF_TRY(ov->rhs.upload(rhs, (size_t)p->d, q));
-  LVF_HIP(hipStreamSynchronize(q));            // the caller's arrays are free from here on (and the previous copies are no longer read)
-  p->ov = std::move(ov);
-  return LVF_OK;
-}
-// the reduced step of the last iteration (natural order, the coordinates of the system: the chain solves the unscaled system, the Jacobi
-// scaling only enters the damping) and the raw SC_FAIL flag
-int lvf_problem_debug_download_step(lvf_problem* p, double* x, int* fail) {
-  LVF_REQUIRE(p && x && fail, "lvf_problem_debug_download_step: null argument");
-  if (!p->step_ready) { set_error("lvf_problem_debug_download_step: no iteration yet"); return LVF_ERR_STATE; }
-  LVF_TRY(lvf::enter(p->ctx));
-  hipStream_t q = p->ctx->stream;
-  LVF_HIP(hipMemcpyAsync(x, p->dxc.p, (size_t)p->d * 8, hipMemcpyDeviceToHost, q));
-  LVF_HIP(hipMemcpyAsync(fail, reinterpret_cast<const int*>(p->scal.p + SC_FAIL), sizeof(int), hipMemcpyDeviceToHost, q));
-  LVF_HIP(hipStreamSynchronize(q));
-  return LVF_OK;
-}
-int lvf_problem_debug_last_solved(lvf_problem* p) { return (p && p->step_ready) ? p->last_solved : -1; }
-// the layout the elimination plan gave the factorised matrix: block steps of the dense corner; per keyframe, whether its (v, ba, bg) block stayed there
-int lvf_problem_debug_plan(lvf_problem* p, int* nb, int* dense_kf) {
-  LVF_REQUIRE(p && nb, "lvf_problem_debug_plan: null argument");
-  if ((int)p->perm_h.size() < p->d || p->d != 15 * p->n_kf) { set_error("lvf_problem_debug_plan: no elimination plan yet"); return LVF_ERR_STATE; }
-  *nb = p->nb;
-  if (dense_kf) for (int k = 0; k < p->n_kf; ++k) dense_kf[k] = p->perm_h[(size_t)p->dp + 9 * k] >= p->off ? 1 : 0;
-  return LVF_OK;
-}
-int lvf_debug_landmark_window(void) { return 16 * kLmEPre; }
-void lvf_debug_fail_codes(int* sparse_base, int* handover_base) {
-  if (sparse_base) *sparse_base = kFailSparse;
-  if (handover_base) *handover_base = kFailHandover;
-}
-
-// ---- batch of windows
-int lvf_problem_batch_create(lvf_ctx* ctx, lvf_problem* const* problems, int n, lvf_problem_batch** out) {
-  LVF_REQUIRE(ctx && out && n >= 1 && problems, "lvf_problem_batch_create: bad arguments");
-  for (int i = 0; i < n; ++i) {
-    LVF_REQUIRE(problems[i], "lvf_problem_batch_create: problem %d is null", i);
-    LVF_REQUIRE(problems[i]->ctx == ctx, "lvf_problem_batch_create: problem %d belongs to another context", i);
-    for (int j = 0; j < i; ++j) LVF_REQUIRE(problems[j] != problems[i] && problems[j]->st != problems[i]->st, "lvf_problem_batch_create: windows %d and %d share state", j, i);
-  }
-  auto* b = new lvf_problem_batch();
-  b->ctx = ctx; b->W = n; b->probs.assign(problems, problems + n);
-  for (lvf_problem* p : b->probs) p->batches.push_back(b);
-  *out = b;
-  return LVF_OK;
-}
-// (members are only told that the batch is gone: nothing of theirs was changed by it)
-int lvf_problem_batch_destroy(lvf_problem_batch* b) {
-  if (b && !b->orphaned)
-    for (lvf_problem* p : b->probs) p->batches.erase(std::remove(p->batches.begin(), p->batches.end(), b), p->batches.end());
-  delete b;
-  return LVF_OK;
-}
-int lvf_problem_batch_size(const lvf_problem_batch* b) { return b ? b->W : -1; }
-// diagnostic (LVF_LM_HISTORY=1): {iteration, cost_before, cost_new, model, accepted, fail flag, radius, gradient max} of the passes of the last solve
-int lvf_problem_debug_history(lvf_problem* p, double* out512) {
-  LVF_REQUIRE(p && out512, "lvf_problem_debug_history: null argument");
-  if (!p->dbg_hist.p) { set_error("lvf_problem_debug_history: LVF_LM_HISTORY is not set"); return LVF_ERR_STATE; }
-  LVF_TRY(lvf::enter(p->ctx));
-  LVF_HIP(hipMemcpyAsync(out512, p->dbg_hist.p, 512 * 8, hipMemcpyDeviceToHost, p->ctx->stream));
-  LVF_HIP(hipStreamSynchronize(p->ctx->stream));
-  return LVF_OK;
-}
-// 1: the current chain runs the dense back substitution on the stored block products T_kj, 0: on S and Dinv (builds the chain if stale)
-int lvf_problem_debug_back_blocks(lvf_problem* p) {
-  if (!p || lvf::enter(p->ctx) != LVF_OK) return -1;
-  if (chain_stale(p) && build_chain(p) != LVF_OK) return -1;
-  return p->chain->back_blocks ? 1 : 0;
-}
-// 1: the current chain takes the sparse back substitution as a product with G, 0: it runs the sequential levels (builds the chain if stale)
-int lvf_problem_debug_back_product(lvf_problem* p) {
-  if (!p || lvf::enter(p->ctx) != LVF_OK) return -1;
-  if (chain_stale(p) && build_chain(p) != LVF_OK) return -1;
-  return p->chain->back_product ? 1 : 0;
-}
-// test hook (see lvf.h)
-int lvf_problem_debug_force_handover_timeout(lvf_problem* p, int n) {
-  LVF_REQUIRE(p && n >= 0, "lvf_problem_debug_force_handover_timeout: bad argument");
-  p->force_handover_timeouts = n; p->no_chain = false; p->chain_ready = false;
-  return LVF_OK;
-}
-int lvf_problem_batch_uses_tables(lvf_problem_batch* b, const lvf_solver_options* o) {
-  if (!b || !o || lvf::enter(b->ctx) != LVF_OK || batch_build_tables(b, o->huber_a) != LVF_OK) return -1;
-  return b->tables ? 1 : 0;
-}
-
-// one LM iteration of every window (no tolerance tests); all arrays have one entry per window
-int lvf_problem_batch_lm_iteration(lvf_problem_batch* b, const lvf_solver_options* o, double* radius, double* decrease_factor, double* cost_before,
-                                   double* cost_after, int* accepted) {
-  LVF_REQUIRE(b && o && radius && decrease_factor, "lvf_problem_batch_lm_iteration: null argument");
-  LVF_TRY(lvf::enter(b->ctx));
-  LVF_TRY(batch_build_tables(b, o->huber_a));
-  for (int w = 0; w < b->W; ++w) {
-    LVF_REQUIRE(radius[w] > 0.0 && decrease_factor[w] > 0.0, "radius and decrease_factor must be positive");
-    LmCtl c;
-    ctl_from_options(o, radius[w], decrease_factor[w], 1, false, &c);
-    b->probs[w]->huber = o->huber_a;
-    LVF_TRY(upload_ctl(b->probs[w], c));
-  }
-  LVF_TRY(batch_enqueue_iteration(b, false));
-  {
-    // windows whose chained hand-over timed out repeat the iteration un-chained (the others are done: their launches return at once)
-    bool again = false;
-    for (int w = 0; w < b->W; ++w) {
-      LmCtl c;
-      LVF_TRY(download_ctl(b->probs[w], &c));
-      if (handover_pending(b->probs[w], c)) { LVF_TRY(rearm_after_handover(b->probs[w], &c)); again = true; }
-    }
-    if (again) { LVF_TRY(batch_build_tables(b, o->huber_a)); LVF_TRY(batch_enqueue_iteration(b, false)); }
-  }
-  for (int w = 0; w < b->W; ++w) {
-    LmCtl c;
-    LVF_TRY(download_ctl(b->probs[w], &c));
-    b->probs[w]->last_radius = c.last_radius;
-    radius[w] = c.radius; decrease_factor[w] = c.decrease;
-    if (cost_before) cost_before[w] = c.cost_before;
-    if (cost_after) cost_after[w] = c.cost_after;
-    if (accepted) accepted[w] = c.accepted;
-  }
-  return LVF_OK;
-}
-
-int lvf_problem_batch_solve(lvf_problem_batch* b, const lvf_solver_options* o, lvf_solver_summary* summaries) {
-  LVF_REQUIRE(b && o && summaries, "lvf_problem_batch_solve: null argument");
-  LVF_TRY(lvf::enter(b->ctx));
-  LVF_TRY(batch_build_tables(b, o->huber_a));
-  if (o->max_num_iterations <= 0) {
-    for (int w = 0; w < b->W; ++w) LVF_TRY(lvf_problem_solve(b->probs[w], o, &summaries[w]));
-    return LVF_OK;
-  }
-  for (int w = 0; w < b->W; ++w) {
-    LmCtl c;
-    ctl_from_options(o, o->initial_trust_region_radius, 2.0, o->max_num_iterations, true, &c);
-    b->probs[w]->huber = o->huber_a;
-    LVF_TRY(upload_ctl(b->probs[w], c));
-  }
-  const auto wall0 = std::chrono::steady_clock::now();
-  std::vector<LmCtl> cs((size_t)b->W);
-  for (int round = 0;; ++round) {
-    // (after a hand-over retry the windows stand at different iteration counts: the wait is for "one more than when this pass started")
-    int base = o->max_num_iterations;
-    for (int w = 0; w < b->W; ++w) if (!b->probs[w]->rec->done) base = std::min(base, (int)b->probs[w]->rec->iter);
-    for (int it = base; it < o->max_num_iterations; ++it) {
-      LVF_TRY(batch_enqueue_iteration(b, true));
-      bool all_done = true;
-      for (int w = 0; w < b->W; ++w) {
-        if (it >= base + 1) LVF_TRY(wait_for_iteration(b->probs[w], it));
-        all_done = all_done && b->probs[w]->rec->done;
-      }
-      if (all_done) break;
-      if (o->max_solver_time_in_seconds > 0.0 &&
-          std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() >= o->max_solver_time_in_seconds) break;
-    }
-    bool again = false;
-    for (int w = 0; w < b->W; ++w) {
-      LVF_TRY(download_ctl(b->probs[w], &cs[w]));
-      if (handover_pending(b->probs[w], cs[w])) { LVF_TRY(rearm_after_handover(b->probs[w], &cs[w])); again = true; }
-    }
-    if (!again) break;
-    LVF_TRY(batch_build_tables(b, o->huber_a));        // the re-armed windows' chains changed shape
-  }
-  for (int w = 0; w < b->W; ++w) {
-    b->probs[w]->last_radius = cs[w].last_radius;
-    summary_from_ctl(b->probs[w], cs[w], &summaries[w]);
-  }
-  return LVF_OK;
-}
-
-}  // extern "C"
