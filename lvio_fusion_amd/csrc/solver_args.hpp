@@ -1,6 +1,6 @@
-// solver_args.hpp — what the kernels of the LM iteration (solver_kernels.hip) and its host side (solver_chain.hip, solver_plan.hip,
+// solver_args.hpp — what the kernels of the LM iteration (solver_kernels.hip, solver_assemble.hip, solver_chol.hip, solver_back.hip) and its host side (solver_chain.hip, solver_plan.hip,
 // solver_batch.hip, solver_api.hip) share: the problem object, every kernel argument block, the constants that size grids and LDS, and a
-// prototype of every kernel the host launches.  The kernels themselves, with their __launch_bounds__, are defined in solver_kernels.hip.
+// prototype of every kernel the host launches.  The kernels themselves, with their __launch_bounds__, are defined in those four units, each in exactly one.
 #pragma once
 #include <memory>
 #include <vector>
@@ -57,7 +57,7 @@ constexpr int kFailSparse = 100000, kFailHandover = 300000;
 // Test tap (lvf_problem_debug_override_reduced): a caller's reduced system S [d x d] / rhs [d] in the natural unknown order, written over the
 // assembled one before any elimination level starts
 struct ReducedOverride { int d = 0; DevBuf<double> S, rhs; };
-// (debug_taps.hip: the copy kernel lives in a translation unit of its own, so solver_kernels.hip's device code is what it is without the tap)
+// (debug_taps.hip: the copy kernel lives in a translation unit of its own, so the kernel units' device code is what it is without the tap)
 int launch_override_reduced(hipStream_t q, int d, int ld, int aug, const int* perm, const double* Sov, const double* rhs, double* S);
 }
 struct lvf_problem {
@@ -65,7 +65,7 @@ struct lvf_problem {
   lvf_state* st = nullptr;
   lvf_batch *tc = nullptr, *tf = nullptr, *po = nullptr, *imu = nullptr, *prior = nullptr;
   int n_kf = 0, n_lm = 0, d = 0, dp = 0, ldE = 0, dpad = 0, nb = 0;
-  // layout of the factorised matrix S (see "elimination order" in solver_kernels.hip): [sparse (v,ba,bg) blocks | dense (v,ba,bg) blocks | poses | rhs row | pad]
+  // layout of the factorised matrix S (see "elimination order" in solver_assemble.hip): [sparse (v,ba,bg) blocks | dense (v,ba,bg) blocks | poses | rhs row | pad]
   int ld = 0, off = 0, off_pose = 0, ndense = 0, aug = 0, sp_wstride = 0;
   lvf::SpLevels sp_levels{};
   std::vector<int> sp_tiles, sp_shmem;          // per level: workgroups per node, dynamic LDS bytes
@@ -332,7 +332,9 @@ constexpr int kDT = 256;
 struct FusedArgs { LinArgs lin; DecideArgs dec; GP<double> cost_new; int nblocks; GP<const int> done; ZeroList zero; int zero_wgs; };
 
 // ------------------------------------------------------------------------------------------------ kernels launched from the host side
-// (prototypes only: the definitions in solver_kernels.hip carry the launch bounds and occupancy attributes)
+// (prototypes only: the definitions carry the launch bounds and occupancy attributes — k_tf_reduce*, k_prepare*, the Schur, layout and sparse-level
+// kernels in solver_assemble.hip, k_chol_step* in solver_chol.hip, k_chol_backsolve*, k_step_tail* and k_backsolve_tail in solver_back.hip, the
+// linearisation, cost and decision kernels in solver_kernels.hip)
 __global__ void k_zero_multi(ZeroList z);
 __global__ void k_zero_multi_ranges(ZeroList z, int n_lm, int* __restrict__ kmin, int* __restrict__ kmax);
 __global__ void k_zero_table(const ZeroList* __restrict__ t);

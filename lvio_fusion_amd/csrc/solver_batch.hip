@@ -62,7 +62,7 @@ static int batch_build_tables(lvf_problem_batch* b, double huber) {
   hipStream_t q = b->ctx->stream;
   const int W = b->W;
   bool all = true;
-  static const int batch_rows = [] { const char* e = std::getenv("LVF_BATCH_BAND_ROWS"); return e ? std::atoi(e) : 128; }();
+  const int batch_rows = solver_env().batch_band_rows;
   if (b->orphaned) { set_error("lvf_problem_batch: a member problem was destroyed before the batch"); return LVF_ERR_STATE; }
   for (size_t w = 0; w < b->probs.size(); ++w)
     if (b->probs[w]->ov) { set_error("lvf_problem_batch: window %d has an overridden reduced system (lvf_problem_debug_override_reduced): the batched chains have no such tap", (int)w); return LVF_ERR_STATE; }
@@ -150,7 +150,7 @@ static int batch_enqueue_iteration(lvf_problem_batch* b, bool end_zero) {
   for (lvf_problem* p : b->probs) { clean = clean && p->accum_clean; p->accum_clean = false; }
   if (!clean) hipLaunchKernelGGL(k_zero_table, dim3(512, W), dim3(kT), 0, q, b->zero.p);
   // LVF_BATCH_TRANSPOSE (bit mask, default 127: all; measured 8 windows 20.7k -> 22.1k it/s, 32 windows 28.9k -> 29.9k): which of lin (1), tf_reduce (2), prepare (4), Schur (8), block steps (16), tail (32), cost (64) are launched with blockIdx.x = window
-  static const int tr = [] { const char* e = std::getenv("LVF_BATCH_TRANSPOSE"); return e ? std::atoi(e) : 127; }();
+  const int tr = solver_env().batch_transpose;
   const bool fits_y = std::max(std::max(b->g_lin, b->g_red), std::max(b->g_prep, b->g_ssp0)) <= 65535;
   if ((tr & 1) && fits_y) hipLaunchKernelGGL(k_lin_visual_bt, dim3(W, b->g_lin), dim3(kT), b->lds_lin, q, b->lin.p);
   else hipLaunchKernelGGL(k_lin_visual_b, dim3(b->g_lin, W), dim3(kT), b->lds_lin, q, b->lin.p);
@@ -165,8 +165,8 @@ static int batch_enqueue_iteration(lvf_problem_batch* b, bool end_zero) {
   for (int lv = b->first_own_level; lv < b->max_levels; ++lv)
     if (b->g_sp[lv] > 0) hipLaunchKernelGGL(k_sp_eliminate_b, dim3(b->g_sp[lv], W), dim3(256), b->lds_sp[lv], q, b->sp[lv].p);
   for (int kb = 0; kb < b->max_nb; ++kb) {
-    if (tr & 16) hipLaunchKernelGGL(chol_subblock_on() ? k_chol_step_bt : k_chol_step_pp_bt, dim3(W, chol_step_grid(b->max_nb, kb)), dim3(kCT), 0, q, b->chol.p, kb);
-    else hipLaunchKernelGGL(chol_subblock_on() ? k_chol_step_b : k_chol_step_pp_b, dim3(chol_step_grid(b->max_nb, kb), W), dim3(kCT), 0, q, b->chol.p, kb);
+    if (tr & 16) hipLaunchKernelGGL(solver_env().chol_subblock ? k_chol_step_bt : k_chol_step_pp_bt, dim3(W, chol_step_grid(b->max_nb, kb)), dim3(kCT), 0, q, b->chol.p, kb);
+    else hipLaunchKernelGGL(solver_env().chol_subblock ? k_chol_step_b : k_chol_step_pp_b, dim3(chol_step_grid(b->max_nb, kb), W), dim3(kCT), 0, q, b->chol.p, kb);
   }
   hipLaunchKernelGGL(k_chol_backsolve_b, dim3(1, W), dim3(kBT), b->lds_back, q, b->back.p);
   if ((tr & 32) && b->g_tail <= 65535) hipLaunchKernelGGL(k_step_tail_bt, dim3(W, b->g_tail), dim3(kT), b->lds_tail, q, b->tail.p);

@@ -1,6 +1,7 @@
 // solver_chain.hip — the host side of one window's LM iteration: the argument blocks of the chain (build_chain), the launches of an
 // iteration (enqueue_linearize, enqueue_reduced_system, enqueue_iteration), the stage clock, and the LM driver around the device-resident
-// control block.  Everything executed per enqueued iteration is in this file; the kernels are in solver_kernels.hip.
+// control block.  Everything executed per enqueued iteration is in this file; the kernels are in solver_kernels.hip,
+// solver_assemble.hip, solver_chol.hip and solver_back.hip.
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <chrono>
@@ -10,9 +11,6 @@
 #include "solver_host.hpp"
 
 namespace lvf {
-
-// which sweep the block steps of the dense Cholesky run (solver_kernels.hip: k_chol_step* / k_chol_step_pp*)
-bool chol_subblock_on() { static const bool on = [] { const char* e = std::getenv("LVF_CHOL_SUBBLOCK"); return !(e && e[0] == '0'); }(); return on; }
 
 static void fill_cost_visual(const lvf_problem* p, CostVisual& a) {
   a = CostVisual{};
@@ -120,9 +118,7 @@ static bool schur_merged(const lvf_problem* p) { return p->n_lm && p->band_ready
 // hand-overs are allowed at all (a problem whose hand-over timed out keeps its launches apart: lvf_problem::no_chain); its flag lives in the
 // arrival-counter block, which is then cleared with the accumulators whether or not sparse levels are chained
 static bool back_tail_wanted(const lvf_problem* p) {
-  static const bool bt_merge_on = [] { const char* e = std::getenv("LVF_BACK_TAIL_MERGE"); return !(e && e[0] == '0'); }();
-  static const bool bt_chain_on = [] { const char* e = std::getenv("LVF_CHAIN_LEVELS"); return !(e && std::atoi(e) <= 0); }();
-  return bt_merge_on && bt_chain_on && !p->no_chain && p->n_lm > 0;
+  return solver_env().back_tail_merge && solver_env().chain_levels > 0 && !p->no_chain && p->n_lm > 0;
 }
 // the candidate state x + dx as the kernels read it
 static StateP candidate_ptrs(const lvf_problem* p) { return StateP{p->poses2.p, p->vel2.p, p->ba2.p, p->bg2.p, p->invd2.p, p->st->w_visual.p}; }
@@ -133,7 +129,7 @@ static StateP candidate_ptrs(const lvf_problem* p) { return StateP{p->poses2.p, 
 static int chain_zero_lists(lvf_problem* p, Chain& c) {
   const bool bt_wanted = back_tail_wanted(p);
   int k = 0;
-  static const bool tri_on = [] { const char* e = std::getenv("LVF_ZERO_TRI"); return !(e && e[0] == '0'); }();
+  const bool tri_on = solver_env().zero_tri;
   bool overflow = false;
   auto add = [&](double* ptr, size_t n, int tri = 0) {
     if (!(ptr && n)) return;
@@ -177,7 +173,7 @@ static void chain_linearize_args(lvf_problem* p, Chain& c) {
       for (int k = 0; k < 8; ++k) a.imu_J.j[k] = p->imu->jac[k].p;
       a.imu = ImuEvalArgs{p->imu->n, p->imu->pre.p, p->imu->sqrt_info.p, p->imu->idx_a.p, p->imu->idx_b.p};
     }
-    static const int staged_on = [] { const char* e = std::getenv("LVF_STAGED"); return (e && e[0] == '0') ? 0 : 1; }();
+    const int staged_on = solver_env().staged ? 1 : 0;
     a.cp = TfCompact{0, nullptr, nullptr, nullptr, nullptr, staged_on};
     if (p->compact) {
       a.cp = TfCompact{1, p->tf_slot.p, p->slotB.p, p->slabP.p, p->slabQ.p, staged_on};
@@ -226,9 +222,9 @@ static void chain_sparse_levels(lvf_problem* p, Chain& c) {
     a.nodes = p->sp_nodes.p; a.first = p->sp_levels.first[lv]; a.tiles = p->sp_tiles[lv]; a.rows = p->sp_rows.p; a.S = p->S.p; a.ld = p->ld; a.W = p->sp_W.p;
     a.wstride = p->sp_wstride; a.Lout = p->sp_L.p; a.fail = fail; a.nblocks = p->sp_levels.count[lv] * p->sp_tiles[lv]; a.done = done;
     // (0.5 ms at 100 MHz before a chained level gives up on the level below — a hand-over normally takes microseconds, and a retry costs one iteration of 0.2 ms: round 4 waited 2 ms, ten iterations of latency on a shared GPU; LVF_CHAIN_TIMEOUT_US overrides; LVF_CHAIN_FENCE=0: relaxed hand-over, A/B only)
-    static const unsigned chain_timeout = [] { const char* e = std::getenv("LVF_CHAIN_TIMEOUT_US"); return e ? (unsigned)std::max(1, std::atoi(e)) * 100u : 50000u; }();
-    static const int chain_fenced = [] { const char* e = std::getenv("LVF_CHAIN_FENCE"); return (e && e[0] == '0') ? 0 : 1; }();
-    a.src = c.early ? SpSrc{p->B.p, p->dpad, p->dp, p->gc.p, radius, p->sp_rows_nat.p, nullptr, 0, nullptr, chain_fenced, chain_timeout, p->off, std::getenv("LVF_CHAIN_RMW_READ") ? 1 : 0, nullptr, lv == 0 ? 1 : 0}
+    const unsigned chain_timeout = solver_env().chain_timeout_ticks;
+    const int chain_fenced = solver_env().chain_fence != 0 ? 1 : 0;
+    a.src = c.early ? SpSrc{p->B.p, p->dpad, p->dp, p->gc.p, radius, p->sp_rows_nat.p, nullptr, 0, nullptr, chain_fenced, chain_timeout, p->off, solver_env().chain_rmw_read ? 1 : 0, nullptr, lv == 0 ? 1 : 0}
                     : SpSrc{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, chain_fenced, chain_timeout, p->off, 0, nullptr, 0};
     a.src.jac = jac;
     c.sp_lds[lv] = p->sp_shmem[lv];
@@ -243,10 +239,8 @@ static void chain_sparse_levels(lvf_problem* p, Chain& c) {
     // k_tf_reduce's launch costs ~0 us, in k_prepare's ~2 us, a launch of its own 7.6 us.  So the LAST three levels go to the Schur launch
     // and only what is left over rides in the two launches ahead (16 / 20 keyframes, three levels: 0.111 / 0.125 -> 0.098 / 0.118 ms
     // with the chain alone, 0.103 / 0.123 with riders in front of it).  LVF_RIDE_TF / LVF_RIDE_PREP = 0 | 1 override, LVF_CHAIN_LEVELS = 0..2.
-    static const int ride_tf_env = [] { const char* e = std::getenv("LVF_RIDE_TF"); return e ? std::atoi(e) : -1; }();
-    static const int ride_prep_env = [] { const char* e = std::getenv("LVF_RIDE_PREP"); return e ? std::atoi(e) : -1; }();
-    static const int chain_n_env = [] { const char* e = std::getenv("LVF_CHAIN_LEVELS"); return e ? std::max(0, std::min(2, std::atoi(e))) : 2; }();
-    const int chain_n = p->no_chain ? 0 : chain_n_env;      // (a hand-over that timed out once: every level in a launch of its own from then on)
+    const int ride_tf_env = solver_env().ride_tf, ride_prep_env = solver_env().ride_prep;
+    const int chain_n = p->no_chain ? 0 : solver_env().chain_levels;      // (a hand-over that timed out once: every level in a launch of its own from then on)
     const int excess = std::max(0, c.n_levels - (1 + chain_n));
     const bool ride_tf = ride_tf_env >= 0 ? ride_tf_env != 0 : (p->compact && excess >= 1);
     const bool ride_prep = ride_prep_env >= 0 ? ride_prep_env != 0 : (excess >= 2 || (excess >= 1 && !(ride_tf && p->compact)));
@@ -305,8 +299,7 @@ static int chain_solve_args(lvf_problem* p, Chain& c) {
   {
     TailArgs& a = c.tail;
     // (640 workgroups take the 10 000 landmarks of the BASELINE window in one pass of 16 per workgroup; measured 1-2 % of an iteration over a cap of 256)
-    static const int tail_cap = [] { const char* e = std::getenv("LVF_TAIL_WGS"); return e ? std::atoi(e) : 640; }();
-    a.g_lm = p->n_lm ? std::min(tail_cap, (p->n_lm + kT / 16 - 1) / (kT / 16)) : 0;
+    a.g_lm = p->n_lm ? std::min(solver_env().tail_wgs, (p->n_lm + kT / 16 - 1) / (kT / 16)) : 0;
     a.n_lm = p->n_lm; a.dp = p->dp; a.ldE = p->ldE; a.E = p->E.p; a.C = p->compact ? p->Ct.p : p->C.p; a.Cd = p->Cd.p;
     a.gr = p->compact ? p->grt.p : p->gr.p; a.dxc = p->dxc.p; a.dxl = p->dxl.p; a.scal = p->scal.p;
     a.kmin = p->band_ready ? p->lm_kmin.p : nullptr; a.kmax = p->lm_kmax.p; a.n_kf = p->n_kf; a.s = s; a.poses2 = p->poses2.p; a.vel2 = p->vel2.p; a.ba2 = p->ba2.p;
@@ -314,8 +307,8 @@ static int chain_solve_args(lvf_problem* p, Chain& c) {
     c.tail_lds = (size_t)p->ldE * sizeof(double);
   }
   {
-    static const unsigned bt_timeout = [] { const char* e = std::getenv("LVF_CHAIN_TIMEOUT_US"); return e ? (unsigned)std::max(1, std::atoi(e)) * 100u : 50000u; }();
-    static const int bt_fenced = [] { const char* e = std::getenv("LVF_CHAIN_FENCE"); return e ? std::atoi(e) : 1; }();
+    const unsigned bt_timeout = solver_env().chain_timeout_ticks;
+    const int bt_fenced = solver_env().chain_fence;
     static const bool bt_big_lds = hipFuncSetAttribute(reinterpret_cast<const void*>(k_backsolve_tail), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) == hipSuccess;
     c.back_tail_merged = bt_wanted && c.tail.g_lm > 0;
     if (c.back_tail_merged) {
@@ -325,11 +318,9 @@ static int chain_solve_args(lvf_problem* p, Chain& c) {
       m.back.n_pose = p->dp;
       // (one round of workgroups: the launch's register and LDS footprint is the back substitution's, so about one workgroup fits a CU, and a
       // landmark workgroup that has to wait for a CU starts after the others are done)
-      static const int bt_wgs = [] { const char* e = std::getenv("LVF_BACK_TAIL_WGS"); return e ? std::max(1, std::atoi(e)) : 224; }();
-      m.g_lm = std::min(bt_wgs, (p->n_lm + kBT / 16 - 1) / (kBT / 16));
+      m.g_lm = std::min(solver_env().back_tail_wgs, (p->n_lm + kBT / 16 - 1) / (kBT / 16));
       m.fenced = bt_fenced == 2; m.back.pose_fenced = bt_fenced == 2; m.timeout_ticks = bt_timeout; m.fail = fail;
-      static const int bt_early = [] { const char* e = std::getenv("LVF_BACK_EARLY"); return (e && e[0] == '0') ? 0 : 1; }();
-      m.early = bt_early;
+      m.early = solver_env().back_early ? 1 : 0;
       if (p->force_handover_timeouts > 1) { m.back.pose_ready = reinterpret_cast<int*>(p->sp_sync.p) + 2 * kSpMaxLevels - 4; m.timeout_ticks = 2000u; }      // test hook (n >= 2): a flag nobody raises
       c.bt_lds = std::max(c.back_lds, c.tail_lds);
       if (c.bt_lds > 64 * 1024 && !bt_big_lds) c.back_tail_merged = false;
@@ -338,9 +329,8 @@ static int chain_solve_args(lvf_problem* p, Chain& c) {
     // kb) and the merged launch is in use.  Its G workgroups must fit the chip in ONE round beside workgroup 0, the pose workgroup and the
     // landmark workgroups (about one workgroup of this launch fits a compute unit; a workgroup that has to wait for one starts after the
     // others are done), each owns whole keyframes, one thread per unknown.
-    static const bool prod_on = [] { const char* e = std::getenv("LVF_BACK_PRODUCT"); return !(e && e[0] == '0'); }();
     c.back_product = false; c.gride = GRide{}; c.gride.n = 0;
-    if (prod_on && c.back_tail_merged && c.n_levels >= 1 && c.n_levels <= p->nb && p->ldG > 0) {
+    if (solver_env().back_product && c.back_tail_merged && c.n_levels >= 1 && c.n_levels <= p->nb && p->ldG > 0) {
       static const int n_cu = [] { int dev = 0, n = 0; return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }();
       const int room = n_cu - 2 - c.bt.g_lm;
       const int kpw = room >= 1 ? (p->n_kf + std::min(room, p->n_kf) - 1) / std::min(room, p->n_kf) : 0;
@@ -359,14 +349,13 @@ static int chain_solve_args(lvf_problem* p, Chain& c) {
     // product form, three beside the sparse levels' items.  Off where the augmented row sits alone in the last factor block (d a multiple of
     // 64: the first solved block would take its right-hand side from a panel, not from Ldiag — a corner the plan's cost steers away from, it
     // pays a block step for one row) and in the chain-free re-run after a hand-over time-out; those read S and Dinv as before.
-    static const bool blocks_on = [] { const char* e = std::getenv("LVF_BACK_BLOCKS"); return !(e && e[0] == '0'); }();
     c.back_blocks = false; c.tride = TRide{0, nullptr};
-    if (blocks_on && !p->no_chain && p->nb >= 2 && p->ndense % kNB != 0 && p->nb - 1 <= (c.back_product ? kBackTJ : kBackTJLevels)) {
+    if (solver_env().back_blocks && !p->no_chain && p->nb >= 2 && p->ndense % kNB != 0 && p->nb - 1 <= (c.back_product ? kBackTJ : kBackTJLevels)) {
       LVF_TRY(p->sp_T.ensure((size_t)p->nb * p->nb * kNB * kNB));
       c.tride = TRide{0, p->sp_T.p};
       c.back_blocks = true;
     }
-    static const bool chain_info = std::getenv("LVF_CHAIN_INFO") != nullptr;
+    const bool chain_info = solver_env().chain_info;
     if (chain_info) std::fprintf(stderr, "chain: n_kf %d n_lm %d fast %d has_imu %d early %d compact %d levels %d no_chain %d merged_level0 %d back_tail_merged %d (g_lm %d, lds %zu) back_product %d (nb %d, %d G workgroups of %d keyframes)\n", p->n_kf, p->n_lm, (int)c.fast, (int)c.has_imu,
                                  (int)c.early, (int)p->compact, c.n_levels, (int)p->no_chain, (int)c.merged_level0, (int)c.back_tail_merged, c.bt.g_lm, c.bt_lds,
                                  (int)c.back_product, p->nb, c.bt.g_prod, c.bt.kpw);
@@ -384,7 +373,7 @@ static int chain_cost_decide_args(lvf_problem* p, Chain& c) {
   c.cost.nblocks = c.cost.a.g_tc + c.cost.a.g_tf + grid(c.cost.a.n_po);
   {
     // two tiles of kT blocks per workgroup: half as many workgroups to dispatch ahead of the decision (measured -1 % of an iteration; three: same)
-    static const int cost_tiles = [] { const char* e = std::getenv("LVF_COST_TILES"); return e ? std::atoi(e) : 2; }();
+    const int cost_tiles = solver_env().cost_tiles;
     if (cost_tiles > 1) {
       CostArgs& k = c.cost;
       const int per = kT * cost_tiles;
@@ -402,9 +391,8 @@ static int chain_cost_decide_args(lvf_problem* p, Chain& c) {
     a.scal = p->scal.p; a.ctl = ctl; a.rec = p->rec; a.ticket = reinterpret_cast<int*>(p->scal.p + SC_TICKET); a.n_kf = p->n_kf; a.n_lm = p->n_lm;
     a.poses = p->st->poses.p; a.vel = p->st->vel.p; a.ba = p->st->ba.p; a.bg = p->st->bg.p; a.invd = p->st->inv_depth.p;
     a.poses2 = p->poses2.p; a.vel2 = p->vel2.p; a.ba2 = p->ba2.p; a.bg2 = p->bg2.p; a.invd2 = p->invd2.p;
-    static const bool lm_history = std::getenv("LVF_LM_HISTORY") != nullptr;
     a.hist = nullptr;
-    if (lm_history) { LVF_TRY(p->dbg_hist.ensure(8 * 64)); a.hist = p->dbg_hist.p; }
+    if (solver_env().lm_history) { LVF_TRY(p->dbg_hist.ensure(8 * 64)); a.hist = p->dbg_hist.p; }
   }
   return LVF_OK;
 }
@@ -413,8 +401,7 @@ static int chain_cost_decide_args(lvf_problem* p, Chain& c) {
 static void chain_fused_args(lvf_problem* p, Chain& c) {
   const int* done = &p->ctl.p->done;
   const StateP s2 = candidate_ptrs(p);
-  static const bool fused_on = [] { const char* e = std::getenv("LVF_FUSED_LIN"); return !(e && e[0] == '0'); }();
-  c.fused_ok = fused_on && c.fast && p->compact && !c.has_prior && c.merged_level0 && p->n_lm > 0 && c.lin.nblocks > 0 && c.cost.nblocks > 0 &&
+  c.fused_ok = solver_env().fused_lin && c.fast && p->compact && !c.has_prior && c.merged_level0 && p->n_lm > 0 && c.lin.nblocks > 0 && c.cost.nblocks > 0 &&
                (!c.has_imu || (c.imu_in_cost && c.lin.v.imu.pre));
   p->acc1_ready = false;            // the second set is allocated and cleared by the first fused solve (ensure_acc1)
   if (c.fused_ok) {
@@ -452,10 +439,9 @@ int build_chain(lvf_problem* p) {
   c.has_prior = p->prior && p->prior->n;
   {
     // LVF_EARLY_LEVELS=0: the classic order (A/B measurements); LVF_POISON_S fills S with NaN before the assembly, which only the classic form survives
-    static const bool early_on = [] { const char* e = std::getenv("LVF_EARLY_LEVELS"); return !(e && e[0] == '0') && std::getenv("LVF_POISON_S") == nullptr; }();
     bool fits = true;
     for (int lv = 0; lv < std::min(3, p->sp_levels.n); ++lv) fits = fits && (size_t)p->sp_shmem[lv] <= 64 * 1024;
-    c.early = early_on && c.fast && c.has_imu && schur_merged(p) && fits && p->sp_levels.n >= 2;      // (one level: it already hides in the Schur launch)
+    c.early = solver_env().early_levels && c.fast && c.has_imu && schur_merged(p) && fits && p->sp_levels.n >= 2;      // (one level: it already hides in the Schur launch)
   }
   LVF_TRY(chain_zero_lists(p, c));
   chain_linearize_args(p, c);
@@ -561,9 +547,9 @@ int enqueue_linearize(lvf_problem* p, double huber, bool gated, bool iteration, 
     la.huber = huber;
     if (!gated) la.done = nullptr;
     if (!iteration) la.scal_reset = nullptr;
-    static const bool lin_timing = std::getenv("LVF_LIN_TIMING") != nullptr;
+    const bool lin_timing = solver_env().lin_timing;
     if (lin_timing) { LVF_TRY(p->dbg_lin.ensure((size_t)la.v.n_tfw * 24 + 8)); la.dbg = p->dbg_lin.p; }
-    static const size_t lds_pad = [] { const char* e = std::getenv("LVF_LIN_LDS_PAD"); return e ? (size_t)std::atoi(e) : (size_t)0; }();      // experiment: fewer workgroups per CU
+    const size_t lds_pad = solver_env().lin_lds_pad;      // experiment: fewer workgroups per CU
     if (lin) LVF_CHAIN_LAUNCH(p, ST_LIN_VISUAL, k_lin_visual, dim3(la.nblocks), dim3(kT), c.lin_lds + lds_pad, q, la);      // (into set 0: a pass starts with LmCtl::aset = 0)
     stage_mark(p, ST_LIN_VISUAL, lin ? 1 : 0);
     if (p->compact) {
@@ -709,8 +695,7 @@ int enqueue_reduced_system(lvf_problem* p, const double* radius_dev, bool reset_
   if (!gated) pa.done = nullptr;
   // LVF_POISON_S=1 (diagnostic): every byte of S is 0xff (NaN) before the assembly, so whatever the assembly does not write — the upper
   // triangle — stays NaN; results must not change (tests/test_gpu_solver.py runs the parity cases this way too)
-  static const bool poison = std::getenv("LVF_POISON_S") != nullptr;
-  if (poison) LVF_HIP(hipMemsetAsync(p->S.p, 0xff, (size_t)p->ld * p->ld * 8, q));
+  if (solver_env().poison_s) LVF_HIP(hipMemsetAsync(p->S.p, 0xff, (size_t)p->ld * p->ld * 8, q));
   LVF_CHAIN_LAUNCH(p, ST_PREPARE, k_prepare, dim3(pa.nblocks), dim3(kT), pa.ride.nblocks > 0 ? c.prep_lds : 0, q, pa);
   stage_mark(p, ST_PREPARE, 1);
   if (!early && c.early) p->accum_clean = false;       // the tap wrote S: the next iteration must clear it
@@ -722,7 +707,7 @@ int enqueue_reduced_system(lvf_problem* p, const double* radius_dev, bool reset_
       if (acc) { sa.acc = *acc; acc_patch(sa.sp, acc); acc_patch(sa.sp_b, acc); acc_patch(sa.sp_c, acc); }
       if (!gated) sa.done = nullptr;
       if (!level0_done) { sa.nblocks = sa.n_work; sa.sp.nblocks = 0; sa.sp_b.nblocks = 0; sa.sp_c.nblocks = 0; }       // the Schur complement alone (parity tap)
-      static const bool schur_timing = std::getenv("LVF_SCHUR_TIMING") != nullptr;
+      const bool schur_timing = solver_env().schur_timing;
       const int ns = sa.n_work;
       if (schur_timing) { LVF_TRY(p->dbg_lin.ensure((size_t)ns * 8 + 8)); LVF_HIP(hipMemsetAsync(p->dbg_lin.p, 0, (size_t)ns * 64, q)); sa.dbg = p->dbg_lin.p; }
       if (sa.nblocks > 0) LVF_CHAIN_LAUNCH(p, ST_SCHUR_SP0, k_schur_sp0, dim3(sa.nblocks), dim3(256), c.ssp0_lds, q, sa);
@@ -762,7 +747,7 @@ int enqueue_iteration(lvf_problem* p, bool end_zero, int fused) {
   if (ov) LVF_REQUIRE(ov->d == p->d, "the overridden reduced system has %d unknowns, the problem now has %d: clear or set it again", ov->d, p->d);      // (before any launch)
   if (!c.fused_ok || !p->acc1_ready || ov) fused = 0;
   const AccSel* acc = (fused & kFusedOn) ? &c.acc : nullptr;
-  static const bool sp_timing = std::getenv("LVF_SP_TIMING") != nullptr;
+  const bool sp_timing = solver_env().sp_timing;
   if (sp_timing && c.early) {
     // diagnostic: the levels' stamps (the chain is rebuilt with the debug pointer in every level's arguments; printed by the next call)
     const int n_nodes = p->sp_levels.n ? p->sp_levels.first[p->sp_levels.n - 1] + p->sp_levels.count[p->sp_levels.n - 1] : 0;
@@ -810,19 +795,18 @@ int enqueue_iteration(lvf_problem* p, bool end_zero, int fused) {
   stage_mark(p, ST_SP_LEVELS, std::max(0, c.n_levels - own0));
   for (int kb = 0; kb < p->nb; ++kb) {
     CholArgs cha = c.chol;
-    static const bool chol_timing = std::getenv("LVF_CHOL_TIMING") != nullptr;
-    if (chol_timing) { LVF_TRY(p->dbg.ensure(128)); cha.dbg = p->dbg.p; }      // [0, 64): phases of 8 block steps; [64, 128): their sub-block stages
+    if (solver_env().chol_timing) { LVF_TRY(p->dbg.ensure(128)); cha.dbg = p->dbg.p; }      // [0, 64): phases of 8 block steps; [64, 128): their sub-block stages
     GRide gr = c.gride;                                   // the riders that form G: the top level first, one level per launch
     const int glv = c.n_levels - 1 - kb;
     if (c.back_product && glv >= 0) { gr.first = p->sp_levels.first[glv]; gr.n = p->sp_levels.count[glv]; } else gr.n = 0;
     TRide tr = c.tride;                                   // the riders that form T_kj, k = kb - 1: both factors are final since launch kb - 1
     tr.n = (c.back_blocks && kb >= 1) ? p->nb - kb : 0;
-    if (chol_subblock_on()) LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step, dim3(chol_step_grid(p->nb, kb) + gr.n + tr.n), dim3(kCT), 0, q, cha, kb, gr, tr);
+    if (solver_env().chol_subblock) LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step, dim3(chol_step_grid(p->nb, kb) + gr.n + tr.n), dim3(kCT), 0, q, cha, kb, gr, tr);
     else LVF_CHAIN_LAUNCH(p, ST_CHOL, k_chol_step_pp, dim3(chol_step_grid(p->nb, kb) + gr.n + tr.n), dim3(kCT), 0, q, cha, kb, gr, tr);
   }
   {
     BackArgs ba = c.back;
-    static const bool back_timing = std::getenv("LVF_BACK_TIMING") != nullptr;
+    const bool back_timing = solver_env().back_timing;
     if (back_timing) { LVF_TRY(p->dbg.ensure(64)); ba.sp.dbg = p->dbg.p; }
     if (c.back_blocks) ba.T = p->sp_T.p;
     stage_mark(p, ST_CHOL, p->nb);
@@ -867,8 +851,7 @@ int enqueue_iteration(lvf_problem* p, bool end_zero, int fused) {
   if (ca.nblocks > 0) {
     if (!end_zero) ca.zero_wgs = 0;
     DecideArgs da = c.dec;
-    static const bool cost_timing = std::getenv("LVF_COST_TIMING") != nullptr;
-    if (cost_timing) { LVF_TRY(p->dbg.ensure(64)); da.dbg = p->dbg.p; }
+    if (solver_env().cost_timing) { LVF_TRY(p->dbg.ensure(64)); da.dbg = p->dbg.p; }
     LVF_CHAIN_LAUNCH(p, ST_COST, k_cost_decide, dim3(ca.nblocks + ca.zero_wgs), dim3(kT), 0, q, ca, da, end_zero ? 1 : 0);
     p->accum_clean = ca.zero_wgs > 0;
     if (p->accum_clean) p->linearized = false;         // the normal equations of this iteration are gone: no reduced-system tap
@@ -935,12 +918,12 @@ int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* radius, do
     LVF_TRY(enqueue_iteration(p, false));
     LVF_TRY(download_ctl(p, &c));
   }
-  if (p->dbg.p && std::getenv("LVF_CHOL_TIMING")) {
+  if (p->dbg.p && solver_env().chol_timing) {
     unsigned long long t[128];
     LVF_HIP(hipMemcpy(t, p->dbg.p, sizeof(t), hipMemcpyDeviceToHost));
     for (int kb = 0; kb < p->nb && kb < 8; ++kb) {
       const unsigned long long* u = t + 8 * kb;
-      if (chol_subblock_on() && kb + 2 < p->nb + 1) {      // a full block: per stage, sweep + exchange | tile products (seen by wave 0 of workgroup 1)
+      if (solver_env().chol_subblock && kb + 2 < p->nb + 1) {      // a full block: per stage, sweep + exchange | tile products (seen by wave 0 of workgroup 1)
         const unsigned long long* v = t + 64 + 8 * kb;
         std::fprintf(stderr, "chol step %d stages (us): %.2f | %.2f ; %.2f | %.2f ; %.2f | %.2f ; %.2f\n", kb, (double)(v[0] - u[3]) * 0.01, (double)(v[1] - v[0]) * 0.01,
                      (double)(v[2] - v[1]) * 0.01, (double)(v[3] - v[2]) * 0.01, (double)(v[4] - v[3]) * 0.01, (double)(v[5] - v[4]) * 0.01, (double)(v[6] - v[5]) * 0.01);
@@ -950,14 +933,14 @@ int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* radius, do
                         (double)(u[2] - u[1]) * 0.01, (double)(u[3] - u[2]) * 0.01, (double)(u[4] - u[3]) * 0.01, (double)(u[5] - u[4]) * 0.01, (double)(u[0] - u[-3]) * 0.01);
     }
   }
-  if (p->dbg.p && std::getenv("LVF_COST_TIMING")) {
+  if (p->dbg.p && solver_env().cost_timing) {
     unsigned long long t[64];
     LVF_HIP(hipMemcpy(t, p->dbg.p, sizeof(t), hipMemcpyDeviceToHost));
     auto us = [&](int a, int b) { return ((double)t[b] - (double)t[a]) * 0.01; };
     std::fprintf(stderr, "cost+decide (us): imu wg0 stage %.2f | raw (one lane) %.2f | weight+sum %.2f ; first visual wg %.2f (starts %.2f after imu wg0) ; decision starts %.2f after imu wg0's start: sums %.2f | logic %.2f | commit %.2f | record %.2f\n",
                  us(8, 9), us(9, 10), us(10, 11), us(12, 13), us(8, 12), us(8, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5));
   }
-  if (p->dbg.p && std::getenv("LVF_BACK_TIMING")) {
+  if (p->dbg.p && solver_env().back_timing) {
     unsigned long long t[64];
     LVF_HIP(hipMemcpy(t, p->dbg.p, sizeof(t), hipMemcpyDeviceToHost));
     std::fprintf(stderr, "backsolve phases (us):");

@@ -10,6 +10,78 @@ static inline StateP state_ptrs(const lvf_state* st) { return StateP{st->poses.p
 static inline int grid(int n) { return (n + kT - 1) / kT; }
 static inline int band_rows_clamped(int rows) { return std::min(kBandRowsMax, std::max(16, rows)); }
 
+// The solver's environment switches: every LVF_* value that solver_chain.hip, solver_plan.hip and solver_batch.hip read — one
+// field per name, filled once per process when the solver is first used (solver_env()).  "unless 0": on unless the value starts with '0';
+// "if set": on when the variable exists, whatever its value; integers go through atoi.
+struct SolverEnv {
+  // ---- forms of the chain (the defaults are the production chain; the other forms are also reached by problem shape)
+  bool sparse_vb;             // LVF_SPARSE_VB        unless 0   the (v, ba, bg) blocks eliminated level by level ahead of the dense Cholesky
+  int force_levels;           // LVF_FORCE_LEVELS     0          > 0: at most this many sparse levels (experiment)
+  bool schur_band;            // LVF_SCHUR_BAND       unless 0   band-limited Schur complement over sorted landmark tracks
+  bool compact;               // LVF_COMPACT          unless 0   atomic-free TwoFrame linearisation (slabs and track slots, summed by k_tf_reduce / k_prepare)
+  bool tf_k1sort;             // LVF_TF_K1SORT        unless 0   TwoFrame blocks of a current keyframe ordered by first keyframe
+  bool staged;                // LVF_STAGED           unless 0   segmented first-keyframe sums through the wave's LDS stage (TfCompact::staged)
+  bool zero_tri;              // LVF_ZERO_TRI         unless 0   clears of lower-triangular accumulators skip the upper blocks
+  bool early_levels;          // LVF_EARLY_LEVELS     unless 0   sparse levels ride in k_tf_reduce / k_prepare / the Schur launch; off when LVF_POISON_S is set
+  int ride_tf, ride_prep;     // LVF_RIDE_TF / _PREP  -1         >= 0 forces a level to ride (non-zero) or not (0) in k_tf_reduce / k_prepare; -1: by the plan
+  int chain_levels;           // LVF_CHAIN_LEVELS     2          clamped to 0..2: levels chained inside one launch; the merged back substitution needs > 0
+  int chain_fence;            // LVF_CHAIN_FENCE      1          0 relaxed hand-over between chained levels, otherwise fenced; 2: full release in k_backsolve_tail too
+                              //                                 (atoi for both uses: text that is no number counts as 0, "02" as 2)
+  unsigned chain_timeout_ticks; // LVF_CHAIN_TIMEOUT_US 500      how long a chained workgroup waits for its hand-over, kept in 100 MHz ticks (at least 1 us)
+  bool chain_rmw_read;        // LVF_CHAIN_RMW_READ   if set     chained levels read by returning atomics instead of agent-scope loads (SpSrc::rmw_read)
+  bool chol_subblock;         // LVF_CHOL_SUBBLOCK    unless 0   16-pivot sub-block sweep of the dense Cholesky (k_chol_step*); 0: pair-pivot sweep (k_chol_step_pp*)
+  bool back_tail_merge;       // LVF_BACK_TAIL_MERGE  unless 0   back substitution and step tail as one launch (k_backsolve_tail)
+  bool back_product;          // LVF_BACK_PRODUCT     unless 0   sparse back substitution as one product with G (GRide)
+  bool back_blocks;           // LVF_BACK_BLOCKS      unless 0   dense back substitution on stored block products T_kj (TRide)
+  bool back_early;            // LVF_BACK_EARLY       unless 0   landmark and pose workgroups of k_backsolve_tail request their operands ahead of the wait
+  bool fused_lin;             // LVF_FUSED_LIN        unless 0   candidate pass linearises (k_lin_cost_decide, two accumulator sets)
+  // ---- launch shapes (A/B)
+  int tail_wgs;               // LVF_TAIL_WGS         640        cap on the landmark workgroups of k_step_tail
+  int back_tail_wgs;          // LVF_BACK_TAIL_WGS    224        cap on the landmark workgroups of k_backsolve_tail (at least 1)
+  int cost_tiles;             // LVF_COST_TILES       2          tiles of kT blocks per workgroup of the candidate-cost pass
+  size_t lin_lds_pad;         // LVF_LIN_LDS_PAD      0          bytes of dynamic LDS added to k_lin_visual (fewer workgroups per CU)
+  int batch_band_rows;        // LVF_BATCH_BAND_ROWS  128        landmark rows per slice of a batch's band Schur complement
+  int batch_transpose;        // LVF_BATCH_TRANSPOSE  127        bit per table launch of a batch: window index in blockIdx.x (transposed) instead of .y
+  // ---- diagnostics
+  bool poison_s;              // LVF_POISON_S         if set     S filled with NaN bytes before each reduced system (proves every entry is written)
+  bool chain_info;            // LVF_CHAIN_INFO       if set     build_chain prints the chain's form ("chain: ..." on stderr)
+  bool lm_history;            // LVF_LM_HISTORY       if set     the decision records its scalars per iteration (DecideArgs::hist)
+  bool configure_timing;      // LVF_CONFIGURE_TIMING if set     problem_configure prints its phases' host times
+  // (phase stamps: written by the stage's kernels into a debug buffer and printed on stderr; the enqueue and the read-back test the same field)
+  bool lin_timing;            // LVF_LIN_TIMING       if set     phase stamps of k_lin_visual's TwoFrame workgroups and waves
+  bool schur_timing;          // LVF_SCHUR_TIMING     if set     phase stamps of the band Schur complement's workgroups
+  bool sp_timing;             // LVF_SP_TIMING        if set     phase stamps of the early sparse levels
+  bool chol_timing;           // LVF_CHOL_TIMING      if set     phase stamps of the first 8 block steps of the dense Cholesky
+  bool back_timing;           // LVF_BACK_TIMING      if set     phase stamps of the back substitution
+  bool cost_timing;           // LVF_COST_TIMING      if set     phase stamps of the candidate-cost pass and the decision
+};
+inline const SolverEnv& solver_env() {
+  static const SolverEnv env = [] {
+    auto set = [](const char* name) { return std::getenv(name) != nullptr; };
+    auto unless0 = [](const char* name) { const char* e = std::getenv(name); return !(e && e[0] == '0'); };
+    auto num = [](const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; };
+    SolverEnv v{};
+    v.sparse_vb = unless0("LVF_SPARSE_VB"); v.force_levels = num("LVF_FORCE_LEVELS", 0); v.schur_band = unless0("LVF_SCHUR_BAND");
+    v.compact = unless0("LVF_COMPACT"); v.tf_k1sort = unless0("LVF_TF_K1SORT"); v.staged = unless0("LVF_STAGED"); v.zero_tri = unless0("LVF_ZERO_TRI");
+    v.poison_s = set("LVF_POISON_S");
+    v.early_levels = unless0("LVF_EARLY_LEVELS") && !v.poison_s;
+    v.ride_tf = num("LVF_RIDE_TF", -1); v.ride_prep = num("LVF_RIDE_PREP", -1);
+    v.chain_levels = std::max(0, std::min(2, num("LVF_CHAIN_LEVELS", 2)));
+    v.chain_fence = num("LVF_CHAIN_FENCE", 1);
+    v.chain_timeout_ticks = (unsigned)std::max(1, num("LVF_CHAIN_TIMEOUT_US", 500)) * 100u;
+    v.chain_rmw_read = set("LVF_CHAIN_RMW_READ");
+    v.chol_subblock = unless0("LVF_CHOL_SUBBLOCK"); v.back_tail_merge = unless0("LVF_BACK_TAIL_MERGE"); v.back_product = unless0("LVF_BACK_PRODUCT");
+    v.back_blocks = unless0("LVF_BACK_BLOCKS"); v.back_early = unless0("LVF_BACK_EARLY"); v.fused_lin = unless0("LVF_FUSED_LIN");
+    v.tail_wgs = num("LVF_TAIL_WGS", 640); v.back_tail_wgs = std::max(1, num("LVF_BACK_TAIL_WGS", 224)); v.cost_tiles = num("LVF_COST_TILES", 2);
+    v.lin_lds_pad = (size_t)num("LVF_LIN_LDS_PAD", 0); v.batch_band_rows = num("LVF_BATCH_BAND_ROWS", 128); v.batch_transpose = num("LVF_BATCH_TRANSPOSE", 127);
+    v.chain_info = set("LVF_CHAIN_INFO"); v.lm_history = set("LVF_LM_HISTORY"); v.configure_timing = set("LVF_CONFIGURE_TIMING");
+    v.lin_timing = set("LVF_LIN_TIMING"); v.schur_timing = set("LVF_SCHUR_TIMING"); v.sp_timing = set("LVF_SP_TIMING");
+    v.chol_timing = set("LVF_CHOL_TIMING"); v.back_timing = set("LVF_BACK_TIMING"); v.cost_timing = set("LVF_COST_TIMING");
+    return v;
+  }();
+  return env;
+}
+
 // The argument blocks of ONE LM iteration of a window.  Nothing in them changes from iteration to iteration (the trust-region radius,
 // the accept / reject state and the termination flag live in the device-resident LmCtl; an accepted candidate is COPIED into the state
 // buffers by k_lm_decide), so they are built once per problem_configure and
@@ -77,7 +149,6 @@ enum { kFusedOn = 1, kFusedNoLin = 2, kFusedTail = 4 };
 struct IterOut { double cost_before, cost_after, model, dxnorm, xnorm, gmax; bool accepted, solved; };
 
 // ---- solver_chain.hip
-bool chol_subblock_on();      // LVF_CHOL_SUBBLOCK=0: the pair-pivot sweep of the dense Cholesky (k_chol_step_pp*) instead of the 16-pivot sub-block sweep
 void stage_clock_free(StageClock* k);
 int enqueue_cost(lvf_problem* p, const StateP& s, const lvf_state* imu_state_view, double huber, double* cost_slot);
 int build_band_work(lvf_problem* p, int rows_in, DevBuf<int4>& work, int* n_work, bool defer = false);

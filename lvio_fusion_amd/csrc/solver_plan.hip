@@ -1,5 +1,5 @@
 // solver_plan.hip — what is decided once per problem_configure: the elimination plan of the (v, ba, bg) blocks (host) and the problem's
-// buffers, TwoFrame work list, landmark tracks and compact layout (host + the layout kernels of solver_kernels.hip).
+// buffers, TwoFrame work list, landmark tracks and compact layout (host + the layout kernels of solver_assemble.hip).
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -22,9 +22,8 @@ static int build_elimination_plan(lvf_problem* p) {
     if (have_idx) { key.insert(key.end(), imu->host_kf1.begin(), imu->host_kf1.end()); key.insert(key.end(), imu->host_kf2.begin(), imu->host_kf2.end()); }
   }
   if (key == p->plan_key && p->ld > 0) return LVF_OK;
-  static const bool sparse_on = [] { const char* e = std::getenv("LVF_SPARSE_VB"); return !(e && e[0] == '0'); }();
   std::vector<std::vector<char>> va(n, std::vector<char>(n, 0)), pa(n, std::vector<char>(n, 0));
-  bool sparse = sparse_on && (!imu || imu->n == 0 || have_idx);
+  bool sparse = solver_env().sparse_vb && (!imu || imu->n == 0 || have_idx);
   if (have_idx)
     for (int f = 0; f < imu->n; ++f) {
       const int i = imu->host_kf1[f], j = imu->host_kf2[f];
@@ -70,7 +69,7 @@ static int build_elimination_plan(lvf_problem* p) {
       const double cost = 8.5 * (double)l + 18.0 * steps;
       if (cost < best - 1e-9) { best = cost; max_levels = (int)l + 1; }
     }
-    static const int force_levels = [] { const char* e = std::getenv("LVF_FORCE_LEVELS"); return e ? std::atoi(e) : 0; }();      // experiment
+    const int force_levels = solver_env().force_levels;      // experiment
     if (force_levels > 0) max_levels = std::min((int)left_after.size(), force_levels);
   }
   while (sparse && lv.n < std::min(max_levels, kSpMaxLevels)) {
@@ -168,7 +167,7 @@ static int build_elimination_plan(lvf_problem* p) {
 }
 
 int problem_configure(lvf_problem* p) {
-  static const bool cfg_timing = std::getenv("LVF_CONFIGURE_TIMING") != nullptr;
+  const bool cfg_timing = solver_env().configure_timing;
   const auto cfg_t0 = std::chrono::steady_clock::now();
   auto cfg_mark = [&](const char* what) {
     if (cfg_timing) std::fprintf(stderr, "  problem_configure: %s at %.3f ms\n", what, 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - cfg_t0).count());
@@ -222,8 +221,7 @@ int problem_configure(lvf_problem* p) {
     const std::vector<int32_t>& k2 = two_frame->host_kf2; const std::vector<int32_t>& k1 = two_frame->host_kf1;
     const std::vector<int32_t>& lmh = two_frame->host_lm;
     const int n = two_frame->n, nkf = p->n_kf;
-    static const bool k1sort_on = [] { const char* e = std::getenv("LVF_TF_K1SORT"); return !(e && e[0] == '0'); }();
-    const bool want_hist = k1sort_on && nkf <= 256;
+    const bool want_hist = solver_env().tf_k1sort && nkf <= 256;
     bool ok = true, k1_first = true;
     bool uniq = two_frame->unique_lk2_known || lmh.size() == (size_t)n;
     const bool check_uniq = uniq && !two_frame->unique_lk2_known;
@@ -290,14 +288,12 @@ int problem_configure(lvf_problem* p) {
   cfg_mark("TwoFrame work list + shape checks");
   // landmark tracks -> band-limited Schur (device side: the TwoFrame indices already live there)
   p->band_ready = false;
-  static const bool band_on = [] { const char* e = std::getenv("LVF_SCHUR_BAND"); return !(e && e[0] == '0'); }();
-  const bool band_ok = band_on && p->n_lm > 0 && (size_t)(4 * p->n_kf + 1) * sizeof(int) <= 48 * 1024;
+  const bool band_ok = solver_env().schur_band && p->n_lm > 0 && (size_t)(4 * p->n_kf + 1) * sizeof(int) <= 48 * 1024;
   // compact landmark layout + slabs (atomic-free TwoFrame linearisation): needs the sorted work list, one block per (landmark,
   // keyframe), the landmark's first keyframe ahead of its observations, and the merged band-Schur launch
-  static const bool compact_on = [] { const char* e = std::getenv("LVF_COMPACT"); return !(e && e[0] == '0'); }();
   const size_t shb = ((size_t)kSchurRows * (p->ldE + 16) + kSchurRows) * sizeof(double) + kBandRowsMax * sizeof(int);
   const bool merged = shb <= 64 * 1024 && p->sp_levels.n > 0 && (size_t)p->sp_shmem[0] <= 64 * 1024;
-  const bool want_compact = band_ok && compact_on && merged && p->dp <= 320 && two_frame && two_frame->n && p->tf_work.n && p->n_kf <= kMaxStagedKf && p->tf_unique_lk2 && p->tf_k1_first;
+  const bool want_compact = band_ok && solver_env().compact && merged && p->dp <= 320 && two_frame && two_frame->n && p->tf_work.n && p->n_kf <= kMaxStagedKf && p->tf_unique_lk2 && p->tf_k1_first;
   LVF_TRY(p->E.ensure((size_t)p->n_lm * p->ldE));
   if (band_ok) { LVF_TRY(p->lm_kmin.ensure(p->n_lm)); LVF_TRY(p->lm_kmax.ensure(p->n_lm)); LVF_TRY(p->lm_order.ensure(p->n_lm)); LVF_TRY(p->lm_nactive.ensure(1)); }
   // atomic-free mode: E's non-zero pattern is fixed for the problem and fully overwritten by every linearisation — cleared once, here;

@@ -1,4 +1,4 @@
-"""The product form of the (v, ba, bg) back substitution (csrc/solver_kernels.hip: back_product_ride, back_product_body,
+"""The product form of the (v, ba, bg) back substitution (csrc/solver_chol.hip: back_product_ride; csrc/solver_back.hip: back_product_body,
 chol_backsolve_body<false>): x_sparse = G [x_dense ; -1], with G formed by workgroups riding behind the block-step launches of the dense
 Cholesky and multiplied by sibling workgroups of k_backsolve_tail, against the sequential sparse levels it replaces (LVF_BACK_PRODUCT=0).
 

@@ -99,7 +99,7 @@ def test_config4_full_window_lm_iterations(ctx, oracle, ids_by_birth):
 
 
 def test_more_than_16k_landmarks(ctx, oracle):
-    """20 000 landmarks in a short window: the one-workgroup scans of problem_configure (k_lm_offsets) and of the device-side window
+    """20 000 landmarks in a short window: the one-workgroup scans of problem_configure (k_lm_sort_offsets) and of the device-side window
     assembly (k_da_scan) work in passes of 16 k landmarks — both are taken through their second pass here.  The flat problem is
     compared with the oracle; the persistent window must then reproduce the flat problem's iteration."""
     from lvio_fusion_amd import api

@@ -1,4 +1,4 @@
-"""The dense Cholesky's 16-pivot sub-block sweep (csrc/solver_kernels.hip, sub_pivots / chol_step_body<true>) at the corner sizes where
+"""The dense Cholesky's 16-pivot sub-block sweep (csrc/solver_chol.hip, sub_pivots / chol_step_body<true>) at the corner sizes where
 it can go wrong.  The corner has d = 6 n_kf unknowns plus the right-hand-side row, in blocks of 64 that are swept in stages of 16:
 
     n_kf   d + 1   exercises

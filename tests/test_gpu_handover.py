@@ -1,4 +1,4 @@
-"""The in-launch hand-over between chained sparse levels (csrc/solver_kernels.hip, SpSrc) must never turn a scheduling delay into a
+"""The in-launch hand-over between chained sparse levels (csrc/solver_assemble.hip, SpSrc) must never turn a scheduling delay into a
 numerical outcome: a consumer that does not see its producers in time raises a flag, the device loop stops WITHOUT judging the step, and
 the host re-runs the iteration with un-chained launches (lvf_solver_summary::hand_over_retries).  Exercised three ways: a forced
 time-out on an idle GPU (single window, per-call API, batch), the configs[3] solve under a second context's traffic — the reference runs

@@ -3,7 +3,7 @@ did not ask for (the compiler sinks loads behind branches: DESIGN 9c.8).  Input:
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-fast-math -gline-tables-only -Iinclude --save-temps=obj -c lvio_fusion_amd/csrc/<tu>.hip
 usage: python tools/isa_serial_loads.py <kernel name substring> [path to the *-gfx950.s]      prints (source line, count) pairs"""
 import re,sys,collections
-s=open(sys.argv[2] if len(sys.argv) > 2 else '/tmp/isag/solver_kernels-hip-amdgcn-amd-amdhsa-gfx950.s').read()
+s=open(sys.argv[2] if len(sys.argv) > 2 else '/tmp/isag/solver_assemble-hip-amdgcn-amd-amdhsa-gfx950.s').read()
 funcs=[(m.start(), m.group(1)) for m in re.finditer(r'\n(_Z\w+):\s*; @', s)]
 want=sys.argv[1]
 for k,(pos,name) in enumerate(funcs):
