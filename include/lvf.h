@@ -347,6 +347,36 @@ int lvf_cloud_deskew(const lvf_cloud* in, const lvf_trajectory* traj, double fra
 int lvf_lidar_extract_deskewed(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7,
                                const lvf_trajectory* traj, double frame_time, const double* frame_pose7, lvf_cloud** ground_out, lvf_cloud** surf_out,
                                lvf_lidar_extract_debug* dbg);
+/* ---- LiDAR edge picks inside the extraction chain ---------------------------------------------------------------------------------------- */
+/* The reference declares points_sharp / points_less_sharp (lidar/feature.h:23-24, commented out) and computes the curvature that would
+ * select them (association.cpp:149-166) but only uses it to keep points out of the surf set (:202).  DECLARED pick rule (LOAM's, restated
+ * in tests/edge_ref.py): per ring and per sector [sp, ep] of ExtractFeatures (association.cpp:186-194), independently, a candidate is a
+ * non-ground point with curvature >= edge_threshold (the curvature array of the surf test, stale ends read as 0; the default 1.0f is the
+ * complement of that test, so surf and edge sets are disjoint).  Repeatedly the unsuppressed candidate that is largest under (curvature
+ * descending, segmented index ascending) is taken and every point of the sector within +-5 segmented indices of it is suppressed, until
+ * n_less_sharp picks were made or no candidate is left.  The first n_sharp picks of a sector form `sharp`, all of them `less_sharp`; both
+ * clouds are emitted in ascending segmented index, intensity = ring + relative time as for the other picks. */
+typedef struct lvf_edge_params {
+  float edge_threshold;    /* 1.0f */
+  int n_sharp;             /* 2 (LOAM) */
+  int n_less_sharp;        /* 20 (LOAM) */
+} lvf_edge_params;
+void lvf_edge_params_default(lvf_edge_params* p);
+/* optional taps (host arrays, may each be NULL): sharp_raw / less_sharp_raw = the picks in the SENSOR frame before any deskew, sized
+ * min(num_scans*horizon_scan, n)*4 floats; curvature, sharp_flags, less_sharp_flags = one entry per segmented point
+ * (lvf_lidar_extract_debug.n_segmented of them; size min(num_scans*horizon_scan, n)) */
+typedef struct lvf_edge_extract_debug {
+  int n_sharp_raw, n_less_sharp_raw;
+  float* sharp_raw; float* less_sharp_raw; float* curvature; int32_t* sharp_flags; int32_t* less_sharp_flags;
+} lvf_edge_extract_debug;
+/* lvf_lidar_extract (traj == NULL; frame_time and frame_pose7 are ignored) or lvf_lidar_extract_deskewed (traj given) with the edge picks
+ * made inside the same one-wait launch chain: ground_out / surf_out are that call's, bit for bit.  sharp_out / less_sharp_out are NEW device
+ * clouds in the robot frame: the raw picks, deskewed like lvf_cloud_deskew when traj is given, then lvf_cloud_transform by extrinsic7.  No
+ * voxel or outlier filter is applied to them (lvf_cloud_voxel_filter is there for callers who want one). */
+int lvf_lidar_extract_edges(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7,
+                            const lvf_edge_params* edge, const lvf_trajectory* traj, double frame_time, const double* frame_pose7,
+                            lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_cloud** sharp_out, lvf_cloud** less_sharp_out,
+                            lvf_lidar_extract_debug* dbg, lvf_edge_extract_debug* edge_dbg);
 /* kNN index / query scan straight from device-resident clouds (no host round trip) */
 int lvf_map_create_from_cloud(const lvf_cloud* c, float max_radius2, lvf_map** out);
 /* ... of n device-resident clouds in one call (lvf_map_create_batch's shared waits and launches, no upload): the old-frame maps of a set of
@@ -376,6 +406,43 @@ typedef struct lvf_icp_summary {
 int lvf_icp_solve(lvf_map* m, lvf_scan* s, const double* map_pose, const double* frame_pose, double* rpyxyz,
                   const lvf_icp_options* opt, lvf_icp_summary* summary);
 
+/* ---- LiDAR edge features: line association, point-to-line factor, the yaw-x-y solve over planes AND lines ----
+ * The reference declares edge clouds (lidar/feature.h:23-24, commented out) and has no edge functor at this commit: the semantics below
+ * are DECLARED (LOAM's published line test and point-to-line distance), restated in numpy in tests/edge_ref.py.
+ *
+ * Line association.  Per scan point: the float transform of lvf_knn3, its FIVE nearest map points by the same float d2 (ties by
+ * ascending map index) on the grid pyramid the map owns.  From the five float points as doubles, in neighbour order: centroid
+ * c = (plain sum) / 5, C = sum (x - c)(x - c)^T, eigenvalues l1 >= l2 >= l3; d = unit eigenvector of l1.  valid iff all five d2 < thr
+ * and l1 > 0 and l1 > min_eigen_ratio * l2 (LOAM: 3).  The line is stored as c and the projector I - d d^T (independent of d's sign).
+ * Outputs are owned by the scan, beside (not over) the plane correspondences of lvf_knn3 / lvf_icp_solve. */
+int lvf_edge_associate(lvf_map* m, lvf_scan* s, const double* pose, float thr, double min_eigen_ratio);
+/* idx5[Q][5], d2_5[Q][5], valid[Q], corr12[12][Q] (SoA rows: scan point xyz | centroid xyz | projector 00 01 02 11 12 22; zero for an
+ * invalid point).  Any output may be NULL.  idx5 / d2_5 are exact for valid points (as lvf_knn3's). */
+int lvf_scan_download_edges(lvf_scan* s, int32_t* idx5, float* d2_5, uint8_t* valid, double* corr12);
+
+/* LidarEdgeErrorYXY / LidarEdgeErrorRPZ <3,1,1,1> evaluated stand-alone for n blocks: r = weight * P (Twc2 p - c) with
+ * Twc2 = Twc1 * RpyxyzToSE3(rpyxyz) as LidarPlaneErrorYXY / RPZ form it (lidar_error.hpp:42-110); row k is the plane residual with normal
+ * P[k,:] and anchor c.  mode 0: parameters (pitch, roll, z); mode 1: (yaw, x, y).  Host arrays p[n][3], c[n][3], proj6[n][6]
+ * (00 01 02 11 12 22); residuals[n][3]; jacobians (may be NULL) [n][3][3] = d r_k / d parameter_j.  No loss function is applied. */
+int lvf_lidar_edge_evaluate(lvf_ctx* ctx, int mode, int n, const double* p, const double* c, const double* proj6, const double* Twc1,
+                            const double* rpyxyz, double weight, double* residuals, double* jacobians);
+
+typedef struct lvf_edge_icp_options {
+  float thr;               /* squared distance gate of the 5-NN */
+  double weight;           /* factor weight */
+  double huber_a;          /* HuberLoss width on the BLOCK (s = |r|^2, all three rows scaled by sqrt(rho'(s))); <= 0: TrivialLoss */
+  double min_eigen_ratio;  /* line test */
+} lvf_edge_icp_options;
+/* declared values (no reference value exists): the surf gate resolution^2 * 25, the surf weight (double)0.01f, HuberLoss(0.1), ratio 3 */
+void lvf_edge_icp_options_default(lvf_edge_icp_options* o, double lidar_resolution);
+/* lvf_icp_solve's (yaw, x, y) problem with point-to-line blocks beside the point-to-plane blocks: both associations run at frame_pose,
+ * then the same device-resident LM runs over planes and lines (an edge block adds three rows to the normal equations, rho(s) / 2 to the
+ * cost and one residual block).  opt->mode must be 1.  Either (map, scan) pair may be NULL; with the edge pair NULL this IS
+ * lvf_icp_solve.  num_residual_blocks = planes + lines (+ 1 with the prior). */
+int lvf_icp_solve_edges(lvf_map* map_surf, lvf_scan* scan_surf, lvf_map* map_edge, lvf_scan* scan_edge, const double* map_pose,
+                        const double* frame_pose, double* rpyxyz, const lvf_icp_options* opt, const lvf_edge_icp_options* edge_opt,
+                        lvf_icp_summary* summary);
+
 /* ---- one frame's scan-to-map update: Mapping::Optimize's body (mapping.cpp:147-178) / Mapping::Relocate (:251-300) ---- */
 typedef struct lvf_scan_match_options {
   float thr_ground, thr_surf;      /* resolution^2 * 100 / * 25 (association.cpp:285,343) */
@@ -399,6 +466,12 @@ void lvf_scan_match_options_default(lvf_scan_match_options* o, double lidar_reso
 int lvf_scan_match(lvf_map* map_ground, lvf_scan* scan_ground, lvf_map* map_surf, lvf_scan* scan_surf, const double* map_pose,
                    const double* frame_pose, const double* last_pose, const lvf_scan_match_options* opt,
                    lvf_scan_match_result* result);
+/* The same update with lvf_icp_solve_edges as the second sub-problem of every outer iteration (planes and lines together; result->surf
+ * and score_surf count both).  With the edge pair NULL this IS lvf_scan_match.  A single-frame chain: the pose is composed on the host
+ * between the sub-problems. */
+int lvf_scan_match_edges(lvf_map* map_ground, lvf_scan* scan_ground, lvf_map* map_surf, lvf_scan* scan_surf, lvf_map* map_edge,
+                         lvf_scan* scan_edge, const double* map_pose, const double* frame_pose, const double* last_pose,
+                         const lvf_scan_match_options* opt, const lvf_edge_icp_options* edge_opt, lvf_scan_match_result* result);
 
 /* Many scan-to-map updates of ONE context advanced side by side: the loop-closure candidates Relocator::Relocate evaluates one after the
  * other (relocator.cpp:196-206 -> Mapping::Relocate, mapping.cpp:251-300: no shared mutable state between candidates).  Every launch of

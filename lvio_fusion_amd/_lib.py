@@ -33,6 +33,10 @@ class IcpSummary(C.Structure):
                 ("num_iterations", C.c_int), ("num_successful_steps", C.c_int)]
 
 
+class EdgeIcpOptions(C.Structure):
+    _fields_ = [("thr", C.c_float), ("weight", C.c_double), ("huber_a", C.c_double), ("min_eigen_ratio", C.c_double)]
+
+
 class ScanMatchOptions(C.Structure):
     _fields_ = [("thr_ground", C.c_float), ("thr_surf", C.c_float), ("weight_ground", C.c_double), ("weight_surf", C.c_double),
                 ("huber_surf", C.c_double), ("prior_weight", C.c_double), ("outer_iterations", C.c_int), ("max_num_iterations", C.c_int)]
@@ -62,6 +66,15 @@ class LidarExtractDebug(C.Structure):
     _fields_ = [("n_filtered", C.c_int), ("n_segmented", C.c_int), ("n_ground_raw", C.c_int), ("n_surf_raw", C.c_int),
                 ("label_mat", C.POINTER(C.c_int32)), ("ground_mat", C.POINTER(C.c_int8)), ("range_mat", c_float_p), ("ground_raw", c_float_p),
                 ("surf_raw", c_float_p)]
+
+
+class EdgeParams(C.Structure):
+    _fields_ = [("edge_threshold", C.c_float), ("n_sharp", C.c_int), ("n_less_sharp", C.c_int)]
+
+
+class EdgeExtractDebug(C.Structure):
+    _fields_ = [("n_sharp_raw", C.c_int), ("n_less_sharp_raw", C.c_int), ("sharp_raw", c_float_p), ("less_sharp_raw", c_float_p), ("curvature", c_float_p),
+                ("sharp_flags", C.POINTER(C.c_int32)), ("less_sharp_flags", C.POINTER(C.c_int32))]
 
 
 class SolverOptions(C.Structure):
@@ -244,6 +257,11 @@ _SIGS = {
     "lvf_debug_sort_pairs_u32": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP]),
     "lvf_knn3_debug_stats2": (C.c_int, [_VP, _VP, c_double_p, C.c_float, c_int_p, C.c_int, c_float_p, C.POINTER(C.c_int)]),
     "lvf_icp_solve": (C.c_int, [_VP, _VP, c_double_p, c_double_p, c_double_p, C.POINTER(IcpOptions), C.POINTER(IcpSummary)]),
+    "lvf_edge_associate": (C.c_int, [_VP, _VP, c_double_p, C.c_float, C.c_double]),
+    "lvf_scan_download_edges": (C.c_int, [_VP, c_int_p, c_float_p, c_u8_p, c_double_p]),
+    "lvf_lidar_edge_evaluate": (C.c_int, [_VP, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p]),
+    "lvf_edge_icp_options_default": (None, [C.POINTER(EdgeIcpOptions), C.c_double]),
+    "lvf_icp_solve_edges": (C.c_int, [_VP, _VP, _VP, _VP, c_double_p, c_double_p, c_double_p, C.POINTER(IcpOptions), C.POINTER(EdgeIcpOptions), C.POINTER(IcpSummary)]),
     "lvf_cloud_create": (C.c_int, [_VP, c_float_p, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
     "lvf_cloud_destroy": (C.c_int, [_VP]),
     "lvf_cloud_size": (C.c_int, [_VP]),
@@ -270,8 +288,13 @@ _SIGS = {
     "lvf_cloud_deskew": (C.c_int, [_VP, _VP, C.c_double, c_double_p, C.c_double, c_double_p, C.POINTER(_VP)]),
     "lvf_lidar_extract_deskewed": (C.c_int, [_VP, c_float_p, C.c_int, C.c_int, C.POINTER(LidarParams), c_double_p, _VP, C.c_double, c_double_p, C.POINTER(_VP),
                                              C.POINTER(_VP), C.POINTER(LidarExtractDebug)]),
+    "lvf_edge_params_default": (None, [C.POINTER(EdgeParams)]),
+    "lvf_lidar_extract_edges": (C.c_int, [_VP, c_float_p, C.c_int, C.c_int, C.POINTER(LidarParams), c_double_p, C.POINTER(EdgeParams), _VP, C.c_double, c_double_p,
+                                          C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP), C.POINTER(LidarExtractDebug), C.POINTER(EdgeExtractDebug)]),
     "lvf_scan_match_options_default": (None, [C.POINTER(ScanMatchOptions), C.c_double]),
     "lvf_scan_match": (C.c_int, [_VP, _VP, _VP, _VP, c_double_p, c_double_p, c_double_p, C.POINTER(ScanMatchOptions), C.POINTER(ScanMatchResult)]),
+    "lvf_scan_match_edges": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, c_double_p, c_double_p, c_double_p, C.POINTER(ScanMatchOptions), C.POINTER(EdgeIcpOptions),
+                                       C.POINTER(ScanMatchResult)]),
     "lvf_scan_match_batch": (C.c_int, [_VP, C.POINTER(ScanMatchJob), C.c_int, C.POINTER(ScanMatchOptions), C.c_int, C.POINTER(ScanMatchResult), c_int_p]),
     "lvf_lidar_solve": (C.c_int, [_VP, c_double_p, C.POINTER(IcpOptions), C.POINTER(IcpSummary)]),
     "lvf_prior3_evaluate": (C.c_int, [_VP, C.c_int, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p]),

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, SolverOptions, SolverSummary, NavsatBcOptions, NavsatBcResult, FlowOptions, OrbOptions, Distortion
+from ._lib import LidarExtractDebug, LidarParams, WindowOptions, Camera, IcpOptions, IcpSummary, ScanMatchJob, ScanMatchOptions, ScanMatchResult, EdgeIcpOptions, EdgeParams, EdgeExtractDebug, SolverOptions, SolverSummary, NavsatBcOptions, NavsatBcResult, FlowOptions, OrbOptions, Distortion
 
 POSES, VEL, BA, BG, INV_DEPTH, W_VISUAL = range(6)
 IMU_BLOCK_SIZES = (7, 3, 3, 3, 7, 3, 3, 3)
@@ -783,6 +783,44 @@ def lidar_extract_deskewed(ctx, points, extrinsic, traj, frame_time, frame_pose,
         C.byref(hg), C.byref(hs), dbg))
 
 
+def edge_params(**kw):
+    p = EdgeParams()
+    _lib.lib().lvf_edge_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def lidar_extract_edges(ctx, points, extrinsic, edge=None, traj=None, frame_time=0.0, frame_pose=None, params=None, debug=False):
+    """lidar_extract (traj None) / lidar_extract_deskewed with the edge picks made inside the same launch chain:
+    (ground, surf, sharp, less_sharp Clouds[, debug dict]).  The debug dict is lidar_extract's plus sharp_raw / less_sharp_raw (the picks in the
+    sensor frame, before any deskew) and, per segmented point, curvature / sharp_flags / less_sharp_flags."""
+    ep = edge if edge is not None else edge_params()
+    fp = _d(frame_pose) if frame_pose is not None else None
+    prm = params if params is not None else lidar_params()
+    hsh, hls = C.c_void_p(), C.c_void_p()
+    ed = keep = None
+    if debug:
+        cap = max(prm.num_scans * prm.horizon_scan, 1)
+        keep = dict(sharp_raw=np.zeros((cap, 4), np.float32), less_sharp_raw=np.zeros((cap, 4), np.float32), curvature=np.zeros(cap, np.float32),
+                    sharp_flags=np.zeros(cap, np.int32), less_sharp_flags=np.zeros(cap, np.int32))
+        ed = EdgeExtractDebug()
+        ed.sharp_raw, ed.less_sharp_raw, ed.curvature = (keep[k].ctypes.data_as(_lib.c_float_p) for k in ("sharp_raw", "less_sharp_raw", "curvature"))
+        ed.sharp_flags, ed.less_sharp_flags = (keep[k].ctypes.data_as(C.POINTER(C.c_int32)) for k in ("sharp_flags", "less_sharp_flags"))
+    out = _lidar_extract(ctx, points, extrinsic, prm, debug, lambda a, prm_, e, hg, hs, dbg: ctx.L.lvf_lidar_extract_edges(
+        ctx.h, a.ctypes.data_as(_lib.c_float_p), a.shape[0], a.shape[1], C.byref(prm_), _dp(e), C.byref(ep), traj.h if traj is not None else None, float(frame_time),
+        _dp(fp) if fp is not None else None, C.byref(hg), C.byref(hs), C.byref(hsh), C.byref(hls), dbg, C.byref(ed) if ed is not None else None))
+    sh, ls = Cloud(ctx, _h=hsh), Cloud(ctx, _h=hls)
+    if not debug:
+        return out[0], out[1], sh, ls
+    d = out[2]
+    ns = d["n_segmented"]
+    d.update(sharp_raw=keep["sharp_raw"][:ed.n_sharp_raw].copy(), less_sharp_raw=keep["less_sharp_raw"][:ed.n_less_sharp_raw].copy(), curvature=keep["curvature"][:ns].copy(),
+             sharp_flags=keep["sharp_flags"][:ns].copy(), less_sharp_flags=keep["less_sharp_flags"][:ns].copy())
+    return out[0], out[1], sh, ls, d
+
+
 class Map:
     def __init__(self, ctx, xyz, max_radius2):
         self.ctx = ctx
@@ -852,6 +890,14 @@ class Scan:
         _chk(self.ctx.L.lvf_scan_download(self.h, _ip(idx), d2.ctypes.data_as(_lib.c_float_p), valid.ctypes.data_as(_lib.c_u8_p)))
         return idx, d2, valid
 
+    def download_edges(self):
+        """lvf_edge_associate's outputs: idx5 [Q][5], d2_5 [Q][5], valid [Q], scan point p [Q][3], centroid c [Q][3], projector proj6 [Q][6]
+        (00 01 02 11 12 22; p, c and proj6 read zero for an invalid point)"""
+        idx = np.empty((self.Q, 5), np.int32); d2 = np.empty((self.Q, 5), np.float32); valid = np.empty(self.Q, np.uint8)
+        corr = np.empty((12, self.Q), np.float64)
+        _chk(self.ctx.L.lvf_scan_download_edges(self.h, _ip(idx), d2.ctypes.data_as(_lib.c_float_p), valid.ctypes.data_as(_lib.c_u8_p), _dp(corr)))
+        return idx, d2, valid, np.ascontiguousarray(corr[0:3].T), np.ascontiguousarray(corr[3:6].T), np.ascontiguousarray(corr[6:12].T)
+
     def close(self):
         if self.h:
             self.ctx.L.lvf_scan_destroy(self.h)
@@ -871,6 +917,56 @@ def icp_solve(map_, scan, map_pose, frame_pose, rpyxyz, mode, thr, weight, huber
     summ = IcpSummary()
     _chk(map_.ctx.L.lvf_icp_solve(map_.h, scan.h, _dp(mp), _dp(fp), _dp(rpyxyz), C.byref(opt), C.byref(summ)))
     return summ
+
+
+def edge_associate(map_, scan, pose, thr, min_eigen_ratio=3.0):
+    """5-NN + line fit of every scan point against a map of edge points (lvf_edge_associate); results: scan.download_edges()"""
+    p = _d(pose)
+    _chk(map_.ctx.L.lvf_edge_associate(map_.h, scan.h, _dp(p), float(thr), float(min_eigen_ratio)))
+
+
+def lidar_edge_evaluate(ctx, mode, p, c, proj6, Twc1, rpyxyz, weight, jacobians=True):
+    """LidarEdgeErrorRPZ (mode 0) / LidarEdgeErrorYXY (mode 1) for n blocks: residuals [n][3], Jacobians [n][3][3] (row k, parameter j) or None"""
+    p, c, pr, T, x = _d(p).reshape(-1, 3), _d(c).reshape(-1, 3), _d(proj6).reshape(-1, 6), _d(Twc1), _d(rpyxyz)
+    n = p.shape[0]
+    r = np.empty((n, 3)); J = np.empty((n, 3, 3)) if jacobians else None
+    _chk(ctx.L.lvf_lidar_edge_evaluate(ctx.h, int(mode), n, _dp(p), _dp(c), _dp(pr), _dp(T), _dp(x), float(weight), _dp(r), _dp(J) if jacobians else None))
+    return r, J
+
+
+def edge_icp_options(resolution=0.2, **kw):
+    o = EdgeIcpOptions()
+    _lib.lib().lvf_edge_icp_options_default(C.byref(o), float(resolution))
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
+def icp_solve_edges(map_surf, scan_surf, map_edge, scan_edge, map_pose, frame_pose, rpyxyz, thr, weight, huber_a, edge_opt=None, prior_weight=0.0,
+                    max_num_iterations=4):
+    """The (yaw, x, y) solve over planes and lines (lvf_icp_solve_edges); either pair may be None.  rpyxyz is updated IN PLACE."""
+    assert rpyxyz.dtype == np.float64 and rpyxyz.flags.c_contiguous and rpyxyz.size == 6
+    mp, fp = _d(map_pose), _d(frame_pose)
+    opt = IcpOptions(1, float(thr), float(weight), float(huber_a), float(prior_weight), int(max_num_iterations))
+    summ = IcpSummary()
+    anyh = map_surf if map_surf is not None else map_edge
+    h = lambda x: x.h if x is not None else None
+    _chk(anyh.ctx.L.lvf_icp_solve_edges(h(map_surf), h(scan_surf), h(map_edge), h(scan_edge), _dp(mp), _dp(fp), _dp(rpyxyz), C.byref(opt),
+                                        C.byref(edge_opt) if edge_opt is not None else None, C.byref(summ)))
+    return summ
+
+
+def scan_match_edges(map_ground, scan_ground, map_surf, scan_surf, map_edge, scan_edge, map_pose, frame_pose, opt, edge_opt=None, last_pose=None):
+    """lvf_scan_match with planes and lines in the (yaw, x, y) sub-problem; with the edge pair None it is scan_match."""
+    mp, fp = _d(map_pose), _d(frame_pose)
+    lp = _d(last_pose) if last_pose is not None else None
+    res = ScanMatchResult()
+    anyh = next(x for x in (map_ground, map_surf, map_edge) if x is not None)
+    h = lambda x: x.h if x is not None else None
+    _chk(anyh.ctx.L.lvf_scan_match_edges(h(map_ground), h(scan_ground), h(map_surf), h(scan_surf), h(map_edge), h(scan_edge), _dp(mp), _dp(fp),
+                                         _dp(lp) if lp is not None else None, C.byref(opt), C.byref(edge_opt) if edge_opt is not None else None, C.byref(res)))
+    return res
 
 
 def scan_match_options(resolution=0.2, outer_iterations=1, prior_weight=0.0):

@@ -228,7 +228,7 @@ __host__ __device__ inline OriP find_start_end(const float4 first, const float4 
   return o;
 }
 // what the device-counted path keeps on the device between launches
-struct ExDev { int cnt[4]; /* filtered, segmented, ground picks, surf picks */ };
+struct ExDev { int cnt[6]; /* filtered, segmented, ground picks, surf picks, sharp picks, less-sharp picks */ };
 // the device-counted path's source of the orientations: the filtered cloud's first and last point (count on the device)
 struct OriSrc { const float4* filtered; const int* m_dev; double cycle; };
 __device__ __forceinline__ OriP ori_of(const OriSrc& src) {
@@ -332,9 +332,74 @@ __device__ __forceinline__ void pick_body(const int k, const int m, int Cn, cons
   pick_surf[k] = (in && !g && curv < 1.0f) ? 1 : 0;
 }
 
+// ---- edge picks: LOAM's greedy selection per (ring, sector), one wavefront each (384 waves at 64 x 1800; a sector is at most
+// horizon_scan / 6 + 1 points, a few per lane).  The sector's keys — the curvature of a candidate, -inf for everything else — sit in LDS;
+// a pick round is a wave arg-max of (curvature, lowest index) packed into 64 bits, reduced on the DPP path, then the lanes clear the
+// +-5 neighbourhood.  Every pick is a flag of its segmented point: the scan + compaction that follows gives the ascending order.  No atomics.
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
+  return (unsigned long long)__double_as_longlong(quad_perm<CTRL>(__longlong_as_double((long long)v)));      // (two v_mov_dpp: bits, no arithmetic)
+}
+__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {      // all 64 lanes active; every lane returns the maximum
+  v = umax64(v, dpp_u64<0xB1>(v));      // lanes [1,0,3,2]
+  v = umax64(v, dpp_u64<0x4E>(v));      // lanes [2,3,0,1]
+  v = umax64(v, dpp_u64<0x141>(v));     // row_half_mirror
+  v = umax64(v, dpp_u64<0x140>(v));     // row_mirror
+  const double d = __longlong_as_double((long long)v);
+  const unsigned long long a = (unsigned long long)__double_as_longlong(lane_bcast(d, 0)), b = (unsigned long long)__double_as_longlong(lane_bcast(d, 16));
+  const unsigned long long c = (unsigned long long)__double_as_longlong(lane_bcast(d, 32)), e = (unsigned long long)__double_as_longlong(lane_bcast(d, 48));
+  return umax64(umax64(a, b), umax64(c, e));
+}
+struct EdgePickP { float thr; int n_sharp, n_less, cap; };      // cap: floats of LDS per workgroup (>= the longest sector)
+__global__ __launch_bounds__(64) void k_ex_edge_pick(int m, const int* __restrict__ m_dev, int Cn, const float* __restrict__ curv, const int* __restrict__ seg_ground,
+                                                     const int* __restrict__ pixpos, const EdgePickP E, int* __restrict__ pick_sharp, int* __restrict__ pick_less) {
+  extern __shared__ float key[];
+  if (m_dev) m = min(m, *m_dev);
+  const int row = blockIdx.x / 6, j = blockIdx.x - 6 * row, lane = threadIdx.x;
+  const int start = pixpos[(size_t)row * Cn] - 1 + 5, end = pixpos[(size_t)(row + 1) * Cn] - 1 - 5;   // start/end_ring_index, as pick_body
+  const int sp = (start * (6 - j) + end * j) / 6, ep = (start * (5 - j) + end * (j + 1)) / 6 - 1;
+  if (!(sp < ep) || sp < 0 || ep >= m) return;                       // (uniform) an empty sector contributes nothing
+  const int len = min(ep - sp + 1, E.cap);
+  for (int i = lane; i < len; i += 64) {
+    const float c = curv[sp + i];
+    key[i] = (seg_ground[sp + i] == 0 && c >= E.thr) ? c : -INFINITY;
+  }
+  __syncthreads();
+  for (int round = 0; round < E.n_less; ++round) {
+    unsigned long long best = 0ull;                                  // 0: no candidate
+    for (int i = lane; i < len; i += 64) {
+      const float c = key[i];
+      if (c == -INFINITY) continue;
+      unsigned u = __float_as_uint(c);
+      u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                // order-preserving map of the float
+      best = umax64(best, ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (unsigned)i));      // a tie goes to the lower index
+    }
+    best = wave_max_u64(best);
+    if (best == 0ull) break;                                         // (uniform)
+    const int at = (int)(0xffffffffu - (unsigned)(best & 0xffffffffull));
+    if (lane == 0) { pick_less[sp + at] = 1; if (round < E.n_sharp) pick_sharp[sp + at] = 1; }
+    const int z = at - 5 + lane;
+    if (lane < 11 && z >= 0 && z < len) key[z] = -INFINITY;
+    __syncthreads();
+  }
+}
+
 }  // namespace lvf
 
 using namespace lvf;
+
+// what lvf_lidar_extract_edges adds to a chain (null: exactly lvf_lidar_extract[_deskewed]'s launches)
+struct EdgeReq { lvf_edge_params prm; lvf_cloud** sharp_out; lvf_cloud** less_out; lvf_edge_extract_debug* dbg; };
+// pick_sharp and pick_less are the two halves of ONE block (pick_less = pick_sharp + capacity): one memset clears both
+static int launch_edge_pick(hipStream_t s, int cap_m, const int* m_dev, int R, int Cn, const float* curv, const int* seg_ground, const int* pixpos, const lvf_edge_params& e,
+                            int* pick_sharp, int* pick_less) {
+  LVF_HIP(hipMemsetAsync(pick_sharp, 0, (size_t)(pick_less - pick_sharp) * 8, s));      // both flag arrays: halves of one block, pick_less behind pick_sharp
+  const EdgePickP E{e.edge_threshold, e.n_sharp, e.n_less_sharp, Cn / 6 + 8};
+  hipLaunchKernelGGL(k_ex_edge_pick, dim3(R * 6), dim3(64), (size_t)4 * E.cap, s, cap_m, m_dev, Cn, curv, seg_ground, pixpos, E, pick_sharp, pick_less);
+  LVF_HIP(hipGetLastError());
+  return LVF_OK;
+}
 
 static std::atomic<int> g_extract_host_counts{[] { const char* e = std::getenv("LVF_EXTRACT_HOST_COUNTS"); return (e && e[0] == '1') ? 1 : 0; }()};
 static std::atomic<int> g_extract_fallbacks{0};      // scans the device-counted path handed to the host-counted one (lvf_debug_extract_fallbacks)
@@ -344,7 +409,7 @@ static std::atomic<int> g_extract_fallbacks{0};      // scans the device-counted
 // dk (here and in the device-counted path; null: none, exactly lvf_lidar_extract's launches): the deskew of the two pick clouds, in place, where
 // AdjustDistortion's TODO stands — nothing between that line and the PCL tail reads a coordinate (association.cpp:144-208)
 static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7, const ExP& P,
-                                const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg) {
+                                const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg, const EdgeReq* er = nullptr) {
   hipStream_t s = ctx->stream;
   const int npix = P.R * P.Cn;
   // ---- Preprocess
@@ -358,7 +423,7 @@ static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int st
     LVF_HIP(hipGetLastError());
     LVF_TRY(compact_points(ctx, packed.p, n, flags.p, &filtered));
   }
-  struct Guard { lvf_cloud* c[8]; int k = 0; ~Guard() { for (int i = 0; i < k; ++i) if (c[i]) lvf_cloud_destroy(c[i]); } void add(lvf_cloud* x) { c[k++] = x; } } guard;
+  struct Guard { lvf_cloud* c[12]; int k = 0; ~Guard() { for (int i = 0; i < k; ++i) if (c[i]) lvf_cloud_destroy(c[i]); } void add(lvf_cloud* x) { c[k++] = x; } } guard;
   guard.add(filtered);
   const int m = filtered->n;
   // ---- projection, ground, segmentation
@@ -408,6 +473,24 @@ static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int st
   }
   LVF_TRY(compact_points(ctx, seg.p, num, pick_g.p, &g_raw)); guard.add(g_raw);
   LVF_TRY(compact_points(ctx, seg.p, num, pick_s.p, &s_raw)); guard.add(s_raw);
+  lvf_cloud* e_raw[2] = {nullptr, nullptr};      // sharp, less sharp: the raw picks
+  if (er) {
+    DevBuf<int> pick_both;                       // sharp flags | less-sharp flags
+    LVF_TRY(pick_both.alloc((size_t)2 * mm));
+    int* const pick_e[2] = {pick_both.p, pick_both.p + mm};
+    LVF_TRY(launch_edge_pick(s, num, nullptr, P.R, P.Cn, curv.p, seg_ground.p, pos.p, er->prm, pick_e[0], pick_e[1]));
+    for (int k = 0; k < 2; ++k) { LVF_TRY(compact_points(ctx, seg.p, num, pick_e[k], &e_raw[k])); guard.add(e_raw[k]); }
+    if (lvf_edge_extract_debug* ed = er->dbg) {
+      ed->n_sharp_raw = e_raw[0]->n; ed->n_less_sharp_raw = e_raw[1]->n;
+      if (ed->sharp_raw && e_raw[0]->n) LVF_HIP(hipMemcpyAsync(ed->sharp_raw, e_raw[0]->pts.p, (size_t)16 * e_raw[0]->n, hipMemcpyDeviceToHost, s));
+      if (ed->less_sharp_raw && e_raw[1]->n) LVF_HIP(hipMemcpyAsync(ed->less_sharp_raw, e_raw[1]->pts.p, (size_t)16 * e_raw[1]->n, hipMemcpyDeviceToHost, s));
+      if (ed->curvature && num) LVF_HIP(hipMemcpyAsync(ed->curvature, curv.p, (size_t)4 * num, hipMemcpyDeviceToHost, s));
+      if (ed->sharp_flags && num) LVF_HIP(hipMemcpyAsync(ed->sharp_flags, pick_e[0], (size_t)4 * num, hipMemcpyDeviceToHost, s));
+      if (ed->less_sharp_flags && num) LVF_HIP(hipMemcpyAsync(ed->less_sharp_flags, pick_e[1], (size_t)4 * num, hipMemcpyDeviceToHost, s));
+      LVF_HIP(hipStreamSynchronize(s));
+    }
+    if (dk) for (int k = 0; k < 2; ++k) LVF_TRY(deskew_launch(s, e_raw[k]->n, nullptr, e_raw[k]->pts.p, e_raw[k]->pts.p, *dk));
+  }
   if (dk) {
     LVF_TRY(deskew_launch(s, g_raw->n, nullptr, g_raw->pts.p, g_raw->pts.p, *dk));
     LVF_TRY(deskew_launch(s, s_raw->n, nullptr, s_raw->pts.p, s_raw->pts.p, *dk));
@@ -428,8 +511,15 @@ static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int st
   LVF_TRY(lvf_cloud_voxel_filter(g_raw, 2 * prm->resolution, &gv)); guard.add(gv);
   LVF_TRY(lvf_cloud_segment_plane(gv, 0.1f * prm->resolution, 100, prm->ransac_seed, &gp, nullptr, nullptr)); guard.add(gp);
   LVF_TRY(lvf_cloud_transform(gp, extrinsic7, ground_out));
-  const int rc = lvf_cloud_transform(sr, extrinsic7, surf_out);
-  if (rc != LVF_OK) { lvf_cloud_destroy(*ground_out); *ground_out = nullptr; return rc; }
+  int rc = lvf_cloud_transform(sr, extrinsic7, surf_out);
+  if (rc == LVF_OK && er) rc = lvf_cloud_transform(e_raw[0], extrinsic7, er->sharp_out);
+  if (rc == LVF_OK && er) rc = lvf_cloud_transform(e_raw[1], extrinsic7, er->less_out);
+  if (rc != LVF_OK) {
+    lvf_cloud_destroy(*ground_out); *ground_out = nullptr;
+    if (*surf_out) { lvf_cloud_destroy(*surf_out); *surf_out = nullptr; }
+    if (er && *er->sharp_out) { lvf_cloud_destroy(*er->sharp_out); *er->sharp_out = nullptr; }
+    return rc;
+  }
   LVF_HIP(hipStreamSynchronize(s));
   return LVF_OK;
 }
@@ -442,7 +532,7 @@ static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int st
 // (Deskewed picks may leave the range gate's ball the tail's plan is sized from.  The tail derives its voxel keys and its radius grid from the
 // MEASURED box of what it is given and raises its verdict when they do not fit the plan: such a scan goes through the host-counted path.)
 static int extract_device_counted(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7, const ExP& P,
-                                  const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg, bool* done) {
+                                  const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg, bool* done, const EdgeReq* er = nullptr) {
   hipStream_t s = ctx->stream;
   *done = false;
   static const bool timing = std::getenv("LVF_EXTRACT_TIMING") != nullptr;
@@ -510,8 +600,21 @@ static int extract_device_counted(lvf_ctx* ctx, const float* points, int n, int 
   LVF_TRY(device_scan1_on(ctx, s, 0, pick_s.p, capseg, num_dev, nullptr, &ex->cnt[3], seg.p, s_raw.p));
   if (dk) LVF_TRY(deskew_launch(s, capseg, &ex->cnt[3], s_raw.p, s_raw.p, *dk));
   LVF_TRY(dc_tail_run(ctx, plan, q, s_raw.p, &ex->cnt[3], g_raw.p, &ex->cnt[2], (unsigned long long)prm->ransac_seed, tail_state, tail_keep, surf_pre, ground_pre));
-  // ---- the one read-back: the four counts here, the tail's four and its verdict
-  int hc[4] = {0, 0, 0, 0}, ht[5] = {0, 0, 0, 0, 0};
+  // ---- the edge picks, behind the tails on this stream (nothing of lvf_lidar_extract's chain waits for them): flags, two compactions, the deskew
+  DevBuf<int> pick_both; DevBuf<float4> e_raw[2], e_dk[2];      // pick_both: sharp flags | less-sharp flags
+  int* pick_e[2] = {nullptr, nullptr};
+  if (er) {
+    LVF_TRY(pick_both.alloc((size_t)2 * mm));
+    pick_e[0] = pick_both.p; pick_e[1] = pick_both.p + mm;
+    for (int k = 0; k < 2; ++k) { LVF_TRY(e_raw[k].alloc(mm)); if (dk) LVF_TRY(e_dk[k].alloc(mm)); }
+    LVF_TRY(launch_edge_pick(s, capseg, num_dev, P.R, P.Cn, curv.p, seg_ground.p, pos.p, er->prm, pick_e[0], pick_e[1]));
+    for (int k = 0; k < 2; ++k) {
+      LVF_TRY(device_scan1_on(ctx, s, 0, pick_e[k], capseg, num_dev, nullptr, &ex->cnt[4 + k], seg.p, e_raw[k].p));
+      if (dk) LVF_TRY(deskew_launch(s, capseg, &ex->cnt[4 + k], e_raw[k].p, e_dk[k].p, *dk));      // (out of place: the tap keeps the raw picks)
+    }
+  }
+  // ---- the one read-back: the six counts here, the tail's four and its verdict
+  int hc[6] = {0, 0, 0, 0, 0, 0}, ht[5] = {0, 0, 0, 0, 0};
   {
     LVF_TRY(ctx->mailbox.reserve(4096));
     char* mb = ctx->mailbox.p;
@@ -533,10 +636,27 @@ static int extract_device_counted(lvf_ctx* ctx, const float* points, int n, int 
     if (dbg->surf_raw && hc[3]) LVF_HIP(hipMemcpyAsync(dbg->surf_raw, s_raw.p, (size_t)16 * hc[3], hipMemcpyDeviceToHost, s));
     LVF_HIP(hipStreamSynchronize(s));
   }
+  if (er && er->dbg) {
+    lvf_edge_extract_debug* ed = er->dbg;
+    ed->n_sharp_raw = hc[4]; ed->n_less_sharp_raw = hc[5];
+    if (ed->sharp_raw && hc[4]) LVF_HIP(hipMemcpyAsync(ed->sharp_raw, e_raw[0].p, (size_t)16 * hc[4], hipMemcpyDeviceToHost, s));
+    if (ed->less_sharp_raw && hc[5]) LVF_HIP(hipMemcpyAsync(ed->less_sharp_raw, e_raw[1].p, (size_t)16 * hc[5], hipMemcpyDeviceToHost, s));
+    if (ed->curvature && hc[1]) LVF_HIP(hipMemcpyAsync(ed->curvature, curv.p, (size_t)4 * hc[1], hipMemcpyDeviceToHost, s));
+    if (ed->sharp_flags && hc[1]) LVF_HIP(hipMemcpyAsync(ed->sharp_flags, pick_e[0], (size_t)4 * hc[1], hipMemcpyDeviceToHost, s));
+    if (ed->less_sharp_flags && hc[1]) LVF_HIP(hipMemcpyAsync(ed->less_sharp_flags, pick_e[1], (size_t)4 * hc[1], hipMemcpyDeviceToHost, s));
+    LVF_HIP(hipStreamSynchronize(s));
+  }
   // ---- Sensor2Robot (association.cpp:236-247), sized exactly; consumed on the same stream, nothing to wait for
   LVF_TRY(transform_points(ctx, ground_pre.p, ht[3], extrinsic7, ground_out));
-  const int rc = transform_points(ctx, surf_pre.p, ht[1], extrinsic7, surf_out);
-  if (rc != LVF_OK) { lvf_cloud_destroy(*ground_out); *ground_out = nullptr; return rc; }
+  int rc = transform_points(ctx, surf_pre.p, ht[1], extrinsic7, surf_out);
+  if (rc == LVF_OK && er) rc = transform_points(ctx, (dk ? e_dk[0] : e_raw[0]).p, hc[4], extrinsic7, er->sharp_out);
+  if (rc == LVF_OK && er) rc = transform_points(ctx, (dk ? e_dk[1] : e_raw[1]).p, hc[5], extrinsic7, er->less_out);
+  if (rc != LVF_OK) {
+    lvf_cloud_destroy(*ground_out); *ground_out = nullptr;
+    if (*surf_out) { lvf_cloud_destroy(*surf_out); *surf_out = nullptr; }
+    if (er && *er->sharp_out) { lvf_cloud_destroy(*er->sharp_out); *er->sharp_out = nullptr; }
+    return rc;
+  }
   *done = true;
   return LVF_OK;
 }
@@ -551,7 +671,7 @@ extern "C" void lvf_lidar_params_default(lvf_lidar_params* p) {
 // lvf_lidar_extract and lvf_lidar_extract_deskewed (traj != null)
 static int extract_entry(const char* who, lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7,
                          const lvf_trajectory* traj, double frame_time, const double* frame_pose7, lvf_cloud** ground_out, lvf_cloud** surf_out,
-                         lvf_lidar_extract_debug* dbg) {
+                         lvf_lidar_extract_debug* dbg, const EdgeReq* er = nullptr) {
   LVF_REQUIRE(ctx && prm && extrinsic7 && ground_out && surf_out, "%s: null argument", who);
   LVF_REQUIRE(n >= 0 && (n == 0 || points) && stride_floats >= 3, "%s: bad scan (n=%d stride=%d)", who, n, stride_floats);
   LVF_REQUIRE(prm->num_scans > 1 && prm->num_scans <= 64 && prm->horizon_scan > 0 && prm->ground_rows >= 0 && prm->ground_rows < prm->num_scans,
@@ -575,11 +695,11 @@ static int extract_entry(const char* who, lvf_ctx* ctx, const float* points, int
   *ground_out = nullptr; *surf_out = nullptr;
   if (n > 0 && !g_extract_host_counts.load()) {
     bool done = false;
-    LVF_TRY(extract_device_counted(ctx, points, n, stride_floats, prm, extrinsic7, P, dk, ground_out, surf_out, dbg, &done));
+    LVF_TRY(extract_device_counted(ctx, points, n, stride_floats, prm, extrinsic7, P, dk, ground_out, surf_out, dbg, &done, er));
     if (done) return LVF_OK;
     g_extract_fallbacks.fetch_add(1);
   }
-  return extract_host_counted(ctx, points, n, stride_floats, prm, extrinsic7, P, dk, ground_out, surf_out, dbg);
+  return extract_host_counted(ctx, points, n, stride_floats, prm, extrinsic7, P, dk, ground_out, surf_out, dbg, er);
 }
 
 extern "C" {
@@ -594,6 +714,25 @@ int lvf_lidar_extract_deskewed(lvf_ctx* ctx, const float* points, int n, int str
                                lvf_lidar_extract_debug* dbg) {
   LVF_REQUIRE(traj, "lvf_lidar_extract_deskewed: null trajectory");
   return extract_entry("lvf_lidar_extract_deskewed", ctx, points, n, stride_floats, prm, extrinsic7, traj, frame_time, frame_pose7, ground_out, surf_out, dbg);
+}
+
+void lvf_edge_params_default(lvf_edge_params* p) {
+  if (!p) return;
+  p->edge_threshold = 1.0f;      // the complement of the surf test (association.cpp:202): surf and edge sets are disjoint
+  p->n_sharp = 2; p->n_less_sharp = 20;      // LOAM's counts per sector
+}
+
+int lvf_lidar_extract_edges(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7,
+                            const lvf_edge_params* edge, const lvf_trajectory* traj, double frame_time, const double* frame_pose7, lvf_cloud** ground_out,
+                            lvf_cloud** surf_out, lvf_cloud** sharp_out, lvf_cloud** less_sharp_out, lvf_lidar_extract_debug* dbg, lvf_edge_extract_debug* edge_dbg) {
+  LVF_REQUIRE(edge && sharp_out && less_sharp_out, "lvf_lidar_extract_edges: null argument");
+  LVF_REQUIRE(edge->n_sharp >= 0 && edge->n_less_sharp >= edge->n_sharp && !(edge->edge_threshold != edge->edge_threshold),
+              "lvf_lidar_extract_edges: bad edge parameters (0 <= n_sharp <= n_less_sharp, a threshold that is a number)");
+  LVF_REQUIRE(!traj || frame_pose7, "lvf_lidar_extract_edges: a trajectory needs frame_pose7");
+  *sharp_out = nullptr; *less_sharp_out = nullptr;
+  if (edge_dbg) edge_dbg->n_sharp_raw = edge_dbg->n_less_sharp_raw = 0;
+  const EdgeReq er{*edge, sharp_out, less_sharp_out, edge_dbg};
+  return extract_entry("lvf_lidar_extract_edges", ctx, points, n, stride_floats, prm, extrinsic7, traj, frame_time, frame_pose7, ground_out, surf_out, dbg, &er);
 }
 
 // Test / A-B hook: 1 = lvf_lidar_extract takes the host-counted path (process-wide).  Not part of the reference surface.

@@ -204,6 +204,98 @@ __global__ __launch_bounds__(kTI) void k_icp_eval_b(const IcpJob* __restrict__ j
   icp_eval_body<CAND, WITH_J>(blockIdx.x, nbx, J.Q, J.P, J.PA, J.N, J.valid, J.args, &D.icp);
 }
 
+// ---- planes AND lines (lvf_icp_solve_edges): the pass of k_icp_eval striding over the point-to-plane correspondences and then over the
+// point-to-line blocks of the edge scan (EC = p | c | projector, SoA [12][Qe]).  An edge block adds its three rows, scaled by sqrt(rho'(s))
+// with s = |r|^2 as Ceres applies a loss to a block, to H and g, rho(s) / 2 to the cost and 1 to the block count.  Same eleven
+// accumulators, same ticket tail, icp_step / icp_decide as they are: one launch per LM iteration.
+struct EdgeArgs { double weight, huber; };
+template <bool CAND, bool WITH_J>
+__global__ __launch_bounds__(kTI) void k_icp_eval_pe(int Q, const double* __restrict__ P, const double* __restrict__ PA, const double* __restrict__ N,
+                                                     const uint8_t* __restrict__ valid, int Qe, const double* __restrict__ EC,
+                                                     const uint8_t* __restrict__ evalid, const IcpArgs args, const EdgeArgs eargs, IcpDev* __restrict__ dev) {
+  __shared__ LidarU U, UE;
+  if (dev->done) return;                              // uniform: the flag is only written by single-thread kernels
+  const int bx = blockIdx.x, nbx = gridDim.x;
+  if (threadIdx.x == 0) {
+    LidarArgs a;
+    for (int k = 0; k < 7; ++k) a.Twc1[k] = args.Twc1[k];
+    for (int k = 0; k < 6; ++k) a.rpyxyz[k] = dev->rpyxyz[k];
+    int i0, i1, i2;
+    param_slots(args.mode, i0, i1, i2);
+    const double* x = CAND ? dev->xc : dev->x;
+    a.rpyxyz[i0] = x[0]; a.rpyxyz[i1] = x[1]; a.rpyxyz[i2] = x[2];
+    a.weight = args.weight; a.mode = args.mode;
+    derive_lidar(a, U);
+    UE = U; UE.w = eargs.weight;                      // the same Twc2, the edge factor's weight
+  }
+  __syncthreads();
+  double v[11];
+#pragma unroll
+  for (int q = 0; q < 11; ++q) v[q] = 0.0;
+  for (int i = bx * kTI + threadIdx.x; i < Q; i += nbx * kTI) {
+    if (valid && !valid[i]) continue;
+    if (WITH_J) v[10] += 1.0;
+    const double pp[3] = {P[i], P[Q + i], P[2 * Q + i]}, qa[3] = {PA[i], PA[Q + i], PA[2 * Q + i]}, nn[3] = {N[i], N[Q + i], N[2 * Q + i]};
+    double r, J[3];
+    lidar_point(U, args.mode, pp, qa, nn, r, J);
+    double rho;
+    const double sc = robust_scale(args.huber, r * r, rho);
+    v[9] += 0.5 * rho;
+    if (WITH_J) {
+      const double rs = sc * r, j0 = sc * J[0], j1 = sc * J[1], j2 = sc * J[2];
+      v[0] += j0 * j0; v[1] += j1 * j0; v[2] += j1 * j1; v[3] += j2 * j0; v[4] += j2 * j1; v[5] += j2 * j2;
+      v[6] += j0 * rs; v[7] += j1 * rs; v[8] += j2 * rs;
+    }
+  }
+  for (int i = bx * kTI + threadIdx.x; i < Qe; i += nbx * kTI) {
+    if (!evalid[i]) continue;
+    if (WITH_J) v[10] += 1.0;
+    double pp[3], cc[3], pr[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { pp[k] = EC[(size_t)k * Qe + i]; cc[k] = EC[(size_t)(3 + k) * Qe + i]; }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) pr[k] = EC[(size_t)(6 + k) * Qe + i];
+    double r[3], J[3][3];
+    lidar_edge_block(UE, args.mode, pp, cc, pr, r, J);
+    double rho;
+    const double sc = robust_scale(eargs.huber, (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2], rho);
+    v[9] += 0.5 * rho;
+    if (WITH_J) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double rs = sc * r[k], j0 = sc * J[k][0], j1 = sc * J[k][1], j2 = sc * J[k][2];
+        v[0] += j0 * j0; v[1] += j1 * j0; v[2] += j1 * j1; v[3] += j2 * j0; v[4] += j2 * j1; v[5] += j2 * j2;
+        v[6] += j0 * rs; v[7] += j1 * rs; v[8] += j2 * rs;
+      }
+    }
+  }
+  __shared__ double s_part[kTI / 64][11];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = WITH_J ? 0 : 9; q < (WITH_J ? 11 : 10); ++q) {
+    const double s = wave_sum(v[q]);
+    if (lane == 0) s_part[wid][q] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 11 && (WITH_J || threadIdx.x == 9)) {
+    double s = 0.0;
+#pragma unroll
+    for (int w2 = 0; w2 < kTI / 64; ++w2) s += s_part[w2][threadIdx.x];
+    if (s != 0.0) atomicAdd(CAND ? &dev->accC[threadIdx.x] : &dev->acc[threadIdx.x], s);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {                             // the last workgroup runs the scalar tail (k_icp_eval's)
+    __threadfence();
+    const unsigned t = atomicAdd(&dev->ticket, 1u);
+    if (t == (unsigned)nbx - 1u) {
+      __threadfence();
+      dev->ticket = 0;
+      if (CAND) icp_decide(args, dev, WITH_J);
+      if (WITH_J) icp_step(args, dev);
+    }
+  }
+}
+
 }  // namespace lvf
 
 namespace lvf {
@@ -282,6 +374,71 @@ extern "C" int lvf_icp_solve(lvf_map* m, lvf_scan* sc, const double* map_pose, c
   // 3. LM iterations, all on device
   LVF_TRY(run_lm(q, Q, P, PA, N, sc->valid.p, a, dev, &h));
   rpyxyz[i0] = h.x[0]; rpyxyz[i1] = h.x[1]; rpyxyz[i2] = h.x[2];
+  summary->initial_cost = h.initial_cost; summary->final_cost = h.cost_cur;
+  summary->num_residual_blocks = h.nvalid + (opt->prior_weight > 0.0 ? 1 : 0);
+  summary->num_iterations = h.iters; summary->num_successful_steps = h.successes;
+  return LVF_OK;
+}
+
+extern "C" void lvf_edge_icp_options_default(lvf_edge_icp_options* o, double resolution) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  // declared values — the reference has no edge functor: the surf gate (association.cpp:343), the surf weight (frame.cpp:15, a float), the surf
+  // loss (association.cpp:330) and LOAM's published line test
+  o->thr = (float)(resolution * resolution * 25.0);
+  o->weight = (double)0.01f;
+  o->huber_a = 0.1;
+  o->min_eigen_ratio = 3.0;
+}
+
+extern "C" int lvf_icp_solve_edges(lvf_map* ms, lvf_scan* ss, lvf_map* me, lvf_scan* se, const double* map_pose, const double* frame_pose, double* rpyxyz,
+                                   const lvf_icp_options* opt, const lvf_edge_icp_options* eopt, lvf_icp_summary* summary) {
+  LVF_REQUIRE(map_pose && frame_pose && rpyxyz && opt && summary, "lvf_icp_solve_edges: null argument");
+  LVF_REQUIRE((ms != nullptr) == (ss != nullptr) && (me != nullptr) == (se != nullptr), "lvf_icp_solve_edges: a map and its scan must be given together");
+  LVF_REQUIRE(ms || me, "lvf_icp_solve_edges: neither a surf pair nor an edge pair");
+  LVF_REQUIRE(opt->mode == 1, "lvf_icp_solve_edges: the (yaw, x, y) problem: opt->mode must be 1");
+  if (!me) return lvf_icp_solve(ms, ss, map_pose, frame_pose, rpyxyz, opt, summary);
+  LVF_REQUIRE(eopt, "lvf_icp_solve_edges: an edge pair needs edge_opt");
+  LVF_REQUIRE(opt->thr > 0.0f && opt->max_num_iterations >= 0, "lvf_icp_solve_edges: bad options");
+  LVF_REQUIRE(eopt->thr > 0.0f && eopt->min_eigen_ratio >= 1.0 && std::isfinite(eopt->min_eigen_ratio), "lvf_icp_solve_edges: bad edge options");
+  lvf_ctx* ctx = me->ctx;
+  LVF_REQUIRE(se->ctx == ctx && (!ms || (ms->ctx == ctx && ss->ctx == ctx)), "lvf_icp_solve_edges: handles of different contexts");
+  LVF_REQUIRE(ss != se, "lvf_icp_solve_edges: one scan handle as surf AND edge");
+  LVF_TRY(lvf::enter(ctx));
+  hipStream_t q = ctx->stream;
+  std::memset(summary, 0, sizeof(*summary));
+  // both associations at the frame's current pose, one launch each
+  const int Q = ss ? ss->Q : 0, Qe = se->Q;
+  if (ss) {
+    if (ss->corr.n < (size_t)9 * std::max(Q, 1)) LVF_TRY(ss->corr.alloc((size_t)9 * std::max(Q, 1)));
+    LVF_TRY(launch_knn3_build(ms, ss, frame_pose, opt->thr, ss->corr.p));
+  }
+  LVF_TRY(launch_edge_associate(me, se, frame_pose, eopt->thr, eopt->min_eigen_ratio));
+  // the solver state lives with the edge scan
+  if (!se->icp_dev.p) LVF_TRY(se->icp_dev.alloc(sizeof(IcpDev)));
+  LVF_TRY(se->icp_host.reserve(sizeof(IcpDev)));
+  IcpDev& h = *reinterpret_cast<IcpDev*>(se->icp_host.p);
+  init_dev(h, 1, rpyxyz);
+  h.count_valid = 1;
+  IcpDev* dev = reinterpret_cast<IcpDev*>(se->icp_dev.p);
+  LVF_HIP(hipMemcpyAsync(dev, &h, sizeof(h), hipMemcpyHostToDevice, q));
+  const IcpArgs a = make_args(map_pose, opt);
+  const EdgeArgs ea{eopt->weight, eopt->huber_a};
+  const double* P = ss ? ss->corr.p : nullptr; const double* PA = P ? P + (size_t)3 * Q : nullptr; const double* N = P ? PA + (size_t)3 * Q : nullptr;
+  const uint8_t* valid = ss ? ss->valid.p : nullptr;
+  const int total = Q + Qe;
+  const dim3 grid(icp_blocks(total)), block(kTI);
+  if (total > 0) hipLaunchKernelGGL((k_icp_eval_pe<false, true>), grid, block, 0, q, Q, P, PA, N, valid, Qe, se->ecorr.p, se->evalid.p, a, ea, dev);
+  else hipLaunchKernelGGL(k_icp_step, dim3(1), dim3(1), 0, q, a, dev);
+  for (int it = 0; it < a.max_iters; ++it) {
+    if (total <= 0) hipLaunchKernelGGL(k_icp_decide_step, dim3(1), dim3(1), 0, q, a, dev);
+    else if (it + 1 == a.max_iters) hipLaunchKernelGGL((k_icp_eval_pe<true, false>), grid, block, 0, q, Q, P, PA, N, valid, Qe, se->ecorr.p, se->evalid.p, a, ea, dev);
+    else hipLaunchKernelGGL((k_icp_eval_pe<true, true>), grid, block, 0, q, Q, P, PA, N, valid, Qe, se->ecorr.p, se->evalid.p, a, ea, dev);
+  }
+  LVF_HIP(hipGetLastError());
+  LVF_HIP(hipMemcpyAsync(&h, dev, sizeof(IcpDev), hipMemcpyDeviceToHost, q));
+  LVF_HIP(hipStreamSynchronize(q));
+  rpyxyz[0] = h.x[0]; rpyxyz[3] = h.x[1]; rpyxyz[4] = h.x[2];
   summary->initial_cost = h.initial_cost; summary->final_cost = h.cost_cur;
   summary->num_residual_blocks = h.nvalid + (opt->prior_weight > 0.0 ? 1 : 0);
   summary->num_iterations = h.iters; summary->num_successful_steps = h.successes;

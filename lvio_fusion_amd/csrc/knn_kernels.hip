@@ -527,6 +527,195 @@ __global__ __launch_bounds__(kB) void k_knn3_b(const KnnJob* __restrict__ jobs, 
   knn3_body<false, true>(blockIdx.x, J.Q, J.scan, D.tf, J.L, J.thr, J.idx, J.d2, J.valid, nullptr, J.map_raw, J.corr);
 }
 
+// ---- line association (lvf_edge_associate): exact 5-NN on the same grid pyramid + the principal-axis fit of the five neighbours ----
+// The search is k_knn3's — eight lanes per query, the shell schedule, the pruning radius, the cooperative scan of long ranges — written out
+// again for a best-FIVE list: the 3-NN path above does not go through any of it.  Edge clouds hold hundreds to a few thousand points, so
+// a launch is a handful of workgroups and its time is the dependent chain of one query.
+__device__ __forceinline__ void best5_push(float d, int i, float bd[5], int bi[5]) {
+  if (!lex_less(d, i, bd[4], bi[4]) || i == bi[0] || i == bi[1] || i == bi[2] || i == bi[3]) return;   // worse than 5th, or already held
+  // the list is sorted, so "new < old[k]" is monotone in k: slot k takes the new entry where it first holds, old[k - 1] below that
+  const bool l0 = lex_less(d, i, bd[0], bi[0]), l1 = lex_less(d, i, bd[1], bi[1]), l2 = lex_less(d, i, bd[2], bi[2]), l3 = lex_less(d, i, bd[3], bi[3]);
+  bd[4] = l3 ? bd[3] : d; bi[4] = l3 ? bi[3] : i;
+  if (l3) { bd[3] = l2 ? bd[2] : d; bi[3] = l2 ? bi[2] : i; }
+  if (l2) { bd[2] = l1 ? bd[1] : d; bi[2] = l1 ? bi[1] : i; }
+  if (l1) { bd[1] = l0 ? bd[0] : d; bi[1] = l0 ? bi[0] : i; }
+  if (l0) { bd[0] = d; bi[0] = i; }
+}
+__device__ __forceinline__ void scan_range5(const float4* __restrict__ sorted, int lo, int hi, int step, float qx, float qy, float qz, float bd[5], int bi[5]) {
+  // step = 1: one lane walks the range; step = kGroup: the group's lanes take every kGroup-th candidate (lo already offset by the lane)
+  for (int j = lo; j < hi; j += 4 * step) {
+    const int last = hi - 1;
+    const float4 mm[4] = {sorted[j], sorted[min(j + step, last)], sorted[min(j + 2 * step, last)], sorted[min(j + 3 * step, last)]};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {   // a clamped duplicate of the last point is rejected by best5_push (same index)
+      const float dx = sub_rn(qx, mm[u].x), dy = sub_rn(qy, mm[u].y), dz = sub_rn(qz, mm[u].z);
+      const float d = add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
+      best5_push(d, __float_as_int(mm[u].w), bd, bi);
+    }
+  }
+}
+// scan_shell for the best-five list: rows dealt round-robin to the group's lanes (no packed shell 1), pruning by the 5th-best d2
+__device__ __forceinline__ float scan_shell5(const LevelP& L, int cx, int cy, int cz, int r, int g_lane, float qx, float qy, float qz, float bd[5], int bi[5]) {
+  const GridP& g = L.g;
+  const int side = 2 * r + 1;
+  const float prune2 = bd[4];
+  const float slack = 1e-6f * g.cell;
+  const int group_shift = (threadIdx.x & 63) & ~(kGroup - 1);
+  for (int it = 0; it * kGroup < side * side; ++it) {
+    const int row_id = it * kGroup + g_lane;
+    int la = 0, ha = 0, lb = 0, hb = 0;
+    if (row_id < side * side) {
+      const int dz = row_id / side - r, dy = row_id % side - r;
+      const int z = cz + dz, y = cy + dy;
+      if (z >= 0 && z < g.nz && y >= 0 && y < g.ny) {
+        float gy = 0.0f, gz = 0.0f;
+        if (y > cy) gy = (g.oy + (float)y * g.cell) - qy; else if (y < cy) gy = qy - (g.oy + (float)(y + 1) * g.cell);
+        if (z > cz) gz = (g.oz + (float)z * g.cell) - qz; else if (z < cz) gz = qz - (g.oz + (float)(z + 1) * g.cell);
+        gy = fmaxf(gy * 0.9999f - slack, 0.0f); gz = fmaxf(gz * 0.9999f - slack, 0.0f);
+        const float base2 = gy * gy + gz * gz;
+        if (!(base2 > prune2)) {
+          int xlo = 0, xhi = g.nx - 1;
+          if (prune2 < INFINITY) {
+            const float dxm = sqrtf(prune2 - base2) * 1.0001f + slack;
+            xlo = max(xlo, (int)floorf((qx - dxm - g.ox) * g.inv_cell - 1e-3f));
+            xhi = min(xhi, (int)floorf((qx + dxm - g.ox) * g.inv_cell + 1e-3f));
+          }
+          const int row = (z * g.ny + y) * g.nx;
+          if (abs(dz) == r || abs(dy) == r) {
+            const int x0 = max(cx - r, xlo), x1 = min(cx + r, xhi);
+            if (x0 <= x1) { la = L.cell_start[row + x0]; ha = L.cell_start[row + x1 + 1]; }
+          } else {
+            const int xa = cx - r, xb = cx + r;
+            if (xa >= xlo && xa <= xhi) { la = L.cell_start[row + xa]; ha = L.cell_start[row + xa + 1]; }
+            if (xb <= xhi && xb >= xlo) { lb = L.cell_start[row + xb]; hb = L.cell_start[row + xb + 1]; }
+          }
+        }
+      }
+    }
+    const bool long_a = (ha - la) > kLongRange, long_b = (hb - lb) > kLongRange;
+    if (!long_a && ha > la) scan_range5(L.sorted, la, ha, 1, qx, qy, qz, bd, bi);
+    if (!long_b && hb > lb) scan_range5(L.sorted, lb, hb, 1, qx, qy, qz, bd, bi);
+    unsigned owners = (unsigned)((__ballot(long_a || long_b) >> group_shift) & ((1u << kGroup) - 1u));
+    while (owners) {
+      const int k = __ffs(owners) - 1;
+      owners &= owners - 1;
+      const int src = group_shift + k;
+      const int rla = __shfl(la, src), rha = __shfl(ha, src), rlb = __shfl(lb, src), rhb = __shfl(hb, src);
+      if (rha - rla > kLongRange) scan_range5(L.sorted, rla + g_lane, rha, kGroup, qx, qy, qz, bd, bi);
+      if (rhb - rlb > kLongRange) scan_range5(L.sorted, rlb + g_lane, rhb, kGroup, qx, qy, qz, bd, bi);
+    }
+  }
+  float m = INFINITY;
+  if (cx + r + 1 <= g.nx - 1) m = fminf(m, (g.ox + (float)(cx + r + 1) * g.cell) - qx);
+  if (cx - r - 1 >= 0) m = fminf(m, qx - (g.ox + (float)(cx - r) * g.cell));
+  if (cy + r + 1 <= g.ny - 1) m = fminf(m, (g.oy + (float)(cy + r + 1) * g.cell) - qy);
+  if (cy - r - 1 >= 0) m = fminf(m, qy - (g.oy + (float)(cy - r) * g.cell));
+  if (cz + r + 1 <= g.nz - 1) m = fminf(m, (g.oz + (float)(cz + r + 1) * g.cell) - qz);
+  if (cz - r - 1 >= 0) m = fminf(m, qz - (g.oz + (float)(cz - r) * g.cell));
+  return m;
+}
+template <int CTRL>
+__device__ __forceinline__ void merge_step5(float bd[5], int bi[5]) {
+  float od[5]; int oi[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) { od[k] = __int_as_float(dpp_i<CTRL>(__float_as_int(bd[k]))); oi[k] = dpp_i<CTRL>(bi[k]); }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) if (oi[k] >= 0) best5_push(od[k], oi[k], bd, bi);
+}
+static_assert(kGroup == 8, "merge_step5's DPP partners pair the lanes of an 8-lane group");
+
+// one Jacobi rotation of the symmetric 3 x 3 matrix in the (p, q) plane; r is the third index.  V's columns follow.
+__device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double vp[3], double vq[3]) {
+  if (apq == 0.0) return;
+  const double theta = (aqq - app) / (2.0 * apq);
+  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));      // (|theta| huge: t = 0)
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  app -= t * apq; aqq += t * apq; apq = 0.0;
+  const double xp = arp, xq = arq;
+  arp = c * xp - s * xq; arq = s * xp + c * xq;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { const double a = vp[k], b = vq[k]; vp[k] = c * a - s * b; vq[k] = s * a + c * b; }
+}
+// centroid, scatter matrix and principal axis of five points (doubles of the float map points, in neighbour order): cyclic Jacobi in
+// the writer lane.  Returns the line test l1 > 0 && l1 > ratio * l2; c[3] and the projector's upper triangle pr[6] are always written.
+constexpr int kJacobiSweeps = 8;
+__device__ __forceinline__ bool line_fit5(const double x[5][3], double ratio, double c[3], double pr[6]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) c[k] = ((((x[0][k] + x[1][k]) + x[2][k]) + x[3][k]) + x[4][k]) / 5.0;
+  double a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const double dx = x[j][0] - c[0], dy = x[j][1] - c[1], dz = x[j][2] - c[2];
+    a00 += dx * dx; a01 += dx * dy; a02 += dx * dz; a11 += dy * dy; a12 += dy * dz; a22 += dz * dz;
+  }
+  double v0[3] = {1, 0, 0}, v1[3] = {0, 1, 0}, v2[3] = {0, 0, 1};
+  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+    if (fabs(a01) + fabs(a02) + fabs(a12) <= 1e-22 * (fabs(a00) + fabs(a11) + fabs(a22))) break;      // converged (quadratically: a sweep or two past 1e-8)
+    jacobi_rot(a00, a11, a01, a02, a12, v0, v1);
+    jacobi_rot(a00, a22, a02, a01, a12, v0, v2);
+    jacobi_rot(a11, a22, a12, a01, a02, v1, v2);
+  }
+  // largest eigenvalue and its vector, the second largest
+  double l1 = a00, l2 = fmax(a11, a22), d[3] = {v0[0], v0[1], v0[2]};
+  if (a11 > l1 && a11 >= a22) { l1 = a11; l2 = fmax(a00, a22); d[0] = v1[0]; d[1] = v1[1]; d[2] = v1[2]; }
+  else if (a22 > l1) { l1 = a22; l2 = fmax(a00, a11); d[0] = v2[0]; d[1] = v2[1]; d[2] = v2[2]; }
+  const double inv = 1.0 / sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  d[0] *= inv; d[1] *= inv; d[2] *= inv;
+  pr[0] = 1.0 - d[0] * d[0]; pr[1] = -(d[0] * d[1]); pr[2] = -(d[0] * d[2]);
+  pr[3] = 1.0 - d[1] * d[1]; pr[4] = -(d[1] * d[2]); pr[5] = 1.0 - d[2] * d[2];
+  return l1 > 0.0 && l1 > ratio * l2;
+}
+
+__global__ __launch_bounds__(kB) void k_edge_associate(int Q, const float4* __restrict__ scan, const TfArg tfa, const LevelsP L, float thr, double ratio,
+                                                       const float4* __restrict__ map_raw, int* __restrict__ idx, float* __restrict__ d2,
+                                                       uint8_t* __restrict__ valid, double* __restrict__ corr /* [12][Q] */) {
+  const int t = blockIdx.x * kB + threadIdx.x;
+  const int g_lane = t & (kGroup - 1);
+  const int i = min(t / kGroup, Q - 1);          // surplus groups of the last block shadow the last query (no divergent exit before the shuffles)
+  const bool writer = (t / kGroup) < Q && g_lane == 0;
+  const Tf32 T = make_tf32(tfa.v);
+  const float4 p = scan[i];
+  const float qx = tf_row(T.a + 0, p.x, p.y, p.z, p.x, T.t[0]);
+  const float qy = tf_row(T.a + 3, p.x, p.y, p.z, p.y, T.t[1]);
+  const float qz = tf_row(T.a + 6, p.x, p.y, p.z, p.z, T.t[2]);
+  float bd[5] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY};
+  int bi[5] = {-1, -1, -1, -1, -1};
+  for (int lv = 0; lv < L.n; ++lv) {             // the level / shell schedule of knn3_body
+    const LevelP& lev = L.l[lv];
+    const GridP& g = lev.g;
+    const int cx = cell_coord(qx, g.ox, g.inv_cell, g.nx), cy = cell_coord(qy, g.oy, g.inv_cell, g.ny), cz = cell_coord(qz, g.oz, g.inv_cell, g.nz);
+    const int rcap = (lv == L.n - 1) ? max(g.nx, max(g.ny, g.nz)) : (lv == 0 ? 1 : 2);
+    bool done = false;
+    for (int r = 0; r <= rcap; ++r) {
+      const float m = scan_shell5(lev, cx, cy, cz, r, g_lane, qx, qy, qz, bd, bi);
+      merge_step5<0xB1>(bd, bi); merge_step5<0x4E>(bd, bi); merge_step5<0x141>(bd, bi);      // lane ^ 1, lane ^ 2, mirror inside the half row
+      if (!(m < INFINITY)) { done = true; break; }
+      const float ms = fmaxf(m, 0.0f) * 0.9999f - 1e-6f * g.cell;
+      const float ms2 = ms > 0.0f ? ms * ms : 0.0f;
+      if (bd[4] < ms2 || ms2 >= thr) { done = true; break; }         // 5th best beats anything unvisited / beyond the gate
+    }
+    if (done) break;
+  }
+  if (!writer) return;
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) { idx[5 * i + k] = bi[k]; d2[5 * i + k] = bd[k]; ok = ok && bi[k] >= 0 && bd[k] < thr; }
+  double c[3] = {0, 0, 0}, pr[6] = {0, 0, 0, 0, 0, 0};
+  if (ok) {
+    double x[5][3];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { const float4 a = map_raw[bi[k]]; x[k][0] = (double)a.x; x[k][1] = (double)a.y; x[k][2] = (double)a.z; }
+    ok = line_fit5(x, ratio, c, pr);
+  }
+  valid[i] = ok ? 1 : 0;
+  // (an invalid point's record reads zero)
+  corr[i] = ok ? (double)p.x : 0.0; corr[(size_t)Q + i] = ok ? (double)p.y : 0.0; corr[(size_t)2 * Q + i] = ok ? (double)p.z : 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) corr[(size_t)(3 + k) * Q + i] = ok ? c[k] : 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) corr[(size_t)(6 + k) * Q + i] = ok ? pr[k] : 0.0;
+}
+
 // exclusive prefix sum of n ints on the context's stream; out has n + 1 entries (out[n] = grand total).  in != out.
 int device_exclusive_scan_i32(lvf_ctx* ctx, const int* in, int n, int* out) {
   hipStream_t s = ctx->stream;
@@ -567,6 +756,21 @@ int launch_knn3_build(lvf_map* m, lvf_scan* sc, const double* pose, float thr, d
                      m->raw.p, corr);
   LVF_HIP(hipGetLastError());
   sc->searched = true;
+  return LVF_OK;
+}
+int launch_edge_associate(lvf_map* m, lvf_scan* sc, const double* pose, float thr, double min_eigen_ratio) {
+  const int Q = sc->Q;
+  if (sc->eidx.n < (size_t)5 * std::max(Q, 1)) {
+    LVF_TRY(sc->eidx.alloc((size_t)5 * std::max(Q, 1))); LVF_TRY(sc->ed2.alloc((size_t)5 * std::max(Q, 1)));
+    LVF_TRY(sc->evalid.alloc(std::max(Q, 1))); LVF_TRY(sc->ecorr.alloc((size_t)12 * std::max(Q, 1)));
+  }
+  sc->edge_searched = true;
+  if (Q <= 0) return LVF_OK;
+  TfArg tf;
+  for (int k = 0; k < 7; ++k) tf.v[k] = (float)pose[k];
+  hipLaunchKernelGGL(k_edge_associate, dim3(knn_grid(Q)), dim3(kB), 0, m->ctx->stream, Q, sc->pts.p, tf, levels_of(m), thr, min_eigen_ratio, m->raw.p,
+                     sc->eidx.p, sc->ed2.p, sc->evalid.p, sc->ecorr.p);
+  LVF_HIP(hipGetLastError());
   return LVF_OK;
 }
 int launch_knn3_batch(hipStream_t q, const KnnJob* jobs, const SmDev* devs, int n, int sub, int max_Q) {
@@ -875,6 +1079,29 @@ int lvf_knn3(lvf_map* m, lvf_scan* sc, const double* pose, float thr) {
     LVF_HIP(hipGetLastError());
   }
   sc->searched = true;
+  return LVF_OK;
+}
+
+int lvf_edge_associate(lvf_map* m, lvf_scan* sc, const double* pose, float thr, double min_eigen_ratio) {
+  LVF_REQUIRE(m && sc && pose, "lvf_edge_associate: null argument");
+  LVF_REQUIRE(m->ctx == sc->ctx, "lvf_edge_associate: map and scan belong to different contexts");
+  LVF_REQUIRE(!(thr != thr) && thr > 0.0f, "lvf_edge_associate: thr must be > 0");
+  LVF_REQUIRE(min_eigen_ratio >= 1.0 && std::isfinite(min_eigen_ratio), "lvf_edge_associate: min_eigen_ratio must be finite and >= 1");
+  LVF_TRY(lvf::enter(m->ctx));
+  return launch_edge_associate(m, sc, pose, thr, min_eigen_ratio);
+}
+
+int lvf_scan_download_edges(lvf_scan* sc, int32_t* idx5, float* d2_5, uint8_t* valid, double* corr12) {
+  LVF_REQUIRE(sc, "lvf_scan_download_edges: null scan");
+  if (!sc->edge_searched) { set_error("lvf_scan_download_edges: no lvf_edge_associate result yet"); return LVF_ERR_STATE; }
+  hipStream_t s = sc->ctx->stream;
+  if (sc->Q > 0) {
+    if (idx5) LVF_HIP(hipMemcpyAsync(idx5, sc->eidx.p, (size_t)5 * sc->Q * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (d2_5) LVF_HIP(hipMemcpyAsync(d2_5, sc->ed2.p, (size_t)5 * sc->Q * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (valid) LVF_HIP(hipMemcpyAsync(valid, sc->evalid.p, (size_t)sc->Q, hipMemcpyDeviceToHost, s));
+    if (corr12) LVF_HIP(hipMemcpyAsync(corr12, sc->ecorr.p, (size_t)12 * sc->Q * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  LVF_HIP(hipStreamSynchronize(s));
   return LVF_OK;
 }
 

@@ -93,6 +93,15 @@ __device__ __forceinline__ void lidar_point(const LidarU& U, int mode, const dou
   }
 }
 
+// one point-to-line block (LidarEdgeErrorYXY / RPZ <3,1,1,1>): r = w P (Twc2 p - c) with the projector P = I - d d^T of the line through c,
+// stored as its upper triangle pr[6] = (00 01 02 11 12 22).  Row k is the plane residual with "normal" P[k,:] and anchor c.
+__device__ __forceinline__ void lidar_edge_block(const LidarU& U, int mode, const double p[3], const double c[3], const double pr[6],
+                                                 double r[3], double J[3][3]) {
+  const double n0[3] = {pr[0], pr[1], pr[2]}, n1[3] = {pr[1], pr[3], pr[4]}, n2[3] = {pr[2], pr[4], pr[5]};
+  lidar_point(U, mode, p, c, n0, r[0], J[0]);
+  lidar_point(U, mode, p, c, n1, r[1], J[1]);
+  lidar_point(U, mode, p, c, n2, r[2], J[2]);
+}
 
 // LidarPlaneError ctor (lidar_error.hpp:13-18): unit normal of the plane through pa, pb, pc (Eigen cross + normalize)
 __device__ __forceinline__ void plane_normal(const double pa[3], const double pb[3], const double pc[3], double n[3]) {

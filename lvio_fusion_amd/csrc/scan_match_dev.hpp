@@ -64,5 +64,7 @@ int launch_knn3_batch(hipStream_t q, const KnnJob* jobs, const SmDev* devs, int 
 int launch_knn3_build(lvf_map* m, lvf_scan* sc, const double* pose, float thr, double* corr);                 // the same for one (map, scan) pair
 int launch_icp_eval_batch(hipStream_t q, const IcpJob* jobs, SmDev* devs, int n, int sub, int max_Q, bool candidate, bool last);   // candidate: the pass at xc (decision + next step) instead of the opening pass at x; last: cost only
 LevelsP levels_of(const lvf_map* m);
+// line association of one (map, scan) pair: 5-NN + line fit into the scan's edge outputs (knn_kernels.hip); nothing is waited for
+int launch_edge_associate(lvf_map* m, lvf_scan* sc, const double* pose, float thr, double min_eigen_ratio);
 
 }  // namespace lvf
