@@ -843,6 +843,60 @@ int lvf_orb_search(lvf_ctx* ctx, const lvf_orb_options* opt, const lvf_camera* c
                    const int32_t* cur_octave, const float* cur_angle, const uint8_t* cur_desc, const uint8_t* skip, int32_t* match, int32_t* best,
                    int32_t* second);
 
+/* ---- visual relocalisation: the body Relocator::RelocateByImage declares (relocator.cpp:164-173) ------------------------- */
+/* Semantics are DECLARED (the reference never builds the step); tests/reloc_ref.py is the statement of record.
+ * lvf_orb_match: cv::BFMatcher(NORM_HAMMING).knnMatch(query, train, k = 2) plus the gate of local_map.cpp:342-346, without the radius /
+ * level / angle pre-selection.  Per query: the best and second-best Hamming distance over ALL train descriptors (ties to the lower train
+ * index); accepted iff nt >= 2, best < max_distance, float(best) < ratio * float(second) and, with cross_check, the query is the best
+ * (ties to the lower index) of its train descriptor.  match [nq] = train index or -1; best / second [nq] (may be NULL), -1 where absent.
+ * nq, nt <= 8192 (LVF_ERR_INVALID beyond); nq == 0 or nt == 0 returns at once with no match. */
+typedef struct lvf_match_options {
+  int max_distance;     /* 50 */
+  float ratio;          /* 0.8f */
+  int cross_check;      /* 1 */
+} lvf_match_options;
+void lvf_match_options_default(lvf_match_options* o);
+int lvf_orb_match(lvf_ctx* ctx, int nq, const uint8_t* query_desc, int nt, const uint8_t* train_desc, const lvf_match_options* opt, int32_t* match, int32_t* best,
+                  int32_t* second);
+/* Robust absolute pose from 3D-2D correspondences.  A hypothesis is a body pose Twb; its error for correspondence i is the norm of
+ * PoseOnlyReprojectionError's residual at weight 1 for (pt_i, pw_i, cam0), +inf where the sensor-frame depth is <= 0; an inlier has squared
+ * error < max_reproj_px^2.  num_hypotheses (1 .. 4096, no adaptive stopping) triples are drawn by the counter-based sampler
+ * mix32(seed ^ mix32(h * 0x9E3779B1 + c)) % n (c = 0, 1, ...; a draw equal to an earlier one of the same hypothesis is skipped; at most 64
+ * draws), each solved by P3P (at most four poses, positive depth at the three points); a hypothesis counts the inliers of its best pose
+ * (ties to the pose the solver lists first), the winner is the largest count (ties to init_pose7, then to the lowest index).  Then
+ * refine_rounds rounds of {classify every correspondence at the current pose; solve LocalMap::LocalBA's problem (local_map.cpp:158-181: one
+ * pose, EigenQuaternionParameterization + Identity(3), one PoseOnlyReprojectionError per inlier at weight 1 under HuberLoss(huber_a)) by up
+ * to refine_iterations iterations of the declared Ceres loop}; a last classification gives inlier [n] (may be NULL) and *score = its
+ * population count.  summary (may be NULL) is the last round's.  With n < min_matches nothing is launched, *score = 0 and pose7 is left
+ * untouched; the same when no hypothesis yields a pose.  pt [n][2] are float pixels, widened to double.  n <= 8192. */
+typedef struct lvf_pnp_options {
+  int num_hypotheses;       /* 512 */
+  uint32_t seed;            /* 0 */
+  double max_reproj_px;     /* 3.0 */
+  int min_matches;          /* 21: with the base score of 20 (relocator.cpp:167) anything less is a rejection anyway; >= 3 */
+  int refine_rounds;        /* 2 */
+  int refine_iterations;    /* 10 */
+  double huber_a;           /* 1.0 */
+} lvf_pnp_options;
+void lvf_pnp_options_default(lvf_pnp_options* o);
+int lvf_pnp_ransac(lvf_ctx* ctx, const lvf_camera* cam0, int n, const double* pw, const float* pt, const double* init_pose7, const lvf_pnp_options* opt, double* pose7,
+                   int32_t* score, uint8_t* inlier, lvf_solver_summary* summary);
+/* RelocateByImage: queries = the current frame's features (cur_pt [n_cur][2], cur_desc [n_cur][32]), train = the old frame's (old_pw
+ * [n_old][3] world, old_desc [n_old][32]).  The match, the gate and compaction, the hypotheses and the refinement are queued on the
+ * context's stream with one wait and one download at the end; the matched pairs never leave the device in between.  relative_o_c7: in, the
+ * caller's initial value (old_pose^-1 * init_pose, relocator.cpp:141), which joins as the initial pose old_pose * relative_o_c; out,
+ * old_pose^-1 * pose (the Sophus product as lvf_forward_update forms it).  *score is the integer of `loop_closure->score += score - 20`.
+ * With fewer than min_matches accepted pairs the pose kernels return at once, *score = 0 and relative_o_c7 is left untouched.
+ * match is lvf_orb_match's result whatever becomes of the candidate (n_old == 0 or n_cur == 0: nothing is launched, no match).
+ * match [n_cur] (may be NULL) = index into the old features or -1; inlier [n_cur] (may be NULL). */
+int lvf_relocate_by_image(lvf_ctx* ctx, const lvf_camera* cam0, const double* old_pose7, int n_old, const double* old_pw, const uint8_t* old_desc, int n_cur,
+                          const float* cur_pt, const uint8_t* cur_desc, const lvf_match_options* match_opt, const lvf_pnp_options* pnp_opt, double* relative_o_c7,
+                          int32_t* score, int32_t* match, uint8_t* inlier, lvf_solver_summary* summary);
+/* Test tap: per hypothesis the sample triple (-1: none), the number of P3P poses, the best inlier count and (poses may be NULL) that pose
+ * [num_hypotheses][7].  3 <= n <= 8192.  Not part of the reference surface. */
+int lvf_pnp_debug_hypotheses(lvf_ctx* ctx, const lvf_camera* cam0, int n, const double* pw, const float* pt, const lvf_pnp_options* opt, int32_t* triples,
+                             int32_t* n_poses, int32_t* count, double* poses);
+
 /* ---- multi-GPU: the path's only exchange, for a C / C++ host ----------------------------------------------------------- */
 /* Independent windows / loop-closure candidates shard one per GPU: one process per GPU, one lvf_ctx each, no data-path collective.  The
  * single exchange is an all-gather of fixed-size records (score, relative_o_c[7], candidate id: relocator.cpp:196-206) over RCCL / xGMI.

@@ -121,6 +121,15 @@ class OrbOptions(C.Structure):
                 ("patch_size", C.c_int), ("edge_threshold", C.c_int), ("max_candidates", C.c_int)]
 
 
+class MatchOptions(C.Structure):
+    _fields_ = [("max_distance", C.c_int), ("ratio", C.c_float), ("cross_check", C.c_int)]
+
+
+class PnpOptions(C.Structure):
+    _fields_ = [("num_hypotheses", C.c_int), ("seed", C.c_uint32), ("max_reproj_px", C.c_double), ("min_matches", C.c_int), ("refine_rounds", C.c_int),
+                ("refine_iterations", C.c_int), ("huber_a", C.c_double)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into liblvf_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".hpp"))]
@@ -208,6 +217,14 @@ _SIGS = {
     "lvf_orb_download_level": (C.c_int, [_VP, C.c_int, c_int_p, c_int_p, c_u8_p, c_u8_p, c_u8_p]),
     "lvf_orb_search": (C.c_int, [_VP, C.POINTER(OrbOptions), C.POINTER(Camera), c_double_p, C.c_int, c_float_p, c_int_p, c_float_p, c_u8_p, C.c_int, c_double_p,
                                  c_int_p, c_float_p, c_u8_p, c_u8_p, c_int_p, c_int_p, c_int_p]),
+    "lvf_match_options_default": (None, [C.POINTER(MatchOptions)]),
+    "lvf_pnp_options_default": (None, [C.POINTER(PnpOptions)]),
+    "lvf_orb_match": (C.c_int, [_VP, C.c_int, c_u8_p, C.c_int, c_u8_p, C.POINTER(MatchOptions), c_int_p, c_int_p, c_int_p]),
+    "lvf_pnp_ransac": (C.c_int, [_VP, C.POINTER(Camera), C.c_int, c_double_p, c_float_p, c_double_p, C.POINTER(PnpOptions), c_double_p, c_int_p, c_u8_p,
+                                 C.POINTER(SolverSummary)]),
+    "lvf_relocate_by_image": (C.c_int, [_VP, C.POINTER(Camera), c_double_p, C.c_int, c_double_p, c_u8_p, C.c_int, c_float_p, c_u8_p, C.POINTER(MatchOptions),
+                                        C.POINTER(PnpOptions), c_double_p, c_int_p, c_int_p, c_u8_p, C.POINTER(SolverSummary)]),
+    "lvf_pnp_debug_hypotheses": (C.c_int, [_VP, C.POINTER(Camera), C.c_int, c_double_p, c_float_p, C.POINTER(PnpOptions), c_int_p, c_int_p, c_int_p, c_double_p]),
     "lvf_window_reject_outliers": (C.c_int, [_VP, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int)]),
     "lvf_comm_get_unique_id": (C.c_int, [_VP]),
     "lvf_comm_create": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.POINTER(_VP)]),

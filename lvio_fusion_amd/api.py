@@ -593,6 +593,78 @@ def orb_search(ctx, cam0, last_pose, last_pt, last_octave, last_angle, last_desc
     return m, b, s2
 
 
+def _options(cls, default, who, kw):
+    o = cls()
+    getattr(_lib.lib(), default)(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise ValueError(f"{who}: no field {k}")
+        setattr(o, k, v)
+    return o
+
+
+def match_options(**kw):
+    """lvf_match_options with its defaults (max_distance 50, ratio 0.8f, cross_check 1), fields overridden by keyword."""
+    return _options(_lib.MatchOptions, "lvf_match_options_default", "match_options", kw)
+
+
+def pnp_options(**kw):
+    """lvf_pnp_options with its defaults (512 hypotheses, seed 0, 3 px, min_matches 21, 2 rounds of 10 iterations, Huber 1), overridden by keyword."""
+    return _options(_lib.PnpOptions, "lvf_pnp_options_default", "pnp_options", kw)
+
+
+def _desc(a):
+    return np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 32)
+
+
+def orb_match(ctx, query_desc, train_desc, opt=None):
+    """Brute-force Hamming 2-NN with the ratio gate and the cross-check: returns match [nq] (train index, -1 where none), best, second [nq]."""
+    q, t = _desc(query_desc), _desc(train_desc)
+    n = len(q)
+    m, b, s2 = np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    _chk(ctx.L.lvf_orb_match(ctx.h, n, _u8p(q), len(t), _u8p(t), C.byref(opt) if opt is not None else None, _ip(m), _ip(b), _ip(s2)))
+    return m, b, s2
+
+
+def pnp_ransac(ctx, cam0, pw, pt, init_pose=None, opt=None):
+    """P3P RANSAC + refinement on given 3D-2D correspondences: returns dict(pose (None when left untouched), score, inlier [n] uint8, summary)."""
+    w, p = _d(pw).reshape(-1, 3), _pts(pt)
+    if len(w) != len(p):
+        raise ValueError("pnp_ransac: pw and pt differ in length")
+    n = len(w)
+    ini = _d(init_pose) if init_pose is not None else None
+    pose, score, inl, summ = np.full(7, np.nan), C.c_int32(0), np.zeros(n, np.uint8), SolverSummary()
+    c0 = make_camera(cam0)
+    _chk(ctx.L.lvf_pnp_ransac(ctx.h, C.byref(c0), n, _dp(w), _fp(p), _dp(ini) if ini is not None else None, C.byref(opt) if opt is not None else None, _dp(pose),
+                              C.byref(score), _u8p(inl), C.byref(summ)))
+    return dict(pose=None if np.isnan(pose).any() else pose, score=score.value, inlier=inl, summary=summ)
+
+
+def relocate_by_image(ctx, cam0, old_pose, old_pw, old_desc, cur_pt, cur_desc, relative_o_c, match_opt=None, pnp_opt=None):
+    """The body of Relocator::RelocateByImage: returns dict(relative_o_c (the caller's value when the candidate is rejected), score, match [n_cur],
+    inlier [n_cur] uint8, summary)."""
+    w, od, p, cd = _d(old_pw).reshape(-1, 3), _desc(old_desc), _pts(cur_pt), _desc(cur_desc)
+    if len(w) != len(od) or len(p) != len(cd):
+        raise ValueError("relocate_by_image: feature arrays differ in length")
+    n = len(p)
+    rel, score, m, inl, summ = _d(relative_o_c).copy(), C.c_int32(0), np.full(n, -1, np.int32), np.zeros(n, np.uint8), SolverSummary()
+    c0 = make_camera(cam0)
+    _chk(ctx.L.lvf_relocate_by_image(ctx.h, C.byref(c0), _dp(_d(old_pose)), len(w), _dp(w), _u8p(od), n, _fp(p), _u8p(cd), C.byref(match_opt) if match_opt is not None else None,
+                                     C.byref(pnp_opt) if pnp_opt is not None else None, _dp(rel), C.byref(score), _ip(m), _u8p(inl), C.byref(summ)))
+    return dict(relative_o_c=rel, score=score.value, match=m, inlier=inl, summary=summ)
+
+
+def pnp_debug_hypotheses(ctx, cam0, pw, pt, opt=None):
+    """Test tap: triples [H, 3], n_poses [H], count [H], poses [H, 7] of the hypotheses lvf_pnp_ransac would score."""
+    w, p = _d(pw).reshape(-1, 3), _pts(pt)
+    o = opt if opt is not None else pnp_options()
+    H = o.num_hypotheses
+    tri, npo, cnt, poses = np.zeros((H, 3), np.int32), np.zeros(H, np.int32), np.zeros(H, np.int32), np.zeros((H, 7))
+    c0 = make_camera(cam0)
+    _chk(ctx.L.lvf_pnp_debug_hypotheses(ctx.h, C.byref(c0), len(w), _dp(w), _fp(p), C.byref(o), _ip(tri), _ip(npo), _ip(cnt), _dp(poses)))
+    return tri, npo, cnt, poses
+
+
 def prior3_evaluate(ctx, mode, target3, weight, x3):
     """PoseErrorRPZ / PoseErrorYXY stand-alone (lvf_prior3_evaluate): returns r[3], J[3 blocks][3 rows]."""
     t, x = _d(target3), _d(x3)

@@ -84,6 +84,30 @@ def evaluate_candidate(api, ctx, cand, resolution=0.2):
             x.close()
 
 
+MODE_NONE, MODE_VISUAL_ONLY, MODE_LIDAR_ONLY, MODE_VISUAL_AND_LIDAR = 0, 1, 2, 3      # Relocator::Mode (relocator.h:29-35)
+
+
+def combined_score(image_score, mapping_score, mode):
+    """loop_closure->score as Relocator::Relocate accumulates it (relocator.cpp:137-157): 0, plus `score - 20` of RelocateByImage in modes 1 / 3 and
+    of RelocateByPoints in modes 2 / 3.  A score of None means that half was not called (the orientation check failed / a frame has no LiDAR
+    features).  The candidate qualifies when the result is > 0 (or the mode is None)."""
+    if mode not in (MODE_NONE, MODE_VISUAL_ONLY, MODE_LIDAR_ONLY, MODE_VISUAL_AND_LIDAR):
+        raise ValueError(f"combined_score: mode {mode}")
+    score = 0
+    if mode in (MODE_VISUAL_ONLY, MODE_VISUAL_AND_LIDAR) and image_score is not None:
+        score += int(image_score) - RELOCATE_BASE_SCORE
+    if mode in (MODE_LIDAR_ONLY, MODE_VISUAL_AND_LIDAR) and mapping_score is not None:
+        score += int(mapping_score) - RELOCATE_BASE_SCORE
+    return score
+
+
+def evaluate_candidate_visual(api, ctx, cand, match_opt=None, pnp_opt=None):
+    """cand: dict(cam0, old_pose, old_pw [n_old, 3], old_desc [n_old, 32], cur_pt [n_cur, 2], cur_desc [n_cur, 32], relative_o_c (the value
+    Relocator::Relocate sets before the call, relocator.cpp:141)).  RelocateByImage: returns api.relocate_by_image's dict (score, relative_o_c, ...)."""
+    return api.relocate_by_image(ctx, cand["cam0"], cand["old_pose"], cand["old_pw"], cand["old_desc"], cand["cur_pt"], cand["cur_desc"], cand["relative_o_c"],
+                                 match_opt, pnp_opt)
+
+
 def split_candidate(cand):
     """(map ground, map surf, query ground, query surf) point arrays of a candidate — the reference holds them as separate clouds
     (frame->feature_lidar->points_ground / points_surf); the synthetic candidates carry masks."""
