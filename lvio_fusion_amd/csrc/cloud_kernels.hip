@@ -34,6 +34,7 @@
 #include "lvf_internal.hpp"
 
 #pragma clang fp contract(off)   // the float SE3 transform must round after every multiply and add (bit-exact with the oracle)
+#include "float_tf.hpp"          // (requires the pragma above of its includers)
 
 namespace lvf {
 
@@ -58,39 +59,21 @@ __global__ __launch_bounds__(kC) void k_align_slice(int first, int count, const 
   out[i] = make_float4(p.x, p.y, p.z, 0.0f);
 }
 
-struct Tf32c { float a[9]; float t[3]; };
-// float instantiation of ceres::QuaternionRotatePoint (1.x): normalise, then the expanded polynomial — same sequence of
-// rounded operations as knn_kernels.hip::make_tf32 and oracle/knn.h::transform_query_f32
-__device__ __forceinline__ Tf32c make_tf(const float tf[7]) {
-  const float q0 = tf[3], q1 = tf[0], q2 = tf[1], q3 = tf[2];
-  const float ss = ((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3;
-  const float scale = 1.0f / __builtin_sqrtf(ss);
-  const float u0 = scale * q0, u1 = scale * q1, u2 = scale * q2, u3 = scale * q3;
-  const float t2 = u0 * u1, t3 = u0 * u2, t4 = u0 * u3, t5 = -u1 * u1, t6 = u1 * u2, t7 = u1 * u3, t8 = -u2 * u2, t9 = u2 * u3, t1 = -u3 * u3;
-  Tf32c T;
-  T.a[0] = t8 + t1; T.a[1] = t6 - t4; T.a[2] = t3 + t7;
-  T.a[3] = t4 + t6; T.a[4] = t5 + t1; T.a[5] = t9 - t2;
-  T.a[6] = t7 - t3; T.a[7] = t2 + t9; T.a[8] = t5 + t8;
-  T.t[0] = tf[4]; T.t[1] = tf[5]; T.t[2] = tf[6];
-  return T;
-}
-struct TfArgC { float v[7]; };
-__global__ __launch_bounds__(kC) void k_cloud_transform(int n, const float4* __restrict__ in, TfArgC tfa, float4* __restrict__ out) {
+// (the float instantiation of ceres::QuaternionRotatePoint: float_tf.hpp — one definition for this file and the association's queries)
+__global__ __launch_bounds__(kC) void k_cloud_transform(int n, const float4* __restrict__ in, TfArg tfa, float4* __restrict__ out) {
   const int i = blockIdx.x * kC + threadIdx.x;
   if (i >= n) return;
-  const Tf32c T = make_tf(tfa.v);
+  const Tf32 T = make_tf32(tfa.v);
   const float4 p = in[i];
   float4 o;
-  o.x = (2.0f * ((T.a[0] * p.x + T.a[1] * p.y) + T.a[2] * p.z) + p.x) + T.t[0];
-  o.y = (2.0f * ((T.a[3] * p.x + T.a[4] * p.y) + T.a[5] * p.z) + p.y) + T.t[1];
-  o.z = (2.0f * ((T.a[6] * p.x + T.a[7] * p.y) + T.a[8] * p.z) + p.z) + T.t[2];
+  o.x = tf_row(T.a + 0, p.x, p.y, p.z, p.x, T.t[0]);
+  o.y = tf_row(T.a + 3, p.x, p.y, p.z, p.y, T.t[1]);
+  o.z = tf_row(T.a + 6, p.x, p.y, p.z, p.z, T.t[2]);
   o.w = p.w;                                   // intensity rides along (mapping.cpp:201)
   out[i] = o;
 }
 
 // ---------------------------------------------------------------------------------------------- bounds
-__device__ __forceinline__ unsigned f2ord_c(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-static inline float ord2f_c(unsigned u) { u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; float f; memcpy(&f, &u, 4); return f; }
 // capped grid + workgroup-level reduction: 6 atomics per WORKGROUP (one per wave cost 50-110 us on 100 k points, see cell_runs)
 constexpr int kCapBlocks = 256;
 __global__ __launch_bounds__(kC) void k_cloud_bounds(int n, const float4* __restrict__ pts, unsigned* __restrict__ bounds) {
@@ -110,7 +93,7 @@ __global__ __launch_bounds__(kC) void k_cloud_bounds(int n, const float4* __rest
   if (threadIdx.x < 6) {
     float v = red[0][threadIdx.x];
     for (int k = 1; k < kC / 64; ++k) v = threadIdx.x < 3 ? fminf(v, red[k][threadIdx.x]) : fmaxf(v, red[k][threadIdx.x]);
-    if (threadIdx.x < 3) atomicMin(bounds + threadIdx.x, f2ord_c(v)); else atomicMax(bounds + threadIdx.x, f2ord_c(v));
+    if (threadIdx.x < 3) atomicMin(bounds + threadIdx.x, f2ord(v)); else atomicMax(bounds + threadIdx.x, f2ord(v));
   }
 }
 static int cloud_bounds(const lvf_cloud* c, float lo[3], float hi[3]) {
@@ -123,7 +106,7 @@ static int cloud_bounds(const lvf_cloud* c, float lo[3], float hi[3]) {
   hipLaunchKernelGGL(k_cloud_bounds, dim3(std::min(kCapBlocks, gridc(c->n))), dim3(kC), 0, s, c->n, c->pts.p, b.p);
   unsigned h[6];
   LVF_TRY(read_back(c->ctx, h, b.p, sizeof(h)));
-  for (int k = 0; k < 3; ++k) { lo[k] = ord2f_c(h[k]); hi[k] = ord2f_c(h[3 + k]); }
+  for (int k = 0; k < 3; ++k) { lo[k] = ord2f(h[k]); hi[k] = ord2f(h[3 + k]); }
   for (int k = 0; k < 3; ++k)
     if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) { set_error("cloud has non-finite coordinates"); return LVF_ERR_INVALID; }
   return LVF_OK;
@@ -542,7 +525,6 @@ __global__ void k_dc_init(DcState* __restrict__ st, int* __restrict__ ransac_cou
   if (t < 19) st->mom.v[t] = 0ull;
   if (t == 0) { st->err = 0; st->ransac_used = 0; st->grid_ncell = 1; st->plane[0].valid = 0; st->plane[1].valid = 0; }
 }
-__device__ __forceinline__ float ord2f_dev(unsigned u) { u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; return __uint_as_float(u); }
 // what the last workgroup of a bounds pass derives from the box
 constexpr int kDcBoundsBlocks = 64;      // (arrival atomics on one address: a few dozen workgroups, not hundreds)
 struct DcSetup {
@@ -576,7 +558,7 @@ __global__ __launch_bounds__(kC) void k_dc_bounds(int cap, const int* __restrict
   if (threadIdx.x < 6 && (long long)blockIdx.x * kC < (long long)n) {
     float v = red[0][threadIdx.x];
     for (int k = 1; k < kC / 64; ++k) v = threadIdx.x < 3 ? fminf(v, red[k][threadIdx.x]) : fmaxf(v, red[k][threadIdx.x]);
-    s_seen[threadIdx.x] = threadIdx.x < 3 ? atomicMin(bounds + threadIdx.x, f2ord_c(v)) : atomicMax(bounds + threadIdx.x, f2ord_c(v));
+    s_seen[threadIdx.x] = threadIdx.x < 3 ? atomicMin(bounds + threadIdx.x, f2ord(v)) : atomicMax(bounds + threadIdx.x, f2ord(v));
   }
   __syncthreads();
   if (threadIdx.x == 0) s_last = atomicAdd(&st->tick[su.slot], 1) == (int)gridDim.x - 1;
@@ -585,8 +567,8 @@ __global__ __launch_bounds__(kC) void k_dc_bounds(int cap, const int* __restrict
   float lo[3], hi[3];
   bool finite = true;
   for (int k = 0; k < 3; ++k) {
-    lo[k] = ord2f_dev(__hip_atomic_load(bounds + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    hi[k] = ord2f_dev(__hip_atomic_load(bounds + 3 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    lo[k] = ord2f(__hip_atomic_load(bounds + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    hi[k] = ord2f(__hip_atomic_load(bounds + 3 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     finite = finite && isfinite(lo[k]) && isfinite(hi[k]);
   }
   if (n > 0 && !finite) atomicOr(&st->err, kDcErrBounds);
@@ -812,9 +794,7 @@ int dc_tail_run(lvf_ctx* ctx, const DcTailPlan& plan, hipStream_t q, const float
 int transform_points(lvf_ctx* ctx, const float4* in, int n, const double* pose, lvf_cloud** out) {
   lvf_cloud* c = nullptr;
   LVF_TRY(new_cloud(ctx, n, &c));
-  TfArgC tf;
-  for (int k = 0; k < 7; ++k) tf.v[k] = (float)pose[k];
-  if (n) hipLaunchKernelGGL(k_cloud_transform, dim3(gridc(n)), dim3(kC), 0, ctx->stream, n, in, tf, c->pts.p);
+  if (n) hipLaunchKernelGGL(k_cloud_transform, dim3(gridc(n)), dim3(kC), 0, ctx->stream, n, in, tf_arg(pose), c->pts.p);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { delete c; return ::lvf::hip_fail(e, "k_cloud_transform", __FILE__, __LINE__); }
   *out = c;
@@ -859,9 +839,7 @@ int lvf_cloud_transform(const lvf_cloud* in, const double* pose, lvf_cloud** out
   LVF_TRY(lvf::enter(in->ctx));
   lvf_cloud* c = nullptr;
   LVF_TRY(new_cloud(in->ctx, in->n, &c));
-  TfArgC tf;
-  for (int k = 0; k < 7; ++k) tf.v[k] = (float)pose[k];          // Sophus SE3d::cast<float>()  mapping.cpp:195
-  if (in->n) hipLaunchKernelGGL(k_cloud_transform, dim3(gridc(in->n)), dim3(kC), 0, in->ctx->stream, in->n, in->pts.p, tf, c->pts.p);
+  if (in->n) hipLaunchKernelGGL(k_cloud_transform, dim3(gridc(in->n)), dim3(kC), 0, in->ctx->stream, in->n, in->pts.p, tf_arg(pose), c->pts.p);
   LVF_HIP(hipGetLastError());
   *out = c;
   return LVF_OK;

@@ -1,18 +1,24 @@
-// knn_kernels.hip — scan-to-map association: float32 SE3 transform + exact 3-nearest-neighbour + gate.
+// knn_kernels.hip — scan-to-map association: float32 SE3 transform + exact K-nearest-neighbour search + gate.
 //
 // Replaces, per scan-to-map call of src/lvio_fusion/src/association.cpp:
 //   pcl::KdTreeFLANN<PointI>::setInputCloud(deep copy)        :278-279, :336-337   -> lvf_map_create
 //   SE3TransformPoint<float>(tf, p_i) ; nearestKSearch(.,3,..) :294-296, :352-354   -> k_knn3
 //   all-three d2 < threshold gate                              :298-300, :356-358   -> valid flag
+//   the line association's nearestKSearch(.,5,..) and principal-axis fit            -> k_edge_associate
 //
 // MI355X design: a kd-tree traversal is pointer-chasing; instead the map is bucketed into a uniform grid
 // (counting sort on device: histogram -> 3-phase exclusive scan -> scatter into a cell-sorted float4 array
-// {x,y,z,original index}); a query walks cubic shells of cells outward and stops as soon as the 3rd-best d2 is
+// {x,y,z,original index}); a query walks cubic shells of cells outward and stops as soon as the K-th best d2 is
 // provably smaller than anything unvisited, or the shell lies beyond the gate radius.  x-adjacent cells are
 // contiguous in memory, so a shell row is ONE contiguous float4 range.  Arithmetic is the reference's, bit for
 // bit: the transform is the float instantiation of the Ceres-1.x normalise-then-rotate polynomial, distances are
 // (dx*dx + dy*dy) + dz*dz with explicit round-to-nearest mul/add (no FMA contraction); ties resolve by
 // ascending (d2, map index), which makes the result independent of traversal order.
+//
+// There is ONE search, knn_search, a template on the length K of the sorted best list (with best_push, scan_range, scan_shell and
+// group_merge under it); what a kernel does with a query's list is the epilogue it passes.  The plane association (k_knn3<STATS>,
+// k_knn3_build, k_knn3_b) instantiates it with K = 3 and adds the gate and the optional plane-normal build; the line association
+// (k_edge_associate) instantiates it with K = 5 and adds the gate, the line fit and the zeroed records of invalid points.
 #include <cmath>
 #include <cstdlib>
 #include "lvf_internal.hpp"
@@ -20,29 +26,16 @@
 #include "lidar_eval.hpp"
 
 // The float32 arithmetic below must round after every multiply and add (bit-exact d2 / transform): the default
-// -ffp-contract=fast would fuse them (HIP's own __fmul_rn/__fadd_rn are plain operators compiled with the
-// `contract` flag and DO get fused after inlining — checked in the ISA), so contraction is switched off for this
-// whole translation unit and the primitives are re-declared below it.
+// -ffp-contract=fast would fuse them, so contraction is switched off for this whole translation unit, from the top; the
+// round-to-nearest primitives and the transform come from float_tf.hpp, which requires exactly that of its includers.
 #pragma clang fp contract(off)
+#include "float_tf.hpp"
 
 namespace lvf {
 
 constexpr int kB = 256;
 
-// round-to-nearest primitives defined UNDER the pragma above (the HIP header versions carry the `contract` flag)
-__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
-__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
-__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
-__device__ __forceinline__ float div_rn(float a, float b) { return a / b; }
-__device__ __forceinline__ float sqrt_rn(float a) { return __builtin_sqrtf(a); }
-
 // (GridP / LevelP / LevelsP: scan_match_dev.hpp)
-
-__device__ __forceinline__ unsigned f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__host__ __device__ inline float ord2f(unsigned u) {
-  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-  float f; memcpy(&f, &u, 4); return f;
-}
 
 // pack strided xyz records into float4 and reduce the bounding box (ordered-uint atomics).  The grid is capped and strides over
 // the cloud, and every workgroup reduces through LDS first: atomics on ONE address serialise at ~65 ns each in L2 (measured: one
@@ -243,31 +236,13 @@ __global__ __launch_bounds__(kB) void k_pack(int Q, const float* __restrict__ sr
 }
 
 // ---- the query ----
-struct Tf32 { float a[9]; float t[3]; };   // out = 2*((a0 p0 + a1 p1) + a2 p2) + p0 + t0 ...
-
-// float instantiation of QuaternionRotatePoint's coefficients (oracle/se3_ops.h UnitQuatRotate_wxyz), RN ops only
-__device__ __forceinline__ Tf32 make_tf32(const float tf[7]) {
-  const float q0 = tf[3], q1 = tf[0], q2 = tf[1], q3 = tf[2];
-  const float ss = add_rn(add_rn(add_rn(mul_rn(q0, q0), mul_rn(q1, q1)), mul_rn(q2, q2)), mul_rn(q3, q3));
-  const float scale = div_rn(1.0f, sqrt_rn(ss));
-  const float u0 = mul_rn(scale, q0), u1 = mul_rn(scale, q1), u2 = mul_rn(scale, q2), u3 = mul_rn(scale, q3);
-  const float t2 = mul_rn(u0, u1), t3 = mul_rn(u0, u2), t4 = mul_rn(u0, u3);
-  const float t5 = mul_rn(-u1, u1), t6 = mul_rn(u1, u2), t7 = mul_rn(u1, u3);
-  const float t8 = mul_rn(-u2, u2), t9 = mul_rn(u2, u3), t1 = mul_rn(-u3, u3);
-  Tf32 T;
-  T.a[0] = add_rn(t8, t1); T.a[1] = sub_rn(t6, t4); T.a[2] = add_rn(t3, t7);
-  T.a[3] = add_rn(t4, t6); T.a[4] = add_rn(t5, t1); T.a[5] = sub_rn(t9, t2);
-  T.a[6] = sub_rn(t7, t3); T.a[7] = add_rn(t2, t9); T.a[8] = add_rn(t5, t8);
-  T.t[0] = tf[4]; T.t[1] = tf[5]; T.t[2] = tf[6];
-  return T;
-}
-__device__ __forceinline__ float tf_row(const float* a, float p0, float p1, float p2, float pk, float t) {
-  const float s = add_rn(add_rn(mul_rn(a[0], p0), mul_rn(a[1], p1)), mul_rn(a[2], p2));
-  return add_rn(add_rn(mul_rn(2.0f, s), pk), t);
-}
-
+// The sorted best-K list (bd = d2, bi = map index, ascending (d2, index); empty slots are (INFINITY, -1)) takes one candidate.  An index
+// the list already holds is rejected, so a point may be met any number of times: clamped loads, overlapping levels, merged lists.
 __device__ __forceinline__ bool lex_less(float da, int ia, float db, int ib) { return da < db || (da == db && (unsigned)ia < (unsigned)ib); }
-__device__ __forceinline__ void best3_push(float d, int i, float bd[3], int bi[3]) {
+template <int K>
+__device__ __forceinline__ void best_push(float d, int i, float bd[K], int bi[K]);
+template <>
+__device__ __forceinline__ void best_push<3>(float d, int i, float bd[3], int bi[3]) {
   if (!lex_less(d, i, bd[2], bi[2]) || i == bi[0] || i == bi[1]) return;   // worse than 3rd, or already held
   if (lex_less(d, i, bd[1], bi[1])) {
     bd[2] = bd[1]; bi[2] = bi[1];
@@ -275,67 +250,62 @@ __device__ __forceinline__ void best3_push(float d, int i, float bd[3], int bi[3
     else { bd[1] = d; bi[1] = i; }
   } else { bd[2] = d; bi[2] = i; }
 }
+template <>
+__device__ __forceinline__ void best_push<5>(float d, int i, float bd[5], int bi[5]) {
+  if (!lex_less(d, i, bd[4], bi[4]) || i == bi[0] || i == bi[1] || i == bi[2] || i == bi[3]) return;   // worse than 5th, or already held
+  // the list is sorted, so "new < old[k]" is monotone in k: slot k takes the new entry where it first holds, old[k - 1] below that
+  const bool l0 = lex_less(d, i, bd[0], bi[0]), l1 = lex_less(d, i, bd[1], bi[1]), l2 = lex_less(d, i, bd[2], bi[2]), l3 = lex_less(d, i, bd[3], bi[3]);
+  bd[4] = l3 ? bd[3] : d; bi[4] = l3 ? bi[3] : i;
+  if (l3) { bd[3] = l2 ? bd[2] : d; bi[3] = l2 ? bi[2] : i; }
+  if (l2) { bd[2] = l1 ? bd[1] : d; bi[2] = l1 ? bi[1] : i; }
+  if (l1) { bd[1] = l0 ? bd[0] : d; bi[1] = l0 ? bi[0] : i; }
+  if (l0) { bd[0] = d; bi[0] = i; }
+}
 
 struct KnnStats { int candidates, lookups, level, shells, t_start, t_end; };   // t_*: wall_clock64() (100 MHz) of the query's wave, low 31 bits
 
 constexpr int kGroup = 8;   // lanes cooperating on one query (8 queries per wave64)
 
-// Candidates of one contiguous cell range.  Loads are issued four at a time so that four 16-B gathers are in flight
-// per lane (the loop is otherwise a chain of dependent L2/MALL round trips).
-__device__ __forceinline__ void scan_range(const float4* __restrict__ sorted, int lo, int hi, float qx, float qy, float qz,
-                                           float bd[3], int bi[3], KnnStats* st = nullptr) {
-  for (int j = lo; j < hi; j += 4) {
+// Candidates lo, lo + step, lo + 2 step, ... below hi of one contiguous cell range.  step = 1: one lane walks the range.  step = kGroup
+// with lo offset by the group lane: the whole group scans ONE long range, lane g taking candidates lo+g, lo+g+8, ... (coalesced 128-B
+// rows) — for ranges a single lane would take hundreds of dependent round trips to walk.  Loads are issued four at a time so that four
+// 16-B gathers are in flight per lane (the loop is otherwise a chain of dependent L2/MALL round trips).
+template <int K>
+__device__ __forceinline__ void scan_range(const float4* __restrict__ sorted, int lo, int hi, int step, float qx, float qy, float qz,
+                                           float bd[K], int bi[K]) {
+  for (int j = lo; j < hi; j += 4 * step) {
     const int last = hi - 1;
-    const float4 m0 = sorted[j], m1 = sorted[min(j + 1, last)], m2 = sorted[min(j + 2, last)], m3 = sorted[min(j + 3, last)];
-    const float4 mm[4] = {m0, m1, m2, m3};
+    const float4 mm[4] = {sorted[j], sorted[min(j + step, last)], sorted[min(j + 2 * step, last)], sorted[min(j + 3 * step, last)]};
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {   // a clamped duplicate of the last point is rejected by best3_push (same index)
+    for (int u = 0; u < 4; ++u) {   // a clamped duplicate of the last point is rejected by best_push (same index)
       const float dx = sub_rn(qx, mm[u].x), dy = sub_rn(qy, mm[u].y), dz = sub_rn(qz, mm[u].z);
       const float d = add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
-      best3_push(d, __float_as_int(mm[u].w), bd, bi);
-    }
-  }
-}
-
-// The whole group scans ONE long range: lane g takes candidates lo+g, lo+g+8, ... (coalesced 128-B rows), four
-// strides in flight per lane.  Used for ranges a single lane would take hundreds of dependent round trips to walk.
-__device__ __forceinline__ void scan_range_group(const float4* __restrict__ sorted, int lo, int hi, int g_lane, float qx,
-                                                 float qy, float qz, float bd[3], int bi[3]) {
-  for (int j = lo + g_lane; j < hi; j += 4 * kGroup) {
-    const int last = hi - 1;
-    const float4 mm[4] = {sorted[j], sorted[min(j + kGroup, last)], sorted[min(j + 2 * kGroup, last)], sorted[min(j + 3 * kGroup, last)]};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float dx = sub_rn(qx, mm[u].x), dy = sub_rn(qy, mm[u].y), dz = sub_rn(qz, mm[u].z);
-      const float d = add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
-      best3_push(d, __float_as_int(mm[u].w), bd, bi);
+      best_push<K>(d, __float_as_int(mm[u].w), bd, bi);
     }
   }
 }
 
 constexpr int kLongRange = 12;   // candidates; longer ranges are deferred to the cooperative scan
 
-struct TfArg { float v[7]; };
-
-
 // One cubic shell of cells around (cx,cy,cz); the (dz,dy) rows of the shell are dealt round-robin to the kGroup lanes
 // of the query's group (lane `g` takes rows g, g+kGroup, ...).  Returns the lower bound on the distance to any point
 // of THIS level's grid outside shells 0..r (INFINITY when the shells already cover the whole grid).
+// PACKED: shell 1 has 8 perimeter rows (one range each) + the centre row (two end caps); they are packed into ONE lock-step pass — the
+// eight lanes take the perimeter rows and lanes 0 / 1 carry the centre row's caps in their second range slot — instead of a second pass
+// in which a single lane works (every pass is a chain of dependent look-ups).
+template <int K, bool PACKED>
 __device__ __forceinline__ float scan_shell(const LevelP& L, int cx, int cy, int cz, int r, int g_lane, float qx, float qy,
-                                            float qz, float bd[3], int bi[3], KnnStats* st) {
+                                            float qz, float bd[K], int bi[K], KnnStats* st) {
   const GridP& g = L.g;
   const int side = 2 * r + 1;
-  // Pruning radius: the group's 3rd-best d2 as of the previous shell (all lanes hold the merged list).  A cell whose
+  // Pruning radius: the group's K-th best d2 as of the previous shell (all lanes hold the merged list).  A cell whose
   // closest corner is farther than that cannot contribute (ties included: only strictly farther cells are skipped);
   // gaps are shrunk by 1e-4 relative + 1e-6 cell to stay conservative against float cell-assignment rounding.
-  const float prune2 = bd[2];
+  const float prune2 = bd[K - 1];
   const float slack = 1e-6f * g.cell;
   const int lane_in_wave = threadIdx.x & 63;
   const int group_shift = lane_in_wave & ~(kGroup - 1);
-  // shell 1 has 8 perimeter rows (one range each) + the centre row (two end caps): packed into ONE lock-step pass — the eight
-  // lanes take the perimeter rows and lanes 0 / 1 carry the centre row's caps in their second range slot — instead of a second
-  // pass in which a single lane works (every pass is a chain of dependent look-ups)
-  const bool packed = (r == 1) && (kGroup == 8);
+  const bool packed = PACKED && r == 1;
   for (int it = 0; it * kGroup < (packed ? kGroup : side * side); ++it) {       // lock-step over the group: lane g owns row it*kGroup+g
     const int row_id = packed ? (g_lane < 4 ? g_lane : g_lane + 1) : it * kGroup + g_lane;
     int la = 0, ha = 0, lb = 0, hb = 0;                    // up to two candidate ranges for this lane's row
@@ -379,8 +349,8 @@ __device__ __forceinline__ float scan_shell(const LevelP& L, int cx, int cy, int
     }
     if (st) { st->lookups += (ha > la) + (hb > lb); st->candidates += (ha - la) + (hb - lb); }
     const bool long_a = (ha - la) > kLongRange, long_b = (hb - lb) > kLongRange;
-    if (!long_a && ha > la) scan_range(L.sorted, la, ha, qx, qy, qz, bd, bi);
-    if (!long_b && hb > lb) scan_range(L.sorted, lb, hb, qx, qy, qz, bd, bi);
+    if (!long_a && ha > la) scan_range<K>(L.sorted, la, ha, 1, qx, qy, qz, bd, bi);
+    if (!long_b && hb > lb) scan_range<K>(L.sorted, lb, hb, 1, qx, qy, qz, bd, bi);
     // long ranges: every lane of the group helps, one owner at a time
     unsigned owners = (unsigned)((__ballot(long_a || long_b) >> group_shift) & ((1u << kGroup) - 1u));
     while (owners) {
@@ -388,8 +358,8 @@ __device__ __forceinline__ float scan_shell(const LevelP& L, int cx, int cy, int
       owners &= owners - 1;
       const int src = group_shift + k;
       const int rla = __shfl(la, src), rha = __shfl(ha, src), rlb = __shfl(lb, src), rhb = __shfl(hb, src);
-      if (rha - rla > kLongRange) scan_range_group(L.sorted, rla, rha, g_lane, qx, qy, qz, bd, bi);
-      if (rhb - rlb > kLongRange) scan_range_group(L.sorted, rlb, rhb, g_lane, qx, qy, qz, bd, bi);
+      if (rha - rla > kLongRange) scan_range<K>(L.sorted, rla + g_lane, rha, kGroup, qx, qy, qz, bd, bi);
+      if (rhb - rlb > kLongRange) scan_range<K>(L.sorted, rlb + g_lane, rhb, kGroup, qx, qy, qz, bd, bi);
     }
   }
   float m = INFINITY;
@@ -402,45 +372,46 @@ __device__ __forceinline__ float scan_shell(const LevelP& L, int cx, int cy, int
   return m;
 }
 
-// butterfly all-reduce of the per-lane best-3 lists inside each aligned kGroup-lane group; the (d2, index) order with
+// butterfly all-reduce of the per-lane best-K lists inside each aligned kGroup-lane group; the (d2, index) order with
 // same-index rejection makes the merge commutative/associative, so every lane ends with the identical list.
+// Partner lanes come through DPP (VALU latency) instead of ds_bpermute round trips: lane ^ 1, lane ^ 2 (quad_perm), then the mirror
+// image inside the 8-lane half row (i <-> 7 - i), which pairs the two quads just as well as lane ^ 4.
+static_assert(kGroup == 8, "the DPP controls of group_merge (and the packed shell 1) pair the lanes of an 8-lane group");
 template <int CTRL>
 __device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, true); }
-template <int CTRL>
-__device__ __forceinline__ void merge_step(float bd[3], int bi[3]) {
-  float od[3]; int oi[3];
+template <int K, int CTRL>
+__device__ __forceinline__ void merge_step(float bd[K], int bi[K]) {
+  float od[K]; int oi[K];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { od[k] = __int_as_float(dpp_i<CTRL>(__float_as_int(bd[k]))); oi[k] = dpp_i<CTRL>(bi[k]); }
+  for (int k = 0; k < K; ++k) { od[k] = __int_as_float(dpp_i<CTRL>(__float_as_int(bd[k]))); oi[k] = dpp_i<CTRL>(bi[k]); }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) if (oi[k] >= 0) best3_push(od[k], oi[k], bd, bi);
+  for (int k = 0; k < K; ++k) if (oi[k] >= 0) best_push<K>(od[k], oi[k], bd, bi);
 }
-__device__ __forceinline__ void group_merge_best3(float bd[3], int bi[3]) {
-  if (kGroup == 8) {
-    // partner lanes through DPP (VALU latency) instead of ds_bpermute round trips: lane ^ 1, lane ^ 2 (quad_perm), then the mirror
-    // image inside the 8-lane half row (i <-> 7 - i), which pairs the two quads just as well as lane ^ 4
-    merge_step<0xB1>(bd, bi);
-    merge_step<0x4E>(bd, bi);
-    merge_step<0x141>(bd, bi);
-    return;
-  }
-#pragma unroll
-  for (int mask = 1; mask < kGroup; mask <<= 1) {
-    float od[3]; int oi[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { od[k] = __shfl_xor(bd[k], mask); oi[k] = __shfl_xor(bi[k], mask); }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) if (oi[k] >= 0) best3_push(od[k], oi[k], bd, bi);
-  }
+template <int K>
+__device__ __forceinline__ void group_merge(float bd[K], int bi[K]) {
+  merge_step<K, 0xB1>(bd, bi);
+  merge_step<K, 0x4E>(bd, bi);
+  merge_step<K, 0x141>(bd, bi);
 }
 
-// BUILD: the query's writer lane also builds the point-to-plane correspondence of an accepted query (association.cpp:303-314: the scan point
-// and its first neighbour as doubles, the unit normal of the plane through the three neighbours) into corr = P | PA | N (SoA [3][Q] each) — what
-// k_icp_build did in a launch of its own: one launch and the round trip of the indices less per sub-problem.
-template <bool STATS, bool BUILD = false>
-__device__ __forceinline__ void knn3_body(const int bx, int Q, const float4* __restrict__ scan, const float* tfv, const LevelsP& L,
-                                          float thr, int* __restrict__ idx, float* __restrict__ d2,
-                                          uint8_t* __restrict__ valid, KnnStats* __restrict__ stats,
-                                          const float4* __restrict__ map_raw = nullptr, double* __restrict__ corr = nullptr) {
+// THE SEARCH: the exact K nearest map points of the query of this thread's group (8 lanes per query, 32 queries per workgroup); the query's
+// writer lane then hands (query, scan point, lists) to `epilogue`.  The prologue, the lists and the level / shell loop stand in ONE function
+// on purpose: with the loop in a callee that takes the lists by pointer, the 3-NN kernels came out 1 % longer and the 100 k-query
+// association + linearisation pass measured 2 % slower (the callee is optimised once with the lists still in memory).
+// fine -> coarse: shells 0..1 of the finest grid, shells 0..2 of every coarser one, every shell of the coarsest; dense neighbourhoods finish
+// in the finest grid, sparse ones escalate to a grid whose cells are 2x larger instead of walking dozens of empty fine shells.
+// Re-visited points are rejected by best_push (same index), so levels can overlap freely.  Measured at configs[2], K = 3
+// (ground / surf gate): pyramid ratio 4 with 2 shells per level 626 / 657 Mpairs/s; ratio 2: 756 / 849; ratio 2 with one shell pair
+// per level 706 / 999; ratio 2 with this schedule 755 / 952.  (Choosing the starting level from the occupancy of the query's
+// own cell at every level — one more round trip — was slower: 463 / 748.)  Then the finest level itself: the point-weighted
+// occupancy target kTargetOcc 12 -> 24 -> 48 -> 96..192 gave 755 -> 913 -> 927 -> 1100 Mpairs/s (384: 515, the grid becomes too
+// coarse), and handing ranges longer than kLongRange 24 -> 12 candidates to the cooperative scan another 2-5 %: dependent
+// cell look-ups cost more than streaming a few dozen extra candidates.
+// PACKED is timing only: the (d2, index) order with same-index rejection makes the lists independent of the order in which candidates are
+// met.  The plane association packs shell 1; the line association deals its rows round-robin, as it did when it had a search of its own.
+template <int K, bool PACKED, bool STATS, class Epilogue>
+__device__ __forceinline__ void knn_search(const int bx, int Q, const float4* __restrict__ scan, const float* tfv, const LevelsP& L, float thr,
+                                           KnnStats* __restrict__ stats, const Epilogue& epilogue) {
   // (taking the blocks of queries from both ends alternately, or last to first, so that the expensive end of a scan does not start last:
   // measured 15 % / 40 % SLOWER — neighbouring workgroups share map cells in L2, and the dense near field is better met by a chip that is full)
   const int t = bx * kB + threadIdx.x;
@@ -452,20 +423,14 @@ __device__ __forceinline__ void knn3_body(const int bx, int Q, const float4* __r
   const float qx = tf_row(T.a + 0, p.x, p.y, p.z, p.x, T.t[0]);
   const float qy = tf_row(T.a + 3, p.x, p.y, p.z, p.y, T.t[1]);
   const float qz = tf_row(T.a + 6, p.x, p.y, p.z, p.z, T.t[2]);
-  float bd[3] = {INFINITY, INFINITY, INFINITY};
-  int bi[3] = {-1, -1, -1};
+  // (the lists are sized for the longest K and brace-initialised; slots K.. are never touched.  An initialising loop keeps them in memory
+  // until it is unrolled, and the level loop is then peeled: 3-NN kernels of 2700 instructions and 69 VGPRs instead of 1980 and 62)
+  static_assert(K <= 5, "the empty list below has five slots");
+  float bd[5] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY};
+  int bi[5] = {-1, -1, -1, -1, -1};
   KnnStats st{0, 0, 0, 0, 0, 0};
   if (STATS) st.t_start = (int)((long long)wall_clock64() & 0x7fffffff);
   KnnStats* stp = STATS ? &st : nullptr;
-  // fine -> coarse: shells 0..1 of the finest grid, shells 0..2 of every coarser one; dense neighbourhoods finish in the
-  // finest grid, sparse ones escalate to a grid whose cells are 2x larger instead of walking dozens of empty fine shells.
-  // Re-visited points are rejected by best3_push (same index), so levels can overlap freely.  Measured at configs[2]
-  // (ground / surf gate): pyramid ratio 4 with 2 shells per level 626 / 657 Mpairs/s; ratio 2: 756 / 849; ratio 2 with one shell pair
-  // per level 706 / 999; ratio 2 with this schedule 755 / 952.  (Choosing the starting level from the occupancy of the query's
-  // own cell at every level — one more round trip — was slower: 463 / 748.)  Then the finest level itself: the point-weighted
-  // occupancy target kTargetOcc 12 -> 24 -> 48 -> 96..192 gave 755 -> 913 -> 927 -> 1100 Mpairs/s (384: 515, the grid becomes too
-  // coarse), and handing ranges longer than kLongRange 24 -> 12 candidates to the cooperative scan another 2-5 %: dependent
-  // cell look-ups cost more than streaming a few dozen extra candidates.
   for (int lv = 0; lv < L.n; ++lv) {
     const LevelP& lev = L.l[lv];
     const GridP& g = lev.g;
@@ -473,13 +438,13 @@ __device__ __forceinline__ void knn3_body(const int bx, int Q, const float4* __r
     const int rcap = (lv == L.n - 1) ? max(g.nx, max(g.ny, g.nz)) : (lv == 0 ? 1 : 2);
     bool done = false;
     for (int r = 0; r <= rcap; ++r) {
-      const float m = scan_shell(lev, cx, cy, cz, r, g_lane, qx, qy, qz, bd, bi, stp);
-      group_merge_best3(bd, bi);
+      const float m = scan_shell<K, PACKED>(lev, cx, cy, cz, r, g_lane, qx, qy, qz, bd, bi, stp);
+      group_merge<K>(bd, bi);
       if (STATS) { st.level = lv; st.shells += 1; }
       if (!(m < INFINITY)) { done = true; break; }                   // every point of the map has been seen
       const float ms = fmaxf(m, 0.0f) * 0.9999f - 1e-6f * g.cell;   // conservative against cell-assignment rounding
       const float ms2 = ms > 0.0f ? ms * ms : 0.0f;
-      if (bd[2] < ms2 || ms2 >= thr) { done = true; break; }         // 3rd best beats anything unvisited / beyond the gate
+      if (bd[K - 1] < ms2 || ms2 >= thr) { done = true; break; }     // K-th best beats anything unvisited / beyond the gate
     }
     if (done) break;
   }
@@ -489,7 +454,19 @@ __device__ __forceinline__ void knn3_body(const int bx, int Q, const float4* __r
     st.t_end = (int)((long long)wall_clock64() & 0x7fffffff);
     if (writer) stats[i] = st;
   }
-  if (writer) {
+  if (writer) epilogue(i, p, bd, bi);
+}
+
+// Plane association: 3-NN + gate.  BUILD: the query's writer lane also builds the point-to-plane correspondence of an accepted query
+// (association.cpp:303-314: the scan point and its first neighbour as doubles, the unit normal of the plane through the three neighbours)
+// into corr = P | PA | N (SoA [3][Q] each) — what k_icp_build did in a launch of its own: one launch and the round trip of the indices less
+// per sub-problem.
+template <bool STATS, bool BUILD = false>
+__device__ __forceinline__ void knn3_body(const int bx, int Q, const float4* __restrict__ scan, const float* tfv, const LevelsP& L,
+                                          float thr, int* __restrict__ idx, float* __restrict__ d2,
+                                          uint8_t* __restrict__ valid, KnnStats* __restrict__ stats,
+                                          const float4* __restrict__ map_raw = nullptr, double* __restrict__ corr = nullptr) {
+  knn_search<3, true, STATS>(bx, Q, scan, tfv, L, thr, stats, [&](int i, const float4& p, const float* bd, const int* bi) {
     idx[3 * i + 0] = bi[0]; idx[3 * i + 1] = bi[1]; idx[3 * i + 2] = bi[2];
     d2[3 * i + 0] = bd[0]; d2[3 * i + 1] = bd[1]; d2[3 * i + 2] = bd[2];
     const bool ok = bi[0] >= 0 && bd[0] < thr && bi[1] >= 0 && bd[1] < thr && bi[2] >= 0 && bd[2] < thr;
@@ -504,7 +481,7 @@ __device__ __forceinline__ void knn3_body(const int bx, int Q, const float4* __r
       PA[i] = pa[0]; PA[Q + i] = pa[1]; PA[2 * Q + i] = pa[2];
       N[i] = n[0]; N[Q + i] = n[1]; N[2 * Q + i] = n[2];
     }
-  }
+  });
 }
 template <bool STATS>
 __global__ __launch_bounds__(kB) void k_knn3(int Q, const float4* __restrict__ scan, const TfArg tfa, const LevelsP L,
@@ -528,101 +505,8 @@ __global__ __launch_bounds__(kB) void k_knn3_b(const KnnJob* __restrict__ jobs, 
 }
 
 // ---- line association (lvf_edge_associate): exact 5-NN on the same grid pyramid + the principal-axis fit of the five neighbours ----
-// The search is k_knn3's — eight lanes per query, the shell schedule, the pruning radius, the cooperative scan of long ranges — written out
-// again for a best-FIVE list: the 3-NN path above does not go through any of it.  Edge clouds hold hundreds to a few thousand points, so
-// a launch is a handful of workgroups and its time is the dependent chain of one query.
-__device__ __forceinline__ void best5_push(float d, int i, float bd[5], int bi[5]) {
-  if (!lex_less(d, i, bd[4], bi[4]) || i == bi[0] || i == bi[1] || i == bi[2] || i == bi[3]) return;   // worse than 5th, or already held
-  // the list is sorted, so "new < old[k]" is monotone in k: slot k takes the new entry where it first holds, old[k - 1] below that
-  const bool l0 = lex_less(d, i, bd[0], bi[0]), l1 = lex_less(d, i, bd[1], bi[1]), l2 = lex_less(d, i, bd[2], bi[2]), l3 = lex_less(d, i, bd[3], bi[3]);
-  bd[4] = l3 ? bd[3] : d; bi[4] = l3 ? bi[3] : i;
-  if (l3) { bd[3] = l2 ? bd[2] : d; bi[3] = l2 ? bi[2] : i; }
-  if (l2) { bd[2] = l1 ? bd[1] : d; bi[2] = l1 ? bi[1] : i; }
-  if (l1) { bd[1] = l0 ? bd[0] : d; bi[1] = l0 ? bi[0] : i; }
-  if (l0) { bd[0] = d; bi[0] = i; }
-}
-__device__ __forceinline__ void scan_range5(const float4* __restrict__ sorted, int lo, int hi, int step, float qx, float qy, float qz, float bd[5], int bi[5]) {
-  // step = 1: one lane walks the range; step = kGroup: the group's lanes take every kGroup-th candidate (lo already offset by the lane)
-  for (int j = lo; j < hi; j += 4 * step) {
-    const int last = hi - 1;
-    const float4 mm[4] = {sorted[j], sorted[min(j + step, last)], sorted[min(j + 2 * step, last)], sorted[min(j + 3 * step, last)]};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {   // a clamped duplicate of the last point is rejected by best5_push (same index)
-      const float dx = sub_rn(qx, mm[u].x), dy = sub_rn(qy, mm[u].y), dz = sub_rn(qz, mm[u].z);
-      const float d = add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
-      best5_push(d, __float_as_int(mm[u].w), bd, bi);
-    }
-  }
-}
-// scan_shell for the best-five list: rows dealt round-robin to the group's lanes (no packed shell 1), pruning by the 5th-best d2
-__device__ __forceinline__ float scan_shell5(const LevelP& L, int cx, int cy, int cz, int r, int g_lane, float qx, float qy, float qz, float bd[5], int bi[5]) {
-  const GridP& g = L.g;
-  const int side = 2 * r + 1;
-  const float prune2 = bd[4];
-  const float slack = 1e-6f * g.cell;
-  const int group_shift = (threadIdx.x & 63) & ~(kGroup - 1);
-  for (int it = 0; it * kGroup < side * side; ++it) {
-    const int row_id = it * kGroup + g_lane;
-    int la = 0, ha = 0, lb = 0, hb = 0;
-    if (row_id < side * side) {
-      const int dz = row_id / side - r, dy = row_id % side - r;
-      const int z = cz + dz, y = cy + dy;
-      if (z >= 0 && z < g.nz && y >= 0 && y < g.ny) {
-        float gy = 0.0f, gz = 0.0f;
-        if (y > cy) gy = (g.oy + (float)y * g.cell) - qy; else if (y < cy) gy = qy - (g.oy + (float)(y + 1) * g.cell);
-        if (z > cz) gz = (g.oz + (float)z * g.cell) - qz; else if (z < cz) gz = qz - (g.oz + (float)(z + 1) * g.cell);
-        gy = fmaxf(gy * 0.9999f - slack, 0.0f); gz = fmaxf(gz * 0.9999f - slack, 0.0f);
-        const float base2 = gy * gy + gz * gz;
-        if (!(base2 > prune2)) {
-          int xlo = 0, xhi = g.nx - 1;
-          if (prune2 < INFINITY) {
-            const float dxm = sqrtf(prune2 - base2) * 1.0001f + slack;
-            xlo = max(xlo, (int)floorf((qx - dxm - g.ox) * g.inv_cell - 1e-3f));
-            xhi = min(xhi, (int)floorf((qx + dxm - g.ox) * g.inv_cell + 1e-3f));
-          }
-          const int row = (z * g.ny + y) * g.nx;
-          if (abs(dz) == r || abs(dy) == r) {
-            const int x0 = max(cx - r, xlo), x1 = min(cx + r, xhi);
-            if (x0 <= x1) { la = L.cell_start[row + x0]; ha = L.cell_start[row + x1 + 1]; }
-          } else {
-            const int xa = cx - r, xb = cx + r;
-            if (xa >= xlo && xa <= xhi) { la = L.cell_start[row + xa]; ha = L.cell_start[row + xa + 1]; }
-            if (xb <= xhi && xb >= xlo) { lb = L.cell_start[row + xb]; hb = L.cell_start[row + xb + 1]; }
-          }
-        }
-      }
-    }
-    const bool long_a = (ha - la) > kLongRange, long_b = (hb - lb) > kLongRange;
-    if (!long_a && ha > la) scan_range5(L.sorted, la, ha, 1, qx, qy, qz, bd, bi);
-    if (!long_b && hb > lb) scan_range5(L.sorted, lb, hb, 1, qx, qy, qz, bd, bi);
-    unsigned owners = (unsigned)((__ballot(long_a || long_b) >> group_shift) & ((1u << kGroup) - 1u));
-    while (owners) {
-      const int k = __ffs(owners) - 1;
-      owners &= owners - 1;
-      const int src = group_shift + k;
-      const int rla = __shfl(la, src), rha = __shfl(ha, src), rlb = __shfl(lb, src), rhb = __shfl(hb, src);
-      if (rha - rla > kLongRange) scan_range5(L.sorted, rla + g_lane, rha, kGroup, qx, qy, qz, bd, bi);
-      if (rhb - rlb > kLongRange) scan_range5(L.sorted, rlb + g_lane, rhb, kGroup, qx, qy, qz, bd, bi);
-    }
-  }
-  float m = INFINITY;
-  if (cx + r + 1 <= g.nx - 1) m = fminf(m, (g.ox + (float)(cx + r + 1) * g.cell) - qx);
-  if (cx - r - 1 >= 0) m = fminf(m, qx - (g.ox + (float)(cx - r) * g.cell));
-  if (cy + r + 1 <= g.ny - 1) m = fminf(m, (g.oy + (float)(cy + r + 1) * g.cell) - qy);
-  if (cy - r - 1 >= 0) m = fminf(m, qy - (g.oy + (float)(cy - r) * g.cell));
-  if (cz + r + 1 <= g.nz - 1) m = fminf(m, (g.oz + (float)(cz + r + 1) * g.cell) - qz);
-  if (cz - r - 1 >= 0) m = fminf(m, qz - (g.oz + (float)(cz - r) * g.cell));
-  return m;
-}
-template <int CTRL>
-__device__ __forceinline__ void merge_step5(float bd[5], int bi[5]) {
-  float od[5]; int oi[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) { od[k] = __int_as_float(dpp_i<CTRL>(__float_as_int(bd[k]))); oi[k] = dpp_i<CTRL>(bi[k]); }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) if (oi[k] >= 0) best5_push(od[k], oi[k], bd, bi);
-}
-static_assert(kGroup == 8, "merge_step5's DPP partners pair the lanes of an 8-lane group");
+// The search is knn_search with K = 5 — the plane association's, with a list of five; what is here is the line fit and the kernel's epilogue.
+// Edge clouds hold hundreds to a few thousand points, so a launch is a handful of workgroups and its time is the dependent chain of one query.
 
 // one Jacobi rotation of the symmetric 3 x 3 matrix in the (p, q) plane; r is the third index.  V's columns follow.
 __device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double vp[3], double vq[3]) {
@@ -669,51 +553,25 @@ __device__ __forceinline__ bool line_fit5(const double x[5][3], double ratio, do
 __global__ __launch_bounds__(kB) void k_edge_associate(int Q, const float4* __restrict__ scan, const TfArg tfa, const LevelsP L, float thr, double ratio,
                                                        const float4* __restrict__ map_raw, int* __restrict__ idx, float* __restrict__ d2,
                                                        uint8_t* __restrict__ valid, double* __restrict__ corr /* [12][Q] */) {
-  const int t = blockIdx.x * kB + threadIdx.x;
-  const int g_lane = t & (kGroup - 1);
-  const int i = min(t / kGroup, Q - 1);          // surplus groups of the last block shadow the last query (no divergent exit before the shuffles)
-  const bool writer = (t / kGroup) < Q && g_lane == 0;
-  const Tf32 T = make_tf32(tfa.v);
-  const float4 p = scan[i];
-  const float qx = tf_row(T.a + 0, p.x, p.y, p.z, p.x, T.t[0]);
-  const float qy = tf_row(T.a + 3, p.x, p.y, p.z, p.y, T.t[1]);
-  const float qz = tf_row(T.a + 6, p.x, p.y, p.z, p.z, T.t[2]);
-  float bd[5] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY};
-  int bi[5] = {-1, -1, -1, -1, -1};
-  for (int lv = 0; lv < L.n; ++lv) {             // the level / shell schedule of knn3_body
-    const LevelP& lev = L.l[lv];
-    const GridP& g = lev.g;
-    const int cx = cell_coord(qx, g.ox, g.inv_cell, g.nx), cy = cell_coord(qy, g.oy, g.inv_cell, g.ny), cz = cell_coord(qz, g.oz, g.inv_cell, g.nz);
-    const int rcap = (lv == L.n - 1) ? max(g.nx, max(g.ny, g.nz)) : (lv == 0 ? 1 : 2);
-    bool done = false;
-    for (int r = 0; r <= rcap; ++r) {
-      const float m = scan_shell5(lev, cx, cy, cz, r, g_lane, qx, qy, qz, bd, bi);
-      merge_step5<0xB1>(bd, bi); merge_step5<0x4E>(bd, bi); merge_step5<0x141>(bd, bi);      // lane ^ 1, lane ^ 2, mirror inside the half row
-      if (!(m < INFINITY)) { done = true; break; }
-      const float ms = fmaxf(m, 0.0f) * 0.9999f - 1e-6f * g.cell;
-      const float ms2 = ms > 0.0f ? ms * ms : 0.0f;
-      if (bd[4] < ms2 || ms2 >= thr) { done = true; break; }         // 5th best beats anything unvisited / beyond the gate
+  knn_search<5, false, false>(blockIdx.x, Q, scan, tfa.v, L, thr, nullptr, [&](int i, const float4& p, const float* bd, const int* bi) {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { idx[5 * i + k] = bi[k]; d2[5 * i + k] = bd[k]; ok = ok && bi[k] >= 0 && bd[k] < thr; }
+    double c[3] = {0, 0, 0}, pr[6] = {0, 0, 0, 0, 0, 0};
+    if (ok) {
+      double x[5][3];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) { const float4 a = map_raw[bi[k]]; x[k][0] = (double)a.x; x[k][1] = (double)a.y; x[k][2] = (double)a.z; }
+      ok = line_fit5(x, ratio, c, pr);
     }
-    if (done) break;
-  }
-  if (!writer) return;
-  bool ok = true;
+    valid[i] = ok ? 1 : 0;
+    // (an invalid point's record reads zero)
+    corr[i] = ok ? (double)p.x : 0.0; corr[(size_t)Q + i] = ok ? (double)p.y : 0.0; corr[(size_t)2 * Q + i] = ok ? (double)p.z : 0.0;
 #pragma unroll
-  for (int k = 0; k < 5; ++k) { idx[5 * i + k] = bi[k]; d2[5 * i + k] = bd[k]; ok = ok && bi[k] >= 0 && bd[k] < thr; }
-  double c[3] = {0, 0, 0}, pr[6] = {0, 0, 0, 0, 0, 0};
-  if (ok) {
-    double x[5][3];
+    for (int k = 0; k < 3; ++k) corr[(size_t)(3 + k) * Q + i] = ok ? c[k] : 0.0;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) { const float4 a = map_raw[bi[k]]; x[k][0] = (double)a.x; x[k][1] = (double)a.y; x[k][2] = (double)a.z; }
-    ok = line_fit5(x, ratio, c, pr);
-  }
-  valid[i] = ok ? 1 : 0;
-  // (an invalid point's record reads zero)
-  corr[i] = ok ? (double)p.x : 0.0; corr[(size_t)Q + i] = ok ? (double)p.y : 0.0; corr[(size_t)2 * Q + i] = ok ? (double)p.z : 0.0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) corr[(size_t)(3 + k) * Q + i] = ok ? c[k] : 0.0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) corr[(size_t)(6 + k) * Q + i] = ok ? pr[k] : 0.0;
+    for (int k = 0; k < 6; ++k) corr[(size_t)(6 + k) * Q + i] = ok ? pr[k] : 0.0;
+  });
 }
 
 // exclusive prefix sum of n ints on the context's stream; out has n + 1 entries (out[n] = grand total).  in != out.
@@ -750,10 +608,8 @@ LevelsP levels_of(const lvf_map* m) {
 }
 int launch_knn3_build(lvf_map* m, lvf_scan* sc, const double* pose, float thr, double* corr) {
   if (sc->Q <= 0) return LVF_OK;
-  TfArg tf;
-  for (int k = 0; k < 7; ++k) tf.v[k] = (float)pose[k];   // Sophus SE3d::cast<float>()  association.cpp:287
-  hipLaunchKernelGGL(k_knn3_build, dim3(knn_grid(sc->Q)), dim3(kB), 0, m->ctx->stream, sc->Q, sc->pts.p, tf, levels_of(m), thr, sc->idx.p, sc->d2.p, sc->valid.p,
-                     m->raw.p, corr);
+  hipLaunchKernelGGL(k_knn3_build, dim3(knn_grid(sc->Q)), dim3(kB), 0, m->ctx->stream, sc->Q, sc->pts.p, tf_arg(pose), levels_of(m), thr, sc->idx.p, sc->d2.p,
+                     sc->valid.p, m->raw.p, corr);
   LVF_HIP(hipGetLastError());
   sc->searched = true;
   return LVF_OK;
@@ -766,9 +622,7 @@ int launch_edge_associate(lvf_map* m, lvf_scan* sc, const double* pose, float th
   }
   sc->edge_searched = true;
   if (Q <= 0) return LVF_OK;
-  TfArg tf;
-  for (int k = 0; k < 7; ++k) tf.v[k] = (float)pose[k];
-  hipLaunchKernelGGL(k_edge_associate, dim3(knn_grid(Q)), dim3(kB), 0, m->ctx->stream, Q, sc->pts.p, tf, levels_of(m), thr, min_eigen_ratio, m->raw.p,
+  hipLaunchKernelGGL(k_edge_associate, dim3(knn_grid(Q)), dim3(kB), 0, m->ctx->stream, Q, sc->pts.p, tf_arg(pose), levels_of(m), thr, min_eigen_ratio, m->raw.p,
                      sc->eidx.p, sc->ed2.p, sc->evalid.p, sc->ecorr.p);
   LVF_HIP(hipGetLastError());
   return LVF_OK;
@@ -1024,6 +878,18 @@ int lvf_scan_create_from_cloud(const lvf_cloud* c, lvf_scan** out) {
 
 int lvf_scan_destroy(lvf_scan* s) { delete s; return LVF_OK; }      // (~lvf_scan waits for the creation's upload before its pinned block returns to the pool)
 
+// the plane association's launch (lvf_knn3); stats != nullptr: the instantiation that also records the per-query statistics there
+static int launch_knn3(lvf_map* m, lvf_scan* sc, const double* pose, float thr, KnnStats* stats) {
+  if (sc->Q > 0) {
+    const auto kernel = stats ? k_knn3<true> : k_knn3<false>;
+    hipLaunchKernelGGL(kernel, dim3(knn_grid(sc->Q)), dim3(kB), 0, m->ctx->stream, sc->Q, sc->pts.p, tf_arg(pose), levels_of(m), thr, sc->idx.p, sc->d2.p,
+                       sc->valid.p, stats);
+    LVF_HIP(hipGetLastError());
+  }
+  sc->searched = true;
+  return LVF_OK;
+}
+
 // diagnostic (not part of the reference surface): per-query search statistics {candidates, range lookups, last level,
 // shells}, and the grid pyramid geometry {cell, nx, ny, nz} per level.
 // lvf_knn3_debug_stats2: `stride` int32 per query, 4 <= stride <= 6: {candidates, range lookups, last level, shells[, wave start, wave end clock]}.
@@ -1045,12 +911,7 @@ static int knn3_debug_stats_impl(lvf_map* m, lvf_scan* sc, const double* pose, f
   if (sc->Q == 0) return LVF_OK;
   DevBuf<KnnStats> st;
   LVF_TRY(st.alloc(sc->Q));
-  TfArg tf;
-  for (int k = 0; k < 7; ++k) tf.v[k] = (float)pose[k];
-  const LevelsP L = levels_of(m);
-  hipLaunchKernelGGL(k_knn3<true>, dim3(knn_grid(sc->Q)), dim3(kB), 0, m->ctx->stream, sc->Q, sc->pts.p, tf, L, thr,
-                     sc->idx.p, sc->d2.p, sc->valid.p, st.p);
-  LVF_HIP(hipGetLastError());
+  LVF_TRY(launch_knn3(m, sc, pose, thr, st.p));
   constexpr int kW = (int)(sizeof(KnnStats) / sizeof(int32_t));
   if (stride == kW) {
     LVF_HIP(hipMemcpyAsync(stats6, st.p, (size_t)sc->Q * sizeof(KnnStats), hipMemcpyDeviceToHost, m->ctx->stream));
@@ -1061,7 +922,6 @@ static int knn3_debug_stats_impl(lvf_map* m, lvf_scan* sc, const double* pose, f
     LVF_HIP(hipStreamSynchronize(m->ctx->stream));
     for (int q = 0; q < sc->Q; ++q) for (int k = 0; k < stride; ++k) stats6[(size_t)q * stride + k] = h[(size_t)q * kW + k];
   }
-  sc->searched = true;
   return LVF_OK;
 }
 
@@ -1070,16 +930,7 @@ int lvf_knn3(lvf_map* m, lvf_scan* sc, const double* pose, float thr) {
   LVF_REQUIRE(m->ctx == sc->ctx, "lvf_knn3: map and scan belong to different contexts");
   LVF_REQUIRE(!(thr != thr) && thr > 0.0f, "lvf_knn3: thr must be > 0");
   LVF_TRY(lvf::enter(m->ctx));
-  if (sc->Q > 0) {
-    TfArg tf;
-    for (int k = 0; k < 7; ++k) tf.v[k] = (float)pose[k];   // Sophus SE3d::cast<float>()  association.cpp:287
-    const LevelsP L = levels_of(m);
-    hipLaunchKernelGGL(k_knn3<false>, dim3(knn_grid(sc->Q)), dim3(kB), 0, m->ctx->stream, sc->Q, sc->pts.p, tf, L, thr,
-                       sc->idx.p, sc->d2.p, sc->valid.p, (KnnStats*)nullptr);
-    LVF_HIP(hipGetLastError());
-  }
-  sc->searched = true;
-  return LVF_OK;
+  return launch_knn3(m, sc, pose, thr, nullptr);
 }
 
 int lvf_edge_associate(lvf_map* m, lvf_scan* sc, const double* pose, float thr, double min_eigen_ratio) {

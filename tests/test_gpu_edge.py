@@ -76,6 +76,35 @@ def test_edge_associate(ctx, scenes, name):
     mp.close(); sn.close()
 
 
+def test_line_association_starts_with_the_plane_association(ctx, scenes):
+    """The two associations are one search with lists of three and of five: on the same (map, scan) the five neighbours begin with the three,
+    indices and d2 bit for bit, and both are the brute-force lists.  300 points in [-2, 2]^3 on a 1 m grid, 41 of them one point (a cell
+    longer than the cooperative scan's threshold, with 40-fold d2 ties), 37 queries (surplus groups in the one workgroup), no gate."""
+    from lvio_fusion_amd import api
+    rng = np.random.default_rng(518)
+    m = np.zeros((300, 4), np.float32); m[:, :3] = rng.uniform(-2, 2, (300, 3))
+    m[100:140] = m[7]
+    pose = scenes["m5"]["pose"]
+    q = rng.uniform(-3, 3, (37, 3))
+    q[0] = (m[7, :3].astype(np.float64) - pose[4:]) @ er.rotmat(pose[:4])          # the duplicated point through the inverse pose
+    q = er._pad(q)
+    lo = m[:, :3].min(0)
+    cell = np.floor((m[:, :3] - lo) / np.float32(1.0)).astype(int)
+    assert (cell == cell[7]).all(1).sum() > 12                                     # kLongRange: the whole group scans this cell
+    r5, rd5 = er.knn_brute(m, er.transform_f32(pose, q), 5)
+    assert (r5 >= 0).all() and list(r5[0]) == [7, 100, 101, 102, 103] and len(set(rd5[0].view(np.uint32))) == 1
+    mp, sn = api.Map(ctx, m, 4.0), api.Scan(ctx, q)
+    api.knn3(mp, sn, pose, np.inf)
+    i3, d3, v3 = sn.download()
+    api.edge_associate(mp, sn, pose, np.inf, 3.0)
+    i5, d5 = sn.download_edges()[:2]
+    mp.close(); sn.close()
+    assert v3.all()
+    assert np.array_equal(i5[:, :3], i3) and np.array_equal(d5[:, :3].view(np.uint32), d3.view(np.uint32))
+    assert np.array_equal(i5, r5) and np.array_equal(d5.view(np.uint32), rd5.view(np.uint32))
+    assert np.array_equal(i3, r5[:, :3]) and np.array_equal(d3.view(np.uint32), rd5[:, :3].view(np.uint32))
+
+
 # ----------------------------------------------------------------------------- factor
 @pytest.mark.parametrize("mode", [0, 1])
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 1000])
