@@ -1,6 +1,8 @@
-// loop_dev.hpp — device pieces shared by the loop-correction tail (loop_kernels.hip) and the GNSS alignment (navsat_kernels.hip):
-// the workgroup sum of the one-workgroup solves, the body of PoseGraph::ForwardUpdate (src/lvio_fusion/src/pose_graph.cpp:245-252) and the
-// Sophus SE3 operations built from the same arithmetic (Hamilton product re-normalised; vectors through Eigen's _transformVector).
+// loop_dev.hpp — device pieces shared by the loop-correction tail (loop_kernels.hip), the GNSS alignment (navsat_kernels.hip) and the visual
+// relocalisation (reloc_kernels.hip), which all reach it through small_lm.hpp: the workgroup sum of one value (the candidate cost and the
+// line search of lm_small, the roll pre-solve's vector sum, the inlier count), the body of PoseGraph::ForwardUpdate
+// (src/lvio_fusion/src/pose_graph.cpp:245-252) and the Sophus SE3 operations built from the same arithmetic (Hamilton product re-normalised;
+// vectors through Eigen's _transformVector).
 #pragma once
 #include "lvf_internal.hpp"
 

@@ -9,11 +9,12 @@
 //
 // RelocateRError goes through SE3Product of the UN-normalised parameter quaternion (the rotation of the translation normalises it,
 // the quaternion product does not), so its ambient 7x4 Jacobian is taken exactly as the reference's autodiff does: dual numbers
-// (djet.hpp).  The problem has 3 tangent unknowns and a few dozen blocks: the whole LM loop (linearise, damped 3x3 solve, candidate
-// cost, accept / reject, trust-region update, termination tests) is ONE launch of one workgroup; the host reads one record.
+// (djet.hpp).  The problem has 3 tangent unknowns and a few dozen blocks: the whole LM loop (lm_small, small_lm.hpp: linearise, damped
+// 3x3 solve, candidate cost, accept / reject, trust-region update, termination tests) is ONE launch of one workgroup; the host reads one
+// record.
 #include "lvf_internal.hpp"
-#include "loop_dev.hpp"
 #include "se3_jet.hpp"
+#include "small_lm.hpp"
 
 namespace lvf {
 
@@ -55,69 +56,45 @@ __global__ __launch_bounds__(64) void k_relocate_r(int n, const double* __restri
   }
 }
 
-struct RelocOpts { int max_iters; double function_tol, gradient_tol, parameter_tol, min_rel_decrease, radius0; };
-struct RelocRecord { double q[4]; double initial_cost, final_cost; int iters, successes, termination, pad; };
-
-__global__ __launch_bounds__(kLT) void k_relocate_solve(int n, const double* __restrict__ relocated, const double* __restrict__ unrelocated,
-                                                        const double* __restrict__ q_in, RelocOpts o, RelocRecord* __restrict__ out) {
-  __shared__ double red[kLT / 64];
-  const int tid = threadIdx.x;
-  double q[4] = {q_in[0], q_in[1], q_in[2], q_in[3]};
-  double radius = o.radius0, decrease = 2.0, cost = 0.0, initial_cost = 0.0;
-  int iters = 0, successes = 0, termination = 1;
-  // ceres::Solve's TrustRegionMinimizer order (declared semantics: oracle/lm.h lm_solve; this problem's restatement: oracle/loop.h)
-  bool first = true;
-  double h0[3] = {0.0, 0.0, 0.0};
-  int invalid_run = 0;
-  for (;;) {
+// lm_small's problem (small_lm.hpp): the RelocateRError blocks on one quaternion, 4 ambient coordinates and 3 tangent unknowns, no loss function
+struct RelocateR {
+  static constexpr bool kBox = false;
+  int n;
+  const double *relocated, *unrelocated;
+  __device__ __forceinline__ void accumulate(const double* q, unsigned, double* acc) const {
     // EigenQuaternionParameterization::ComputeJacobian at q
     const double P[12] = {q[3], q[2], -q[1], -q[2], q[3], q[0], q[1], -q[0], q[3], -q[0], -q[1], -q[2]};
-    double h[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, c = 0.0;
-    for (int i = tid; i < n; i += kLT) {
+    for (int i = threadIdx.x; i < n; i += kLT) {
       double r[7], J[28];
       relocate_r_eval<true>(relocated + 7 * i, unrelocated + 7 * i, q, r, J);
 #pragma unroll
       for (int k = 0; k < 7; ++k) {
-        c += 0.5 * r[k] * r[k];
+        acc[9] += 0.5 * r[k] * r[k];
         double l[3];
 #pragma unroll
         for (int x = 0; x < 3; ++x) l[x] = J[4 * k] * P[x] + J[4 * k + 1] * P[3 + x] + J[4 * k + 2] * P[6 + x] + J[4 * k + 3] * P[9 + x];
-        g[0] += l[0] * r[k]; g[1] += l[1] * r[k]; g[2] += l[2] * r[k];
-        h[0] += l[0] * l[0]; h[1] += l[1] * l[0]; h[2] += l[1] * l[1]; h[3] += l[2] * l[0]; h[4] += l[2] * l[1]; h[5] += l[2] * l[2];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+          acc[6 + u] += l[u] * r[k];
+#pragma unroll
+          for (int v = 0; v <= u; ++v) acc[u * (u + 1) / 2 + v] += l[u] * l[v];
+        }
       }
     }
-    cost = wg_sum(c, red);
+  }
+  __device__ __forceinline__ double cost_part(const double* q) const {
+    double c = 0.0;
+    for (int i = threadIdx.x; i < n; i += kLT) {
+      double r[7], J[28];
+      relocate_r_eval<false>(relocated + 7 * i, unrelocated + 7 * i, q, r, J);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) g[k] = wg_sum(g[k], red);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) h[k] = wg_sum(h[k], red);
-    // every thread holds the same sums and takes the same decisions (no divergence across the barriers below)
-    if (first) { initial_cost = cost; first = false; h0[0] = h[0]; h0[1] = h[2]; h0[2] = h[5]; }      // Jacobi scaling: iteration 0, frozen (Ceres default jacobi_scaling; relocator.cpp:259 solves with default options)
-    if (iters >= o.max_iters) break;
-    if (fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2]))) <= o.gradient_tol) { termination = 0; break; }
-    if (radius < 1e-32) { termination = 0; break; }
-    const double H[3][3] = {{h[0], h[1], h[3]}, {h[1], h[2], h[4]}, {h[3], h[4], h[5]}};
-    double A[3][3];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-#pragma unroll
-      for (int v = 0; v < 3; ++v) A[u][v] = H[u][v];
-      { const double sj = 1.0 / (1.0 + sqrt(h0[u])), s2 = sj * sj; A[u][u] += fmin(fmax(H[u][u] * s2, 1e-6), 1e32) / s2 / radius; }
+      for (int k = 0; k < 7; ++k) c += 0.5 * r[k] * r[k];
     }
-    const double l00 = sqrt(A[0][0]), l10 = A[1][0] / l00, l20 = A[2][0] / l00;
-    const double t11 = A[1][1] - l10 * l10, l11 = sqrt(t11), l21 = (A[2][1] - l20 * l10) / l11;
-    const double t22 = A[2][2] - l20 * l20 - l21 * l21, l22 = sqrt(t22);
-    const bool ok = A[0][0] > 0.0 && t11 > 0.0 && t22 > 0.0;
-    double dx[3] = {0.0, 0.0, 0.0};
-    if (ok) {
-      const double y0 = -g[0] / l00, y1 = (-g[1] - l10 * y0) / l11, y2 = (-g[2] - l20 * y0 - l21 * y1) / l22;
-      dx[2] = y2 / l22; dx[1] = (y1 - l21 * dx[2]) / l11; dx[0] = (y0 - l10 * dx[1] - l20 * dx[2]) / l00;
-    }
-    double model = 0.0;
-#pragma unroll
-    for (int u = 0; u < 3; ++u) model -= dx[u] * (g[u] + 0.5 * (H[u][0] * dx[0] + H[u][1] * dx[1] + H[u][2] * dx[2]));
-    // EigenQuaternionParameterization::Plus
-    double qc[4] = {q[0], q[1], q[2], q[3]};
+    return c;
+  }
+  // EigenQuaternionParameterization::Plus
+  __device__ __forceinline__ void plus(const double* q, const double* dx, double* qc) const {
+    qc[0] = q[0]; qc[1] = q[1]; qc[2] = q[2]; qc[3] = q[3];
     const double dn = sqrt(dx[0] * dx[0] + dx[1] * dx[1] + dx[2] * dx[2]);
     if (dn > 0.0) {
       const double sn = sin(dn) / dn, cw = cos(dn);
@@ -127,37 +104,23 @@ __global__ __launch_bounds__(kLT) void k_relocate_solve(int n, const double* __r
       qc[1] = cw * q[1] - ax * q[2] + ay * q[3] + az * q[0];
       qc[2] = cw * q[2] + ax * q[1] - ay * q[0] + az * q[3];
     }
-    if (!(ok && model > 0.0)) {                      // invalid step (uniform across the workgroup)
-      ++iters;
-      if (++invalid_run >= 5) { termination = 2; break; }
-      radius *= 0.5;
-      continue;
-    }
-    invalid_run = 0;
-    const double xn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const double sn2 = (qc[0] - q[0]) * (qc[0] - q[0]) + (qc[1] - q[1]) * (qc[1] - q[1]) + (qc[2] - q[2]) * (qc[2] - q[2]) + (qc[3] - q[3]) * (qc[3] - q[3]);
-    if (sqrt(sn2) <= o.parameter_tol * (xn + o.parameter_tol)) { termination = 0; break; }
-    double cc = 0.0;
-    for (int i = tid; i < n; i += kLT) {
-      double r[7], J[28];
-      relocate_r_eval<false>(relocated + 7 * i, unrelocated + 7 * i, qc, r, J);
-#pragma unroll
-      for (int k = 0; k < 7; ++k) cc += 0.5 * r[k] * r[k];
-    }
-    const double cand = wg_sum(cc, red);
-    if (fabs(cost - cand) <= o.function_tol * cost) { termination = 0; break; }
-    ++iters;
-    const double rho = (cost - cand) / model;
-    if (rho > o.min_rel_decrease) {
-      q[0] = qc[0]; q[1] = qc[1]; q[2] = qc[2]; q[3] = qc[3];
-      cost = cand; ++successes;
-      const double t = 2.0 * rho - 1.0;
-      radius = fmin(radius / fmax(1.0 / 3.0, 1.0 - t * t * t), 1e16); decrease = 2.0;
-    } else { radius /= decrease; decrease *= 2.0; }
   }
-  if (tid == 0) {
+  __device__ __forceinline__ unsigned norm_mask(unsigned) const { return 15u; }
+};
+
+struct RelocRecord { double q[4]; LmRec lm; };
+
+// Jacobi scaling frozen at iteration 0 is Ceres' default jacobi_scaling: relocator.cpp:259 solves with default options.  This problem's
+// restatement: oracle/loop.h.
+__global__ __launch_bounds__(kLT) void k_relocate_solve(int n, const double* __restrict__ relocated, const double* __restrict__ unrelocated,
+                                                        const double* __restrict__ q_in, LmOpts o, RelocRecord* __restrict__ out) {
+  __shared__ double tile[lm_tile_doubles(3)];
+  double q[4] = {q_in[0], q_in[1], q_in[2], q_in[3]};
+  LmRec rec;
+  lm_small<3, 4, true>(RelocateR{n, relocated, unrelocated}, n, q, 7u, o, rec, tile);
+  if (threadIdx.x == 0) {
     out->q[0] = q[0]; out->q[1] = q[1]; out->q[2] = q[2]; out->q[3] = q[3];
-    out->initial_cost = initial_cost; out->final_cost = cost; out->iters = iters; out->successes = successes; out->termination = termination; out->pad = 0;
+    out->lm = rec;
   }
 }
 
@@ -211,17 +174,18 @@ int lvf_relocate_rotation_solve(lvf_ctx* ctx, int n, const double* relocated, co
   DevBuf<double> a, b, q;
   DevBuf<RelocRecord> rec;
   LVF_TRY(a.upload(relocated, (size_t)7 * n, s)); LVF_TRY(b.upload(unrelocated, (size_t)7 * n, s)); LVF_TRY(q.upload(q4, 4, s)); LVF_TRY(rec.alloc(1));
-  const RelocOpts ro{o->max_num_iterations, o->function_tolerance, o->gradient_tolerance, o->parameter_tolerance, o->min_relative_decrease,
-                     o->initial_trust_region_radius};
-  hipLaunchKernelGGL(k_relocate_solve, dim3(1), dim3(kLT), 0, s, n, a.p, b.p, q.p, ro, rec.p);
+  const LmOpts lo{o->max_num_iterations, o->function_tolerance, o->gradient_tolerance, o->parameter_tolerance, o->min_relative_decrease,
+                  o->initial_trust_region_radius};
+  hipLaunchKernelGGL(k_relocate_solve, dim3(1), dim3(kLT), 0, s, n, a.p, b.p, q.p, lo, rec.p);
   LVF_HIP(hipGetLastError());
   RelocRecord h;
   LVF_HIP(hipMemcpyAsync(&h, rec.p, sizeof(h), hipMemcpyDeviceToHost, s));
   LVF_HIP(hipStreamSynchronize(s));
-  if (h.termination == 2 || !std::isfinite(h.final_cost)) { summary->termination = 2; summary->initial_cost = h.initial_cost; summary->final_cost = h.initial_cost; return LVF_OK; }   // fail soft: q4 untouched
+  const LmRec& r = h.lm;
+  if (r.termination == 2 || !std::isfinite(r.final_cost)) { summary->termination = 2; summary->initial_cost = r.initial_cost; summary->final_cost = r.initial_cost; return LVF_OK; }   // fail soft: q4 untouched
   std::memcpy(q4, h.q, 32);
-  summary->initial_cost = h.initial_cost; summary->final_cost = h.final_cost; summary->num_iterations = h.iters; summary->num_successful_steps = h.successes;
-  summary->termination = h.termination; summary->num_unsuccessful_steps = h.iters - h.successes;
+  summary->initial_cost = r.initial_cost; summary->final_cost = r.final_cost; summary->num_iterations = r.iters; summary->num_successful_steps = r.successes;
+  summary->termination = r.termination; summary->num_unsuccessful_steps = r.iters - r.successes;
   return LVF_OK;
 }
 

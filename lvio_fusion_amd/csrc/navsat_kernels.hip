@@ -6,95 +6,35 @@
 //   the per-keyframe loop of Navsat::Optimize / QuickFix src/lvio_fusion/src/navsat.cpp:150-155, :171-176
 //
 // Every solve is a ceres::Solve(DENSE_QR) of at most six scalar parameter blocks: like Relocator::UpdateNewSubmap's rotation solve
-// (loop_kernels.hip) the whole Levenberg-Marquardt loop is ONE launch of one workgroup and the host reads one record.  lm_small<N> below is
-// that loop for N <= 6 unknowns with what these problems add to it: a loss function on the 3-vector blocks (HuberLoss, Corrector scale
-// sqrt(rho')), constant parameter blocks, and box bounds (SetParameterLowerBound / UpperBound: projection + projected Armijo line search).
+// (loop_kernels.hip) the whole Levenberg-Marquardt loop is ONE launch of one workgroup and the host reads one record.  The loop is lm_small
+// (small_lm.hpp); what these problems bring to it is below: the block lists, and Blocks3, which makes a list of 3-vector blocks the loop's
+// problem — a loss function (HuberLoss, Corrector scale sqrt(rho')), constant parameter blocks (a constant slot gets no dual seed: a zero
+// Jacobian column) and box bounds (SetParameterLowerBound / UpperBound).
 // Declared solver semantics: oracle/lm.h (header), oracle/robust.h; the bounds: DESIGN.md, and tests/navsat_ref.py restates the whole loop.
-//
-// The system is kept N x N whatever is constant: a constant column gets no dual seed (a zero Jacobian column), a unit diagonal and a zero
-// gradient entry, so that its step is exactly 0 and the Cholesky factor of the free columns is, operation for operation, the factor of the
-// reduced system — and no array is ever indexed by a runtime value (no scratch segment).
-#include <cfloat>
-#include <cmath>
-
-#include "loop_dev.hpp"
 #include "navsat_eval.hpp"
+#include "small_lm.hpp"
 
 namespace lvf {
 
-struct LmOpts { int max_iters; double function_tol, gradient_tol, parameter_tol, min_rel_decrease, radius0; };
-struct LmRec { double initial_cost, final_cost; int iters, successes, termination, why, contractions, pad; };
-
-// HuberLoss::Evaluate (rho, rho'); a <= 0: no loss function
-__device__ __forceinline__ void huber_eval(double a, double s, double& rho0, double& rho1) {
-  if (a > 0.0 && s > a * a) {
-    const double r = sqrt(s);
-    rho0 = 2.0 * a * r - a * a; rho1 = fmax(DBL_MIN, a / r);
-  } else { rho0 = s; rho1 = 1.0; }
-}
-
-template <int N>
-__device__ __forceinline__ void project_box(double x[N], unsigned bound_mask, const double lo[N], const double hi[N]) {
-#pragma unroll
-  for (int c = 0; c < N; ++c)
-    if ((bound_mask >> c) & 1u) x[c] = fmin(fmax(x[c], lo[c]), hi[c]);
-}
-
-// 1/2 sum rho(|r_b|^2) at x.  PAR: the blocks are dealt over the workgroup and summed with wg_sum; else every thread walks all of them.
-template <int N, bool PAR, class F>
-__device__ __forceinline__ double lm_cost(const F& f, int nb, const double x[N], double huber_a, double* red) {
-  double c = 0.0;
-  for (int i = PAR ? (int)threadIdx.x : 0; i < nb; i += PAR ? kLT : 1) {
-    if (!f.has(i)) continue;
-    double r[3], J[3 * N];
-    f.template eval<false>(i, x, 0u, r, J);
-    double rho0, rho1;
-    huber_eval(huber_a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], rho0, rho1);
-    c += 0.5 * rho0;
-  }
-  return PAR ? wg_sum(c, red) : c;
-}
-
-// ceres::Solve's TrustRegionMinimizer loop (order of tests: oracle/lm.h lm_solve) on N slots of which those in free_mask are unknowns and
-// those in bound_mask (a subset) carry box bounds.  x is updated in place; a FAILURE leaves it as it came.  Every thread of the workgroup
-// takes the same decisions (PAR: all sums are workgroup sums; else all threads compute the same numbers).
-template <int N, bool PAR, class F>
-__device__ __forceinline__ void lm_small(const F& f, int nb, int n_active, double x[N], unsigned free_mask, unsigned bound_mask, const double lo[N],
-                                         const double hi[N], double huber_a, const LmOpts& o, LmRec& rec, double* red) {
-  rec.initial_cost = 0.0; rec.final_cost = 0.0; rec.iters = 0; rec.successes = 0; rec.termination = 0; rec.why = LVF_WHY_NONE; rec.contractions = 0; rec.pad = 0;
-  if (n_active == 0) return;                         // no residual block: Ceres drops the unused parameter blocks, nothing moves
-  if (free_mask == 0u) {                             // every block constant: the problem has a cost and no unknown
-    const double c = lm_cost<N, PAR>(f, nb, x, huber_a, red);
-    rec.initial_cost = c; rec.final_cost = c;
-    return;
-  }
-  bound_mask &= free_mask;
-  const bool bounded = bound_mask != 0u;
-  double x0[N];
-#pragma unroll
-  for (int c = 0; c < N; ++c) x0[c] = x[c];
-  if (bounded) project_box<N>(x, bound_mask, lo, hi);
-  double radius = o.radius0, decrease = 2.0, cost = 0.0, initial_cost = 0.0;
-  int iters = 0, successes = 0, termination = 1, why = LVF_WHY_MAX_ITERATIONS, invalid_run = 0, contractions = 0;
-  bool first = true;
-  double h0[N];
-#pragma unroll
-  for (int c = 0; c < N; ++c) h0[c] = 0.0;
-  for (;;) {
-    double H[N][N], g[N], cc = 0.0;
-#pragma unroll
-    for (int u = 0; u < N; ++u) {
-      g[u] = 0.0;
-#pragma unroll
-      for (int v = 0; v < N; ++v) H[u][v] = 0.0;
-    }
+// A list F of 3-vector residual blocks over N slots as lm_small's problem: 1/2 sum rho(|r_b|^2), plus is addition, the norms run over the
+// free slots.  PAR: the blocks are dealt over the workgroup; else every thread walks all of them.  BOX: the slots in bound_mask are boxed.
+template <int N, bool PAR, class F, bool BOX = false>
+struct Blocks3 {
+  static constexpr bool kBox = BOX;
+  const F& f;
+  int nb;
+  double huber_a;
+  unsigned bound_mask;
+  double lo[N], hi[N];
+  __device__ __forceinline__ void accumulate(const double* x, unsigned free_mask, double* acc) const {
+    constexpr int T = N * (N + 1) / 2;
     for (int i = PAR ? (int)threadIdx.x : 0; i < nb; i += PAR ? kLT : 1) {
       if (!f.has(i)) continue;
       double r[3], J[3 * N];
       f.template eval<true>(i, x, free_mask, r, J);
       double rho0, rho1;
       huber_eval(huber_a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], rho0, rho1);
-      cc += 0.5 * rho0;
+      acc[T + N] += 0.5 * rho0;
       const double sc = sqrt(rho1);                  // Corrector, rho'' <= 0
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -104,164 +44,31 @@ __device__ __forceinline__ void lm_small(const F& f, int nb, int n_active, doubl
         for (int c = 0; c < N; ++c) l[c] = sc * J[N * k + c];
 #pragma unroll
         for (int u = 0; u < N; ++u) {
-          g[u] += l[u] * rk;
+          acc[T + u] += l[u] * rk;
 #pragma unroll
-          for (int v = 0; v <= u; ++v) H[u][v] += l[u] * l[v];
+          for (int v = 0; v <= u; ++v) acc[u * (u + 1) / 2 + v] += l[u] * l[v];
         }
       }
     }
-    if (PAR) {
-      cc = wg_sum(cc, red);
-#pragma unroll
-      for (int u = 0; u < N; ++u) {
-        g[u] = wg_sum(g[u], red);
-#pragma unroll
-        for (int v = 0; v <= u; ++v) H[u][v] = wg_sum(H[u][v], red);
-      }
+  }
+  __device__ __forceinline__ double cost_part(const double* x) const {
+    double c = 0.0;
+    for (int i = PAR ? (int)threadIdx.x : 0; i < nb; i += PAR ? kLT : 1) {
+      if (!f.has(i)) continue;
+      double r[3], J[3 * N];
+      f.template eval<false>(i, x, 0u, r, J);
+      double rho0, rho1;
+      huber_eval(huber_a, r[0] * r[0] + r[1] * r[1] + r[2] * r[2], rho0, rho1);
+      c += 0.5 * rho0;
     }
-    cost = cc;
-#pragma unroll
-    for (int u = 0; u < N; ++u) {
-#pragma unroll
-      for (int v = u + 1; v < N; ++v) H[u][v] = H[v][u];
-    }
-    if (first) {                                     // Jacobi scaling: iteration 0, frozen
-      initial_cost = cost; first = false;
-#pragma unroll
-      for (int c = 0; c < N; ++c) h0[c] = H[c][c];
-    }
-    if (iters >= o.max_iters) { termination = 1; why = LVF_WHY_MAX_ITERATIONS; break; }
-    double gnorm = 0.0;
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-      if (!((free_mask >> c) & 1u)) continue;
-      double e = g[c];
-      if ((bound_mask >> c) & 1u) e = x[c] - fmin(fmax(x[c] - g[c], lo[c]), hi[c]);      // projected gradient: x - P(x - g)
-      gnorm = fmax(gnorm, fabs(e));
-    }
-    if (gnorm <= o.gradient_tol) { termination = 0; why = LVF_WHY_GRADIENT; break; }
-    if (radius < 1e-32) { termination = 0; why = LVF_WHY_MIN_RADIUS; break; }
-    // damped Cholesky of the N x N system (constant slots: unit diagonal)
-    double L[N][N];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const bool fr = (free_mask >> j) & 1u;
-      double d = 1.0;
-      if (fr) {
-        const double sj = 1.0 / (1.0 + sqrt(h0[j])), s2 = sj * sj;
-        d = H[j][j] + fmin(fmax(H[j][j] * s2, 1e-6), 1e32) / s2 / radius;
-      }
-#pragma unroll
-      for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
-      ok = ok && (d > 0.0);
-      const double l = sqrt(d);
-      L[j][j] = l;
-#pragma unroll
-      for (int i = j + 1; i < N; ++i) {
-        double s = (fr && ((free_mask >> i) & 1u)) ? H[i][j] : 0.0;
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
-        L[i][j] = s / l;
-      }
-    }
-    double dx[N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) dx[c] = 0.0;
-    if (ok) {
-      double y[N];
-#pragma unroll
-      for (int i = 0; i < N; ++i) {
-        double s = ((free_mask >> i) & 1u) ? -g[i] : 0.0;
-#pragma unroll
-        for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
-        y[i] = s / L[i][i];
-      }
-#pragma unroll
-      for (int i = N - 1; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < N; ++k) s -= L[k][i] * dx[k];
-        dx[i] = s / L[i][i];
-      }
-    }
-    double model = 0.0;
-#pragma unroll
-    for (int u = 0; u < N; ++u) {
-      if (!((free_mask >> u) & 1u)) continue;
-      double hd = 0.0;
-#pragma unroll
-      for (int v = 0; v < N; ++v)
-        if ((free_mask >> v) & 1u) hd += H[u][v] * dx[v];
-      model -= dx[u] * (g[u] + 0.5 * hd);
-    }
-    if (!(ok && model > 0.0)) {                      // invalid step
-      ++iters;
-      if (++invalid_run >= 5) { termination = 2; why = LVF_WHY_INVALID_STEPS; break; }
-      radius *= 0.5;
-      continue;
-    }
-    invalid_run = 0;
-    if (bounded) {
-      // projected Armijo search along dx: f(P(x + t dx)) <= f(x) + 1e-4 t g.dx, t = 1 first; quadratic-interpolation contraction
-      // clamped to [1e-3, 0.6] of the last step size; 20 samples, minimum step size 1e-9.  A failed search leaves dx as it is.
-      double gd = 0.0;
-#pragma unroll
-      for (int c = 0; c < N; ++c)
-        if ((free_mask >> c) & 1u) gd += g[c] * dx[c];
-      if (gd < 0.0) {
-        double t = 1.0;
-        bool found = false;
-        for (int sample = 0; sample < 20; ++sample) {
-          double xt[N];
-#pragma unroll
-          for (int c = 0; c < N; ++c) xt[c] = x[c] + t * dx[c];
-          project_box<N>(xt, bound_mask, lo, hi);
-          const double ft = lm_cost<N, PAR>(f, nb, xt, huber_a, red);
-          if (ft <= cost + 1e-4 * t * gd) { found = true; break; }
-          double tn = -gd * t * t / (2.0 * (ft - cost - gd * t));
-          tn = fmin(fmax(tn, 1e-3 * t), 0.6 * t);
-          ++contractions;
-          if (tn < 1e-9) break;
-          t = tn;
-        }
-        if (found) {
-#pragma unroll
-          for (int c = 0; c < N; ++c) dx[c] *= t;
-        }
-      }
-    }
-    double xc[N];
+    return c;
+  }
+  __device__ __forceinline__ void plus(const double* x, const double* dx, double* xc) const {
 #pragma unroll
     for (int c = 0; c < N; ++c) xc[c] = x[c] + dx[c];
-    if (bounded) project_box<N>(xc, bound_mask, lo, hi);
-    double sn2 = 0.0, xn2 = 0.0;
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-      if (!((free_mask >> c) & 1u)) continue;
-      sn2 += (xc[c] - x[c]) * (xc[c] - x[c]); xn2 += x[c] * x[c];
-    }
-    if (sqrt(sn2) <= o.parameter_tol * (sqrt(xn2) + o.parameter_tol)) { termination = 0; why = LVF_WHY_PARAMETER; break; }
-    const double cand = lm_cost<N, PAR>(f, nb, xc, huber_a, red);
-    if (fabs(cost - cand) <= o.function_tol * cost) { termination = 0; why = LVF_WHY_FUNCTION; break; }
-    ++iters;
-    const double rho = (cost - cand) / model;
-    if (rho > o.min_rel_decrease) {
-#pragma unroll
-      for (int c = 0; c < N; ++c) x[c] = xc[c];
-      cost = cand; ++successes;
-      const double t = 2.0 * rho - 1.0;
-      radius = fmin(radius / fmax(1.0 / 3.0, 1.0 - t * t * t), 1e16); decrease = 2.0;
-    } else { radius /= decrease; decrease *= 2.0; }
   }
-  if (termination == 2 || !isfinite(cost)) {         // fail soft, as lvf_relocate_rotation_solve: the parameters stay where they were
-    termination = 2; cost = initial_cost;
-#pragma unroll
-    for (int c = 0; c < N; ++c) x[c] = x0[c];
-  }
-  rec.initial_cost = initial_cost; rec.final_cost = cost; rec.iters = iters; rec.successes = successes; rec.termination = termination; rec.why = why;
-  rec.contractions = contractions;
-}
+  __device__ __forceinline__ unsigned norm_mask(unsigned free_mask) const { return free_mask; }
+};
 
 // ---- the block lists ---------------------------------------------------------------------------------------------------------------
 // NavsatInitError blocks; slots (yaw, x, y) in the order Navsat::Initialize adds the parameter blocks (navsat.cpp:106-108)
@@ -391,13 +198,13 @@ struct InitRecord { double para[6], extrinsic[7]; LmRec stage1, stage2; };
 
 __global__ __launch_bounds__(kLT) void k_navsat_initialize(int n, const double* __restrict__ position, const double* __restrict__ raw, const double* __restrict__ cov,
                                                             LmOpts o, InitRecord* __restrict__ out) {
-  __shared__ double red[kLT / 64];
+  __shared__ double tile[lm_tile_doubles(3)];
   const InitBlocks b{position, raw, cov};
+  const Blocks3<3, true, InitBlocks> p{b, n, 0.0};
   double x[3] = {0.0, 0.0, 0.0};
-  const double none[3] = {0.0, 0.0, 0.0};
   LmRec r1, r2;
-  lm_small<3, true>(b, n, n, x, 1u, 0u, none, none, 0.0, o, r1, red);      // x, y constant (navsat.cpp:109-110)
-  lm_small<3, true>(b, n, n, x, 7u, 0u, none, none, 0.0, o, r2, red);      // all three (navsat.cpp:127-129)
+  lm_small<3, 3, true>(p, n, x, 1u, o, r1, tile);      // x, y constant (navsat.cpp:109-110)
+  lm_small<3, 3, true>(p, n, x, 7u, o, r2, tile);      // all three (navsat.cpp:127-129)
   if (threadIdx.x == 0) {
     const double para[6] = {x[0], 0.0, 0.0, x[1], x[2], 0.0};
     double e[7];
@@ -423,7 +230,7 @@ struct BcRecord { double para[6], transform[7]; LmRec roll, main; };
 
 __global__ __launch_bounds__(kLT) void k_navsat_optimize_bc(BcArgs a, double* __restrict__ poses, const int* __restrict__ has_fix, const double* __restrict__ fix,
                                                              const double* __restrict__ cov, double* __restrict__ p1, BcRecord* __restrict__ out) {
-  __shared__ double red[kLT / 64];
+  __shared__ double tile[lm_tile_doubles(6)];
   const int tid = threadIdx.x;
   double frame[7], inv[7];
 #pragma unroll
@@ -444,23 +251,21 @@ __global__ __launch_bounds__(kLT) void k_navsat_optimize_bc(BcArgs a, double* __
     }
   }
   double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // slots (z, y, x, roll, pitch, yaw)
-  LmRec rr, rm;
-  rr.initial_cost = 0.0; rr.final_cost = 0.0; rr.iters = 0; rr.successes = 0; rr.termination = 0; rr.why = LVF_WHY_NONE; rr.contractions = 0; rr.pad = 0;
+  LmRec rr{}, rm;                                    // (LVF_WHY_NONE is 0)
   if (a.roll_presolve) {
     ROne rb;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) rb.y[k] = wg_sum(ys[k], red);
+    for (int k = 0; k < 3; ++k) rb.y[k] = wg_sum(ys[k], tile);
 #pragma unroll
     for (int k = 0; k < 7; ++k) rb.pose[k] = frame[k];
     double xr[1] = {0.0};
-    const double none[1] = {0.0};
-    lm_small<1, false>(rb, 1, 1, xr, 1u, 0u, none, none, 0.0, a.o, rr, red);      // every thread solves the same 1 x 1 problem
+    lm_small<1, 1, false>(Blocks3<1, false, ROne>{rb, 1, 0.0}, 1, xr, 1u, a.o, rr, nullptr);      // every thread solves the same 1 x 1 problem
     x[3] = xr[0];
   }
   __syncthreads();                                   // p1 is complete
-  RxBlocks b{fix, p1, cov, has_fix, {frame[0], frame[1], frame[2], frame[3], frame[4], frame[5], frame[6]}};
-  const double lo[6] = {a.z_lower, 0.0, 0.0, 0.0, 0.0, 0.0}, hi[6] = {a.z_upper, 0.0, 0.0, 0.0, 0.0, 0.0};
-  lm_small<6, true>(b, a.n, a.n_fix, x, a.free_mask, a.z_bounded ? 1u : 0u, lo, hi, a.huber_a, a.o, rm, red);
+  const RxBlocks b{fix, p1, cov, has_fix, {frame[0], frame[1], frame[2], frame[3], frame[4], frame[5], frame[6]}};
+  const Blocks3<6, true, RxBlocks, true> p{b, a.n, a.huber_a, a.z_bounded ? 1u : 0u, {a.z_lower}, {a.z_upper}};
+  lm_small<6, 6, true>(p, a.n_fix, x, a.free_mask, a.o, rm, tile);
   // frame <- frame * rpyxyz2se3(para); every later pose <- (new * old^-1) * pose (navsat.cpp:265-268)
   const double para[6] = {x[5], x[4], x[3], x[2], x[1], x[0]};
   double rel[7], fresh[7], T[7];
@@ -505,14 +310,12 @@ __global__ __launch_bounds__(kLT) void k_navsat_fix_chain(int n, const double* _
     double inv[7];
     sophus_inverse(b.pose, inv);
     double xs[1] = {0.0};
-    LmRec r;
-    r.initial_cost = 0.0; r.final_cost = 0.0; r.iters = 0; r.successes = 0; r.termination = 0;
+    LmRec r{};
     if (has_fix[k]) {
       sophus_transform_point(inv, b.pose[4], b.pose[5], b.pose[6], b.p1);      // frame^-1 * t_frame (navsat.cpp:256)
 #pragma unroll
       for (int c = 0; c < 3; ++c) { b.fix[c] = fix[3 * k + c]; b.sq[c] = cov2sqrt_info(cov[3 * k + c]); }
-      const double none[1] = {0.0};
-      lm_small<1, false>(b, 1, 1, xs, 1u, 0u, none, none, huber_a, o, r, nullptr);
+      lm_small<1, 1, false>(Blocks3<1, false, RxOne>{b, 1, huber_a}, 1, xs, 1u, o, r, nullptr);
     }
     const double para[6] = {0.0, 0.0, 0.0, xs[0], 0.0, 0.0};
     double rel[7], fresh[7], T[7];

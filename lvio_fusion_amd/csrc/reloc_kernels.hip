@@ -4,12 +4,10 @@
 //   k_orb_match     cv::BFMatcher(NORM_HAMMING).knnMatch(k = 2) in both directions, one wavefront per descriptor row
 //   k_orb_gate      the gate of local_map.cpp:342-346 + the cross-check; k_match_list compacts the accepted pairs behind device_scan1
 //   k_pnp_score     one wavefront per hypothesis: counter-based triple, P3P (Grunert's quartic by Ferrari's factorisation), inlier counts
-//   k_pnp_refine    one workgroup, one launch: winner, then rounds of {classify, LocalMap::LocalBA's pose-only problem under the declared LM loop}
-#include <cfloat>
-#include <cmath>
-
+//   k_pnp_refine    one workgroup, one launch: winner, then rounds of {classify, LocalMap::LocalBA's pose-only problem under the declared LM
+//                   loop: lm_small, small_lm.hpp}
 #include "factor_eval.hpp"
-#include "loop_dev.hpp"
+#include "small_lm.hpp"
 
 namespace lvf {
 
@@ -355,32 +353,60 @@ __device__ __forceinline__ void pose_plus(const double x[7], const double dl[6],
   o[4] = x[4] + dl[3]; o[5] = x[5] + dl[4]; o[6] = x[6] + dl[5];
 }
 
-__device__ __forceinline__ void huber2(double a, double s, double& rho0, double& rho1) {
-  if (a > 0.0 && s > a * a) { const double r = sqrt(s); rho0 = 2.0 * a * r - a * a; rho1 = a / r; }
-  else { rho0 = s; rho1 = 1.0; }
-}
-
-// 1/2 sum rho(|r|^2) over the inliers at pose x
-__device__ __forceinline__ double refine_cost(const PnpArgs& a, int n, const uint8_t* s_in, const double x[7], double* red) {
-  PoseD P;
-  derive_pose(x, P);
-  double c = 0.0;
-  for (int i = threadIdx.x; i < n; i += kRT) {
-    if (!s_in[i]) continue;
-    const int2 m = a.list[i];
-    const float2 p = a.pt[m.x];
-    double rho0, rho1, pcz;      // (the factor's own residual, as the linearisation has it: no depth test inside a solve)
-    huber2(a.huber_a, reproj_raw(P, a.cam, (double)p.x, (double)p.y, a.pw + 3 * (size_t)m.y, pcz), rho0, rho1);
-    c += 0.5 * rho0;
+// lm_small's problem (small_lm.hpp): LocalMap::LocalBA's pose-only blocks on the matches the LDS mask s_in marks, 1/2 sum rho(|r|^2) under
+// HuberLoss; 7 ambient coordinates, 6 tangent unknowns
+struct PoseOnInliers {
+  static constexpr bool kBox = false;
+  const PnpArgs& a;
+  int n;
+  const uint8_t* s_in;
+  __device__ __forceinline__ void accumulate(const double* x, unsigned, double* acc) const {
+    PoseD P;
+    derive_pose(x, P);
+    for (int i = threadIdx.x; i < n; i += kRT) {
+      if (!s_in[i]) continue;
+      const int2 m = a.list[i];
+      const float2 p = a.pt[m.x];
+      double r[2], L[12];
+      eval_pose_only_local(P, a.cam, (double)p.x, (double)p.y, a.pw + 3 * (size_t)m.y, 1.0, r, L);
+      double rho0, rho1;
+      huber_eval(a.huber_a, r[0] * r[0] + r[1] * r[1], rho0, rho1);
+      acc[27] += 0.5 * rho0;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+#pragma unroll
+        for (int u = 0; u < 6; ++u) {
+          const double lu = rho1 * L[6 * k + u];         // rho' J^T J and rho' J^T r: the rows scaled once by rho', not twice by its root
+          acc[21 + u] += lu * r[k];
+#pragma unroll
+          for (int v = 0; v <= u; ++v) acc[u * (u + 1) / 2 + v] += lu * L[6 * k + v];
+        }
+      }
+    }
   }
-  return wg_sum(c, red);
-}
+  __device__ __forceinline__ double cost_part(const double* x) const {
+    PoseD P;
+    derive_pose(x, P);
+    double c = 0.0;
+    for (int i = threadIdx.x; i < n; i += kRT) {
+      if (!s_in[i]) continue;
+      const int2 m = a.list[i];
+      const float2 p = a.pt[m.x];
+      double rho0, rho1, pcz;      // (the factor's own residual, as the linearisation has it: no depth test inside a solve)
+      huber_eval(a.huber_a, reproj_raw(P, a.cam, (double)p.x, (double)p.y, a.pw + 3 * (size_t)m.y, pcz), rho0, rho1);
+      c += 0.5 * rho0;
+    }
+    return c;
+  }
+  __device__ __forceinline__ void plus(const double* x, const double* dx, double* xc) const { pose_plus(x, dx, xc); }
+  __device__ __forceinline__ unsigned norm_mask(unsigned) const { return 127u; }
+};
+static_assert(kRT == kLT, "lm_small sums over a workgroup of kLT threads");
 
 __global__ void __launch_bounds__(kRT) k_pnp_refine(PnpArgs a, const unsigned long long* __restrict__ hkey, const double* __restrict__ hpose, PnpRec* __restrict__ rec,
                                                     uint8_t* __restrict__ inlier) {
   __shared__ uint8_t s_in[kRelocMaxFeatures];
-  __shared__ double red28[kRT / 64][28];
-  __shared__ double red[kRT / 64];
+  __shared__ double tile[lm_tile_doubles(6)];
   __shared__ unsigned long long kred[kRT / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = *a.n_dev;
@@ -408,9 +434,9 @@ __global__ void __launch_bounds__(kRT) k_pnp_refine(PnpArgs a, const unsigned lo
 #pragma unroll
   for (int k = 0; k < 7; ++k) x[k] = hpose[7 * (size_t)slot + k];
   const double gate2 = a.gate2;
-  const double function_tol = 1e-6, gradient_tol = 1e-10, parameter_tol = 1e-8, min_rel_decrease = 1e-3;
-  double initial_cost = 0.0, cost = 0.0;
-  int iters = 0, successes = 0, termination = 0, why = LVF_WHY_NONE, blocks = 0;
+  const LmOpts o{a.iters, 1e-6, 1e-10, 1e-8, 1e-3, 1e4};     // function, gradient, parameter tolerance, min_relative_decrease, radius
+  LmRec lm{};                                              // (LVF_WHY_NONE is 0)
+  int blocks = 0;
   for (int round = 0; round <= a.rounds; ++round) {
     // classify at the current pose
     PoseD P;
@@ -424,7 +450,7 @@ __global__ void __launch_bounds__(kRT) k_pnp_refine(PnpArgs a, const unsigned lo
       s_in[i] = in; mine += in;
     }
     __syncthreads();
-    const int n_in = (int)wg_sum((double)mine, red);
+    const int n_in = (int)wg_sum((double)mine, tile);
     if (round == a.rounds) {                               // the final mask
       for (int i = tid; i < n; i += kRT)
         if (s_in[i]) inlier[a.list[i].x] = 1;
@@ -433,154 +459,15 @@ __global__ void __launch_bounds__(kRT) k_pnp_refine(PnpArgs a, const unsigned lo
 #pragma unroll
         for (int k = 0; k < 7; ++k) { r.pose[k] = x[k]; r.rel[k] = x[k]; }
         if (a.have_old) { double inv[7]; sophus_inverse(a.old, inv); forward_update_pose(inv, x, r.rel); }
-        r.initial_cost = initial_cost; r.final_cost = cost; r.score = n_in; r.n_matches = n; r.winner = hw; r.winner_count = (int)(key >> 32) - 1;
-        r.iters = iters; r.successes = successes; r.termination = termination; r.why = why; r.blocks = blocks; r.found = 1;
+        r.initial_cost = lm.initial_cost; r.final_cost = lm.final_cost; r.score = n_in; r.n_matches = n; r.winner = hw; r.winner_count = (int)(key >> 32) - 1;
+        r.iters = lm.iters; r.successes = lm.successes; r.termination = lm.termination; r.why = lm.why; r.blocks = blocks; r.found = 1;
         *rec = r;
       }
       break;
     }
-    // LocalMap::LocalBA's problem on the inliers: the declared Ceres loop (oracle/lm.h lm_solve), as lm_small with the manifold Plus
+    // LocalMap::LocalBA's problem on the inliers under the declared Ceres loop; a failed solve leaves the pose where the round found it
     blocks = n_in;
-    initial_cost = 0.0; cost = 0.0; iters = 0; successes = 0; termination = 1; why = LVF_WHY_MAX_ITERATIONS;
-    if (n_in == 0) { termination = 0; why = LVF_WHY_NONE; continue; }
-    double x0[7], h0[6], radius = 1e4, decrease = 2.0;
-    int invalid_run = 0;
-    bool first = true;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) x0[k] = x[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) h0[k] = 0.0;
-    for (;;) {
-      double acc[28];                                      // 21 lower-triangle entries of H (row-major), 6 of g, the cost
-#pragma unroll
-      for (int k = 0; k < 28; ++k) acc[k] = 0.0;
-      derive_pose(x, P);
-      for (int i = tid; i < n; i += kRT) {
-        if (!s_in[i]) continue;
-        const int2 m = a.list[i];
-        const float2 p = a.pt[m.x];
-        double r[2], L[12];
-        eval_pose_only_local(P, a.cam, (double)p.x, (double)p.y, a.pw + 3 * (size_t)m.y, 1.0, r, L);
-        double rho0, rho1;
-        huber2(a.huber_a, r[0] * r[0] + r[1] * r[1], rho0, rho1);
-        acc[27] += 0.5 * rho0;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-#pragma unroll
-          for (int u = 0; u < 6; ++u) {
-            const double lu = rho1 * L[6 * k + u];
-            acc[21 + u] += lu * r[k];
-#pragma unroll
-            for (int v = 0; v <= u; ++v) acc[u * (u + 1) / 2 + v] += lu * L[6 * k + v];
-          }
-        }
-      }
-      // fixed order: DPP inside a wave, then the four waves in wave order
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < 28; ++k) {
-        const double sum = wave_sum(acc[k]);
-        if (lane == 0) red28[wave][k] = sum;
-      }
-      __syncthreads();
-      double H[6][6], g[6];
-#pragma unroll
-      for (int u = 0; u < 6; ++u) {
-        g[u] = ((red28[0][21 + u] + red28[1][21 + u]) + red28[2][21 + u]) + red28[3][21 + u];
-#pragma unroll
-        for (int v = 0; v <= u; ++v) {
-          const int k = u * (u + 1) / 2 + v;
-          H[u][v] = ((red28[0][k] + red28[1][k]) + red28[2][k]) + red28[3][k];
-          H[v][u] = H[u][v];
-        }
-      }
-      cost = ((red28[0][27] + red28[1][27]) + red28[2][27]) + red28[3][27];
-      if (first) {
-        initial_cost = cost; first = false;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) h0[c] = H[c][c];
-      }
-      if (iters >= a.iters) { termination = 1; why = LVF_WHY_MAX_ITERATIONS; break; }
-      double gnorm = 0.0;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) gnorm = fmax(gnorm, fabs(g[c]));
-      if (gnorm <= gradient_tol) { termination = 0; why = LVF_WHY_GRADIENT; break; }
-      if (radius < 1e-32) { termination = 0; why = LVF_WHY_MIN_RADIUS; break; }
-      double Lc[6][6];
-      bool ok = true;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const double sj = 1.0 / (1.0 + sqrt(h0[j])), s2 = sj * sj;
-        double d = H[j][j] + fmin(fmax(H[j][j] * s2, 1e-6), 1e32) / s2 / radius;
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= Lc[j][k] * Lc[j][k];
-        ok = ok && (d > 0.0);
-        const double l = sqrt(d);
-        Lc[j][j] = l;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-          double s = H[i][j];
-#pragma unroll
-          for (int k = 0; k < j; ++k) s -= Lc[i][k] * Lc[j][k];
-          Lc[i][j] = s / l;
-        }
-      }
-      double dx[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      if (ok) {
-        double y[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-          double s = -g[i];
-#pragma unroll
-          for (int k = 0; k < i; ++k) s -= Lc[i][k] * y[k];
-          y[i] = s / Lc[i][i];
-        }
-#pragma unroll
-        for (int i = 5; i >= 0; --i) {
-          double s = y[i];
-#pragma unroll
-          for (int k = i + 1; k < 6; ++k) s -= Lc[k][i] * dx[k];
-          dx[i] = s / Lc[i][i];
-        }
-      }
-      double model = 0.0;
-#pragma unroll
-      for (int u = 0; u < 6; ++u) {
-        double hd = 0.0;
-#pragma unroll
-        for (int v = 0; v < 6; ++v) hd += H[u][v] * dx[v];
-        model -= dx[u] * (g[u] + 0.5 * hd);
-      }
-      if (!(ok && model > 0.0)) {                          // invalid step
-        ++iters;
-        if (++invalid_run >= 5) { termination = 2; why = LVF_WHY_INVALID_STEPS; break; }
-        radius *= 0.5;
-        continue;
-      }
-      invalid_run = 0;
-      double xc[7];
-      pose_plus(x, dx, xc);
-      double sn2 = 0.0, xn2 = 0.0;
-#pragma unroll
-      for (int c = 0; c < 7; ++c) { sn2 += (xc[c] - x[c]) * (xc[c] - x[c]); xn2 += x[c] * x[c]; }
-      if (sqrt(sn2) <= parameter_tol * (sqrt(xn2) + parameter_tol)) { termination = 0; why = LVF_WHY_PARAMETER; break; }
-      const double cand = refine_cost(a, n, s_in, xc, red);
-      if (fabs(cost - cand) <= function_tol * cost) { termination = 0; why = LVF_WHY_FUNCTION; break; }
-      ++iters;
-      const double rho = (cost - cand) / model;
-      if (rho > min_rel_decrease) {
-#pragma unroll
-        for (int c = 0; c < 7; ++c) x[c] = xc[c];
-        cost = cand; ++successes;
-        const double t = 2.0 * rho - 1.0;
-        radius = fmin(radius / fmax(1.0 / 3.0, 1.0 - t * t * t), 1e16); decrease = 2.0;
-      } else { radius /= decrease; decrease *= 2.0; }
-    }
-    if (termination == 2 || !isfinite(cost)) {             // fail soft: the pose stays where the round found it
-      termination = 2; cost = initial_cost;
-#pragma unroll
-      for (int c = 0; c < 7; ++c) x[c] = x0[c];
-    }
+    lm_small<6, 7, true>(PoseOnInliers{a, n, s_in}, n_in, x, 63u, o, lm, tile);
   }
 }
 
