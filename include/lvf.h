@@ -897,6 +897,50 @@ int lvf_relocate_by_image(lvf_ctx* ctx, const lvf_camera* cam0, const double* ol
 int lvf_pnp_debug_hypotheses(lvf_ctx* ctx, const lvf_camera* cam0, int n, const double* pw, const float* pt, const lvf_pnp_options* opt, int32_t* triples,
                              int32_t* n_poses, int32_t* count, double* poses);
 
+/* ---- LiDAR place recognition: Scan Context descriptors and their search, the appearance gate beside DetectLoop ----------- */
+/* Semantics are DECLARED (the reference proposes candidates by position only, relocator.cpp:87-133); tests/scanctx_ref.py is the statement of
+ * record.  Descriptor of a SENSOR-FRAME cloud: per point r = sqrtf(x*x + y*y) and th = the correctly rounded atan2f(y, x); a point counts iff r
+ * and z are finite and min_range <= r < max_range; ring = min(num_rings - 1, floor(r * ring_scale)), sector = clamp(floor((th + pi) *
+ * sector_scale), 0, num_sectors - 1), the scales formed once in double and rounded to float; h = z + sensor_height; cell = h > 0 ?
+ * min(255, 1 + floor(h * inv_height_step)) : 0.  The descriptor is the per-cell maximum as uint8 (0 = empty), stored SECTOR-MAJOR:
+ * desc[sector * num_rings + ring]; norm[sector] = sum over rings of cell^2.  Bit-reproducible (an integer maximum has no order).
+ * Distance of query Q to entry D at shift s: column j of Q pairs with column (j + s) % num_sectors of D; pairs with both norms non-zero
+ * contribute dot / sqrt(n2q * n2d) in float64, added in ascending j; d(s) = 1 - sum / count (1 when no pair is valid); the entry's distance is
+ * the minimum over s, the lowest s on a tie.  A query taken at yaw psi_old + s * 2 pi / num_sectors matches at shift s.
+ * LVF_ERR_INVALID: num_rings not a multiple of 4 in [4, 32], num_sectors outside [1, 64], a non-positive range or step, min_range >= max_range.
+ * opt == NULL: the defaults. */
+typedef struct lvf_scanctx_options {
+  int num_rings;            /* 20 */
+  int num_sectors;          /* 60 */
+  float max_range;          /* 80.0f */
+  float min_range;          /* 0.5f */
+  float sensor_height;      /* 2.0f */
+  float inv_height_step;    /* 10.0f */
+} lvf_scanctx_options;
+typedef struct lvf_scanctx_db lvf_scanctx_db;
+void lvf_scanctx_options_default(lvf_scanctx_options* o);
+/* describes one cloud and downloads the result: out_desc_u8 [num_sectors * num_rings], out_norm_u32 [num_sectors] (may be NULL).  An empty
+ * cloud gives an all-zero descriptor. */
+int lvf_scanctx_describe(lvf_ctx* ctx, const lvf_cloud* cloud, const lvf_scanctx_options* opt, uint8_t* out_desc_u8, uint32_t* out_norm_u32);
+/* The database of old keyframes: up to `capacity` (1 .. 2^20) entries on the device, their stamps on the host.  Entries are numbered in the
+ * order they were appended; stamps must be finite and non-decreasing, appending past the capacity is refused (LVF_ERR_INVALID both). */
+int lvf_scanctx_db_create(lvf_ctx* ctx, const lvf_scanctx_options* opt, int capacity, lvf_scanctx_db** out);
+int lvf_scanctx_db_destroy(lvf_scanctx_db* db);
+int lvf_scanctx_db_size(const lvf_scanctx_db* db);
+/* the cloud's descriptor is built on the device straight into the next entry; nothing is downloaded and nothing waits */
+int lvf_scanctx_db_append(lvf_scanctx_db* db, const lvf_cloud* cloud, double stamp);
+/* uploads a descriptor made elsewhere (desc_u8 [num_sectors * num_rings]); the library recomputes the norms */
+int lvf_scanctx_db_append_descriptor(lvf_scanctx_db* db, const uint8_t* desc_u8, double stamp);
+int lvf_scanctx_db_download(const lvf_scanctx_db* db, int index, uint8_t* out_desc_u8, uint32_t* out_norm_u32);
+/* Searches the longest prefix of entries whose stamps are <= max_stamp (the reference looks among keyframes older than frame->time - 30,
+ * relocator.cpp:92) for the k (1 .. 16) smallest (distance, index): out_index / out_shift / out_distance [k], ordered by (distance, index);
+ * slots beyond the prefix's size hold index -1, shift -1, distance +inf (an empty prefix: all of them, LVF_OK).  One wait, 256 bytes down. */
+int lvf_scanctx_search(lvf_scanctx_db* db, const uint8_t* query_desc_u8, double max_stamp, int k, int32_t* out_index, int32_t* out_shift, double* out_distance);
+/* describe + search + (append != 0) append as ONE launch chain with one wait; the descriptor never leaves the device.  The search sees the
+ * database as it was before the call. */
+int lvf_scanctx_detect(lvf_scanctx_db* db, const lvf_cloud* cloud, double stamp, double max_stamp, int k, int32_t* out_index, int32_t* out_shift, double* out_distance,
+                       int append);
+
 /* ---- multi-GPU: the path's only exchange, for a C / C++ host ----------------------------------------------------------- */
 /* Independent windows / loop-closure candidates shard one per GPU: one process per GPU, one lvf_ctx each, no data-path collective.  The
  * single exchange is an all-gather of fixed-size records (score, relative_o_c[7], candidate id: relocator.cpp:196-206) over RCCL / xGMI.

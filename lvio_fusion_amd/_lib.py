@@ -130,6 +130,11 @@ class PnpOptions(C.Structure):
                 ("refine_iterations", C.c_int), ("huber_a", C.c_double)]
 
 
+class ScanCtxOptions(C.Structure):
+    _fields_ = [("num_rings", C.c_int), ("num_sectors", C.c_int), ("max_range", C.c_float), ("min_range", C.c_float), ("sensor_height", C.c_float),
+                ("inv_height_step", C.c_float)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into liblvf_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".hpp"))]
@@ -225,6 +230,16 @@ _SIGS = {
     "lvf_relocate_by_image": (C.c_int, [_VP, C.POINTER(Camera), c_double_p, C.c_int, c_double_p, c_u8_p, C.c_int, c_float_p, c_u8_p, C.POINTER(MatchOptions),
                                         C.POINTER(PnpOptions), c_double_p, c_int_p, c_int_p, c_u8_p, C.POINTER(SolverSummary)]),
     "lvf_pnp_debug_hypotheses": (C.c_int, [_VP, C.POINTER(Camera), C.c_int, c_double_p, c_float_p, C.POINTER(PnpOptions), c_int_p, c_int_p, c_int_p, c_double_p]),
+    "lvf_scanctx_options_default": (None, [C.POINTER(ScanCtxOptions)]),
+    "lvf_scanctx_describe": (C.c_int, [_VP, _VP, C.POINTER(ScanCtxOptions), c_u8_p, C.POINTER(C.c_uint32)]),
+    "lvf_scanctx_db_create": (C.c_int, [_VP, C.POINTER(ScanCtxOptions), C.c_int, C.POINTER(_VP)]),
+    "lvf_scanctx_db_destroy": (C.c_int, [_VP]),
+    "lvf_scanctx_db_size": (C.c_int, [_VP]),
+    "lvf_scanctx_db_append": (C.c_int, [_VP, _VP, C.c_double]),
+    "lvf_scanctx_db_append_descriptor": (C.c_int, [_VP, c_u8_p, C.c_double]),
+    "lvf_scanctx_db_download": (C.c_int, [_VP, C.c_int, c_u8_p, C.POINTER(C.c_uint32)]),
+    "lvf_scanctx_search": (C.c_int, [_VP, c_u8_p, C.c_double, C.c_int, c_int_p, c_int_p, c_double_p]),
+    "lvf_scanctx_detect": (C.c_int, [_VP, _VP, C.c_double, C.c_double, C.c_int, c_int_p, c_int_p, c_double_p, C.c_int]),
     "lvf_window_reject_outliers": (C.c_int, [_VP, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int)]),
     "lvf_comm_get_unique_id": (C.c_int, [_VP]),
     "lvf_comm_create": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.POINTER(_VP)]),

@@ -756,9 +756,71 @@ class Cloud:
         _chk(pc1.ctx.L.lvf_cloud_align_scan(pc1.h, float(stamp1), pc2.h, float(stamp2), float(cycle_time), float(time), C.byref(h), C.byref(ok)))
         return Cloud(pc1.ctx, _h=h), bool(ok.value)
 
+    def scan_context(self, opt=None):
+        """Scan Context descriptor of this sensor-frame cloud: desc [num_sectors, num_rings] uint8 (row j = column j of the polar image),
+        norm [num_sectors] uint32."""
+        o = opt if opt is not None else scanctx_options()
+        desc, norm = np.zeros((o.num_sectors, o.num_rings), np.uint8), np.zeros(o.num_sectors, np.uint32)
+        _chk(self.ctx.L.lvf_scanctx_describe(self.ctx.h, self.h, C.byref(o), _u8p(desc), norm.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return desc, norm
+
     def close(self):
         if self.h:
             self.ctx.L.lvf_cloud_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def scanctx_options(**kw):
+    """lvf_scanctx_options with its defaults (20 rings x 60 sectors, 0.5 .. 80 m, sensor 2 m above ground, 10 height steps per metre), overridden by keyword."""
+    return _options(_lib.ScanCtxOptions, "lvf_scanctx_options_default", "scanctx_options", kw)
+
+
+class ScanContextDb:
+    """The place-recognition database: Scan Context entries of old keyframes on the device, their stamps on the host."""
+
+    def __init__(self, ctx, capacity, opt=None):
+        self.ctx = ctx
+        self.opt = opt if opt is not None else scanctx_options()
+        self.h = C.c_void_p()
+        _chk(ctx.L.lvf_scanctx_db_create(ctx.h, C.byref(self.opt), int(capacity), C.byref(self.h)))
+
+    def __len__(self):
+        return self.ctx.L.lvf_scanctx_db_size(self.h)
+
+    def _desc(self, desc):
+        d = np.ascontiguousarray(desc, dtype=np.uint8)
+        if d.shape != (self.opt.num_sectors, self.opt.num_rings):
+            raise ValueError("ScanContextDb: descriptor of shape %r, expected (%d, %d)" % (d.shape, self.opt.num_sectors, self.opt.num_rings))
+        return d
+
+    def append(self, cloud, stamp):
+        _chk(self.ctx.L.lvf_scanctx_db_append(self.h, cloud.h, float(stamp)))
+
+    def append_descriptor(self, desc, stamp):
+        d = self._desc(desc)
+        _chk(self.ctx.L.lvf_scanctx_db_append_descriptor(self.h, _u8p(d), float(stamp)))
+
+    def download(self, index):
+        desc, norm = np.zeros((self.opt.num_sectors, self.opt.num_rings), np.uint8), np.zeros(self.opt.num_sectors, np.uint32)
+        _chk(self.ctx.L.lvf_scanctx_db_download(self.h, int(index), _u8p(desc), norm.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return desc, norm
+
+    def search(self, desc, max_stamp=np.inf, k=1):
+        """the k best entries with stamps <= max_stamp: index [k], shift [k] (both -1 in unused slots), distance [k] (+inf there)"""
+        d = self._desc(desc)
+        idx, sh, dist = np.zeros(max(int(k), 0), np.int32), np.zeros(max(int(k), 0), np.int32), np.zeros(max(int(k), 0))
+        _chk(self.ctx.L.lvf_scanctx_search(self.h, _u8p(d), float(max_stamp), int(k), _ip(idx), _ip(sh), _dp(dist)))
+        return idx, sh, dist
+
+    def detect(self, cloud, stamp, max_stamp=np.inf, k=1, append=True):
+        """describe + search + (append) append in one launch chain; the search sees the database as it was before the call"""
+        idx, sh, dist = np.zeros(max(int(k), 0), np.int32), np.zeros(max(int(k), 0), np.int32), np.zeros(max(int(k), 0))
+        _chk(self.ctx.L.lvf_scanctx_detect(self.h, cloud.h, float(stamp), float(max_stamp), int(k), _ip(idx), _ip(sh), _dp(dist), 1 if append else 0))
+        return idx, sh, dist
+
+    def close(self):
+        if self.h:
+            self.ctx.L.lvf_scanctx_db_destroy(self.h)
             self.h = C.c_void_p()
 
 

@@ -108,6 +108,65 @@ def evaluate_candidate_visual(api, ctx, cand, match_opt=None, pnp_opt=None):
                                  match_opt, pnp_opt)
 
 
+def detect_loop_by_position(positions_xy, ids, query_xy, threshold):
+    """The gate of Relocator::DetectLoop (relocator.cpp:104-122) on the old keyframes' estimated positions: the three nearest in (x, y) must ALL lie
+    within `threshold` (squared distance < threshold^2); returns the id of the nearest, or None.  Ties go to the lower row.  With fewer than three
+    old keyframes the reference reads past the end of the kd-tree's result; here that is no candidate."""
+    p = np.asarray(positions_xy, np.float64).reshape(-1, 2)
+    if len(p) < 3:
+        return None
+    d2 = ((p - np.asarray(query_xy, np.float64).reshape(1, 2)) ** 2).sum(1)
+    near = np.argsort(d2, kind="stable")[:3]
+    if not (d2[near] < float(threshold) ** 2).all():
+        return None
+    return ids[int(near[0])]
+
+
+def detect_loop_by_scan(db, cloud, stamp, min_age=30.0, k=5, max_distance=0.5):
+    """The appearance gate beside it: the k best Scan Context matches of the sensor-frame `cloud` among the entries of `db`
+    (api.ScanContextDb) at least min_age seconds older than `stamp` (relocator.cpp:92 looks among keyframes older than frame->time - 30); returns
+    the accepted [(index, shift, distance)], distance < max_distance, best first.  The database is left as it is (db.append adds the sweep)."""
+    idx, shift, dist = db.detect(cloud, stamp, max_stamp=stamp - min_age, k=k, append=False)
+    return [(int(i), int(s), float(d)) for i, s, d in zip(idx, shift, dist) if i >= 0 and d < max_distance]
+
+
+def _rotmat(q):
+    x, y, z, w = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _rpy_of(q):
+    """(yaw, pitch, roll) of se32rpyxyz (utility.cpp:27-33)"""
+    x, y, z, w = q
+    return np.array([np.arctan2(2 * (x * y + w * z), 1 - 2 * (y * y + z * z)), np.arcsin(2 * (w * y - x * z)), np.arctan2(2 * (y * z + w * x), 1 - 2 * (x * x + y * y))])
+
+
+def _quat_of(rpy):
+    """the quaternion (x, y, z, w) of rpyxyz2se3 (utility.cpp:35-40)"""
+    hz, hy, hx = rpy[0] / 2, rpy[1] / 2, rpy[2] / 2
+    cz, sz, cy, sy, cx, sx = np.cos(hz), np.sin(hz), np.cos(hy), np.sin(hy), np.cos(hx), np.sin(hx)
+    q = np.array([cz * cy * sx - sz * sy * cx, cz * sy * cx + sz * cy * sx, sz * cy * cx - cz * sy * sx, cz * cy * cx + sz * sy * sx])
+    return q / np.linalg.norm(q)
+
+
+def seed_relative_o_c(old_pose, frame_pose, shift, num_sectors):
+    """relative_o_c as Relocator::Relocate forms it (relocator.cpp:139-141: old_pose^-1 * the frame's pose with the old frame's z), with the frame's
+    yaw replaced by the old frame's yaw + shift * 2 pi / num_sectors — the yaw the Scan Context match gives the revisit; roll and pitch stay the
+    frame's (se32rpyxyz / rpyxyz2se3).  The seed to hand to evaluate_candidates_batched as init_pose = old_pose * relative_o_c."""
+    old, frame = np.asarray(old_pose, np.float64), np.asarray(frame_pose, np.float64)
+    rpy = _rpy_of(frame[:4])
+    rpy[0] = _rpy_of(old[:4])[0] + shift * (2.0 * np.pi / num_sectors)
+    qi, ti = _quat_of(rpy), np.array([frame[4], frame[5], old[6]])
+    qo = np.array([-old[0], -old[1], -old[2], old[3]]) / np.linalg.norm(old[:4])
+    ax, ay, az, aw = qo
+    bx, by, bz, bw = qi
+    q = np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw,
+                  aw * bw - ax * bx - ay * by - az * bz])
+    return np.concatenate([q / np.linalg.norm(q), _rotmat(qo) @ (ti - old[4:7])])
+
+
 def split_candidate(cand):
     """(map ground, map surf, query ground, query surf) point arrays of a candidate — the reference holds them as separate clouds
     (frame->feature_lidar->points_ground / points_surf); the synthetic candidates carry masks."""
