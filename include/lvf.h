@@ -25,6 +25,9 @@
  *   lvf_trajectory_* / lvf_cloud_deskew / lvf_lidar_extract_deskewed
  *                      <- Map::ComputePose, FeatureAssociation::UndistortPointCloud, the TODO of AdjustDistortion
  *                         src/map.cpp:92-102, src/association.cpp:65-83, :142-145
+ *   lvf_lidar_depth_* / lvf_stereo_triangulate_lidar
+ *                      <- declared (no reference text): the sweep's depth for the features LocalMap::Triangulate leaves Far or lost
+ *                         src/local_map.cpp:233-269, include/lvio_fusion/visual/camera.h:38-41
  *   lvf_scan_match     <- Mapping::Optimize's per-frame body / Mapping::Relocate   src/mapping.cpp:147-178, :251-300
  *   lvf_window_*       <- Backend::BuildProblem's assembly kept incrementally          src/backend.cpp:96-183
  *   lvf_problem_*      <- adapt::Problem::{AddParameterBlock,AddResidualBlock,SetParameterBlockConstant}
@@ -940,6 +943,62 @@ int lvf_scanctx_search(lvf_scanctx_db* db, const uint8_t* query_desc_u8, double 
  * database as it was before the call. */
 int lvf_scanctx_detect(lvf_scanctx_db* db, const lvf_cloud* cloud, double stamp, double max_stamp, int k, int32_t* out_index, int32_t* out_shift, double* out_distance,
                        int append);
+
+/* ---- LiDAR depth for visual features: the sweep projected into camera 0, a triangle fit per feature -------------------------- */
+/* Semantics are DECLARED (the reference takes a landmark's depth from the stereo pair only, local_map.cpp:233-269, and merely labels what lies
+ * deeper than 50 baselines, camera.h:38-41); tests/lidar_depth_ref.py is the statement of record and every output is bit equal to it.
+ * PROJECTION of a sensor-frame cloud (deskewed to the image's pose with lvf_cloud_deskew) by cam_from_lidar = [R | t], double[12] row-major
+ * 3x4: in fp64 from the float32 coordinates pc = ((m0*x + m1*y) + m2*z) + m3 per row, u = fx*pc.x/pc.z + cx, v = fy*pc.y/pc.z + cy.  u, v and
+ * pc.z are rounded to float32 ONCE (cv::Point2f); a point is kept iff pc is finite, min_depth <= pc.z < max_depth and the ROUNDED pixel lies
+ * in [0, width) x [0, height).  A kept point is one record; records are binned on a grid of cell x cell pixels (the last row / column may be
+ * partial), cell-row-major, cell_start [cells + 1].  The order of the records inside a cell is not defined.
+ * DEPTH of a feature (u0, v0): the candidates are the records of the cells floor((u0 -+ radius) / cell) x floor((v0 -+ radius) / cell),
+ * clipped to the grid, with d2 = dx*dx + dy*dy <= radius*radius (dx = u - u0, dy = v - v0, fp64).  Quadrant q = (dx >= 0) + 2 (dy >= 0); per
+ * quadrant the winner is the minimum of (d2, source_index).  Fewer than three occupied quadrants: status 0.  Of four winners the largest by
+ * the same order is dropped; the three are A, B, C in ascending order.  With b = B - A, c = C - A, p = -A (pixel offsets from the feature):
+ * det = b.x*c.y - c.x*b.y, wb = (p.x*c.y - c.x*p.y) / det, wc = (b.x*p.y - p.x*b.y) / det, wa = (1 - wb) - wc,
+ * inv_z = (wa/zA + wb/zB) + wc/zC — on a plane inverse depth is affine in the pixel.  Gates, in this order: status 3 |det| < min_det; 4 a
+ * weight < -max_extrapolation; 2 max(z) - min(z) > max_spread (the triangle straddles an occlusion edge); 5 !(inv_z > 0) or 1/inv_z outside
+ * [min_depth, max_depth); else 1 = accepted: depth = 1/inv_z, p_robot = Sensor2Robot_0(Pixel2Sensor_0(kp, depth)), inv_depth =
+ * 1 / Robot2Sensor_1(p_robot).z (camera ONE, local_map.cpp:258), kps_right = float32(Robot2Pixel_1(p_robot)): lvf_stereo_triangulate's
+ * conventions.  All outputs are zero where status != 1; a non-finite feature pixel has status 0.
+ * LVF_ERR_INVALID (nothing launched): cell not 4 / 8 / 16 / 32, radius outside (0, 64], not 0 < min_depth < max_depth, a negative max_spread,
+ * max_extrapolation or far_factor, min_det <= 0, replace_lost not 0 / 1, width or height outside [1, 65536], a non-finite matrix or camera. */
+typedef struct lvf_lidar_depth_options {
+  int cell;                 /* 8: grid cell in pixels (4, 8, 16 or 32) */
+  double radius;            /* 12.0 px */
+  double min_depth;         /* 0.5 m */
+  double max_depth;         /* 80.0 m */
+  double max_spread;        /* 2.0 m, as LVI-SAM's check */
+  double min_det;           /* 4.0 px^2: twice the triangle's area */
+  double max_extrapolation; /* 0.5 */
+  double far_factor;        /* 50.0: lvf_stereo_triangulate_lidar replaces stereo depths beyond far_factor * baseline (0 = always) */
+  int replace_lost;         /* 1: ... and gives depth to the features the stereo flow lost */
+} lvf_lidar_depth_options;
+typedef struct lvf_lidar_depth_record { float u, v, z; int32_t source_index; } lvf_lidar_depth_record;
+typedef struct lvf_lidar_depth lvf_lidar_depth;
+void lvf_lidar_depth_options_default(lvf_lidar_depth_options* o);
+/* projects and bins the cloud: three launches, nothing is downloaded and nothing waits (the record array is sized by the cloud).  Of cam0 the
+ * intrinsics are used.  opt == NULL: the defaults.  An empty cloud gives an empty grid. */
+int lvf_lidar_depth_create(lvf_ctx* ctx, const lvf_cloud* cloud, const lvf_camera* cam0, const double* cam_from_lidar, int width, int height,
+                           const lvf_lidar_depth_options* opt, lvf_lidar_depth** out);
+int lvf_lidar_depth_destroy(lvf_lidar_depth* depth);
+/* the number of kept points (the first call waits for the chain and reads 4 bytes); -1 on error */
+int lvf_lidar_depth_size(lvf_lidar_depth* depth);
+/* Test tap: records [lvf_lidar_depth_size] (may be NULL) and cell_start [cells + 1] (may be NULL), cells = ceil(width / cell) * ceil(height / cell). */
+int lvf_lidar_depth_download(lvf_lidar_depth* depth, lvf_lidar_depth_record* records, int32_t* cell_start);
+/* one launch, one wavefront per feature, one wait.  kps_left [n][2]; status [n], depth_out [n], inv_depth [n], p_robot [n][3], kps_right
+ * [n][2] as above.  cam0's intrinsics must be the ones given to lvf_lidar_depth_create.  n == 0 returns at once. */
+int lvf_lidar_depth_query(const lvf_lidar_depth* depth, const lvf_camera* cam0, const lvf_camera* cam1, int n, const float* kps_left, uint8_t* status,
+                          double* depth_out, double* inv_depth, double* p_robot, float* kps_right);
+/* lvf_stereo_triangulate with the query and one merge launch appended on the same stream; ONE wait.  LiDAR replaces the stereo result of a
+ * feature iff its LiDAR status is 1 AND either the stereo status is 1 and Robot2Sensor_0(p_robot_stereo).z > far_factor * baseline
+ * (far_factor == 0: always), or the stereo status is not 1 and replace_lost is set.  A replaced feature gets status 1, source 2 and the
+ * LiDAR kps_right / inv_depth / p_robot; every other feature keeps exactly what lvf_stereo_triangulate writes, source [n] = 1 where its
+ * status is 1, else 0.  `depth` belongs to the images' context. */
+int lvf_stereo_triangulate_lidar(const lvf_image* left, const lvf_image* right, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n,
+                                 const float* kps_left, float* kps_right, uint8_t* status, double* inv_depth, double* p_robot, const lvf_flow_options* opt,
+                                 const lvf_lidar_depth* depth, uint8_t* source);
 
 /* ---- multi-GPU: the path's only exchange, for a C / C++ host ----------------------------------------------------------- */
 /* Independent windows / loop-closure candidates shard one per GPU: one process per GPU, one lvf_ctx each, no data-path collective.  The

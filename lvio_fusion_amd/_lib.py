@@ -135,6 +135,11 @@ class ScanCtxOptions(C.Structure):
                 ("inv_height_step", C.c_float)]
 
 
+class LidarDepthOptions(C.Structure):
+    _fields_ = [("cell", C.c_int), ("radius", C.c_double), ("min_depth", C.c_double), ("max_depth", C.c_double), ("max_spread", C.c_double),
+                ("min_det", C.c_double), ("max_extrapolation", C.c_double), ("far_factor", C.c_double), ("replace_lost", C.c_int)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into liblvf_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".hpp"))]
@@ -240,6 +245,14 @@ _SIGS = {
     "lvf_scanctx_db_download": (C.c_int, [_VP, C.c_int, c_u8_p, C.POINTER(C.c_uint32)]),
     "lvf_scanctx_search": (C.c_int, [_VP, c_u8_p, C.c_double, C.c_int, c_int_p, c_int_p, c_double_p]),
     "lvf_scanctx_detect": (C.c_int, [_VP, _VP, C.c_double, C.c_double, C.c_int, c_int_p, c_int_p, c_double_p, C.c_int]),
+    "lvf_lidar_depth_options_default": (None, [C.POINTER(LidarDepthOptions)]),
+    "lvf_lidar_depth_create": (C.c_int, [_VP, _VP, C.POINTER(Camera), c_double_p, C.c_int, C.c_int, C.POINTER(LidarDepthOptions), C.POINTER(_VP)]),
+    "lvf_lidar_depth_destroy": (C.c_int, [_VP]),
+    "lvf_lidar_depth_size": (C.c_int, [_VP]),
+    "lvf_lidar_depth_download": (C.c_int, [_VP, _VP, c_int_p]),
+    "lvf_lidar_depth_query": (C.c_int, [_VP, C.POINTER(Camera), C.POINTER(Camera), C.c_int, c_float_p, c_u8_p, c_double_p, c_double_p, c_double_p, c_float_p]),
+    "lvf_stereo_triangulate_lidar": (C.c_int, [_VP, _VP, C.POINTER(Camera), C.POINTER(Camera), C.c_double, C.c_int, c_float_p, c_float_p, c_u8_p, c_double_p,
+                                               c_double_p, C.POINTER(FlowOptions), _VP, c_u8_p]),
     "lvf_window_reject_outliers": (C.c_int, [_VP, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int)]),
     "lvf_comm_get_unique_id": (C.c_int, [_VP]),
     "lvf_comm_create": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.POINTER(_VP)]),

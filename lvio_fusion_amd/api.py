@@ -824,6 +824,83 @@ class ScanContextDb:
             self.h = C.c_void_p()
 
 
+def lidar_depth_options(**kw):
+    """lvf_lidar_depth_options with its defaults (cell 8 px, radius 12 px, 0.5 .. 80 m, spread 2 m, min_det 4 px^2, extrapolation 0.5, far_factor 50,
+    replace_lost 1), overridden by keyword."""
+    return _options(_lib.LidarDepthOptions, "lvf_lidar_depth_options_default", "lidar_depth_options", kw)
+
+
+def cam_from_lidar(cam0, lidar_extrinsic):
+    """The 3x4 matrix [R | t] that takes LiDAR sensor coordinates into camera 0: SE3(cam0 extrinsic).inverse() * SE3(lidar_extrinsic), both
+    sensor -> robot as [qx, qy, qz, qw, tx, ty, tz].  The device takes the matrix as data, so nothing depends on how it was rounded."""
+    from .synthetic import rotmat
+    e0, el = _d(cam0["extrinsic"]), _d(lidar_extrinsic)
+    r0t = rotmat(e0[:4]).T
+    return np.ascontiguousarray(np.hstack([r0t @ rotmat(el[:4]), (r0t @ (el[4:] - e0[4:]))[:, None]]))
+
+
+LIDAR_DEPTH_RECORD = np.dtype([("u", np.float32), ("v", np.float32), ("z", np.float32), ("source_index", np.int32)])
+
+
+class LidarDepth:
+    """A sweep projected into camera 0 and binned on a pixel grid.  `cloud` is a sensor-frame Cloud deskewed to the image's pose,
+    `matrix` = cam_from_lidar(cam0, lidar_extrinsic)."""
+
+    def __init__(self, ctx, cloud, cam0, matrix, width, height, opt=None):
+        self.ctx, self.cam0, self.width, self.height = ctx, cam0, int(width), int(height)
+        self.opt = opt if opt is not None else lidar_depth_options()
+        m = _d(matrix).reshape(12)
+        c0 = make_camera(cam0)
+        self.h = C.c_void_p()
+        _chk(ctx.L.lvf_lidar_depth_create(ctx.h, cloud.h, C.byref(c0), _dp(m), self.width, self.height, C.byref(self.opt), C.byref(self.h)))
+
+    def __len__(self):
+        n = self.ctx.L.lvf_lidar_depth_size(self.h)
+        if n < 0:
+            raise LvfError("lvf_lidar_depth_size: %s" % _lib.lib().lvf_last_error().decode())
+        return n
+
+    @property
+    def grid(self):
+        """(cell columns, cell rows)"""
+        c = self.opt.cell
+        return (self.width + c - 1) // c, (self.height + c - 1) // c
+
+    def download(self):
+        """records [len(self)] (LIDAR_DEPTH_RECORD, in the device's order: unordered inside a cell) and cell_start [cells + 1]"""
+        ncx, ncy = self.grid
+        rec, start = np.zeros(len(self), LIDAR_DEPTH_RECORD), np.zeros(ncx * ncy + 1, np.int32)
+        _chk(self.ctx.L.lvf_lidar_depth_download(self.h, rec.ctypes.data_as(C.c_void_p), _ip(start)))
+        return rec, start
+
+    def query(self, cam1, kps_left):
+        """depth of every feature: status [n] (1 accepted; 0 / 3 / 4 / 2 / 5 the gates of include/lvf.h), depth [n], inv_depth [n], p_robot [n, 3],
+        kps_right [n, 2] float32 — zero where status != 1"""
+        p = _pts(kps_left)
+        n = len(p)
+        st, dz, inv, pb, q = np.zeros(n, np.uint8), np.zeros(n), np.zeros(n), np.zeros((n, 3)), np.zeros((n, 2), np.float32)
+        c0, c1 = make_camera(self.cam0), make_camera(cam1)
+        _chk(self.ctx.L.lvf_lidar_depth_query(self.h, C.byref(c0), C.byref(c1), n, _fp(p), _u8p(st), _dp(dz), _dp(inv), _dp(pb), _fp(q)))
+        return st, dz, inv, pb, q
+
+    def close(self):
+        if self.h:
+            self.ctx.L.lvf_lidar_depth_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def stereo_triangulate_lidar(left, right, cam0, cam1, baseline, kps_left, depth, opt=None):
+    """stereo_triangulate with the sweep's depth merged in behind it (one launch chain, one wait): returns kps_right, status, inv_depth, p_robot as
+    stereo_triangulate does, and source [n]: 0 no depth, 1 stereo, 2 LiDAR."""
+    p = _pts(kps_left)
+    n = len(p)
+    q, st, inv, pb, src = np.zeros((n, 2), np.float32), np.zeros(n, np.uint8), np.zeros(n), np.zeros((n, 3)), np.zeros(n, np.uint8)
+    c0, c1 = make_camera(cam0), make_camera(cam1)
+    _chk(left.ctx.L.lvf_stereo_triangulate_lidar(left.h, right.h, C.byref(c0), C.byref(c1), C.c_double(baseline), n, _fp(p), _fp(q), _u8p(st), _dp(inv), _dp(pb),
+                                                 C.byref(opt) if opt is not None else None, depth.h, _u8p(src)))
+    return q, st, inv, pb, src
+
+
 class Trajectory:
     """Map::keyframes as Map::ComputePose reads it, on the device (DESIGN 16): stamps [n] strictly increasing, poses [n, 7] = [qx,qy,qz,qw,tx,ty,tz]."""
 

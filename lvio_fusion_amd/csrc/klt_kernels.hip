@@ -524,6 +524,8 @@ int lvf_optical_flow(const lvf_image* prev_img, const lvf_image* next_img, int n
   return LVF_OK;
 }
 
+// (lvf_stereo_triangulate_lidar below queues the SAME three launches with the same arguments — the 50-baseline prediction included — and says so
+// in its contract; a change to this chain is a change to that one.  tests/test_gpu_lidar_depth.py compares the two byte for byte.)
 int lvf_stereo_triangulate(const lvf_image* left, const lvf_image* right, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n,
                            const float* kps_left, float* kps_right, uint8_t* status, double* inv_depth, double* p_robot, const lvf_flow_options* opt) {
   lvf_flow_options o;
@@ -549,6 +551,42 @@ int lvf_stereo_triangulate(const lvf_image* left, const lvf_image* right, const 
   LVF_HIP(hipMemcpyAsync(inv_depth, inv.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
   LVF_HIP(hipMemcpyAsync(p_robot, pb.p, (size_t)3 * n * 8, hipMemcpyDeviceToHost, s));
   LVF_HIP(hipStreamSynchronize(s));
+  return LVF_OK;
+}
+
+// lvf_stereo_triangulate's launch chain, restated launch for launch (keep the two in step), then the LiDAR query and the merge
+// (lidar_depth_kernels.hip) behind it: one wait
+int lvf_stereo_triangulate_lidar(const lvf_image* left, const lvf_image* right, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n,
+                                 const float* kps_left, float* kps_right, uint8_t* status, double* inv_depth, double* p_robot, const lvf_flow_options* opt,
+                                 const lvf_lidar_depth* depth, uint8_t* source) {
+  lvf_flow_options o;
+  if (opt) o = *opt; else lvf_flow_options_default(&o);
+  LVF_TRY(check_flow("lvf_stereo_triangulate_lidar", left, right, n, &o));
+  LVF_REQUIRE(cam_ok(cam0) && cam_ok(cam1), "lvf_stereo_triangulate_lidar: bad camera (null, zero focal length or zero extrinsic quaternion)");
+  LVF_REQUIRE(baseline > 0.0, "lvf_stereo_triangulate_lidar: baseline must be > 0");
+  LVF_TRY(lvf::lidar_depth_check("lvf_stereo_triangulate_lidar", depth, left->ctx, cam0, cam1));
+  if (n == 0) return LVF_OK;
+  LVF_REQUIRE(kps_left && kps_right && status && inv_depth && p_robot && source, "lvf_stereo_triangulate_lidar: null point arrays");
+  lvf_ctx* ctx = left->ctx;
+  LVF_TRY(lvf::enter(ctx));
+  hipStream_t s = ctx->stream;
+  const KCam c0 = make_cam(cam0), c1 = make_cam(cam1);
+  DevBuf<float2> p, q; DevBuf<uint8_t> st, src; DevBuf<double> inv, pb;
+  LVF_TRY(p.upload(reinterpret_cast<const float2*>(kps_left), n, s));
+  LVF_TRY(q.alloc(n)); LVF_TRY(st.alloc(n)); LVF_TRY(src.alloc(n)); LVF_TRY(inv.alloc(n)); LVF_TRY(pb.alloc((size_t)3 * n));
+  lvf::StreamWaitGuard wait(s);                  // (an error below: what is queued ends before the buffers go)
+  hipLaunchKernelGGL(k_klt_stereo_predict, dim3(grid_of(n)), dim3(kT), 0, s, n, p.p, q.p, c0, c1, baseline * 50);
+  launch_flow(s, left, right, n, p.p, q.p, st.p, (float*)nullptr, &o);
+  hipLaunchKernelGGL(k_klt_dlt, dim3(grid_of(n)), dim3(kT), 0, s, n, p.p, q.p, st.p, inv.p, pb.p, c0, c1);
+  LVF_HIP(hipGetLastError());
+  LVF_TRY(lvf::lidar_depth_merge_queue(depth, cam0, cam1, baseline, n, p.p, q.p, st.p, inv.p, pb.p, src.p));
+  LVF_HIP(hipMemcpyAsync(kps_right, q.p, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipMemcpyAsync(status, st.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipMemcpyAsync(inv_depth, inv.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipMemcpyAsync(p_robot, pb.p, (size_t)3 * n * 8, hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipMemcpyAsync(source, src.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipStreamSynchronize(s));
+  wait.dismiss();
   return LVF_OK;
 }
 

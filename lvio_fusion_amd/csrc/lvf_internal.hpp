@@ -606,6 +606,12 @@ int deskew_prepare(const char* who, lvf_ctx* ctx, const lvf_trajectory* tr, doub
                    DeskewP* P, bool* active);
 // out[i] = deskewed in[i] for i < min(cap, *n_dev) (n_dev may be null) on stream q; in == out is allowed
 int deskew_launch(hipStream_t q, int cap, const int* n_dev, const float4* in, float4* out, const DeskewP& P);
+// LiDAR depth for visual features (lidar_depth_kernels.hip) as lvf_stereo_triangulate_lidar (klt_kernels.hip) uses it.  lidar_depth_check: the
+// handle, its context (ctx may be null: not compared) and the cameras, on the host (LVF_ERR_INVALID, nothing launched).  lidar_depth_merge_queue:
+// the query of `left` and the merge into the stereo chain's device arrays (all [n]; source [n] is written) on the context's stream; no wait.
+int lidar_depth_check(const char* who, const lvf_lidar_depth* d, lvf_ctx* ctx, const lvf_camera* cam0, const lvf_camera* cam1);
+int lidar_depth_merge_queue(const lvf_lidar_depth* d, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n, const float2* left, float2* right,
+                            uint8_t* status, double* inv_depth, double* p_robot, uint8_t* source);
 // kernels / launchers implemented in the .hip translation units
 int launch_pose_only(lvf_batch* b, const lvf_state* st, bool want_j);
 int launch_two_frame(lvf_batch* b, const lvf_state* st, bool want_j);
