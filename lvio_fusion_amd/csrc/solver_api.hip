@@ -21,7 +21,8 @@ lvf_problem::~lvf_problem() {
 namespace lvf {
 
 static const char* const kStageNames[ST_N] = {"k_zero_multi (only when the accumulators are not known clean)", "k_lin_visual", "k_tf_reduce (+ sparse level 0)", "k_prepare (+ sparse level 1)", "k_schur_sp0 (+ a sparse level)", "k_sp_eliminate (the levels left)",
-                                             "k_chol_step (all block steps)", "k_chol_backsolve", "k_step_tail", "k_cost_decide (candidate cost incl. the ImuError factors; its last workgroup closes the iteration; + prior passes)", "k_lm_decide (windows without visual blocks)",
+                                             "k_chol_step (the block steps launched on their own: all of them, or all but the last where the merged last launch is in use)",
+                                             "k_chol_backsolve / k_backsolve_tail / k_chol_backsolve_tail (the last block step + the back substitution + the step tail)", "k_step_tail", "k_cost_decide (candidate cost incl. the ImuError factors; its last workgroup closes the iteration; + prior passes)", "k_lm_decide (windows without visual blocks)",
                                              "k_lin_cost_decide (fused chain: linearisation at the candidate + its cost; its last workgroup closes the iteration)"};
 
 void summary_from_ctl(const lvf_problem* p, const LmCtl& c, lvf_solver_summary* s) {

@@ -97,6 +97,7 @@ struct lvf_problem {
   // which of a node's own rows (index into sp_rows) a dense-corner / augmented column is, or -1
   lvf::DevBuf<double> sp_G; lvf::DevBuf<int> sp_gmap; int ldG = 0;
   lvf::DevBuf<double> sp_T;      // block form of the dense back substitution (lvf::TRide): nb x nb blocks of 64 x 64, block (k, j) used for k < j
+  lvf::DevBuf<double> x_last;    // merged last launch (lvf::XLast): the solution's last block, handed from the last block step to the back substitution
   lvf::DevBuf<double> Ldiag;                    // the factored diagonal blocks L_kk [nb][64][64] (NOT stored back into S: see chol_step_body)
   std::vector<int> perm_h;
   lvf::DevBuf<double> B, gc, C, gr, E, Cd, S, dxc, dxl, scal;
@@ -286,6 +287,10 @@ __host__ __device__ inline int chol_step_grid(int nb, int kb) {
   return kb >= nb ? 0 : 2 + below + (kb > 0 ? below * (below + 1) / 2 : 0);
 }
 struct TRide { int n; GP<double> T; };
+// The merged last launch (k_chol_backsolve_tail): the inverse workgroup of block step nb - 1 holds L_kk^-T and the forward-substituted
+// right-hand side when its sweep ends, forms the solution's last block x_last = L_kk^-T y_last and publishes its 64 values, then the flag
+// (agent-scope atomic stores, as the pose increments travel: BackArgs::pose_ready).  null flag: nothing is published (k_chol_step*).
+struct XLast { GP<double> x = nullptr; GP<int> flag = nullptr; };
 struct GRide { int n, first; GP<const SpNode> nodes; GP<const int> rows; GP<const double> W; int wstride; GP<const double> Linv; GP<const int> map; GP<double> G; int ldG, off; GP<const int> done; };
 
 // ---- back substitution and step tail (k_chol_backsolve, k_step_tail, k_backsolve_tail)
@@ -301,8 +306,11 @@ constexpr int kBT = 512, kBParts = kBT / 64, kBackPre = 256 / kBParts, kBackInv 
 // pose_ready (merged back-substitution + step tail, k_backsolve_tail): once the dense corner is solved the POSE part of the step (natural
 // unknowns [0, n_pose)) is written out and *pose_ready is raised (release, agent scope) — what the landmark back-substitution waits for
 // T (block form, back_block_ride): the stored products T_kj of this iteration's factor, or null for the form that reads S and Dinv
+// x_ready (merged last launch, block form only): the back substitution does not solve its first block but waits — bounded by x_timeout
+// ticks, then kFailHandover is raised at x_fail — for the flag of XLast and reads the block from x_last
 struct BackArgs { GP<const double> Sd; int ld, d; GP<const double> Dinv; GP<double> xout; SpBack sp; GP<const int> done; GP<const double> Ldiag; GP<int> pose_ready = nullptr; int n_pose = 0; int pose_fenced = 0;
-                  GP<const double> T = nullptr; };
+                  GP<const double> T = nullptr;
+                  GP<const int> x_ready = nullptr; GP<const double> x_last = nullptr; unsigned x_timeout = 0; GP<int> x_fail = nullptr; };
 // block form: links j = nblk - 1 .. 1 whose products a thread holds in registers, eight doubles per block (k, j), k < j.  The dense-corner-only
 // body has the room for a corner of five blocks (ten products); beside the sparse levels' items they take the place of the gather operands
 // (three products: three blocks).  A corner with more blocks keeps the S / Dinv form (build_chain).
@@ -316,7 +324,14 @@ struct TailArgs {
 };
 struct BackTailArgs { BackArgs back; TailArgs tail; int g_lm; int fenced; unsigned timeout_ticks; GP<int> fail;
                       int g_prod = 0, kpw = 0, ldG = 0; GP<const double> G = nullptr; GP<const int> iperm = nullptr;
-                      int early = 1; };      // early: the landmark and pose workgroups request their operands before the wait (LVF_BACK_EARLY=0: behind it)
+                      int early = 1;
+                      // merged last launch: the G rows of the last level are formed by riders of the SAME launch — the G workgroups wait (bounded)
+                      // until g_target of them have arrived at *g_ready before they request anything of G, and read G at the coherence point
+                      GP<const int> g_ready = nullptr; int g_target = 0; };      // early: the landmark and pose workgroups request their operands before the wait (LVF_BACK_EARLY=0: behind it)
+// k_chol_backsolve_tail: block step nb - 1 and k_backsolve_tail as ONE launch (Chain::chol_back_merged).  Workgroups by blockIdx.x, producers
+// first: [0, 2) the column of the last block step (chol_step_body; the second one publishes x_last), 2 the back substitution, [3, 3 + g.n) the
+// G riders of this launch, then the pose workgroup, bt.g_prod G-product workgroups and bt.g_lm landmark workgroups of k_backsolve_tail.
+struct CholBackArgs { CholArgs chol; GRide g; GP<int> g_arrive; TRide tr; XLast xl; BackTailArgs bt; };
 
 // ---- closing an iteration (k_lm_decide, k_cost_decide, k_lin_cost_decide)
 struct DecideArgs {
@@ -333,7 +348,7 @@ struct FusedArgs { LinArgs lin; DecideArgs dec; GP<double> cost_new; int nblocks
 
 // ------------------------------------------------------------------------------------------------ kernels launched from the host side
 // (prototypes only: the definitions carry the launch bounds and occupancy attributes — k_tf_reduce*, k_prepare*, the Schur, layout and sparse-level
-// kernels in solver_assemble.hip, k_chol_step* in solver_chol.hip, k_chol_backsolve*, k_step_tail* and k_backsolve_tail in solver_back.hip, the
+// kernels in solver_assemble.hip, k_chol_step* in solver_chol.hip, k_chol_backsolve*, k_step_tail*, k_backsolve_tail and k_chol_backsolve_tail in solver_back.hip, the
 // linearisation, cost and decision kernels in solver_kernels.hip)
 __global__ void k_zero_multi(ZeroList z);
 __global__ void k_zero_multi_ranges(ZeroList z, int n_lm, int* __restrict__ kmin, int* __restrict__ kmax);
@@ -404,6 +419,7 @@ __global__ void k_step_tail(TailArgs a);
 __global__ void k_step_tail_b(const TailArgs* __restrict__ t);
 __global__ void k_step_tail_bt(const TailArgs* __restrict__ t);
 __global__ void k_backsolve_tail(BackTailArgs a);
+__global__ void k_chol_backsolve_tail(CholBackArgs a);
 __global__ void k_lm_decide(DecideArgs a);
 __global__ void k_cost_decide(CostArgs a, DecideArgs d, int end_zero);
 __global__ void k_cost_decide_b(const CostArgs* __restrict__ t, const DecideArgs* __restrict__ d, int end_zero);

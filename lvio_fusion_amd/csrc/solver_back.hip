@@ -1,5 +1,6 @@
 // solver_back.hip — LM iteration, stage 4: back substitution of the dense corner and the sparse levels, the landmark back substitution
-// and the candidate state x + dx.  Device code only (solver_args.hpp: argument blocks, constants, prototypes).
+// and the candidate state x + dx; the merged last launch (k_chol_backsolve_tail) runs the last block step of stage 3 in front of them
+// (its body: solver_dev.hpp).  Device code only (solver_args.hpp: argument blocks, constants, prototypes).
 #include "solver_dev.hpp"
 
 namespace lvf {
@@ -27,8 +28,12 @@ __device__ __forceinline__ T ld_off32(const T* base, unsigned byte_off) {     //
 // LEVELS = false (the product form, k_backsolve_tail with Chain::back_product): the dense corner only.  The WHOLE dense-corner solution is
 // published — the plan may leave (v, ba, bg) blocks in the corner's padding, and the sibling workgroups' product with G reads them — and the
 // sparse items, the stored L_bb^-1 and the levels are neither requested nor run.
-template <bool LEVELS = true>
+// XL (the back-substitution workgroup of k_chol_backsolve_tail; block form, LEVELS = false): the launch contains the last block step, so the
+// first block is not solved here — nothing of it is requested — but read, behind a bounded wait, from what that step's inverse workgroup
+// publishes (XLast); everything else the links need is final before the launch and in flight long before the flag goes up.
+template <bool LEVELS = true, bool XL = false>
 __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
+  static_assert(!(XL && LEVELS), "the x_last entry exists beside the product form only");
   const int dv = done_flag_issue(A.done);
   const double* S = A.Sd; const int ld = A.ld, d = A.d; const double* Dinv = A.Dinv; double* xout = A.xout; const SpBack& sp = A.sp;
   extern __shared__ double sm[];          // xs[off] | x[nblk*64] | partial[kBParts][64] | rhs[64] | accs[9 max_count] | linv[81 n_nodes]
@@ -75,7 +80,7 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
     const double* yrow = (d / kNB == kb) ? A.Ldiag + (size_t)kb * kNB * kNB + (size_t)(d - r0) * kNB : S + (size_t)d * ld + r0;
     yv = (r0 + c < d) ? ld_off32(yrow, c_off) : 0.0;
   };
-  prefetch(nblk - 1);
+  if constexpr (!XL) prefetch(nblk - 1);
   // the stored L_bb^-1 and the node table go to LDS: ALL of a thread's requests are issued before the first LDS write (written as a
   // copy loop the compiler waits for every load in turn — eight dependent round trips at 50 keyframes, 4 of this kernel's 30 us)
   constexpr int kLinvPre = 8;
@@ -131,8 +136,24 @@ __device__ __forceinline__ void chol_backsolve_body(const BackArgs& A) {
   for (int i = tid; i < sp.off + n; i += kBT) sm[i] = 0.0;
   lds_barrier();
   mark();
+  if constexpr (XL) {
+    // the bounded wait of wait_pose_ready (SpSrc has the rules): thread 0 polls, the workgroup meets at a barrier that leaves the T requests
+    // in flight; on a time-out the hand-over flag is raised and the workgroup goes on — its consumers must see pose_ready either way
+    if (tid == 0) {
+      const unsigned long long t0 = wall_clock64();
+      while (__hip_atomic_load((const int*)A.x_ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
+        __builtin_amdgcn_s_sleep(4);
+        if (wall_clock64() - t0 > (unsigned long long)A.x_timeout) { atomicMax((int*)A.x_fail, kFailHandover + 90001); break; }
+      }
+    }
+    lds_barrier();
+    mark();                                       // LVF_BACK_TIMING: the x_last flag was seen
+    if (tid < kNB) x[(nblk - 1) * kNB + tid] = __hip_atomic_load((const double*)A.x_last + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    lds_barrier();
+    mark();
+  }
   const int kb_last = blocks ? nblk - 1 : 0;      // block form: the first solved block (its right-hand side sits in Ldiag) only
-  for (int kb = nblk - 1; kb >= kb_last; --kb) {
+  for (int kb = nblk - 1; kb >= (XL ? nblk : kb_last); --kb) {
     const int r0 = kb * kNB;
     double s = 0.0;
 #pragma unroll
@@ -540,6 +561,9 @@ __device__ __forceinline__ void wait_pose_ready(const BackTailArgs& a) {
 // published solution — either way it is applied here, exactly once.  16 lanes per row, 32 rows per pass; a lane's share of the first pass
 // is requested into a fixed register window BEFORE the wait (what does not fit, and further passes, are read from memory afterwards).
 constexpr int kGPre = 24, kLmPre = 2;      // kLmPre: passes of a landmark workgroup whose operands are requested before the wait (landmark_back_body)
+// GW (k_chol_backsolve_tail): the riders that form the last level's rows of G run in the same launch — a bounded wait for their arrivals stands in
+// front of the requests (long before the pose increments are due), and G is read with agent-scope atomic loads
+template <bool GW = false>
 __device__ __forceinline__ void back_product_body(const int vb, const BackTailArgs& a) {
   const TailArgs& T = a.tail; const SpBack& sp = a.back.sp;
   extern __shared__ double gsm[];          // xd[ldG]: [x_dense ; -1 ; 0 ..] | xs[9 kpw]: this workgroup's rows of the step
@@ -548,13 +572,25 @@ __device__ __forceinline__ void back_product_body(const int vb, const BackTailAr
   const int k0 = vb * a.kpw, nrows = 9 * min(a.kpw, T.n_kf - k0), i0 = T.dp + 9 * k0;      // the rows' natural unknowns are contiguous from i0
   unsigned long long* dbg = (sp.dbg && vb == 0 && tid == 0) ? sp.dbg + 40 : nullptr;
   if (dbg) dbg[0] = wall_clock64();
+  auto ld_g = [](const double* p) { return GW ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p; };
+  if constexpr (GW) {
+    if (tid == 0 && a.g_target > 0) {
+      const unsigned long long t0 = wall_clock64();
+      while (__hip_atomic_load((const int*)a.g_ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a.g_target) {
+        __builtin_amdgcn_s_sleep(16);
+        if (wall_clock64() - t0 > (unsigned long long)a.timeout_ticks) { atomicMax(a.fail, kFailHandover + 90002); break; }
+      }
+    }
+    __syncthreads();
+    if (dbg) dbg[5] = wall_clock64();      // LVF_BACK_TIMING: the riders of this launch have arrived
+  }
   // ---- requests: nothing below depends on the step
   const int scol = row < nrows ? sp.perm[i0 + row] : -1;
   const bool in_g = scol >= 0 && scol < sp.off;
   const double* grow = a.G + (size_t)(in_g ? scol : 0) * ldG + q;
   double g[kGPre];
 #pragma unroll
-  for (int u = 0; u < kGPre; ++u) g[u] = (in_g && u < nu) ? grow[16 * u] : 0.0;
+  for (int u = 0; u < kGPre; ++u) g[u] = (in_g && u < nu) ? ld_g(grow + 16 * u) : 0.0;
   const int ip0 = tid < ldG ? a.iperm[sp.off + tid] : -1;
   // the operands of this thread's unknown (thread t < nrows applies row t)
   const bool mine = tid < nrows;
@@ -567,6 +603,12 @@ __device__ __forceinline__ void back_product_body(const int vb, const BackTailAr
   const int cm = (mine && T.pose_const) ? T.pose_const[uk] : 0;      // bit 0: pose, bits 1..3: v, ba, bg held constant
   const int frozen = *T.jac.frozen;
   const double inv_radius = 1.0 / *T.radius;
+  if constexpr (GW) {
+    // (consumed here: the requests cannot sink behind the wait, as in landmark_back_body)
+#pragma unroll
+    for (int u = 0; u < kGPre; ++u) asm volatile("" ::"v"(g[u]));
+    if (dbg) dbg[6] = wall_clock64();      // LVF_BACK_TIMING: its share of G is in registers
+  }
   wait_pose_ready(a);
   if (dbg) dbg[1] = wall_clock64();
   // ---- the dense solution, read at the coherence point
@@ -581,7 +623,7 @@ __device__ __forceinline__ void back_product_body(const int vb, const BackTailAr
     double s = 0.0;
 #pragma unroll
     for (int u = 0; u < kGPre; ++u) if (u < nu) s += g[u] * xd[q + 16 * u];
-    if (in_g) for (int u = kGPre; u < nu; ++u) s += grow[16 * u] * xd[q + 16 * u];
+    if (in_g) for (int u = kGPre; u < nu; ++u) s += ld_g(grow + 16 * u) * xd[q + 16 * u];
     s = row16_sum(s);
     if (q == 0 && row < nrows) {
       if (in_g) { xs[row] = s; a.back.xout[i0 + row] = s; }      // (a block of the dense corner was written out by workgroup 0)
@@ -593,7 +635,7 @@ __device__ __forceinline__ void back_product_body(const int vb, const BackTailAr
     const int sc = rw < nrows ? sp.perm[i0 + rw] : -1;
     const bool ing = sc >= 0 && sc < sp.off;
     double s = 0.0;
-    if (ing) { const double* gr = a.G + (size_t)sc * ldG + q; for (int u = 0; u < nu; ++u) s += gr[16 * u] * xd[q + 16 * u]; }
+    if (ing) { const double* gr = a.G + (size_t)sc * ldG + q; for (int u = 0; u < nu; ++u) s += ld_g(gr + 16 * u) * xd[q + 16 * u]; }
     s = row16_sum(s);
     if (q == 0 && rw < nrows) {
       if (ing) { xs[rw] = s; a.back.xout[i0 + rw] = s; }
@@ -618,6 +660,47 @@ __device__ __forceinline__ void back_product_body(const int vb, const BackTailAr
   if ((tid & 63) == 0 && gm != 0.0) atomicMax(reinterpret_cast<unsigned long long*>(T.scal + SC_GMAX + (blockIdx.x & (kStripes - 1))), (unsigned long long)__double_as_longlong(gm));
   if (dbg) dbg[4] = wall_clock64();
 }
+// the pose workgroup of the merged launches: candidate poses and the pose unknowns' share of the model cost change / step norm (the
+// increments are read at the coherence point into LDS; apply_step_ops takes them from there).  What the first 512 unknowns / keyframes read
+// beside the increments — B's diagonal, h0, the gradient, the poses, the constant flags, the radius — is requested and consumed before the
+// wait (a.early; LVF_BACK_EARLY=0: behind it, as it was).
+__device__ __forceinline__ void back_tail_pose_body(const BackTailArgs& a) {
+  const TailArgs& T = a.tail;
+  extern __shared__ double sdx_pose[];
+  const double* const Bt = tail_B(T); const double* const gct = tail_gc(T);
+  StepOps ops{}; double radius = 0.0;
+  if (a.early) {
+    ops = step_ops_load<1>(threadIdx.x, T.n_kf, T.s, T.d, T.ld, Bt, gct, T.pose_const, T.jac);
+    radius = *T.radius;
+    asm volatile("" ::"v"(ops.h), "v"(ops.h0d), "v"(ops.gci), "v"(ops.frozen), "v"(ops.cm_kf), "v"(radius));
+#pragma unroll
+    for (int c = 0; c < 7; ++c) asm volatile("" ::"v"(ops.p[c]));
+  }
+  wait_pose_ready(a);
+  for (int i = threadIdx.x; i < T.dp; i += kBT) sdx_pose[i] = __hip_atomic_load(T.dxc + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (!a.early) { ops = step_ops_load<1>(threadIdx.x, T.n_kf, T.s, T.d, T.ld, Bt, gct, T.pose_const, T.jac); radius = *T.radius; }
+  const double inv_radius = 1.0 / radius;
+  apply_step_ops<kBT, 1>(0, T.n_kf, 0, T.s, sdx_pose, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, inv_radius, ops);
+  for (int vb = 1; vb * kBT < max(T.dp, T.n_kf); ++vb)
+    apply_step_body<kBT, 1>(vb, T.n_kf, 0, T.s, sdx_pose, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, T.ld, Bt, gct, inv_radius, T.pose_const, T.jac);
+  if (a.back.sp.dbg && threadIdx.x == 0) a.back.sp.dbg[62] = wall_clock64();      // LVF_BACK_TIMING: the pose part is applied
+}
+// landmark workgroup vb of a.g_lm of the merged launches (LVF_BACK_TIMING: the first and the last one leave their stamps)
+__device__ __forceinline__ void back_tail_landmark_body(const int vb, const BackTailArgs& a) {
+  const TailArgs& T = a.tail;
+  unsigned long long* ldbg = (a.back.sp.dbg && (vb == 0 || vb == a.g_lm - 1) && threadIdx.x == 0) ? a.back.sp.dbg + (vb == 0 ? 56 : 59) : nullptr;
+  if (ldbg) ldbg[0] = wall_clock64();
+  if (a.early)
+    landmark_back_body<kBT, true, kLmPre>(vb, a.g_lm, T.n_lm, T.dp, T.ldE, tail_E(T), T.C, T.Cd, T.gr, T.dxc, T.s.inv_depth, T.dxl, T.invd2, T.scal, T.kmin, T.kmax,
+                                          [&]() { wait_pose_ready(a); if (ldbg) ldbg[1] = wall_clock64(); });
+  else {
+    wait_pose_ready(a);
+    if (ldbg) ldbg[1] = wall_clock64();
+    landmark_back_body<kBT, true>(vb, a.g_lm, T.n_lm, T.dp, T.ldE, tail_E(T), T.C, T.Cd, T.gr, T.dxc, T.s.inv_depth, T.dxl, T.invd2, T.scal, T.kmin, T.kmax);
+  }
+  if (ldbg) ldbg[2] = wall_clock64();
+}
 __global__ __launch_bounds__(kBT) void k_backsolve_tail(BackTailArgs a) {
   if (a.back.done && *a.back.done) return;                      // (every workgroup tests the same flag: nobody waits for a producer that has left)
   const TailArgs& T = a.tail;
@@ -641,43 +724,37 @@ __global__ __launch_bounds__(kBT) void k_backsolve_tail(BackTailArgs a) {
     if (a.back.sp.dbg && threadIdx.x == 0) a.back.sp.dbg[55] = wall_clock64();      // LVF_BACK_TIMING: the step is applied
     return;
   }
-  unsigned long long* ldbg = (a.back.sp.dbg && (blockIdx.x == 2 || (int)blockIdx.x == 1 + a.g_lm) && threadIdx.x == 0) ? a.back.sp.dbg + (blockIdx.x == 2 ? 56 : 59) : nullptr;
-  if (ldbg) ldbg[0] = wall_clock64();
-  if (blockIdx.x == 1) {
-    // the pose part of the step: candidate poses and the pose unknowns' share of the model cost change / step norm (the increments are read
-    // at the coherence point into LDS; apply_step_ops takes them from there).  What the first 512 unknowns / keyframes read beside the
-    // increments — B's diagonal, h0, the gradient, the poses, the constant flags, the radius — is requested and consumed before the wait
-    // (a.early; LVF_BACK_EARLY=0: behind it, as it was).
-    extern __shared__ double sdx_pose[];
-    const double* const Bt = tail_B(T); const double* const gct = tail_gc(T);
-    StepOps ops{}; double radius = 0.0;
-    if (a.early) {
-      ops = step_ops_load<1>(threadIdx.x, T.n_kf, T.s, T.d, T.ld, Bt, gct, T.pose_const, T.jac);
-      radius = *T.radius;
-      asm volatile("" ::"v"(ops.h), "v"(ops.h0d), "v"(ops.gci), "v"(ops.frozen), "v"(ops.cm_kf), "v"(radius));
-#pragma unroll
-      for (int c = 0; c < 7; ++c) asm volatile("" ::"v"(ops.p[c]));
-    }
-    wait_pose_ready(a);
-    for (int i = threadIdx.x; i < T.dp; i += kBT) sdx_pose[i] = __hip_atomic_load(T.dxc + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (blockIdx.x == 1) { back_tail_pose_body(a); return; }
+  back_tail_landmark_body((int)blockIdx.x - 2, a);
+}
+
+// Block step nb - 1 and k_backsolve_tail as ONE launch (product and block forms, sub-block sweep; CholBackArgs has the roles).  Of the 12.5 us
+// between the last pivot and pose_ready in two launches only the last block of the solution depends on the last diagonal block: the launch
+// boundary, the back substitution's T requests and the consumers' own requests all run under the pivot sweep, which keeps two workgroups
+// busy.  Producers carry the lowest workgroup numbers; nothing DEPENDS on that: every wait is bounded and raises the hand-over flag.  Every
+// role tests `done` before anything else (the column workgroups and the riders inside their bodies), so nobody waits for a producer that left.
+__global__ __launch_bounds__(kBT) void k_chol_backsolve_tail(CholBackArgs a) {
+  static_assert(kCT == kBT, "one launch: the block step's workgroups and the back substitution's have the same size");
+  const int bx = (int)blockIdx.x, kb = a.chol.nb - 1;
+  if (bx < 2) { chol_step_body<true, true>(bx, a.chol, kb, a.xl); return; }
+  const BackTailArgs& b = a.bt;
+  if (bx == 2) {
+    // T_{nb-2, nb-1} first (both factors are final since the launch before: no hand-off), on the kernel's panel buffers, in time that is
+    // idle anyway; the requests of the body below read it back, hence the barrier and the workgroup-scope fences
+    back_block_ride(0, a.chol, kb, a.tr);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
-    if (!a.early) { ops = step_ops_load<1>(threadIdx.x, T.n_kf, T.s, T.d, T.ld, Bt, gct, T.pose_const, T.jac); radius = *T.radius; }
-    const double inv_radius = 1.0 / radius;
-    apply_step_ops<kBT, 1>(0, T.n_kf, 0, T.s, sdx_pose, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, inv_radius, ops);
-    for (int vb = 1; vb * kBT < max(T.dp, T.n_kf); ++vb)
-      apply_step_body<kBT, 1>(vb, T.n_kf, 0, T.s, sdx_pose, T.dxl, T.poses2, T.vel2, T.ba2, T.bg2, T.invd2, T.scal, T.d, T.ld, Bt, gct, inv_radius, T.pose_const, T.jac);
-    if (a.back.sp.dbg && threadIdx.x == 0) a.back.sp.dbg[62] = wall_clock64();      // LVF_BACK_TIMING: the pose part is applied
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    chol_backsolve_body<false, true>(b.back);
+    if (b.back.sp.dbg && threadIdx.x == 0) b.back.sp.dbg[55] = wall_clock64();      // LVF_BACK_TIMING: the back substitution is done
     return;
   }
-  if (a.early)
-    landmark_back_body<kBT, true, kLmPre>((int)blockIdx.x - 2, a.g_lm, T.n_lm, T.dp, T.ldE, tail_E(T), T.C, T.Cd, T.gr, T.dxc, T.s.inv_depth, T.dxl, T.invd2, T.scal, T.kmin, T.kmax,
-                                          [&]() { wait_pose_ready(a); if (ldbg) ldbg[1] = wall_clock64(); });
-  else {
-    wait_pose_ready(a);
-    if (ldbg) ldbg[1] = wall_clock64();
-    landmark_back_body<kBT, true>((int)blockIdx.x - 2, a.g_lm, T.n_lm, T.dp, T.ldE, tail_E(T), T.C, T.Cd, T.gr, T.dxc, T.s.inv_depth, T.dxl, T.invd2, T.scal, T.kmin, T.kmax);
-  }
-  if (ldbg) ldbg[2] = wall_clock64();
+  if (bx < 3 + a.g.n) { back_product_ride<true>(bx - 3, a.g, a.g_arrive); return; }
+  if (b.back.done && *b.back.done) return;
+  const int role = bx - 3 - a.g.n;
+  if (role == 0) back_tail_pose_body(b);
+  else if (role <= b.g_prod) back_product_body<true>(role - 1, b);
+  else back_tail_landmark_body(role - 1 - b.g_prod, b);
 }
 
 }  // namespace lvf

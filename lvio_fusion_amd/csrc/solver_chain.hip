@@ -330,8 +330,8 @@ static int chain_solve_args(lvf_problem* p, Chain& c) {
     // landmark workgroups (about one workgroup of this launch fits a compute unit; a workgroup that has to wait for one starts after the
     // others are done), each owns whole keyframes, one thread per unknown.
     c.back_product = false; c.gride = GRide{}; c.gride.n = 0;
+    static const int n_cu = [] { int dev = 0, n = 0; return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }();
     if (solver_env().back_product && c.back_tail_merged && c.n_levels >= 1 && c.n_levels <= p->nb && p->ldG > 0) {
-      static const int n_cu = [] { int dev = 0, n = 0; return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }();
       const int room = n_cu - 2 - c.bt.g_lm;
       const int kpw = room >= 1 ? (p->n_kf + std::min(room, p->n_kf) - 1) / std::min(room, p->n_kf) : 0;
       const int n_nodes = p->sp_levels.first[c.n_levels - 1] + p->sp_levels.count[c.n_levels - 1];
@@ -355,11 +355,45 @@ static int chain_solve_args(lvf_problem* p, Chain& c) {
       c.tride = TRide{0, p->sp_T.p};
       c.back_blocks = true;
     }
+    // The merged last launch: block step nb - 1 and k_backsolve_tail as one (k_chol_backsolve_tail).  On where the back substitution is the
+    // dense-corner-only body on stored products (product and block forms), with the sub-block sweep; the batched chains, the chain-free re-run
+    // after a hand-over time-out and every other form keep the two launches.  The override tap changes nothing from the block steps on, so
+    // the form is the same with and without it.
+    c.chol_back_merged = false;
+    if (solver_env().chol_back_merge && c.back_tail_merged && c.back_product && c.back_blocks && p->nb >= 2 && solver_env().chol_subblock && !solver_env().back_tail_wgs_set) {
+      constexpr size_t kCbDynMax = 88 * 1024;       // beside the 66 560 B of panel buffers and the small static arrays of the bodies: 160 KB per workgroup
+      static const bool cb_lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_backsolve_tail), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCbDynMax) == hipSuccess;
+      LVF_TRY(p->x_last.ensure(kNB));
+      int* sync = reinterpret_cast<int*>(p->sp_sync.p);
+      CholBackArgs& m = c.cb;
+      m.chol = c.chol; m.tr = TRide{1, p->sp_T.p};
+      m.g = c.gride;                                // the G riders of launch nb - 1: level n_levels - nb (none when the levels ran out earlier)
+      const int glv = c.n_levels - p->nb;
+      if (glv >= 0) { m.g.first = p->sp_levels.first[glv]; m.g.n = p->sp_levels.count[glv]; } else m.g.n = 0;
+      // the flag shares the last int pair of the arrival-counter block with pose_ready (the levels use the first int of pairs 0 .. n_levels - 2),
+      // and is cleared with it at the end of every iteration
+      m.xl = XLast{p->x_last.p, sync + 2 * kSpMaxLevels - 1};
+      m.bt = c.bt;
+      m.bt.back.T = p->sp_T.p; m.bt.back.x_ready = sync + 2 * kSpMaxLevels - 1; m.bt.back.x_last = p->x_last.p; m.bt.back.x_timeout = bt_timeout; m.bt.back.x_fail = fail;
+      if (p->force_handover_timeouts > 1) { m.bt.back.x_ready = sync + 2 * kSpMaxLevels - 3; m.bt.back.x_timeout = 2000u; }      // test hook (n >= 2): a flag nobody raises
+      // one round: the two column workgroups, the back substitution, the riders, the pose workgroup and the G products leave the landmark
+      // pass the rest of the chip (50 keyframes: 256 - 54 = 202, and 157 workgroups hold 10 000 landmarks in their two early passes).  Where the
+      // landmarks need more, nothing depends on the fit: the riders wait for nothing and free their compute units within microseconds.
+      m.bt.g_lm = std::max(1, std::min(c.bt.g_lm, n_cu - (3 + m.g.n + 1 + m.bt.g_prod)));
+      // the G workgroups multiply rows that riders of this launch form: an arrival counter (a free odd int of the block: the levels count in the even ones)
+      m.g_arrive = sync + 2 * kSpMaxLevels - 5; m.bt.g_ready = sync + 2 * kSpMaxLevels - 5; m.bt.g_target = m.g.n;
+      // dynamic LDS: the dense-corner-only body (xs | x | partial | rhs), the landmark and pose workgroups' increments, a G workgroup's [x_dense | rows]
+      const size_t nx = (size_t)((p->ndense + kNB - 1) / kNB) * kNB;
+      c.cb_lds = std::max(std::max(((size_t)p->off + nx + (size_t)(kBParts + 1) * kNB) * sizeof(double), c.tail_lds),
+                          std::max((size_t)p->dp, (size_t)(p->ldG + 9 * m.bt.kpw)) * sizeof(double));
+      c.chol_back_merged = cb_lds_ok && c.cb_lds <= kCbDynMax;
+    }
     const bool chain_info = solver_env().chain_info;
     if (chain_info) std::fprintf(stderr, "chain: n_kf %d n_lm %d fast %d has_imu %d early %d compact %d levels %d no_chain %d merged_level0 %d back_tail_merged %d (g_lm %d, lds %zu) back_product %d (nb %d, %d G workgroups of %d keyframes)\n", p->n_kf, p->n_lm, (int)c.fast, (int)c.has_imu,
                                  (int)c.early, (int)p->compact, c.n_levels, (int)p->no_chain, (int)c.merged_level0, (int)c.back_tail_merged, c.bt.g_lm, c.bt_lds,
                                  (int)c.back_product, p->nb, c.bt.g_prod, c.bt.kpw);
-    if (chain_info) std::fprintf(stderr, "chain: back_blocks %d\n", (int)c.back_blocks);
+    if (chain_info) std::fprintf(stderr, "chain: back_blocks %d chol_back_merged %d (g_lm %d, %d G riders)\n", (int)c.back_blocks, (int)c.chol_back_merged, c.chol_back_merged ? c.cb.bt.g_lm : 0,
+                                 c.chol_back_merged ? c.cb.g.n : 0);
   }
   return LVF_OK;
 }
@@ -793,7 +827,8 @@ int enqueue_iteration(lvf_problem* p, bool end_zero, int fused) {
     LVF_CHAIN_LAUNCH(p, ST_SP_LEVELS, k_sp_eliminate, dim3(la.nblocks), dim3(256), c.sp_lds[lv], q, la);
   }
   stage_mark(p, ST_SP_LEVELS, std::max(0, c.n_levels - own0));
-  for (int kb = 0; kb < p->nb; ++kb) {
+  const int nb_own = c.chol_back_merged ? p->nb - 1 : p->nb;      // (merged last launch: block step nb - 1 runs inside k_chol_backsolve_tail)
+  for (int kb = 0; kb < nb_own; ++kb) {
     CholArgs cha = c.chol;
     if (solver_env().chol_timing) { LVF_TRY(p->dbg.ensure(128)); cha.dbg = p->dbg.p; }      // [0, 64): phases of 8 block steps; [64, 128): their sub-block stages
     GRide gr = c.gride;                                   // the riders that form G: the top level first, one level per launch
@@ -809,8 +844,16 @@ int enqueue_iteration(lvf_problem* p, bool end_zero, int fused) {
     const bool back_timing = solver_env().back_timing;
     if (back_timing) { LVF_TRY(p->dbg.ensure(64)); ba.sp.dbg = p->dbg.p; }
     if (c.back_blocks) ba.T = p->sp_T.p;
-    stage_mark(p, ST_CHOL, p->nb);
-    if (c.back_tail_merged) {
+    stage_mark(p, ST_CHOL, nb_own);
+    if (c.chol_back_merged) {
+      CholBackArgs cb = c.cb;
+      if (solver_env().chol_timing) cb.chol.dbg = p->dbg.p;      // (ensured above: nb_own >= 1)
+      if (back_timing) cb.bt.back.sp.dbg = p->dbg.p;
+      if (acc) cb.bt.tail.acc = *acc;
+      LVF_CHAIN_LAUNCH(p, ST_BACKSOLVE, k_chol_backsolve_tail, dim3(3 + cb.g.n + 1 + cb.bt.g_prod + cb.bt.g_lm), dim3(kBT), c.cb_lds, q, cb);
+      stage_mark(p, ST_BACKSOLVE, 1);
+      stage_mark(p, ST_STEP_TAIL, 0);
+    } else if (c.back_tail_merged) {
       BackTailArgs bt = c.bt;
       if (back_timing) bt.back.sp.dbg = p->dbg.p;
       bt.back.T = ba.T;
@@ -943,7 +986,7 @@ int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* radius, do
   if (p->dbg.p && solver_env().back_timing) {
     unsigned long long t[64];
     LVF_HIP(hipMemcpy(t, p->dbg.p, sizeof(t), hipMemcpyDeviceToHost));
-    std::fprintf(stderr, "backsolve phases (us):");
+    std::fprintf(stderr, p->chain && p->chain->chol_back_merged ? "backsolve phases inside the merged last launch (us: requests | x_last flag seen | x_last read | links .. | published):" : "backsolve phases (us):");
     for (unsigned long long k = 1; k < t[63] && k < 55; ++k) std::fprintf(stderr, " %.2f", (double)(t[k] - t[k - 1]) * 0.01);
     if (p->chain && p->chain->back_tail_merged)
       std::fprintf(stderr, " | merged launch, us after workgroup 0's start: step applied %.2f ; first landmark workgroup starts %.2f, sees the poses %.2f, done %.2f ; last one starts %.2f, sees %.2f, done %.2f",
@@ -953,6 +996,8 @@ int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* radius, do
     if (p->chain && p->chain->back_product)
       std::fprintf(stderr, " | product form (\"step applied\" = workgroup 0 done): first G workgroup starts %.2f, sees the flag %.2f, has the dense solution %.2f, its rows %.2f, applied %.2f",
                    (double)(t[40] - t[0]) * 0.01, (double)(t[41] - t[0]) * 0.01, (double)(t[42] - t[0]) * 0.01, (double)(t[43] - t[0]) * 0.01, (double)(t[44] - t[0]) * 0.01);
+    if (p->chain && p->chain->chol_back_merged)
+      std::fprintf(stderr, " | merged last launch: the first G workgroup sees the riders' arrivals %.2f, holds its share of G %.2f", (double)(t[45] - t[0]) * 0.01, (double)(t[46] - t[0]) * 0.01);
     std::fprintf(stderr, "\n");
   }
   out->cost_before = c.cost_before; out->cost_after = c.cost_after; out->model = c.model; out->dxnorm = c.dxnorm; out->xnorm = c.xnorm; out->gmax = c.gmax;

@@ -34,10 +34,13 @@ struct SolverEnv {
   bool back_product;          // LVF_BACK_PRODUCT     unless 0   sparse back substitution as one product with G (GRide)
   bool back_blocks;           // LVF_BACK_BLOCKS      unless 0   dense back substitution on stored block products T_kj (TRide)
   bool back_early;            // LVF_BACK_EARLY       unless 0   landmark and pose workgroups of k_backsolve_tail request their operands ahead of the wait
+  bool chol_back_merge;       // LVF_CHOL_BACK_MERGE  unless 0   the last block step and k_backsolve_tail as one launch (k_chol_backsolve_tail); 0: two launches (A/B)
   bool fused_lin;             // LVF_FUSED_LIN        unless 0   candidate pass linearises (k_lin_cost_decide, two accumulator sets)
   // ---- launch shapes (A/B)
   int tail_wgs;               // LVF_TAIL_WGS         640        cap on the landmark workgroups of k_step_tail
-  int back_tail_wgs;          // LVF_BACK_TAIL_WGS    224        cap on the landmark workgroups of k_backsolve_tail (at least 1)
+  int back_tail_wgs;          // LVF_BACK_TAIL_WGS    224        cap on the landmark workgroups of k_backsolve_tail (at least 1); set: that kernel's shape is
+                              //                                 the experiment, so k_chol_backsolve_tail (which sizes its own grid) stays off
+  bool back_tail_wgs_set;
   int cost_tiles;             // LVF_COST_TILES       2          tiles of kT blocks per workgroup of the candidate-cost pass
   size_t lin_lds_pad;         // LVF_LIN_LDS_PAD      0          bytes of dynamic LDS added to k_lin_visual (fewer workgroups per CU)
   int batch_band_rows;        // LVF_BATCH_BAND_ROWS  128        landmark rows per slice of a batch's band Schur complement
@@ -71,7 +74,8 @@ inline const SolverEnv& solver_env() {
     v.chain_timeout_ticks = (unsigned)std::max(1, num("LVF_CHAIN_TIMEOUT_US", 500)) * 100u;
     v.chain_rmw_read = set("LVF_CHAIN_RMW_READ");
     v.chol_subblock = unless0("LVF_CHOL_SUBBLOCK"); v.back_tail_merge = unless0("LVF_BACK_TAIL_MERGE"); v.back_product = unless0("LVF_BACK_PRODUCT");
-    v.back_blocks = unless0("LVF_BACK_BLOCKS"); v.back_early = unless0("LVF_BACK_EARLY"); v.fused_lin = unless0("LVF_FUSED_LIN");
+    v.back_blocks = unless0("LVF_BACK_BLOCKS"); v.back_early = unless0("LVF_BACK_EARLY"); v.chol_back_merge = unless0("LVF_CHOL_BACK_MERGE");
+    v.back_tail_wgs_set = set("LVF_BACK_TAIL_WGS"); v.fused_lin = unless0("LVF_FUSED_LIN");
     v.tail_wgs = num("LVF_TAIL_WGS", 640); v.back_tail_wgs = std::max(1, num("LVF_BACK_TAIL_WGS", 224)); v.cost_tiles = num("LVF_COST_TILES", 2);
     v.lin_lds_pad = (size_t)num("LVF_LIN_LDS_PAD", 0); v.batch_band_rows = num("LVF_BATCH_BAND_ROWS", 128); v.batch_transpose = num("LVF_BATCH_TRANSPOSE", 127);
     v.chain_info = set("LVF_CHAIN_INFO"); v.lm_history = set("LVF_LM_HISTORY"); v.configure_timing = set("LVF_CONFIGURE_TIMING");
@@ -115,6 +119,9 @@ struct Chain {
   bool back_product = false; GRide gride{};
   // the dense back substitution on stored block products T_kj, formed by riders of the block-step launches (TRide; LVF_BACK_BLOCKS=0 turns it off)
   bool back_blocks = false; TRide tride{};
+  // block step nb - 1 and k_backsolve_tail as ONE launch (k_chol_backsolve_tail; LVF_CHOL_BACK_MERGE=0 turns it off): on with the product and
+  // block forms, two or more blocks and the sub-block sweep; cb.bt is bt with a landmark grid sized so that the whole launch is one round
+  bool chol_back_merged = false; CholBackArgs cb{}; size_t cb_lds = 0;
   CostArgs cost{};
   DecideArgs dec{};
   // the fused chain (AccSel; LVF_FUSED_LIN=0 turns it off): the second accumulator set's pointers and the standby clears (k_tf_reduce: stand0
