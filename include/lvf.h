@@ -713,6 +713,44 @@ int lvf_navsat_optimize_bc(lvf_ctx* ctx, int n, int n_update, double* poses, con
 int lvf_navsat_fix_chain(lvf_ctx* ctx, int n, double* poses, const int32_t* has_fix, const double* fix_point, const double* cov, double huber_a,
                          const lvf_solver_options* o, double* x, int32_t* iterations, lvf_solver_summary* summary);
 
+/* ---- pose chain: block-tridiagonal Levenberg-Marquardt (Navsat::OptimizeAB, navsat.cpp:271-307; the chain of PoseGraph::BuildProblem) ----- */
+/* n poses [qx,qy,qz,qw,tx,ty,tz] in a row; pose 0 and pose n-1 are constant, the m = n - 2 poses between them are free under
+ * ProductParameterization(EigenQuaternion, Identity3) (6 unknowns each).  Residual blocks:
+ *   edge k (k = 0 .. n-2): PoseGraphError <6,7,7> between pose k and pose k+1 with rpyxyz_ = edge_target6[k], weight edge_weight[k], v edge_v[k],
+ *     no loss.  edge_target6 == NULL: every target is taken from the poses as they come, on the device (PoseGraphError(last_pose, pose));
+ *   one unary block per free pose i (unary_kind[i], entries 0 and n-1 are not read): LVF_CHAIN_NONE; LVF_CHAIN_T = TError <3,7>
+ *     r = w (t - p), p = unary_target4[i][0..3), under HuberLoss(huber_a) (huber_a <= 0: no loss); LVF_CHAIN_R = RError <4,7>
+ *     r = w (q - q0), q0 = unary_target4[i], no loss; w = unary_weight[i].
+ * The whole ceres::Solve is ONE launch of one workgroup: the declared trust-region loop of the other small solves (Jacobi scaling frozen at
+ * iteration 0, the clamped damping term, the order of the termination tests, five invalid steps in a row fail) around a linear solve by
+ * odd-even block cyclic reduction — the Cholesky factorisation of the odd-even permuted block-tridiagonal matrix, depth log2 m.  Costs are
+ * 1/2 sum rho, edges first, then unaries.  n == 2: the cost only, nothing moves.  A FAILURE (termination 2) leaves poses7 bit-equal to the
+ * input and still returns LVF_OK.  n < 2 or n - 2 > lvf_pose_chain_capacity(): LVF_ERR_INVALID. */
+#define LVF_CHAIN_NONE 0
+#define LVF_CHAIN_T 1
+#define LVF_CHAIN_R 2
+int lvf_pose_chain_capacity(void);      /* free poses one call takes (1022) */
+int lvf_pose_chain_solve(lvf_ctx* ctx, int n, double* poses7, const double* edge_target6, const double* edge_weight, const double* edge_v,
+                         const int32_t* unary_kind, const double* unary_target4, const double* unary_weight, double huber_a,
+                         const lvf_solver_options* o, lvf_solver_summary* summary);
+/* Debug / tests: ONE linearisation of the same problem at poses7 and ONE damped solve at `radius` with the Jacobi scaling of this
+ * linearisation; nothing is written back.  dx [6 (n-2)] (zero when *fail), *model = -dx.(g + H dx / 2) on the undamped blocks, *cost, *fail = 1
+ * when a pivot of the reduction was not positive (the numerical "invalid step"). */
+int lvf_pose_chain_debug_step(lvf_ctx* ctx, int n, const double* poses7, const double* edge_target6, const double* edge_weight, const double* edge_v,
+                              const int32_t* unary_kind, const double* unary_target4, const double* unary_weight, double huber_a, double radius,
+                              double* dx, double* model, double* cost, int32_t* fail);
+/* Debug / tests: the undamped normal equations of one linearisation: D [n-2][6][6] (diagonal blocks), O [n-3][6][6] (O[i] = the block in
+ * block-row i+1, block-column i), g [6 (n-2)] = J^T r. */
+int lvf_pose_chain_debug_system(lvf_ctx* ctx, int n, const double* poses7, const double* edge_target6, const double* edge_weight, const double* edge_v,
+                                const int32_t* unary_kind, const double* unary_target4, const double* unary_weight, double huber_a, double* D, double* O,
+                                double* g);
+/* Navsat::OptimizeAB (navsat.cpp:271-307) in ONE launch.  poses7 [n][7] = A, the keyframes of AB in time order, B; stamps [n]; fix_point [n][3]
+ * = what GetFixPoint returns for each keyframe of AB (entries 0 and n-1 are not read); relative_B7 = section.relative_B.  The launch's set-up
+ * phase replaces z of every fix by a B.z + (1 - a) A.z with a = (t - t_A) / (t_B - t_A), takes the edges PoseGraphError(last, frame, 1, 20)
+ * from the poses as they come and the last one as PoseGraphError(relative_B, 10, 20); TError has weight 1 under HuberLoss(huber_a). */
+int lvf_navsat_optimize_ab(lvf_ctx* ctx, int n, double* poses7, const double* stamps, const double* fix_point, const double* relative_B7, double huber_a,
+                           const lvf_solver_options* o, lvf_solver_summary* summary);
+
 /* ---- front-end tracking: utility.cpp optical_flow + triangulate, LocalMap::Triangulate, Frontend::TrackLastFrame --------------------------- */
 /* The semantics of cv::calcOpticalFlowPyrLK are DECLARED (tests/klt_ref.py): OpenCV's structure with floating-point interpolation,
  * not a bit pin against OpenCV.  Points are cv::Point2f = float[2]; images are 8-bit grey.

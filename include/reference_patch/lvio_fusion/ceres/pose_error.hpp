@@ -1,7 +1,8 @@
 // reference_patch/lvio_fusion/ceres/pose_error.hpp — shadows src/lvio_fusion/include/lvio_fusion/ceres/pose_error.hpp on the include path.
 // PoseGraphError::Create (:40-49, both overloads), PoseError::Create (:78-81), RError::Create (:103-106), PoseErrorRPZ::Create (:155-158) and
 // PoseErrorYXY::Create (:183-186) and RelocateRError::Create (:215-218: the blocks of Relocator::UpdateNewSubmap's rotation solve, which gpu::Solve
-// runs as ONE device launch, lvf_relocate_rotation_solve) return the MI355X library's tagged cost functions; TError keeps the reference's host class.
+// runs as ONE device launch, lvf_relocate_rotation_solve) return the MI355X library's tagged cost functions.  TError (:112-130) has no tagged twin: its
+// only site, Navsat::OptimizeAB, is replaced by hand with lvf_navsat_optimize_ab (navsat), which evaluates TError on the device.
 #pragma once
 #define PoseGraphError PoseGraphError_host
 #define PoseError PoseError_host

@@ -199,6 +199,15 @@ _SIGS = {
                                          C.POINTER(NavsatBcResult)]),
     "lvf_navsat_fix_chain": (C.c_int, [_VP, C.c_int, c_double_p, c_int_p, c_double_p, c_double_p, C.c_double, C.POINTER(SolverOptions), c_double_p, c_int_p,
                                        C.POINTER(SolverSummary)]),
+    "lvf_pose_chain_capacity": (C.c_int, []),
+    "lvf_pose_chain_solve": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_double,
+                                       C.POINTER(SolverOptions), C.POINTER(SolverSummary)]),
+    "lvf_pose_chain_debug_step": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_double,
+                                            C.c_double, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "lvf_pose_chain_debug_system": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.c_double,
+                                              c_double_p, c_double_p, c_double_p]),
+    "lvf_navsat_optimize_ab": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, C.POINTER(SolverOptions),
+                                         C.POINTER(SolverSummary)]),
     "lvf_image_create": (C.c_int, [_VP, c_u8_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(_VP)]),
     "lvf_image_destroy": (C.c_int, [_VP]),
     "lvf_image_size": (C.c_int, [_VP, c_int_p, c_int_p, c_int_p]),

@@ -331,9 +331,92 @@ def navsat_quick_fix(ctx, poses, has_fix, fix_point, cov, bc_opt, between=None):
 
 
 def navsat_optimize(ctx, poses, has_fix, fix_point, cov, bc_opt, optimize_ab):
-    """Navsat::Optimize (navsat.cpp:135-156): OptimizeBC(B, C, mode 0), the caller's OptimizeAB (a callable handed the pose array; it stays on
-    the host: INTEGRATION.md), then the per-keyframe chain."""
+    """Navsat::Optimize (navsat.cpp:135-156): OptimizeBC(B, C, mode 0), the caller's OptimizeAB (a callable handed the pose array, run on
+    the host; navsat_optimize_section runs that step on the device), then the per-keyframe chain."""
     return navsat_quick_fix(ctx, poses, has_fix, fix_point, cov, bc_opt, between=optimize_ab)
+
+
+CHAIN_NONE, CHAIN_T, CHAIN_R = 0, 1, 2
+
+
+def pose_chain_capacity():
+    return int(_lib.lib().lvf_pose_chain_capacity())
+
+
+def _chain_args(poses, edge_target, edge_weight, edge_v, unary_kind, unary_target, unary_weight):
+    n = poses.size // 7
+    tg = None if edge_target is None else _d(edge_target).reshape(-1, 6)
+    ew, ev, uk, ut, uw = _d(edge_weight).ravel(), _d(edge_v).ravel(), _i(unary_kind).ravel(), _d(unary_target).reshape(-1, 4), _d(unary_weight).ravel()
+    m1 = max(n - 1, 0)
+    if not ((tg is None or tg.shape[0] == m1) and ew.size == m1 and ev.size == m1 and uk.size == n and ut.shape[0] == n and uw.size == n):
+        raise ValueError("pose chain: edge arrays have n - 1 entries, unary arrays n")
+    keep = (tg, ew, ev, uk, ut, uw)
+    return n, keep, (_dp(tg) if tg is not None else None, _dp(ew), _dp(ev), _ip(uk), _dp(ut), _dp(uw))
+
+
+def pose_chain_solve(ctx, poses, edge_target, edge_weight, edge_v, unary_kind, unary_target, unary_weight, huber_a=0.0, opt=None):
+    """The pose-chain solve (lvf_pose_chain_solve) on the host array `poses` ([n][7], both ends constant), updated IN PLACE.  edge_target
+    [n-1][6] or None (taken from the poses as they come), edge_weight / edge_v [n-1]; unary_kind [n] (CHAIN_NONE / CHAIN_T / CHAIN_R),
+    unary_target [n][4] (p3 or q4), unary_weight [n].  Returns SolverSummary."""
+    if not (isinstance(poses, np.ndarray) and poses.dtype == np.float64 and poses.flags.c_contiguous):
+        raise TypeError("poses must be a C-contiguous float64 array (it is updated in place)")
+    n, keep, ptrs = _chain_args(poses, edge_target, edge_weight, edge_v, unary_kind, unary_target, unary_weight)
+    opt = opt or default_solver_options()
+    summ = _lib.SolverSummary()
+    _chk(ctx.L.lvf_pose_chain_solve(ctx.h, n, _dp(poses), *ptrs, C.c_double(huber_a), C.byref(opt), C.byref(summ)))
+    return summ
+
+
+def pose_chain_debug_step(ctx, poses, edge_target, edge_weight, edge_v, unary_kind, unary_target, unary_weight, huber_a, radius):
+    """One linearisation at `poses` and one damped solve at `radius` (Jacobi scaling from this linearisation); nothing is written back.
+    Returns dict(dx [6 (n-2)], model, cost, fail)."""
+    P = _d(poses)
+    n, keep, ptrs = _chain_args(P, edge_target, edge_weight, edge_v, unary_kind, unary_target, unary_weight)
+    dx = np.zeros(6 * max(n - 2, 0))
+    model, cost, fail = C.c_double(), C.c_double(), C.c_int32()
+    _chk(ctx.L.lvf_pose_chain_debug_step(ctx.h, n, _dp(P), *ptrs, C.c_double(huber_a), C.c_double(radius), _dp(dx), C.byref(model), C.byref(cost), C.byref(fail)))
+    return dict(dx=dx, model=model.value, cost=cost.value, fail=bool(fail.value))
+
+
+def pose_chain_debug_system(ctx, poses, edge_target, edge_weight, edge_v, unary_kind, unary_target, unary_weight, huber_a=0.0):
+    """The undamped normal equations of one linearisation: D [m][6][6], O [m-1][6][6] (block-row i+1, block-column i), g [6 m]; m = n - 2."""
+    P = _d(poses)
+    n, keep, ptrs = _chain_args(P, edge_target, edge_weight, edge_v, unary_kind, unary_target, unary_weight)
+    m = max(n - 2, 0)
+    D, O, g = np.zeros((m, 6, 6)), np.zeros((max(m - 1, 0), 6, 6)), np.zeros(6 * m)
+    _chk(ctx.L.lvf_pose_chain_debug_system(ctx.h, n, _dp(P), *ptrs, C.c_double(huber_a), _dp(D), _dp(O), _dp(g)))
+    return D, O, g
+
+
+def navsat_optimize_ab(ctx, poses, stamps, fix_point, relative_B, huber_a=0.1, opt=None):
+    """Navsat::OptimizeAB on the host array `poses` ([n][7] = A, the keyframes of AB, B), updated IN PLACE; stamps [n], fix_point [n][3] (what
+    GetFixPoint returns; the entries of A and B are not read), relative_B [7].  Returns SolverSummary."""
+    if not (isinstance(poses, np.ndarray) and poses.dtype == np.float64 and poses.flags.c_contiguous):
+        raise TypeError("poses must be a C-contiguous float64 array (it is updated in place)")
+    n = poses.size // 7
+    t, f, rb = _d(stamps).ravel(), _d(fix_point).reshape(-1, 3), _d(relative_B).ravel()
+    if not (t.size == n and f.shape[0] == n and rb.size == 7):
+        raise ValueError("navsat_optimize_ab: stamps / fix_point must have one entry per pose, relative_B seven numbers")
+    opt = opt or default_solver_options()
+    summ = _lib.SolverSummary()
+    _chk(ctx.L.lvf_navsat_optimize_ab(ctx.h, n, _dp(poses), _dp(t), _dp(f), _dp(rb), C.c_double(huber_a), C.byref(opt), C.byref(summ)))
+    return summ
+
+
+def navsat_optimize_section(ctx, poses_ab, stamps_ab, fix_ab, relative_B, poses_bc, has_fix, fix_point, cov, bc_opt):
+    """Navsat::Optimize (navsat.cpp:135-156) entirely on the device: OptimizeBC(B .. C, mode 0), OptimizeAB, then the per-keyframe chain.
+    poses_ab [na][7] = A, the keyframes of AB, B — its last row is overwritten with B as OptimizeBC leaves it (B is poses_bc[0]); na < 3 or
+    None: A == B, no OptimizeAB.  The other arguments are those of navsat_optimize_ab and navsat_quick_fix; both pose arrays are updated in
+    place.  Returns (NavsatBcResult, summary of AB or None, x, iterations, chain summary)."""
+    ab = []
+
+    def between(poses):
+        if poses_ab is not None and poses_ab.size // 7 >= 3:
+            poses_ab.reshape(-1, 7)[-1] = poses.reshape(-1, 7)[0]
+            ab.append(navsat_optimize_ab(ctx, poses_ab, stamps_ab, fix_ab, relative_B, bc_opt.huber_a, bc_opt.solver))
+
+    res, x, it, summ = navsat_quick_fix(ctx, poses_bc, has_fix, fix_point, cov, bc_opt, between=between)
+    return res, (ab[0] if ab else None), x, it, summ
 
 
 def _gray(gray, who):
