@@ -1,6 +1,6 @@
 // loop_dev.hpp — device pieces shared by the loop-correction tail (loop_kernels.hip), the GNSS alignment (navsat_kernels.hip) and the visual
 // relocalisation (reloc_kernels.hip), which all reach it through small_lm.hpp: the workgroup sum of one value (the candidate cost and the
-// line search of lm_small, the roll pre-solve's vector sum, the inlier count), the body of PoseGraph::ForwardUpdate
+// line search of lm_small, the roll pre-solve's vector sum, the inlier count) and its maximum (the pose chain's gradient norm), the body of PoseGraph::ForwardUpdate
 // (src/lvio_fusion/src/pose_graph.cpp:245-252) and the Sophus SE3 operations built from the same arithmetic (Hamilton product re-normalised;
 // vectors through Eigen's _transformVector).
 #pragma once
@@ -20,6 +20,16 @@ __device__ __forceinline__ double wg_sum(double v, double* red) {
 #pragma unroll
   for (int k = 0; k < kLT / 64; ++k) s += red[k];
   return s;
+}
+
+// the largest `v` of the workgroup of kLT threads; every thread returns it (two barriers)
+__device__ __forceinline__ double wg_max(double v, double* red) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
 
 // Eigen QuaternionBase::_transformVector with the quaternion (ux, uy, uz, uw) taken as it is: uv = 2 u x v ; v + w uv + u x uv

@@ -7,9 +7,9 @@
 //
 // n poses, pose 0 and pose n-1 constant, m = n - 2 free poses of 6 tangent unknowns each (EigenQuaternionParameterization (+) Identity(3)).
 // The normal equations are block tridiagonal: D_i (6 x 6) on the diagonal, O_i = the block in block-row i+1, block-column i.  The whole
-// ceres::Solve is ONE launch of one workgroup of kLT threads; the loop is the declared one of small_lm.hpp (lm_small) written for a run-time
-// m: Jacobi scaling frozen at iteration 0, the clamped damping term, the same order of the termination tests, five invalid steps in a row
-// fail, a FAILURE leaves the poses as they came.  tests/pose_chain_ref.py restates it on the host.
+// ceres::Solve is ONE launch of one workgroup of kLT threads over the trust-region rule of small_lm.hpp (LmState, the one lm_small runs; the
+// restatements left outside it are named there).  What the chain brings: the sums, the block-tridiagonal solve, x (+) dx and the norms over
+// a run-time m; Jacobi scaling frozen at iteration 0, a FAILURE leaves the poses as they came.  tests/pose_chain_ref.py restates it on the host.
 //
 // The linear solve is odd-even block cyclic reduction: level l (stride s = 2^l) eliminates the rows e = (2j+1) s - 1 at once — they are
 // independent of one another — into their neighbours e - s and e + s, which form the next level's chain.  Operation for operation this is
@@ -51,28 +51,6 @@ struct ChainArgs {
   double* W;                 // [m][kRowW] when the working set is not in LDS
   ChainRec* rec;
 };
-
-// EigenQuaternionParameterization::Plus (q_delta * q) (+) Identity(3): the arithmetic of the pose-only refinement (reloc_kernels.hip pose_plus)
-__device__ __forceinline__ void chain_pose_plus(const double* x, const double* dl, double* o) {
-  const double nd = sqrt(dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2]);
-  if (nd == 0.0) { o[0] = x[0]; o[1] = x[1]; o[2] = x[2]; o[3] = x[3]; }
-  else {
-    const double k = sin(nd) / nd;
-    const double ax = k * dl[0], ay = k * dl[1], az = k * dl[2], aw = cos(nd), bx = x[0], by = x[1], bz = x[2], bw = x[3];
-    o[0] = aw * bx + ax * bw + ay * bz - az * by; o[1] = aw * by + ay * bw + az * bx - ax * bz; o[2] = aw * bz + az * bw + ax * by - ay * bx;
-    o[3] = aw * bw - ax * bx - ay * by - az * bz;
-  }
-  o[4] = x[4] + dl[3]; o[5] = x[5] + dl[4]; o[6] = x[6] + dl[5];
-}
-
-__device__ __forceinline__ double wg_max(double v, double* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
 
 // rows [6][7] of an ambient Jacobian -> [6][6] local: the quaternion columns through the plus-Jacobian at q, the translation columns as they are
 __device__ __forceinline__ void rows_to_local(const double* J7, const double* q, double* L) {
@@ -202,8 +180,7 @@ __device__ __forceinline__ double chain_linearize(const ChainArgs& a, const doub
       double h = Dl[7 * c];
       if (first) a.h0[6 * f + c] = h;
       else h = a.h0[6 * f + c];
-      const double sj = 1.0 / (1.0 + sqrt(h)), s2 = sj * sj;
-      Dl[7 * c] += fmin(fmax(Dl[7 * c] * s2, 1e-6), 1e32) / s2 / radius;
+      Dl[7 * c] += lm_damping(Dl[7 * c], h) / radius;
     }
 #pragma unroll
     for (int i = 0; i < 36; ++i) row[i] = Dl[i];
@@ -408,6 +385,15 @@ __device__ __forceinline__ double chain_model(const ChainArgs& a, const double* 
   return wg_sum(part, tile);
 }
 
+// The damped solve of the system chain_linearize left in W, and the model decrease of its step; `failed`: a pivot was not positive, dx = 0
+__device__ __forceinline__ double chain_step(const ChainArgs& a, double* W, int* s_fail, double* tile, int& failed) {
+  chain_reduce(a.m, W, s_fail);
+  failed = *s_fail;
+  __syncthreads();                                   // every thread has read the flag
+  if (threadIdx.x == 0) *s_fail = 0;
+  return failed ? 0.0 : chain_model(a, W, tile);
+}
+
 template <bool IN_LDS>
 __global__ __launch_bounds__(kLT) void k_pose_chain(ChainArgs a) {
   extern __shared__ double chain_lds[];
@@ -452,82 +438,52 @@ __global__ __launch_bounds__(kLT) void k_pose_chain(ChainArgs a) {
   if (tid == 0) s_fail = 0;
   __syncthreads();
 
+  // mode 2 is one linearisation, mode 1 one linearisation and one damped solve at a.radius, mode 0 the loop; all three end the same way
   const LmOpts& o = a.o;
-  double radius = a.mode == 1 ? a.radius : o.radius0, decrease = 2.0, cost = 0.0, initial_cost = 0.0, model = 0.0;
-  int iters = 0, successes = 0, termination = 1, why = LVF_WHY_MAX_ITERATIONS, invalid_run = 0, failed = 0;
-  bool first = true;
+  LmState s(a.mode == 1 ? a.radius : o.radius0);
+  double model = 0.0, gn;
+  int failed = 0;
   double *Xp = a.X, *Xc = a.XC;
-  if (m == 0) {                                      // no free pose: the problem has a cost and no unknown
-    cost = chain_cost(a, a.X, tile);
-    initial_cost = cost; termination = 0; why = LVF_WHY_NONE;
-  } else for (;;) {
-    double gn;
-    cost = chain_linearize(a, Xp, W, radius, first, tile, gn);
-    if (first) { initial_cost = cost; first = false; }      // Jacobi scaling: iteration 0, frozen
-    if (a.mode == 2) { termination = 0; why = LVF_WHY_NONE; break; }
-    if (a.mode == 0) {
-      if (iters >= o.max_iters) { termination = 1; why = LVF_WHY_MAX_ITERATIONS; break; }
-      if (gn <= o.gradient_tol) { termination = 0; why = LVF_WHY_GRADIENT; break; }
-      if (radius < 1e-32) { termination = 0; why = LVF_WHY_MIN_RADIUS; break; }
-    }
-    chain_reduce(m, W, &s_fail);
-    failed = s_fail;
-    __syncthreads();                                 // every thread has read the flag
-    if (tid == 0) s_fail = 0;
-    model = failed ? 0.0 : chain_model(a, W, tile);  // a failed factor: dx = 0
+  if (m == 0) s.linearized(chain_cost(a, a.X, tile));       // no free pose: the problem has a cost and no unknown
+  else if (a.mode != 0) {
+    s.linearized(chain_linearize(a, Xp, W, s.radius, true, tile, gn));
     if (a.mode == 1) {
+      model = chain_step(a, W, &s_fail, tile, failed);
       for (int f = tid; f < m; f += kLT) {
 #pragma unroll
         for (int c = 0; c < 6; ++c) a.dx[6 * f + c] = failed ? 0.0 : W[(size_t)kRowW * f + 108 + c];
       }
-      termination = 0; why = LVF_WHY_NONE; break;
     }
-    if (!(!failed && model > 0.0)) {                 // invalid step
-      ++iters;
-      if (++invalid_run >= 5) { termination = 2; why = LVF_WHY_INVALID_STEPS; break; }
-      radius *= 0.5;
-      continue;
-    }
-    invalid_run = 0;
+  } else for (;;) {
+    s.linearized(chain_linearize(a, Xp, W, s.radius, s.first, tile, gn));      // (Jacobi scaling: iteration 0, frozen)
+    if (s.top(o, gn)) break;
+    model = chain_step(a, W, &s_fail, tile, failed);
+    if (!s.valid_step(!failed, model)) { if (s.invalid_step()) break; continue; }
     double sn2 = 0.0, xn2 = 0.0;                     // over the ambient coordinates of the free poses
     for (int f = tid; f < m; f += kLT) {
       const double* x = Xp + 7 * (f + 1);
       double dl[6], xc[7];
 #pragma unroll
       for (int c = 0; c < 6; ++c) dl[c] = W[(size_t)kRowW * f + 108 + c];
-      chain_pose_plus(x, dl, xc);
+      pose_plus(x, dl, xc);
 #pragma unroll
       for (int c = 0; c < 7; ++c) { Xc[7 * (f + 1) + c] = xc[c]; sn2 += (xc[c] - x[c]) * (xc[c] - x[c]); xn2 += x[c] * x[c]; }
     }
     sn2 = wg_sum(sn2, tile); xn2 = wg_sum(xn2, tile);
-    if (sqrt(sn2) <= o.parameter_tol * (sqrt(xn2) + o.parameter_tol)) { termination = 0; why = LVF_WHY_PARAMETER; break; }
+    if (s.parameter_tol(o, sn2, xn2)) break;
     const double cand = chain_cost(a, Xc, tile);
-    if (fabs(cost - cand) <= o.function_tol * cost) { termination = 0; why = LVF_WHY_FUNCTION; break; }
-    ++iters;
-    const double rho = (cost - cand) / model;
-    if (rho > o.min_rel_decrease) {
-      double* t2 = Xp; Xp = Xc; Xc = t2;             // the candidate becomes the iterate (the constant ends are in both)
-      cost = cand; ++successes;
-      const double t = 2.0 * rho - 1.0;
-      radius = fmin(radius / fmax(1.0 / 3.0, 1.0 - t * t * t), 1e16); decrease = 2.0;
-    } else { radius /= decrease; decrease *= 2.0; }
+    if (s.function_tol(o, cand)) break;
+    if (s.accept(o, cand, model)) { double* t2 = Xp; Xp = Xc; Xc = t2; }      // the candidate becomes the iterate (the constant ends are in both)
   }
-  if (termination == 2 || !isfinite(cost)) {         // fail soft: the poses stay as they came
-    termination = 2; cost = initial_cost;
+  const double* out = s.failed() ? a.in : Xp;        // fail soft: the poses stay as they came
+  if (out != a.X) {                                  // the host reads a.X
     for (int i = tid; i < n; i += kLT) {
 #pragma unroll
-      for (int c = 0; c < 7; ++c) a.X[7 * i + c] = a.in[7 * i + c];
-    }
-  } else if (Xp != a.X) {                            // the host reads a.X
-    for (int i = tid; i < n; i += kLT) {
-#pragma unroll
-      for (int c = 0; c < 7; ++c) a.X[7 * i + c] = Xp[7 * i + c];
+      for (int c = 0; c < 7; ++c) a.X[7 * i + c] = out[7 * i + c];
     }
   }
   if (tid == 0) {
-    LmRec& r = a.rec->lm;
-    r.initial_cost = initial_cost; r.final_cost = cost; r.iters = iters; r.successes = successes; r.termination = termination; r.why = why;
-    r.contractions = 0; r.pad = 0;
+    s.fill(a.rec->lm);
     a.rec->model = model; a.rec->fail = failed; a.rec->pad = 0;
   }
 }

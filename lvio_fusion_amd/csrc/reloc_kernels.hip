@@ -340,19 +340,6 @@ __global__ void __launch_bounds__(kRT) k_pnp_score(PnpArgs a, unsigned long long
 }
 
 // ---- selection and refinement ---------------------------------------------------------------------------------------------------------------
-// EigenQuaternionParameterization::Plus (q_delta * q) (+) Identity(3)
-__device__ __forceinline__ void pose_plus(const double x[7], const double dl[6], double o[7]) {
-  const double nd = sqrt(dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2]);
-  if (nd == 0.0) { o[0] = x[0]; o[1] = x[1]; o[2] = x[2]; o[3] = x[3]; }
-  else {
-    const double k = sin(nd) / nd;
-    const double ax = k * dl[0], ay = k * dl[1], az = k * dl[2], aw = cos(nd), bx = x[0], by = x[1], bz = x[2], bw = x[3];
-    o[0] = aw * bx + ax * bw + ay * bz - az * by; o[1] = aw * by + ay * bw + az * bx - ax * bz; o[2] = aw * bz + az * bw + ax * by - ay * bx;
-    o[3] = aw * bw - ax * bx - ay * by - az * bz;
-  }
-  o[4] = x[4] + dl[3]; o[5] = x[5] + dl[4]; o[6] = x[6] + dl[5];
-}
-
 // lm_small's problem (small_lm.hpp): LocalMap::LocalBA's pose-only blocks on the matches the LDS mask s_in marks, 1/2 sum rho(|r|^2) under
 // HuberLoss; 7 ambient coordinates, 6 tangent unknowns
 struct PoseOnInliers {
