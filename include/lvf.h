@@ -1095,6 +1095,30 @@ int lvf_window_counts(const lvf_window* w, int32_t* counts8);
  * kind.  What tests compare with Backend::BuildProblem's own output (backend.cpp:96-183).  Not part of the reference surface. */
 int lvf_window_debug_blocks(lvf_window* w, int kind, int capacity, int64_t* ids, double* vals, int* n);
 
+/* ---- Marginal information and covariance of selected keyframe unknowns (what ceres::Covariance answers for a few parameter blocks).
+ * For the reduced (Schur) system S over the keyframe unknowns — order of lvf_problem_download_reduced: [pose tangent 6 x n_kf | (v, ba, bg)
+ * 9 x n_kf], d = 15 n_kf — and a selection s of m <= 120 unknowns with r the rest:
+ *     info = S_ss - S_sr S_rr^-1 S_rs     (what marginalising the rest leaves as a prior on s)
+ *     cov  = info^-1 = (S^-1)_ss
+ * both [m x m] row-major, row i belonging to sel[i], exactly symmetric; either pointer may be NULL, not both.  S is the UNDAMPED Gauss-Newton
+ * matrix J^T J of the robustified tangent-space Jacobian at the current state, pose priors included.  An unknown whose Jacobian column is
+ * identically zero (a constant pose or (v, ba, bg) block, one no factor touches: S_jj == 0 exactly, never a threshold) is ABSENT: it is left
+ * out of the system and its rows and columns of both outputs are zero.
+ * Stats: fail = 0, or 1 + kb of the 64-column block step of the elimination of the rest that met a non-positive or NaN pivot (rest unknowns in
+ * ascending order, absent ones keeping their place), or one past the last such step for a pivot inside the selection; n_present + n_absent =
+ * d; min_pivot_ratio = the smallest L_jj^2 / S_jj over the present unknowns, in (0, 1]: a conditioning indicator for the caller to gate on
+ * (the library applies no threshold).  A numeric failure is soft: LVF_OK, fail != 0, info / cov untouched, min_pivot_ratio unspecified.
+ * Argument errors (m outside 1 .. 120, an index out of range or twice, both outputs NULL): LVF_ERR_INVALID before anything reaches the device. */
+typedef struct { int fail, n_present, n_absent; double min_pivot_ratio; } lvf_marginal_stats;
+/* The linear algebra alone on a caller's matrix: S [d x d] row-major, only the lower triangle is read; absent iff S_jj == 0. */
+int lvf_marginal_dense(lvf_ctx* ctx, const double* S, int d, const int* sel, int m, double* info, double* cov, lvf_marginal_stats* stats);
+/* Of keyframes kfs[n_sel] (1 .. 8, distinct) of a problem: m = 15 n_sel, each keyframe's unknowns in the order [pose 6, v 3, ba 3, bg 3].
+ * Linearises at the current state with o->huber_a and assembles the undamped reduced system; the state, the step of the last iteration and a
+ * debug override are left alone, and the next iteration computes what it would have computed without the call. */
+int lvf_problem_marginal(lvf_problem* p, const lvf_solver_options* o, const int* kfs, int n_sel, double* info, double* cov, lvf_marginal_stats* stats);
+/* The same for the persistent window, by keyframe id: the window's problem is refreshed as lvf_window_solve refreshes it, without iterating. */
+int lvf_window_marginal(lvf_window* w, const lvf_solver_options* o, const int64_t* kf_ids, int n_sel, double* info, double* cov, lvf_marginal_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,10 @@ class LidarDepthOptions(C.Structure):
                 ("min_det", C.c_double), ("max_extrapolation", C.c_double), ("far_factor", C.c_double), ("replace_lost", C.c_int)]
 
 
+class MarginalStats(C.Structure):
+    _fields_ = [("fail", C.c_int), ("n_present", C.c_int), ("n_absent", C.c_int), ("min_pivot_ratio", C.c_double)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into liblvf_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".hpp"))]
@@ -378,6 +382,9 @@ _SIGS = {
     "lvf_problem_solve": (C.c_int, [_VP, C.POINTER(SolverOptions), C.POINTER(SolverSummary)]),
     "lvf_problem_reduced_dim": (C.c_int, [_VP]),
     "lvf_problem_download_reduced": (C.c_int, [_VP, c_double_p, c_double_p]),
+    "lvf_marginal_dense": (C.c_int, [_VP, c_double_p, C.c_int, c_int_p, C.c_int, c_double_p, c_double_p, C.POINTER(MarginalStats)]),
+    "lvf_problem_marginal": (C.c_int, [_VP, C.POINTER(SolverOptions), c_int_p, C.c_int, c_double_p, c_double_p, C.POINTER(MarginalStats)]),
+    "lvf_window_marginal": (C.c_int, [_VP, C.POINTER(SolverOptions), C.POINTER(C.c_int64), C.c_int, c_double_p, c_double_p, C.POINTER(MarginalStats)]),
 }
 
 

@@ -1388,6 +1388,15 @@ class Window:
         _chk(self.ctx.L.lvf_window_debug_blocks(self.h, int(kind), n.value, ids.ctypes.data_as(C.c_void_p), _dp(vals), C.byref(n)))
         return ids[:n.value], vals[:n.value]
 
+    def marginal(self, opt, kf_ids):
+        """(info, cov, stats) of the keyframes with ids `kf_ids` (1 .. 8) at the window's current state (lvf_window_marginal): the layout of
+        Problem.marginal."""
+        ids = np.ascontiguousarray(kf_ids, dtype=np.int64).ravel()
+        m = 15 * ids.size
+        info, cov, st = np.empty((m, m)), np.empty((m, m)), _lib.MarginalStats()
+        _chk(self.ctx.L.lvf_window_marginal(self.h, C.byref(opt), ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), _dp(info), _dp(cov), C.byref(st)))
+        return _marginal_result(info, cov, st)
+
     def counts(self):
         c = np.zeros(8, np.int32)
         _chk(self.ctx.L.lvf_window_counts(self.h, _ip(c)))
@@ -1468,6 +1477,24 @@ def fail_codes():
 def debug_landmark_window():
     """entries of a landmark's E band (from its 16-aligned start) requested before the wait for the pose increments (lvf_debug_landmark_window)"""
     return int(_lib.lib().lvf_debug_landmark_window())
+
+
+def _marginal_result(info, cov, st):
+    stats = dict(fail=int(st.fail), n_present=int(st.n_present), n_absent=int(st.n_absent), min_pivot_ratio=float(st.min_pivot_ratio))
+    return (info, cov, stats) if st.fail == 0 else (None, None, stats)
+
+
+def marginal_dense(ctx, S, sel):
+    """(info, cov, stats) of the unknowns `sel` (at most 120, distinct, any order) of the symmetric system S [d x d] (lower triangle read;
+    S_jj == 0 marks unknown j absent): info = S_ss - S_sr S_rr^-1 S_rs, cov = info^-1 = (S^-1)_ss, row i for sel[i] (lvf_marginal_dense).
+    After a numeric failure (stats["fail"] != 0) both matrices are None."""
+    S, s = _d(S), _i(sel).ravel()
+    if S.ndim != 2 or S.shape[0] != S.shape[1]:
+        raise ValueError(f"marginal_dense: S {S.shape} is not square")
+    m = max(int(s.size), 1)
+    info, cov, st = np.empty((m, m)), np.empty((m, m)), _lib.MarginalStats()
+    _chk(ctx.L.lvf_marginal_dense(ctx.h, _dp(S), int(S.shape[0]), _ip(s), int(s.size), _dp(info), _dp(cov), C.byref(st)))
+    return _marginal_result(info, cov, st)
 
 
 def default_solver_options():
@@ -1575,6 +1602,15 @@ class Problem:
         S = np.empty((d, d)); rhs = np.empty(d)
         _chk(self.ctx.L.lvf_problem_download_reduced(self.h, _dp(S), _dp(rhs)))
         return S, rhs
+
+    def marginal(self, opt, kfs):
+        """(info, cov, stats) of keyframes `kfs` (1 .. 8 positions) at the current state: [15 n x 15 n] each, a keyframe's unknowns in the order
+        [pose 6, v 3, ba 3, bg 3] (lvf_problem_marginal).  After a numeric failure (stats["fail"] != 0) both matrices are None."""
+        k = _i(kfs).ravel()
+        m = 15 * k.size
+        info, cov, st = np.empty((m, m)), np.empty((m, m)), _lib.MarginalStats()
+        _chk(self.ctx.L.lvf_problem_marginal(self.h, C.byref(opt), _ip(k), int(k.size), _dp(info), _dp(cov), C.byref(st)))
+        return _marginal_result(info, cov, st)
 
     def close(self):
         if self.h:

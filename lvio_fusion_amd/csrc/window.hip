@@ -1389,5 +1389,26 @@ int lvf_window_debug_blocks(lvf_window* w, int kind, int capacity, int64_t* ids,
   return LVF_OK;
 }
 
+// Marginal information / covariance of keyframes of the window (marginal_kernels.hip).  The window's problem is brought up to date by the
+// code path of lvf_window_solve itself, asked for no iteration (it assembles the block lists, configures the problem, evaluates the cost and
+// copies the unchanged state back), then the problem's entry does the rest with the ids translated to positions.
+int lvf_window_marginal(lvf_window* w, const lvf_solver_options* o, const int64_t* kf_ids, int n_sel, double* info, double* cov, lvf_marginal_stats* stats) {
+  LVF_REQUIRE(w && o && kf_ids && stats, "lvf_window_marginal: null argument");
+  LVF_REQUIRE(info || cov, "lvf_window_marginal: info and cov are both NULL");
+  LVF_REQUIRE(n_sel >= 1 && n_sel <= 8, "lvf_window_marginal: %d keyframes selected (1 .. 8)", n_sel);
+  int kfs[8];
+  for (int i = 0; i < n_sel; ++i) {
+    const auto it = w->kf_index.find(kf_ids[i]);
+    LVF_REQUIRE(it != w->kf_index.end(), "lvf_window_marginal: keyframe %lld is not in the window", (long long)kf_ids[i]);
+    kfs[i] = it->second;
+    for (int j = 0; j < i; ++j) LVF_REQUIRE(kfs[j] != kfs[i], "lvf_window_marginal: keyframe %lld listed twice", (long long)kf_ids[i]);
+  }
+  lvf_solver_options refresh = *o;
+  refresh.max_num_iterations = 0;
+  lvf_solver_summary summary;
+  LVF_TRY(lvf_window_solve(w, &refresh, &summary));
+  return lvf_problem_marginal(w->prob, o, kfs, n_sel, info, cov, stats);
+}
+
 }  // extern "C"
 

@@ -122,6 +122,14 @@ def detect_loop_by_position(positions_xy, ids, query_xy, threshold):
     return ids[int(near[0])]
 
 
+def position_gate(cov, k_sigma=3.0):
+    """The radius of the k_sigma position ellipsoid of a keyframe: k_sigma times the square root of the largest eigenvalue of the translation part
+    (tangent entries 3..5 of the pose block) of its marginal covariance `cov` (the first 6 x 6, or the whole 15 x 15, of Problem.marginal /
+    Window.marginal for that keyframe).  A `threshold` for detect_loop_by_position that grows with the drift instead of a constant."""
+    t = np.asarray(cov, np.float64)[3:6, 3:6]
+    return float(k_sigma) * float(np.sqrt(max(np.linalg.eigvalsh(0.5 * (t + t.T))[-1], 0.0)))
+
+
 def detect_loop_by_scan(db, cloud, stamp, min_age=30.0, k=5, max_distance=0.5):
     """The appearance gate beside it: the k best Scan Context matches of the sensor-frame `cloud` among the entries of `db`
     (api.ScanContextDb) at least min_age seconds older than `stamp` (relocator.cpp:92 looks among keyframes older than frame->time - 30); returns
