@@ -20,56 +20,6 @@
 
 namespace lvf {
 
-// ---- SE3 / rpyxyz on device: the same formulas as host_se3.hpp (Sophus SE3d product / inverse on unit quaternions, utility.cpp:27-40)
-namespace dse3 {
-__device__ inline void normalize4(double q[4]) {
-  const double s = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  for (int k = 0; k < 4; ++k) q[k] *= s;
-}
-__device__ inline void rotate(const double q_in[4], const double p[3], double o[3]) {
-  double q[4] = {q_in[0], q_in[1], q_in[2], q_in[3]};
-  normalize4(q);
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double cx = y * p[2] - z * p[1], cy = z * p[0] - x * p[2], cz = x * p[1] - y * p[0];
-  const double dx = y * cz - z * cy, dy = z * cx - x * cz, dz = x * cy - y * cx;
-  o[0] = p[0] + 2.0 * (w * cx + dx); o[1] = p[1] + 2.0 * (w * cy + dy); o[2] = p[2] + 2.0 * (w * cz + dz);
-}
-__device__ inline void quat_mul(const double a[4], const double b[4], double o[4]) {
-  const double aw = a[3], ax = a[0], ay = a[1], az = a[2], bw = b[3], bx = b[0], by = b[1], bz = b[2];
-  o[3] = aw * bw - ax * bx - ay * by - az * bz;
-  o[0] = aw * bx + ax * bw + ay * bz - az * by;
-  o[1] = aw * by - ax * bz + ay * bw + az * bx;
-  o[2] = aw * bz + ax * by - ay * bx + az * bw;
-}
-__device__ inline void mul(const double A[7], const double B[7], double C[7]) {
-  double q[4], t[3];
-  quat_mul(A, B, q);
-  normalize4(q);
-  rotate(A, B + 4, t);
-  for (int k = 0; k < 4; ++k) C[k] = q[k];
-  for (int k = 0; k < 3; ++k) C[4 + k] = A[4 + k] + t[k];
-}
-__device__ inline void to_rpyxyz(const double T[7], double r[6]) {
-  const double w = T[3], x = T[0], y = T[1], z = T[2];
-  r[0] = atan2(2.0 * (x * y + w * z), 1.0 - 2.0 * (y * y + z * z));
-  r[1] = asin(2.0 * (w * y - x * z));
-  r[2] = atan2(2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y));
-  r[3] = T[4]; r[4] = T[5]; r[5] = T[6];
-}
-__device__ inline void from_rpyxyz(const double r[6], double T[7]) {
-  const double hz = r[0] / 2.0, hy = r[1] / 2.0, hx = r[2] / 2.0;
-  const double cz = cos(hz), sz = sin(hz), cy = cos(hy), sy = sin(hy), cx = cos(hx), sx = sin(hx);
-  double q[4];
-  q[3] = cz * cy * cx + sz * sy * sx;
-  q[0] = cz * cy * sx - sz * sy * cx;
-  q[1] = cz * sy * cx + sz * cy * sx;
-  q[2] = sz * cy * cx - cz * sy * sx;
-  normalize4(q);
-  for (int k = 0; k < 4; ++k) T[k] = q[k];
-  T[4] = r[3]; T[5] = r[4]; T[6] = r[5];
-}
-}  // namespace dse3
-
 struct SmStepArgs {
   int n;
   int prev, next;            // sub-problem to close / to open (0 ground, 1 surf, -1 none)
@@ -85,11 +35,12 @@ __global__ __launch_bounds__(64) void k_sm_step(SmDev* __restrict__ devs, const 
   SmDev& d = devs[c];
   if (a.prev >= 0 && d.has[a.prev]) {
     const int m = a.prev;
-    const int i0 = m == 0 ? 1 : 0, i1 = m == 0 ? 2 : 3, i2 = m == 0 ? 5 : 4;
+    int i0, i1, i2;
+    param_slots(m, i0, i1, i2);
     d.rpyxyz[i0] = d.icp.x[0]; d.rpyxyz[i1] = d.icp.x[1]; d.rpyxyz[i2] = d.icp.x[2];
     double dT[7], pose[7];
-    dse3::from_rpyxyz(d.rpyxyz, dT);
-    dse3::mul(d.map_pose, dT, pose);                               // frame->pose = map_frame->pose * rpyxyz2se3(rpyxyz)
+    hse3::from_rpyxyz(d.rpyxyz, dT);
+    hse3::mul(d.map_pose, dT, pose);                               // frame->pose = map_frame->pose * rpyxyz2se3(rpyxyz)
     for (int k = 0; k < 7; ++k) d.pose[k] = pose[k];
     const int nr = d.icp.nvalid + (a.prior_w > 0.0 ? 1 : 0);
     d.nres[m] = nr; d.iters[m] = d.icp.iters; d.succ[m] = d.icp.successes; d.initial_cost[m] = d.icp.initial_cost; d.final_cost[m] = d.icp.cost_cur;
@@ -98,23 +49,16 @@ __global__ __launch_bounds__(64) void k_sm_step(SmDev* __restrict__ devs, const 
   if (a.next >= 0) {
     if (a.first_of_outer) {
       double rel[7], r[6];
-      dse3::mul(d.minv, d.pose, rel);
-      dse3::to_rpyxyz(rel, r);
+      hse3::mul(d.minv, d.pose, rel);
+      hse3::to_rpyxyz(rel, r);
       for (int k = 0; k < 6; ++k) d.rpyxyz[k] = r[k];
     }
     IcpDev& h = d.icp;
-    const int m = a.next;
-    const int i0 = m == 0 ? 1 : 0, i1 = m == 0 ? 2 : 3, i2 = m == 0 ? 5 : 4;
-    h.x[0] = h.x0[0] = d.rpyxyz[i0]; h.x[1] = h.x0[1] = d.rpyxyz[i1]; h.x[2] = h.x0[2] = d.rpyxyz[i2];
-    h.xc[0] = h.xc[1] = h.xc[2] = 0.0;
-    for (int k = 0; k < 6; ++k) h.rpyxyz[k] = d.rpyxyz[k];
-    h.radius = 1e4; h.decrease = 2.0;
-    for (int k = 0; k < 11; ++k) { h.acc[k] = 0.0; h.accC[k] = 0.0; }
-    h.cost_cand = 0.0; h.cost_cur = 0.0; h.initial_cost = 0.0; h.model = 0.0;
-    h.done = d.has[m] ? 0 : 1; h.iters = 0; h.successes = 0; h.nvalid = 0; h.first = 1; h.invalid_run = 0; h.ticket = 0u; h.count_valid = 1;
+    icp_reset(h, a.next, d.rpyxyz);
+    h.done = d.has[a.next] ? 0 : 1; h.count_valid = 1;
     for (int k = 0; k < 7; ++k) d.tf[k] = (float)d.pose[k];        // Sophus SE3d::cast<float>()
   } else {
-    if (d.has_last) dse3::mul(d.linv, d.pose, d.relative_o_c);     // mapping.cpp:298
+    if (d.has_last) hse3::mul(d.linv, d.pose, d.relative_o_c);     // mapping.cpp:298
     else for (int k = 0; k < 7; ++k) d.relative_o_c[k] = d.pose[k];
     d.score_int = (int)(d.score[0] + d.score[1]);                  // int Mapping::Relocate(...) truncates
   }

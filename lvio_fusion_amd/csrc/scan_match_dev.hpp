@@ -17,7 +17,6 @@ struct IcpDev {
   double radius, decrease;
   double acc[11];            // H lower (00,10,11,20,21,22), g (3), cost — at x ; [10] = number of valid correspondences (first pass)
   double accC[11];           // the same sums at the candidate xc (one pass per LM iteration: an accepted candidate's linearisation is already there)
-  double cost_cand;          // (unused since the candidate pass carries its Jacobian: kept for the record layout's readers)
   double cost_cur, initial_cost, model;
   double rpyxyz[6];
   int done, iters, successes, nvalid, first;
@@ -26,6 +25,20 @@ struct IcpDev {
   int count_valid;           // 1: nvalid is taken from acc[10] by the first step (batched chain: nobody else counts)
   double h0[3];              // Jacobi scaling of this solve: diag(J^T J) at its first linearisation, frozen (Ceres default jacobi_scaling; mapping.cpp:159-163 solves with default options)
 };
+
+// where the three unknowns of a sub-problem sit in rpyxyz: mode 0 (pitch, roll, z), mode 1 (yaw, x, y)
+__host__ __device__ inline void param_slots(int mode, int& i0, int& i1, int& i2) {
+  if (mode == 0) { i0 = 1; i1 = 2; i2 = 5; } else { i0 = 0; i1 = 3; i2 = 4; }
+}
+// the state a solve of `mode` starts from, its unknowns taken out of rpyxyz; the caller then sets done / count_valid / nvalid as it needs them
+__host__ __device__ inline void icp_reset(IcpDev& h, int mode, const double* rpyxyz) {
+  h = IcpDev{};
+  int i0, i1, i2;
+  param_slots(mode, i0, i1, i2);
+  h.x[0] = h.x0[0] = rpyxyz[i0]; h.x[1] = h.x0[1] = rpyxyz[i1]; h.x[2] = h.x0[2] = rpyxyz[i2];
+  for (int k = 0; k < 6; ++k) h.rpyxyz[k] = rpyxyz[k];
+  h.radius = 1e4; h.decrease = 2.0; h.first = 1;
+}
 
 struct IcpArgs {
   double Twc1[7];

@@ -15,13 +15,13 @@
 namespace lvf {
 
 // ------------------------------------------------------------------------------------------------ damping
-// (lm_damping: solver_dev.hpp)
+// (lm_damping_fast: solver_dev.hpp)
 // the damping of unknown `slot` whose diagonal entry is h in this pass; the thread that OWNS the entry's assembly records H0 in the first
 // pass.  h0_loaded = jac.h0[slot], requested by the caller together with its other loads (so that it is not a dependent round trip here).
-__device__ __forceinline__ double lm_damping_own(double h, const JacobiDev& j, int slot, int frozen, double h0_loaded) {
+__device__ __forceinline__ double lm_damping_fast_own(double h, const JacobiDev& j, int slot, int frozen, double h0_loaded) {
   double h0 = h0_loaded;
   if (!frozen) { h0 = h; j.h0[slot] = h; }
-  return lm_damping(h, h0);
+  return lm_damping_fast(h, h0);
 }
 
 // ------------------------------------------------------------------------------------------------ elimination order
@@ -88,7 +88,7 @@ __device__ __forceinline__ void sp_eliminate_body(const int vb, const SpNode* __
 #pragma unroll
       for (int c = 0; c < 9; ++c) {
         double b = c <= tid ? braw[c] : 0.0;
-        if (c == tid) b += lm_damping_own(b, src.jac, nb0 + tid, jf, h0d) * inv_radius;      // (every tile workgroup of the node stores the same H0)
+        if (c == tid) b += lm_damping_fast_own(b, src.jac, nb0 + tid, jf, h0d) * inv_radius;      // (every tile workgroup of the node stores the same H0)
         bd[c] = b;
       }
     }
@@ -431,7 +431,7 @@ __device__ __forceinline__ void prepare_body(const unsigned bx0, const PrepArgs&
       if (live && j0 == 0) {
         const double c = C[l] + v[0], g = gr[l] + v[1];
         A.Ct[l] = c; A.grt[l] = g;
-        Cd[l] = c + lm_damping_own(c, A.jac, A.jl0 + l, jf, h0l) * inv_radius;
+        Cd[l] = c + lm_damping_fast_own(c, A.jac, A.jl0 + l, jf, h0l) * inv_radius;
         double* el = E + (size_t)l * ldE;
         el[dp] = g;
         if (len > 0) {
@@ -444,7 +444,7 @@ __device__ __forceinline__ void prepare_body(const unsigned bx0, const PrepArgs&
     const int l = (bx - nS_blocks) * kT + threadIdx.x;
     if (l >= n_lm) return;
     const double c = C[l], h0l = A.jac.h0[A.jl0 + l];
-    Cd[l] = c + lm_damping_own(c, A.jac, A.jl0 + l, jf, h0l) * inv_radius;
+    Cd[l] = c + lm_damping_fast_own(c, A.jac, A.jl0 + l, jf, h0l) * inv_radius;
     E[(size_t)l * ldE + dp] = gr[l];
     return;
   }
@@ -467,7 +467,7 @@ __device__ __forceinline__ void prepare_body(const unsigned bx0, const PrepArgs&
     if (oj >= 0 && J <= I) {
       const double h0d = I == J ? A.jac.h0[oi] : 0.0;
       v = B[(size_t)max(oi, oj) * dpad + min(oi, oj)];
-      if (I == J) v += lm_damping_own(v, A.jac, oi, jf, h0d) * inv_radius;
+      if (I == J) v += lm_damping_fast_own(v, A.jac, oi, jf, h0d) * inv_radius;
     }
   } else if (oi == -2) {
     v = (oj >= 0) ? -gc[oj] : (J == I ? 1e300 : 0.0);   // huge corner keeps the augmented matrix positive definite

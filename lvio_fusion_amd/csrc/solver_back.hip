@@ -468,7 +468,7 @@ __device__ __forceinline__ void apply_step_ops(const int vb, int n_kf, int n_lm,
   if (i < d && ((PARTS & 1) || i >= 6 * n_kf) && ((PARTS & 2) || i < 6 * n_kf)) {
     const double dx = dxc[i];
     const double h = ops.h, h0d = ops.h0d;
-    m = -0.5 * dx * (lm_damping(h, ops.frozen ? h0d : h) * inv_radius * dx - ops.gci);      // (first pass: H0 = H, being recorded by the assembly)
+    m = -0.5 * dx * (lm_damping_fast(h, ops.frozen ? h0d : h) * inv_radius * dx - ops.gci);      // (first pass: H0 = H, being recorded by the assembly)
     const bool rot = i < 6 * n_kf && (i % 6) < 3;           // rotation increments enter through the quaternion difference below
     n2 = rot ? 0.0 : dx * dx;
     g = fabs(ops.gci);
@@ -650,7 +650,7 @@ __device__ __forceinline__ void back_product_body(const int vb, const BackTailAr
   if (mine) {
     const double dx = xs[tid];
     cv[3 * uk + uc % 3] = sval + dx;
-    m = -0.5 * dx * (lm_damping(h, frozen ? h0d : h) * inv_radius * dx - gci);
+    m = -0.5 * dx * (lm_damping_fast(h, frozen ? h0d : h) * inv_radius * dx - gci);
     n2 = dx * dx;
     gm = fabs(gci);
     x2 = (cm & (2 << (uc / 3))) ? 0.0 : sval * sval;

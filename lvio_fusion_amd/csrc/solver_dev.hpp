@@ -1,10 +1,11 @@
 // solver_dev.hpp — the device helpers that kernels of more than one translation unit of the LM iteration call.
-// used by: solver_kernels.hip (block_add, acc_set, zero_lower, zero_list_share, reset_step_scalars)
-// used by: solver_assemble.hip (done_flag_issue, acc_set*, zero_list_share, reset_step_scalars, lm_damping, fmac_row_bcast, double4_t)
+// used by: solver_kernels.hip (block_add, acc_set, zero_lower, zero_list_share, reset_step_scalars; LmState of lm_rule.hpp: lm_decide_body)
+// used by: solver_assemble.hip (done_flag_issue, acc_set*, zero_list_share, reset_step_scalars, lm_damping_fast, fmac_row_bcast, double4_t)
 // used by: solver_chol.hip (chol_step_body, back_product_ride, back_block_ride and what they call: k_chol_step*)
-// used by: solver_back.hip (done_flag_issue, block_add, acc_set_t, lm_damping; chol_step_body, back_product_ride, back_block_ride:
+// used by: solver_back.hip (done_flag_issue, block_add, acc_set_t, lm_damping_fast; chol_step_body, back_product_ride, back_block_ride:
 //          k_chol_backsolve_tail runs the last block step and the back substitution as one launch)
 #pragma once
+#include "lm_rule.hpp"
 #include "lvf_internal.hpp"
 #include "solver_args.hpp"
 
@@ -60,11 +61,11 @@ __device__ __forceinline__ void reset_step_scalars(double* scal) {
 // (the fp64 square root and two divisions of the literal form cost k_prepare / k_tf_reduce / k_step_tail 6.6 us per iteration between them
 // when every diagonal entry took them — profiles/r05_a; they are only needed where the clamp can act:  s^2 h >= 1e-6  <=  h >= 2e-6 (1 + h0),
 // because (1 + sqrt(h0))^2 <= 2 (1 + h0); there clamp(s^2 h) / s^2 = h up to one rounding.  A column that was empty at iteration 0 has s = 1.)
-__device__ __forceinline__ double lm_damping(double h, double h0) {
+// Not the literal form (lm_rule.hpp lm_damping) to the bit where the short cut is taken; the fall-through is the literal form.
+__device__ __forceinline__ double lm_damping_fast(double h, double h0) {
   if (h >= 2e-6 * (1.0 + h0) && h < 1e32) return h;
   if (h0 == 0.0) return fmin(fmax(h, 1e-6), 1e32);
-  const double sj = 1.0 / (1.0 + sqrt(h0)), s2 = sj * sj;
-  return fmin(fmax(h * s2, 1e-6), 1e32) / s2;
+  return lm_damping(h, h0);
 }
 
 // acc += (lane N of each 16-lane row of lv) * m: the DPP row_newbcast operand of v_fmac_f64 hands a row-uniform value to all 16 lanes

@@ -3,8 +3,9 @@
 // because k_cost_decide* and k_lin_cost_decide run the linearisation and cost bodies themselves (lin_visual_run, cost_visual_value): in a unit
 // of their own they would need those 670 lines in a shared header.  The other stages are solver_assemble.hip (slab reduction, damping, Schur
 // forms, layout kernels, sparse levels), solver_chol.hip (blocked Cholesky) and solver_back.hip (back substitution, step tail); what kernels
-// of more than one unit call is in solver_dev.hpp.  Replaces what ceres::Solve does under adapt::Solve for Backend::Optimize
-// (src/lvio_fusion/include/lvio_fusion/adapt/problem.h:83-88; src/lvio_fusion/src/backend.cpp:96-183, 206-211).
+// of more than one unit call is in solver_dev.hpp; the trust-region rule the decision applies is LmState (lm_rule.hpp).  Replaces what
+// ceres::Solve does under adapt::Solve for Backend::Optimize (src/lvio_fusion/include/lvio_fusion/adapt/problem.h:83-88;
+// src/lvio_fusion/src/backend.cpp:96-183, 206-211).
 // Device code only: the argument blocks and constants are in solver_args.hpp, the host side that builds and launches the chain in
 // solver_chain.hip, solver_plan.hip, solver_batch.hip and solver_api.hip.
 #include "factor_eval.hpp"
@@ -960,77 +961,47 @@ __device__ __forceinline__ void lm_decide_body(const DecideArgs& A) {
   if (A.dbg && threadIdx.x == 0) A.dbg[2] = wall_clock64();
   if (!A.fused && threadIdx.x < kStripes) const_cast<double*>((const double*)A.scal)[SC_COST + threadIdx.x] = 0.0;      // read above; the next linearisation adds into it
   if (threadIdx.x == 0) {
-    // the fields of the control block are read up front (independent requests, one wait) and written back once at the end: read and
-    // written where the logic uses them they were 1.2 us of dependent traffic.  (A whole-struct copy goes through a scratch segment.)
-    struct { double radius, decrease, last_radius, cost, initial_cost, cost_before, cost_after, model, dxnorm, xnorm, gmax;
-             double function_tol, gradient_tol, parameter_tol, min_rel_decrease; int max_iters, iter, successes, invalid_run, accepted, solved, done, termination, why, rejected; } lc;
-    lc.radius = c->radius; lc.decrease = c->decrease; lc.cost = c->cost; lc.initial_cost = c->initial_cost;
-    lc.function_tol = c->function_tol; lc.gradient_tol = c->gradient_tol; lc.parameter_tol = c->parameter_tol; lc.min_rel_decrease = c->min_rel_decrease;
-    lc.max_iters = c->max_iters; lc.iter = c->iter; lc.successes = c->successes; lc.invalid_run = c->invalid_run; lc.done = c->done; lc.termination = c->termination; lc.why = c->why; lc.rejected = c->rejected;
+    // the fields of the control block are read up front (independent requests, one wait) into the rule's state (LmState, lm_rule.hpp) and written
+    // back once at the end: read and written where the logic uses them they were 1.2 us of dependent traffic.  (A whole-struct copy goes
+    // through a scratch segment.)
+    const int it = c->iter;
+    LmState s(c->radius);
+    s.decrease = c->decrease; s.cost = c->cost; s.initial_cost = c->initial_cost;
+    s.iters = it; s.successes = c->successes; s.invalid_run = c->invalid_run; s.termination = c->termination; s.why = c->why; s.first = it == 0;
+    const LmOpts o{c->max_iters, c->function_tol, c->gradient_tol, c->parameter_tol, c->min_rel_decrease, 0.0};
+    int rejected = c->rejected;
+    const double stored_cost = s.cost, last_radius = s.radius;
     const int hfail = *reinterpret_cast<const int*>(A.scal + SC_FAIL);
     const double cost_before = s_sum[SC_COST / kStripes], cost_new = s_sum[SC_COST_NEW / kStripes], model = -s_sum[SC_MODEL / kStripes];
-    const double dxnorm = sqrt(s_sum[SC_DXNORM / kStripes]), xnorm = sqrt(s_sum[SC_XNORM / kStripes]);
+    const double dx2 = s_sum[SC_DXNORM / kStripes], x2 = s_sum[SC_XNORM / kStripes];
     const double gmax = s_sum[SC_GMAX / kStripes];             // a max over the stripes (the stored bit patterns are the doubles')
     const bool solved = hfail == 0 && isfinite(cost_new) && isfinite(model);
-    const int it = lc.iter;
-    if (it == 0) { lc.initial_cost = cost_before; lc.cost = cost_before; }
-    lc.cost_before = cost_before; lc.model = model; lc.dxnorm = dxnorm; lc.xnorm = xnorm; lc.gmax = gmax; lc.solved = solved ? 1 : 0;
-    lc.last_radius = lc.radius;
-    bool accepted = false, done = false;
-    int termination = 1, why = LVF_WHY_MAX_ITERATIONS;
-    // ceres::Solve's TrustRegionMinimizer, in its order (declared semantics + citations: oracle/lm.h lm_solve).
+    // the rule judges against the cost summed by THIS pass; the stored cost (c->cost) follows the first pass and the accepted candidates
+    const bool first = s.linearized(cost_before);
+    bool accepted = false, done;
+    // ceres::Solve's TrustRegionMinimizer (declared semantics + citations: oracle/lm.h lm_solve), its iteration split over the launches:
     // Top of the loop (FinalizeIterationAndCheckIfMinimizerCanContinue): the gradient at the point this pass linearised — it ends the
     // solve before a step is taken, so the pass is NOT an iteration; the smallest trust region likewise.
     // a chained sparse level gave up waiting for the level below (SpSrc): nothing about this step is judged — the loop stops where it is
     // (state, radius and counters untouched) and the host re-runs the iteration with un-chained launches
-    if (hfail >= kFailHandover) { done = true; termination = 2; why = LVF_WHY_HANDOVER; }
-    else if (gmax <= lc.gradient_tol) { done = true; termination = 0; why = LVF_WHY_GRADIENT; }
-    else if (lc.radius < 1e-32) { done = true; termination = 0; why = LVF_WHY_MIN_RADIUS; }
+    if (hfail >= kFailHandover) done = s.end(2, LVF_WHY_HANDOVER);
+    else if (s.gradient(o, gmax) || s.min_radius()) done = true;
     else {
       // (num_iterations = what Ceres records in Summary::iterations: accepted, rejected and invalid steps; a trial step that ends the solve
       // through the parameter / function tolerance returns before it is recorded)
-      const bool valid = solved && model > 0.0;      // ComputeTrustRegionStep: solver failure or model_cost_change <= 0 = INVALID step
-      if (!valid) {
-        lc.iter = it + 1;
-        lc.rejected += 1;
-        lc.invalid_run += 1;
-        if (lc.invalid_run >= 5) { done = true; termination = 2; why = LVF_WHY_INVALID_STEPS; }      // max_num_consecutive_invalid_steps
-        else lc.radius *= 0.5;                       // LevenbergMarquardtStrategy::StepIsInvalid (decrease factor untouched)
-      } else {
-        lc.invalid_run = 0;
-        // parameter tolerance, then function tolerance: both BEFORE the step-quality test, and neither takes the candidate
-        if (dxnorm <= lc.parameter_tol * (xnorm + lc.parameter_tol)) { done = true; termination = 0; why = LVF_WHY_PARAMETER; }
-        else if (fabs(cost_before - cost_new) <= lc.function_tol * cost_before) { done = true; termination = 0; why = LVF_WHY_FUNCTION; }
-        else {
-          lc.iter = it + 1;
-          const double rho = (cost_before - cost_new) / model;
-          if (rho > lc.min_rel_decrease) {
-            accepted = true;
-            const double t = 2.0 * rho - 1.0;
-            lc.radius = fmin(lc.radius / fmax(1.0 / 3.0, 1.0 - t * t * t), 1e16);
-            lc.decrease = 2.0;
-            lc.successes += 1;
-            lc.cost = cost_new;
-          } else {
-            lc.radius = lc.radius / lc.decrease;
-            lc.decrease *= 2.0;
-            lc.rejected += 1;
-          }
-        }
-      }
+      if (!s.valid_step(solved, model)) { rejected += 1; done = s.invalid_step(); }      // ComputeTrustRegionStep: solver failure or model_cost_change <= 0
+      // parameter tolerance, then function tolerance: both BEFORE the step-quality test, and neither takes the candidate
+      else if (s.parameter_tol(o, dx2, x2) || s.function_tol(o, cost_new)) done = true;
+      else { done = false; accepted = s.accept(o, cost_new, model); if (!accepted) rejected += 1; }
       // after the step, Finalize's order again: the iteration cap first, then the smallest trust region (the gradient at an accepted point is
       // only known to the next pass)
-      if (!done && lc.iter >= lc.max_iters) { done = true; termination = 1; why = LVF_WHY_MAX_ITERATIONS; }
-      else if (!done && lc.radius < 1e-32) { done = true; termination = 0; why = LVF_WHY_MIN_RADIUS; }
+      if (!done) done = s.cap(o) || s.min_radius();
     }
-    lc.cost_after = accepted ? cost_new : (solved ? cost_new : cost_before);
-    lc.accepted = accepted ? 1 : 0;
-    if (done) { lc.termination = termination; lc.why = why; lc.done = 1; }
     s_commit = accepted ? 1 : 0;
-    c->radius = lc.radius; c->decrease = lc.decrease; c->last_radius = lc.last_radius; c->cost = lc.cost; c->initial_cost = lc.initial_cost;
-    c->cost_before = lc.cost_before; c->cost_after = lc.cost_after; c->model = lc.model; c->dxnorm = lc.dxnorm; c->xnorm = lc.xnorm; c->gmax = lc.gmax;
-    c->iter = lc.iter; c->successes = lc.successes; c->invalid_run = lc.invalid_run; c->accepted = lc.accepted; c->solved = lc.solved;
-    c->done = lc.done; c->termination = lc.termination; c->why = lc.why; c->rejected = lc.rejected;
+    c->radius = s.radius; c->decrease = s.decrease; c->last_radius = last_radius; c->cost = first || accepted ? s.cost : stored_cost; c->initial_cost = s.initial_cost;
+    c->cost_before = cost_before; c->cost_after = accepted ? cost_new : (solved ? cost_new : cost_before); c->model = model; c->dxnorm = sqrt(dx2); c->xnorm = sqrt(x2); c->gmax = gmax;
+    c->iter = s.iters; c->successes = s.successes; c->invalid_run = s.invalid_run; c->accepted = accepted ? 1 : 0; c->solved = solved ? 1 : 0;
+    c->done = done ? 1 : 0; c->termination = s.termination; c->why = s.why; c->rejected = rejected;
     if (hfail < kFailHandover) c->jfrozen = 1;      // the Jacobi scaling of this solve is the first pass's (a pass that is re-run after a hand-over time-out takes it again)
     if (A.fused) {
       // the candidate pass linearised x + dx into the standby set: accepted, that set becomes the active one, its TwoFrame slabs still to be
@@ -1038,10 +1009,10 @@ __device__ __forceinline__ void lm_decide_body(const DecideArgs& A) {
       c->lin_pending = accepted ? 1 : 0;
       if (accepted) c->aset = c->aset ^ 1;
     }
-    s_iter = lc.iter; s_done = lc.done;
+    s_iter = s.iters; s_done = done ? 1 : 0;
     if (A.hist) {                                      // diagnostic: what this pass decided on
       double* h = A.hist + 8 * (it & 63);
-      h[0] = (double)it; h[1] = cost_before; h[2] = cost_new; h[3] = model; h[4] = accepted ? 1.0 : 0.0; h[5] = (double)hfail; h[6] = lc.last_radius; h[7] = gmax;
+      h[0] = (double)it; h[1] = cost_before; h[2] = cost_new; h[3] = model; h[4] = accepted ? 1.0 : 0.0; h[5] = (double)hfail; h[6] = last_radius; h[7] = gmax;
     }
     if (A.dbg) A.dbg[3] = wall_clock64();
   }

@@ -142,3 +142,91 @@ def test_icp_iteration_caps_and_a_far_start(ctx, oracle, scene, max_iters, far):
     if max_iters == 0:
         assert np.array_equal(x, rpyxyz0) and s.num_iterations == 0
     mp.close(); sc.close()
+
+
+# ----------------------------------------------------------------------------- rejected and invalid steps
+# Far starts behind a wide association gate: the scan keeps its correspondences, the first Gauss-Newton-sized steps overshoot, and the
+# trust region has to shrink before a step is taken.  Chosen on the CPU with the references alone (oracle.icp_solve; for the lines
+# tests/edge_ref.py, whose plane-only solves agree with the oracle's on these inputs to 1e-14) so that they report more iterations than
+# successful steps; scans of 250 points (one workgroup per pass) against 20000 map points of configs[2], six iterations allowed.
+#   name: (mode, prior weight, start = (dq, dt) * pose0 with dq the vector part of a quaternion of scalar part 1, gate, line points)
+REJECT_CASES = {
+    "mode0": (0, 0.0, (0.647, -0.293, 0.117), (1.107, -0.332, -1.559), 25.0, 0),
+    "mode1-prior": (1, 0.05, (-0.4, -1.186, -0.449), (-0.002, -0.014, -0.552), 100.0, 0),
+    "edges": (1, 0.0, (0.133, -0.661, -0.278), (-0.798, -0.016, -1.496), 100.0, 12),
+}
+REJECT_ITERS = 6
+_reject_cache = {}
+
+
+def reject_inputs(case):
+    """dict(map, scan, map_edge, scan_edge, map_pose, pose0, rpyxyz0, mode, prior, thr, weight, huber): the arrays of one REJECT_CASES entry"""
+    from tests import edge_ref as er
+    if "c" not in _reject_cache:
+        _reject_cache["c"] = syn.config3_icp()
+    c = _reject_cache["c"]
+    mode, prior, dq, dt, thr, n_lines = case
+    r = np.random.default_rng(7 + mode)
+    qa = c["query"][c["query_ground"]] if mode == 0 else c["query"][~c["query_ground"]]
+    ma = c["map"][c["map_ground"]] if mode == 0 else c["map"][~c["map_ground"]]
+    qq = qa[np.sort(r.choice(qa.shape[0], 250, replace=False))]
+    mm = ma[np.sort(r.choice(ma.shape[0], 20000, replace=False))]
+    d = np.array(list(dq) + [1.0]); d /= np.linalg.norm(d)
+    pose0 = er.se3_mul(np.concatenate([d, dt]), np.array(c["pose0"], float))
+    out = dict(map=mm, scan=qq, map_edge=None, scan_edge=None, map_pose=np.array(c["map_pose"], float), pose0=pose0, mode=mode, prior=prior, thr=thr,
+               rpyxyz0=er.se3_to_rpyxyz(er.se3_mul(er.se3_inv(c["map_pose"]), pose0)), weight=syn.W_LIDAR_GROUND if mode == 0 else syn.W_LIDAR_SURF,
+               huber=0.0 if mode == 0 else 0.1)
+    if n_lines:      # three poles around the true pose in the map, n_lines points of them in the scan
+        pt = np.array(c["pose_true"], float)
+        R, t = er.rotmat(pt[:4]), pt[4:]
+        rng = np.random.default_rng(12)
+        poles = [t[:2] + o for o in ([3.0, 2.0], [-3.0, 2.5], [4.0, -2.0])]
+        out["map_edge"] = er._pad(np.concatenate([er._pole(rng, xy, 80, t[2] - 1.5, t[2] + 1.5) for xy in poles]))
+        out["scan_edge"] = er._pad((np.concatenate([er._pole(rng, xy, n_lines // 3, t[2] - 1.2, t[2] + 1.2) for xy in poles]) - t) @ R)
+    return out
+
+
+def run_reject_case(ctx, case):
+    """(rpyxyz, summary) of the device solve of one REJECT_CASES entry"""
+    from lvio_fusion_amd import api
+    i = reject_inputs(case)
+    mp, sc = api.Map(ctx, i["map"], i["thr"]), api.Scan(ctx, i["scan"])
+    x = i["rpyxyz0"].copy()
+    if i["map_edge"] is None:
+        s = api.icp_solve(mp, sc, i["map_pose"], i["pose0"], x, i["mode"], i["thr"], i["weight"], i["huber"], prior_weight=i["prior"], max_num_iterations=REJECT_ITERS)
+    else:
+        me, se = api.Map(ctx, i["map_edge"], i["thr"]), api.Scan(ctx, i["scan_edge"])
+        s = api.icp_solve_edges(mp, sc, me, se, i["map_pose"], i["pose0"], x, i["thr"], i["weight"], i["huber"], api.edge_icp_options(0.2, thr=i["thr"]),
+                                prior_weight=i["prior"], max_num_iterations=REJECT_ITERS)
+        me.close(); se.close()
+    mp.close(); sc.close()
+    return x, s
+
+
+@pytest.mark.parametrize("name", list(REJECT_CASES))
+def test_icp_rejected_steps_parity(ctx, oracle, name):
+    """The decision path of the device loop off its main line: steps that are rejected (the radius divided by a doubling factor) or invalid
+    (the radius halved) before one is taken.  The CPU reference must report such steps by itself, then test_icp_solve_parity's tolerances."""
+    from tests import edge_ref as er
+    i = reject_inputs(REJECT_CASES[name])
+    if i["map_edge"] is None:
+        ref_x, ref = oracle.icp_solve(i["map"], i["scan"], i["map_pose"], i["pose0"], i["rpyxyz0"], i["mode"], i["thr"], i["weight"], i["huber"], prior_w=i["prior"],
+                                      max_iters=REJECT_ITERS)
+    else:
+        ref_x, ref = er.icp_solve_edges(i["map"], i["scan"], i["map_edge"], i["scan_edge"], i["map_pose"], i["pose0"], i["rpyxyz0"], i["thr"], i["weight"], i["huber"],
+                                        dict(er.edge_defaults(0.2), thr=i["thr"]), prior_w=i["prior"], max_iters=REJECT_ITERS)
+        n_planes = er.plane_correspondences(i["map"], i["scan"], i["pose0"], i["thr"])[0].shape[0]
+        assert ref["num_residual_blocks"] - n_planes >= 3                      # a few line blocks beside the planes
+    assert ref["num_iterations"] > ref["num_successful_steps"] >= 1            # the reference alone: a rejected or invalid step, and an accepted one
+    assert i["scan"].shape[0] <= 256 and ref["num_residual_blocks"] >= 100
+    x, s = run_reject_case(ctx, REJECT_CASES[name])
+    print(f"{name}: blocks {s.num_residual_blocks}, iterations {s.num_iterations} / {s.num_successful_steps} (reference {ref['num_iterations']} / "
+          f"{ref['num_successful_steps']}), cost {s.initial_cost:.9e} -> {s.final_cost:.9e} (reference {ref['initial_cost']:.9e} -> {ref['final_cost']:.9e}), "
+          f"|dx| {np.abs(x - ref_x).max():.2e}")
+    assert s.num_residual_blocks == ref["num_residual_blocks"]
+    assert s.num_iterations == ref["num_iterations"] and s.num_successful_steps == ref["num_successful_steps"]
+    assert abs(s.initial_cost - ref["initial_cost"]) <= 1e-9 * abs(ref["initial_cost"])
+    assert abs(s.final_cost - ref["final_cost"]) <= 1e-6 * abs(ref["final_cost"])
+    assert np.allclose(x, ref_x, rtol=1e-6, atol=1e-9)
+    untouched = [0, 3, 4] if i["mode"] == 0 else [1, 2, 5]
+    assert np.array_equal(x[untouched], i["rpyxyz0"][untouched])
