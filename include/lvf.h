@@ -183,6 +183,25 @@ int lvf_pose_prior_create(lvf_ctx* ctx, int n, const int32_t* kf_a, const int32_
                           const double* weight, const double* v, lvf_batch** out);
 /* rpyxyz6 = SE3ToRpyxyz(last_pose^-1 * pose): the constant PoseGraphError's constructor stores (host arithmetic). */
 int lvf_relative_rpyxyz(const double* last_pose, const double* pose, double* rpyxyz6);
+/* LiDAR planes on full keyframe poses: LidarPlaneError<1,7> (lidar_error.hpp:10-40, declared by the reference and never added to a
+ * problem) as blocks of the sliding-window problem (lvf_problem_set_lidar_planes).  Block i: r = w_i n_i . (R(q/|q|) p_i + t - pa_i) on
+ * pose[kf_idx[i]], n_i the unit normal of (pa - pb) x (pa - pc) (a zero cross product stays zero: a null block), p in the keyframe's body
+ * frame, pa, pb, pc in the world frame; all [n][3].  weight (NULL = 1) and huber_a (NULL or <= 0 = no loss) are per block — the one
+ * deviation from the functor: ground blocks take w = 1 and no loss, surf blocks w = 0.01 and a = 0.1 (mapping.cpp's conventions).  Blocks may
+ * come in any order.  LVF_ERR_INVALID: a negative index, a non-finite input, a negative weight.  Declared semantics: tests/lidar_window_ref.py.
+ * Parameter block 0 = pose[kf_idx]; 1 residual (lvf_batch_evaluate: st required; the raw residual, no loss applied). */
+int lvf_lidar_pose_create(lvf_ctx* ctx, int n, const double* p, const double* pa, const double* pb, const double* pc, const int32_t* kf_idx,
+                          const double* weight, const double* huber_a, lvf_batch** out);
+/* The same batch from what lvf_knn3 left in n_scans (map, scan) pairs, gathered on the device (one launch per 16 scans, no wait): scan k's
+ * queries become blocks on keyframe kf_idx[k] (non-decreasing) with the scan's weight[k] / huber_a[k] (NULL as above), the floats widened
+ * to double as association.cpp:303-314 does.  Nothing is compacted: a query that failed the gate is a block of weight 0.
+ * LVF_ERR_INVALID for a scan that was not searched (an empty scan has nothing to search and is accepted). */
+int lvf_lidar_pose_from_scans(lvf_ctx* ctx, int n_scans, lvf_map* const* maps, lvf_scan* const* scans, const int32_t* kf_idx,
+                              const double* weight, const double* huber_a, lvf_batch** out);
+/* blocks of weight > 0; for a device-built batch this is the one call that waits for the gather */
+int lvf_lidar_pose_num_valid(lvf_batch* b, int* n);
+/* copies of the batch's inputs (each may be NULL): p, pa [n][3], kf_idx, weight, huber_a [n] */
+int lvf_lidar_pose_download(lvf_batch* b, double* p, double* pa, int32_t* kf_idx, double* weight, double* huber_a);
 int lvf_batch_destroy(lvf_batch* b);
 int lvf_batch_size(const lvf_batch* b);
 int lvf_batch_num_param_blocks(const lvf_batch* b);
@@ -203,7 +222,7 @@ void* lvf_batch_jacobian_dev(lvf_batch* b, int block);
 
 /* Batched Problem::Evaluate surface (upstream ceres::Problem::Evaluate with apply_loss_function = true): residuals [n][R] with the loss
  * function's Corrector applied (visual batches: rows scaled by sqrt(rho'(|r|^2)) of HuberLoss(huber_a); huber_a <= 0 or non-visual
- * batches: unchanged) and Jacobians [n][R][L] in LOCAL coordinates, the block's parameter blocks concatenated in functor order with every
+ * batches: unchanged; lidar-pose batches: each block's OWN huber_a, the argument does not apply) and Jacobians [n][R][L] in LOCAL coordinates, the block's parameter blocks concatenated in functor order with every
  * 7-sized pose block reduced to its 6 tangent columns (ProductParameterization(EigenQuaternion, Identity3), backend.cpp:99-101); absent
  * pose blocks (PoseError / RError priors) are zero.  L = lvf_batch_local_columns(b).  jacobians_local may be NULL.  Host outputs. */
 int lvf_batch_local_columns(const lvf_batch* b);
@@ -539,6 +558,10 @@ int lvf_problem_create(lvf_ctx* ctx, lvf_state* st, lvf_batch* two_camera, lvf_b
 int lvf_problem_destroy(lvf_problem* p);
 /* Adds (or with NULL removes) the window's pose-prior batch (ProblemType::Other blocks with no loss function). */
 int lvf_problem_set_pose_priors(lvf_problem* p, lvf_batch* pose_priors);
+/* Adds (or with NULL removes) LiDAR plane blocks on the window's keyframe poses (lvf_lidar_pose_create / _from_scans; the batch is
+ * borrowed).  Every entry that linearises or evaluates the problem sees them: cost, gradient, lm_iteration, solve, download_reduced,
+ * marginal.  A problem with such blocks runs the chain a problem with pose priors runs (no fused candidate pass, no table launches). */
+int lvf_problem_set_lidar_planes(lvf_problem* p, lvf_batch* lidar_planes);
 int lvf_problem_set_pose_constant(lvf_problem* p, int kf, int is_constant);
 /* SetParameterBlockConstant on keyframe kf's velocity / accelerometer-bias / gyroscope-bias blocks (Environment::Optimize holds all of
  * them, and the previous frame's, constant: environment.cpp:62-68): the ImuError factors keep their residuals, the blocks get no
@@ -1089,6 +1112,14 @@ int lvf_window_get_imu(const lvf_window* w, int64_t kf_id, double* vel3, double*
 int lvf_window_get_inv_depth(const lvf_window* w, int64_t lm_id, double* inv_depth);
 /* counts8 = {keyframes, landmarks in the problem, TwoCamera, TwoFrame, PoseOnly, ImuError, prior blocks, landmarks known} of the last solve */
 int lvf_window_counts(const lvf_window* w, int32_t* counts8);
+/* LiDAR planes of one active keyframe's sweep (lvf_lidar_pose_create's blocks, all on kf_id): replaces that keyframe's set, n = 0 removes
+ * it.  _set_lidar_scan takes them from what lvf_knn3 left in `scan` against `map`, on the device, with one weight and Huber a for the
+ * scan.  The next lvf_window_solve adds the sets of the active keyframes to its problem; lvf_window_slide drops those of departed ones. */
+int lvf_window_set_lidar_planes(lvf_window* w, int64_t kf_id, int n, const double* p, const double* pa, const double* pb, const double* pc,
+                                const double* weight, const double* huber_a);
+int lvf_window_set_lidar_scan(lvf_window* w, int64_t kf_id, lvf_map* map, lvf_scan* scan, double weight, double huber_a);
+/* lidar plane blocks held for the active keyframes (blocks of weight 0 included) */
+int lvf_window_lidar_count(const lvf_window* w, int32_t* n);
 /* Test hook: the block lists of the last lvf_window_solve, kind 0 TwoCamera / 1 PoseOnly / 2 TwoFrame / 3 ImuError / 4 weak-constraint priors,
  * in the device batches' order with keyframe and landmark IDS: ids[capacity][3] = {landmark, first / previous keyframe, keyframe} (-1 where a
  * kind has none), vals[capacity][8] = {weight handed to the reference's Create, ob x, y, first (right) ob x, y, pw x, y, z}; *n = blocks of the

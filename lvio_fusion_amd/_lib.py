@@ -294,6 +294,11 @@ _SIGS = {
     "lvf_pose_prior_create": (C.c_int, [_VP, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_double_p, C.POINTER(_VP)]),
     "lvf_relative_rpyxyz": (C.c_int, [c_double_p, c_double_p, c_double_p]),
     "lvf_problem_set_pose_priors": (C.c_int, [_VP, _VP]),
+    "lvf_lidar_pose_create": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, C.POINTER(_VP)]),
+    "lvf_lidar_pose_from_scans": (C.c_int, [_VP, C.c_int, C.POINTER(_VP), C.POINTER(_VP), c_int_p, c_double_p, c_double_p, C.POINTER(_VP)]),
+    "lvf_lidar_pose_num_valid": (C.c_int, [_VP, C.POINTER(C.c_int)]),
+    "lvf_lidar_pose_download": (C.c_int, [_VP, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p]),
+    "lvf_problem_set_lidar_planes": (C.c_int, [_VP, _VP]),
     "lvf_batch_destroy": (C.c_int, [_VP]),
     "lvf_batch_size": (C.c_int, [_VP]),
     "lvf_batch_num_param_blocks": (C.c_int, [_VP]),
@@ -371,6 +376,9 @@ _SIGS = {
     "lvf_window_get_imu": (C.c_int, [_VP, C.c_int64, c_double_p, c_double_p, c_double_p]),
     "lvf_window_get_inv_depth": (C.c_int, [_VP, C.c_int64, c_double_p]),
     "lvf_window_counts": (C.c_int, [_VP, c_int_p]),
+    "lvf_window_set_lidar_planes": (C.c_int, [_VP, C.c_int64, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "lvf_window_set_lidar_scan": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_double, C.c_double]),
+    "lvf_window_lidar_count": (C.c_int, [_VP, c_int_p]),
     "lvf_window_debug_blocks": (C.c_int, [_VP, C.c_int, C.c_int, _VP, c_double_p, C.POINTER(C.c_int)]),
     "lvf_solver_options_default": (None, [C.POINTER(SolverOptions)]),
     "lvf_problem_create": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(_VP)]),

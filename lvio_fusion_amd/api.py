@@ -191,6 +191,53 @@ def lidar_plane_batch(ctx, mode, p, pa, pb, pc, Twc1, weight):
     return Batch(ctx, h, p.shape[0], 1, (1, 1, 1))
 
 
+class LidarPoseBatch(Batch):
+    """LiDAR planes on keyframe poses (lvf_lidar_pose_*): a Batch with its inputs readable."""
+
+    def num_valid(self):
+        """blocks of weight > 0; on a device-built batch the one call that waits for the gather"""
+        n = C.c_int()
+        _chk(self.ctx.L.lvf_lidar_pose_num_valid(self.h, C.byref(n)))
+        return n.value
+
+    def download(self):
+        """dict(p, pa [n][3], kf_idx, weight, huber_a [n]) as the device holds them"""
+        p, pa = np.empty((self.n, 3)), np.empty((self.n, 3))
+        kf, w, a = np.empty(self.n, np.int32), np.empty(self.n), np.empty(self.n)
+        _chk(self.ctx.L.lvf_lidar_pose_download(self.h, _dp(p), _dp(pa), _ip(kf), _dp(w), _dp(a)))
+        return dict(p=p, pa=pa, kf_idx=kf, weight=w, huber_a=a)
+
+
+def _opt_d(a, n):
+    if a is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), (n,)))
+
+
+def lidar_pose_batch(ctx, p, pa, pb, pc, kf_idx, weight=None, huber_a=None):
+    """LidarPlaneError<1,7> blocks on pose[kf_idx[i]] (lvf_lidar_pose_create): p in the keyframe's body frame, pa, pb, pc in the world frame;
+    weight (None = 1) and huber_a (None or <= 0 = no loss) per block or scalar."""
+    p, pa, pb, pc, kf_idx = _d(p).reshape(-1, 3), _d(pa).reshape(-1, 3), _d(pb).reshape(-1, 3), _d(pc).reshape(-1, 3), _i(kf_idx)
+    n = p.shape[0]
+    w, a = _opt_d(weight, n), _opt_d(huber_a, n)
+    h = C.c_void_p()
+    _chk(ctx.L.lvf_lidar_pose_create(ctx.h, n, _dp(p), _dp(pa), _dp(pb), _dp(pc), _ip(kf_idx), _dp(w) if w is not None else None,
+                                     _dp(a) if a is not None else None, C.byref(h)))
+    return LidarPoseBatch(ctx, h, n, 1, (7,))
+
+
+def lidar_pose_from_scans(ctx, maps, scans, kf_idx, weight=None, huber_a=None):
+    """The same batch gathered on the device from what knn3 left in each (map, scan) pair (lvf_lidar_pose_from_scans): scan k's queries are
+    blocks on keyframe kf_idx[k] (non-decreasing); a query that failed the gate is a block of weight 0.  Nothing is waited for."""
+    n = len(scans)
+    kf_idx = _i(kf_idx)
+    w, a = _opt_d(weight, n), _opt_d(huber_a, n)
+    hm = (C.c_void_p * max(n, 1))(*[m.h for m in maps]); hs = (C.c_void_p * max(n, 1))(*[s.h for s in scans])
+    h = C.c_void_p()
+    _chk(ctx.L.lvf_lidar_pose_from_scans(ctx.h, n, hm, hs, _ip(kf_idx), _dp(w) if w is not None else None, _dp(a) if a is not None else None, C.byref(h)))
+    return LidarPoseBatch(ctx, h, sum(s.Q for s in scans), 1, (7,))
+
+
 def pose_prior_batch(ctx, kf_a, kf_b, target, weight, v):
     """kf_a[i] < 0: PoseError on pose kf_b[i] with origin target[i][:7]; else PoseGraphError(kf_a, kf_b) with
     target[i][:6] = rpyxyz_ (see relative_rpyxyz)."""
@@ -1397,6 +1444,23 @@ class Window:
         _chk(self.ctx.L.lvf_window_marginal(self.h, C.byref(opt), ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), _dp(info), _dp(cov), C.byref(st)))
         return _marginal_result(info, cov, st)
 
+    def set_lidar_planes(self, kf_id, p, pa, pb, pc, weight=None, huber_a=None):
+        """the plane blocks of keyframe kf_id's sweep (lidar_pose_batch's arrays); replaces that keyframe's set, empty arrays remove it"""
+        p, pa, pb, pc = _d(p).reshape(-1, 3), _d(pa).reshape(-1, 3), _d(pb).reshape(-1, 3), _d(pc).reshape(-1, 3)
+        n = p.shape[0]
+        w, a = _opt_d(weight, n), _opt_d(huber_a, n)
+        _chk(self.ctx.L.lvf_window_set_lidar_planes(self.h, int(kf_id), n, _dp(p), _dp(pa), _dp(pb), _dp(pc), _dp(w) if w is not None else None,
+                                                    _dp(a) if a is not None else None))
+
+    def set_lidar_scan(self, kf_id, map_, scan, weight=1.0, huber_a=0.0):
+        """the same from what knn3 left in `scan` against `map_`, gathered on the device"""
+        _chk(self.ctx.L.lvf_window_set_lidar_scan(self.h, int(kf_id), map_.h, scan.h, float(weight), float(huber_a)))
+
+    def lidar_count(self):
+        n = np.zeros(1, np.int32)
+        _chk(self.ctx.L.lvf_window_lidar_count(self.h, _ip(n)))
+        return int(n[0])
+
     def counts(self):
         c = np.zeros(8, np.int32)
         _chk(self.ctx.L.lvf_window_counts(self.h, _ip(c)))
@@ -1512,6 +1576,10 @@ class Problem:
 
     def set_pose_priors(self, batch):
         _chk(self.ctx.L.lvf_problem_set_pose_priors(self.h, batch.h if batch is not None else None))
+
+    def set_lidar_planes(self, batch):
+        """adds (None: removes) LiDAR plane blocks on the keyframe poses (lidar_pose_batch / lidar_pose_from_scans); the batch is borrowed"""
+        _chk(self.ctx.L.lvf_problem_set_lidar_planes(self.h, batch.h if batch is not None else None))
 
     def set_pose_constant(self, kf, const=True):
         _chk(self.ctx.L.lvf_problem_set_pose_constant(self.h, int(kf), 1 if const else 0))

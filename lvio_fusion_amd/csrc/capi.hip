@@ -535,6 +535,9 @@ int lvf_batch_evaluate(lvf_batch* b, const lvf_state* st, const double* rpyxyz, 
       case LVF_K_POSE_PRIOR:
         LVF_REQUIRE(st->n_kf >= b->min_n_kf, "pose-prior batch indices exceed the state (n_kf=%d)", st->n_kf);
         rc = launch_pose_prior(b, st, wj); break;
+      case LVF_K_LIDAR_POSE:
+        LVF_REQUIRE(st->n_kf >= b->min_n_kf, "lidar-pose batch indices exceed the state (n_kf=%d)", st->n_kf);
+        rc = launch_lidar_pose(b, st, wj); break;
       default: set_error("unknown batch kind %d", b->kind); return LVF_ERR_INVALID;
     }
   }
@@ -560,7 +563,7 @@ int lvf_batch_download_jacobian(lvf_batch* b, int block, double* host) {
 }
 int lvf_batch_download_normals(lvf_batch* b, double* host) {
   LVF_REQUIRE(b && host, "lvf_batch_download_normals: null argument");
-  LVF_REQUIRE(b->kind == LVF_K_LIDAR, "normals exist only for lidar batches");
+  LVF_REQUIRE(b->kind == LVF_K_LIDAR || b->kind == LVF_K_LIDAR_POSE, "normals exist only for lidar batches");
   std::vector<double> soa((size_t)3 * b->n);
   LVF_TRY(download(b, b->lnrm.p, soa.data(), soa.size()));
   for (int i = 0; i < b->n; ++i) { host[3 * i] = soa[i]; host[3 * i + 1] = soa[(size_t)b->n + i]; host[3 * i + 2] = soa[(size_t)2 * b->n + i]; }

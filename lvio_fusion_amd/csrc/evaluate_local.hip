@@ -17,6 +17,7 @@ struct LocalDesc {
   const double* res;               // [n][R]
   const double* poses;             // [n_kf][7]
   double huber;                    // <= 0: no robustification
+  const double* huber_blk;         // per-block thresholds (lidar planes on poses), or null: `huber` for every block
   int robust_rows;                 // rows whose squared norm feeds the loss (= R for the visual functors)
 };
 
@@ -25,11 +26,12 @@ __global__ __launch_bounds__(256) void k_to_local(LocalDesc d, double* __restric
   if (e >= d.n * d.R) return;
   const int i = e / d.R;
   double sc = 1.0;
-  if (d.huber > 0.0) {
+  const double a = d.huber_blk ? d.huber_blk[i] : d.huber;
+  if (a > 0.0) {
     double s = 0.0;
     for (int k = 0; k < d.robust_rows; ++k) { const double v = d.res[(size_t)i * d.R + k]; s += v * v; }
     double rho;
-    sc = robust_scale(d.huber, s, rho);
+    sc = robust_scale(a, s, rho);
   }
   out_res[e] = sc * d.res[e];
   double* o = out_jac + (size_t)e * d.L;
@@ -76,7 +78,7 @@ int lvf_batch_evaluate_local(lvf_batch* b, const lvf_state* st, double huber_a, 
   LVF_TRY(lvf_batch_evaluate(b, st, nullptr, jacobians_local ? 1 : 0));
   if (b->n == 0) return LVF_OK;
   hipStream_t s = b->ctx->stream;
-  if (!jacobians_local && !(huber_a > 0.0)) return lvf_batch_download_residuals(b, residuals);
+  if (!jacobians_local && !(huber_a > 0.0) && b->kind != LVF_K_LIDAR_POSE) return lvf_batch_download_residuals(b, residuals);
   LocalDesc d{};
   d.n = b->n; d.R = b->n_res; d.nb = jacobians_local ? b->n_blocks : 0; d.L = lvf_batch_local_columns(b);
   d.res = b->res.p; d.poses = st->poses.p;
@@ -89,6 +91,7 @@ int lvf_batch_evaluate_local(lvf_batch* b, const lvf_state* st, double huber_a, 
     case LVF_K_TWO_FRAME: d.kf[1] = b->idx_b.p; d.kf[2] = b->idx_c.p; break;
     case LVF_K_IMU: d.kf[0] = b->idx_a.p; d.kf[4] = b->idx_b.p; break;
     case LVF_K_POSE_PRIOR: d.kf[0] = b->idx_a.p; d.kf[1] = b->idx_b.p; break;
+    case LVF_K_LIDAR_POSE: d.kf[0] = b->idx_a.p; d.huber_blk = b->ob_b.p; break;      // the batch's own per-block loss (huber_a does not apply)
     default: break;
   }
   DevBuf<double> orr, oj;

@@ -354,7 +354,7 @@ struct lvf_state {
   lvf::DevBuf<double> poses, vel, ba, bg, inv_depth, w_visual;
 };
 
-enum lvf_batch_kind { LVF_K_POSE_ONLY = 0, LVF_K_TWO_FRAME = 1, LVF_K_TWO_CAMERA = 2, LVF_K_IMU = 3, LVF_K_LIDAR = 4, LVF_K_POSE_PRIOR = 5 };
+enum lvf_batch_kind { LVF_K_POSE_ONLY = 0, LVF_K_TWO_FRAME = 1, LVF_K_TWO_CAMERA = 2, LVF_K_IMU = 3, LVF_K_LIDAR = 4, LVF_K_POSE_PRIOR = 5, LVF_K_LIDAR_POSE = 6 };
 
 struct lvf_batch {
   lvf_ctx* ctx = nullptr;
@@ -384,6 +384,9 @@ struct lvf_batch {
   lvf::DevBuf<double> lp, lpa, lnrm;     // SoA [3][n]
   lvf::DevBuf<char> icp_dev;             // device LM state of lvf_lidar_solve
   lvf::HostPin<char> icp_host;           // its pinned host mirror (initial state up, result down: real asynchronous copies)
+  // lidar planes on keyframe poses (LVF_K_LIDAR_POSE): lp | lpa | lnrm as above, idx_a = keyframe, ob_a = weight [n], ob_b = huber_a [n] (<= 0: no loss)
+  lvf::DevBuf<int> n_valid_dev;          // blocks of weight > 0, counted by the launch that built the batch on the device ...
+  int n_valid = -1;                      // ... or on the host at creation (-1: still on the device, lvf_lidar_pose_num_valid fetches it)
   // imu
   lvf::DevBuf<double> pre;               // [n][467] flattened lvf_preint
   lvf::DevBuf<double> sqrt_info;         // [n][225]
@@ -662,5 +665,6 @@ int launch_imu_args(hipStream_t s, const ImuArgs& a, bool want_j);
 int launch_imu_table(hipStream_t s, const ImuArgs* table_dev, int n_windows, int max_blocks, bool want_j);
 constexpr int kImuZeroWgs = 4096;
 int launch_pose_prior(lvf_batch* b, const lvf_state* st, bool want_j);
+int launch_lidar_pose(lvf_batch* b, const lvf_state* st, bool want_j);      // solver_lidar.hip
 void make_camd(const lvf_camera& c, CamD& d);
 }  // namespace lvf

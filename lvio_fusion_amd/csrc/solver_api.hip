@@ -27,7 +27,8 @@ static const char* const kStageNames[ST_N] = {"k_zero_multi (only when the accum
 
 void summary_from_ctl(const lvf_problem* p, const LmCtl& c, lvf_solver_summary* s) {
   std::memset(s, 0, sizeof(*s));
-  s->num_residual_blocks = (p->tc ? p->tc->n : 0) + (p->tf ? p->tf->n : 0) + (p->po ? p->po->n : 0) + (p->imu ? p->imu->n : 0) + (p->prior ? p->prior->n : 0);
+  s->num_residual_blocks = (p->tc ? p->tc->n : 0) + (p->tf ? p->tf->n : 0) + (p->po ? p->po->n : 0) + (p->imu ? p->imu->n : 0) + (p->prior ? p->prior->n : 0) +
+                           (p->lidar ? p->lidar->n : 0);
   s->initial_cost = c.initial_cost; s->final_cost = c.cost; s->num_iterations = c.iter; s->num_successful_steps = c.successes; s->termination = c.termination;
   s->num_unsuccessful_steps = c.rejected; s->termination_reason = c.why; s->hand_over_retries = p->handover_retries;
 }
@@ -77,6 +78,19 @@ int lvf_problem_set_pose_priors(lvf_problem* p, lvf_batch* pose_priors) {
     LVF_REQUIRE(pose_priors->min_n_kf <= p->n_kf, "pose-prior batch references keyframe %d but the window has %d", pose_priors->min_n_kf - 1, p->n_kf);
   }
   p->prior = pose_priors;
+  p->linearized = false;
+  p->chain_ready = false;
+  return LVF_OK;
+}
+
+int lvf_problem_set_lidar_planes(lvf_problem* p, lvf_batch* lidar_planes) {
+  LVF_REQUIRE(p, "lvf_problem_set_lidar_planes: null problem");
+  if (lidar_planes) {
+    LVF_REQUIRE(lidar_planes->kind == LVF_K_LIDAR_POSE, "lidar_planes batch has the wrong kind");
+    LVF_REQUIRE(lidar_planes->ctx == p->ctx, "batch belongs to another context");
+    LVF_REQUIRE(lidar_planes->min_n_kf <= p->n_kf, "lidar-plane batch references keyframe %d but the window has %d", lidar_planes->min_n_kf - 1, p->n_kf);
+  }
+  p->lidar = lidar_planes;
   p->linearized = false;
   p->chain_ready = false;
   return LVF_OK;

@@ -63,7 +63,7 @@ int launch_override_reduced(hipStream_t q, int d, int ld, int aug, const int* pe
 struct lvf_problem {
   lvf_ctx* ctx = nullptr;
   lvf_state* st = nullptr;
-  lvf_batch *tc = nullptr, *tf = nullptr, *po = nullptr, *imu = nullptr, *prior = nullptr;
+  lvf_batch *tc = nullptr, *tf = nullptr, *po = nullptr, *imu = nullptr, *prior = nullptr, *lidar = nullptr;
   int n_kf = 0, n_lm = 0, d = 0, dp = 0, ldE = 0, dpad = 0, nb = 0;
   // layout of the factorised matrix S (see "elimination order" in solver_assemble.hip): [sparse (v,ba,bg) blocks | dense (v,ba,bg) blocks | poses | rhs row | pad]
   int ld = 0, off = 0, off_pose = 0, ndense = 0, aug = 0, sp_wstride = 0;
@@ -380,6 +380,12 @@ __global__ void k_prior_lin(PriorArgs P, const double* __restrict__ poses, const
     int ld, double* __restrict__ gc, double* __restrict__ cost);
 __global__ void k_prior_cost(PriorArgs P, const double* __restrict__ poses, double* __restrict__ cost);
 __global__ void k_cost_sq(int n, const double* __restrict__ res, double* __restrict__ cost);
+// LiDAR planes on keyframe poses (solver_lidar.hip): p | pa | nrm SoA [3][n], the block's keyframe, weight and Huber a (<= 0: no loss)
+struct LidarPoseArgs { int n; GP<const double> p, pa, nrm; GP<const int> kf; GP<const double> w, a; };
+static inline LidarPoseArgs lidar_pose_args(const lvf_batch* b) { return LidarPoseArgs{b->n, b->lp.p, b->lpa.p, b->lnrm.p, b->idx_a.p, b->ob_a.p, b->ob_b.p}; }
+__global__ void k_lidar_lin(LidarPoseArgs L, int n_kf, const double* __restrict__ poses, const uint8_t* __restrict__ pose_const, double* __restrict__ B,
+    int ld, double* __restrict__ gc, double* __restrict__ cost);
+__global__ void k_lidar_cost(LidarPoseArgs L, int n_kf, const double* __restrict__ poses, double* __restrict__ cost);
 __global__ void k_prepare(PrepArgs a);
 __global__ void k_prepare_b(const PrepArgs* __restrict__ t);
 __global__ void k_prepare_bt(const PrepArgs* __restrict__ t);

@@ -93,8 +93,8 @@ inline const SolverEnv& solver_env() {
 //   * stored as one entry per window in device tables, every launch of the chain then covering a whole batch of windows (blockIdx.y).
 struct Chain {
   bool fast = false;            // merged linearisation (sorted TwoFrame work list) available
-  bool batchable = false;       // every launch of the iteration has a table form (fast + band Schur merged with sparse level 0 + no priors)
-  bool has_imu = false, has_prior = false, imu_in_cost = false;
+  bool batchable = false;       // every launch of the iteration has a table form (fast + band Schur merged with sparse level 0 + no priors, no lidar planes)
+  bool has_imu = false, has_prior = false, has_lidar = false, imu_in_cost = false;
   ZeroList zero_end{};
   ZeroList zero{};              // everything a linearisation accumulates into (explicit k_zero_multi when the accumulators are not known clean)
   ImuArgs imu_lin{}, imu_cost{};

@@ -100,12 +100,18 @@ struct lvf_window {
   lvf::HostPin<unsigned char> h_stage;                   // the tick's packed upload (records + plain segments)
   lvf::DevBuf<unsigned char> d_stage;
   lvf_problem* prob = nullptr;
+  // LiDAR planes (lvf_window_set_lidar_planes / _set_lidar_scan): one device segment per keyframe id (a batch on keyframe 0), concatenated in
+  // active-keyframe order into `lidar` whenever a segment or the keyframes' positions changed; nothing here exists until a segment is set
+  std::unordered_map<int64_t, lvf_batch*> lidar_seg;
+  lvf_batch* lidar = nullptr;
+  bool lidar_dirty = false;
   // assembly of the last solve
   std::vector<int> slot_lm;                              // dense landmark slot -> index into lms
   int n_tc = 0, n_tf = 0, n_po = 0, n_imu = 0, n_prior = 0, n_lm_problem = 0;
   ~lvf_window() {
     if (prob) lvf_problem_destroy(prob);
-    for (lvf_batch* b : {tc, tf, po, imu, prior, rej}) if (b) lvf_batch_destroy(b);
+    for (lvf_batch* b : {tc, tf, po, imu, prior, rej, lidar}) if (b) lvf_batch_destroy(b);
+    for (auto& kv : lidar_seg) lvf_batch_destroy(kv.second);
     if (st) lvf_state_destroy(st);
     if (rej_st) lvf_state_destroy(rej_st);
     if (ev_counts) (void)hipEventDestroy(ev_counts);
@@ -626,6 +632,11 @@ int lvf_window_slide(lvf_window* w, int64_t first_active_kf_id) {
       if (it != w->departed.end()) { to_world(w->right, l.right_ob, l.inv_depth, it->second.data(), l.pw); l.fixed = true; w->mark_lm((int)i); }
     }
   }
+  for (size_t k = 0; k < drop; ++k) {
+    auto is = w->lidar_seg.find(w->kfs[k].id);
+    if (is != w->lidar_seg.end()) { lvf_batch_destroy(is->second); w->lidar_seg.erase(is); }
+  }
+  if (w->lidar) w->lidar_dirty = true;                     // (the positions of the keyframes that stay have changed)
   w->kfs.erase(w->kfs.begin(), w->kfs.begin() + drop);
   w->kf_index.clear();
   for (size_t k = 0; k < w->kfs.size(); ++k) w->kf_index[w->kfs[k].id] = (int)k;
@@ -666,6 +677,41 @@ int lvf_window_get_inv_depth(const lvf_window* w, int64_t lm_id, double* inv_dep
   *inv_depth = w->lms[il->second].inv_depth;
   return LVF_OK;
 }
+static int window_put_lidar_segment(lvf_window* w, int64_t kf_id, lvf_batch* seg) {
+  auto is = w->lidar_seg.find(kf_id);
+  if (is != w->lidar_seg.end()) { lvf_batch_destroy(is->second); w->lidar_seg.erase(is); }
+  if (seg && seg->n) w->lidar_seg[kf_id] = seg; else if (seg) lvf_batch_destroy(seg);
+  w->lidar_dirty = true;
+  return LVF_OK;
+}
+int lvf_window_set_lidar_planes(lvf_window* w, int64_t kf_id, int n, const double* p, const double* pa, const double* pb, const double* pc, const double* weight,
+                                const double* huber_a) {
+  LVF_REQUIRE(w, "lvf_window_set_lidar_planes: null window");
+  LVF_REQUIRE(w->kf_index.count(kf_id), "lvf_window_set_lidar_planes: keyframe %lld is not in the window", (long long)kf_id);
+  LVF_REQUIRE(n >= 0, "lvf_window_set_lidar_planes: negative size");
+  lvf_batch* seg = nullptr;
+  if (n > 0) {
+    const std::vector<int32_t> kf((size_t)n, 0);
+    LVF_TRY(lvf_lidar_pose_create(w->ctx, n, p, pa, pb, pc, kf.data(), weight, huber_a, &seg));
+  }
+  return window_put_lidar_segment(w, kf_id, seg);
+}
+int lvf_window_set_lidar_scan(lvf_window* w, int64_t kf_id, lvf_map* map, lvf_scan* scan, double weight, double huber_a) {
+  LVF_REQUIRE(w && map && scan, "lvf_window_set_lidar_scan: null argument");
+  LVF_REQUIRE(w->kf_index.count(kf_id), "lvf_window_set_lidar_scan: keyframe %lld is not in the window", (long long)kf_id);
+  const int32_t kf = 0;
+  lvf_batch* seg = nullptr;
+  LVF_TRY(lvf_lidar_pose_from_scans(w->ctx, 1, &map, &scan, &kf, &weight, &huber_a, &seg));
+  return window_put_lidar_segment(w, kf_id, seg);
+}
+/* lidar plane blocks the window holds for its active keyframes (zero-weight blocks of failed queries included) */
+int lvf_window_lidar_count(const lvf_window* w, int32_t* n) {
+  LVF_REQUIRE(w && n, "lvf_window_lidar_count: null argument");
+  long long total = 0;
+  for (const auto& kv : w->lidar_seg) total += kv.second->n;
+  *n = (int32_t)total;
+  return LVF_OK;
+}
 int lvf_window_counts(const lvf_window* w, int32_t* counts8) {
   LVF_REQUIRE(w && counts8, "lvf_window_counts: null argument");
   counts8[0] = (int)w->kfs.size(); counts8[1] = w->n_lm_problem; counts8[2] = w->n_tc; counts8[3] = w->n_tf; counts8[4] = w->n_po;
@@ -676,6 +722,21 @@ int lvf_window_counts(const lvf_window* w, int32_t* counts8) {
 
 // lvf_window_solve with the block lists assembled on the device (see "device-side assembly" above).
 }  // extern "C"
+namespace lvf { int lidar_pose_assemble(lvf_ctx* ctx, int n_kf, lvf_batch* const* seg, lvf_batch** dst); }      // solver_lidar.hip
+// the window's lidar planes -> its problem, behind the assembly of the other blocks (a window that never had a segment does nothing here)
+static int window_attach_lidar(lvf_window* w) {
+  if (!w->lidar && !w->lidar_dirty) return LVF_OK;
+  if (w->lidar_dirty) {
+    std::vector<lvf_batch*> seg(w->kfs.size(), nullptr);
+    for (size_t k = 0; k < w->kfs.size(); ++k) {
+      auto is = w->lidar_seg.find(w->kfs[k].id);
+      if (is != w->lidar_seg.end()) seg[k] = is->second;
+    }
+    LVF_TRY(lvf::lidar_pose_assemble(w->ctx, (int)seg.size(), seg.data(), &w->lidar));
+    w->lidar_dirty = false;
+  }
+  return lvf_problem_set_lidar_planes(w->prob, w->lidar->n ? w->lidar : nullptr);
+}
 static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_solver_summary* summary) {
   lvf_ctx* ctx = w->ctx;
   hipStream_t s = ctx->stream;
@@ -964,6 +1025,7 @@ static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_s
   } else {
     LVF_TRY(problem_configure(w->prob));
   }
+  LVF_TRY(window_attach_lidar(w));
   const auto t_configured = now();
   // ---- solve, with the read-back (poses, velocities, biases by keyframe position; inverse depths in landmark-index order) enqueued
   // behind the last iteration and ahead of the wait that ends the solve: ONE stream wait per tick for both
@@ -1226,6 +1288,7 @@ int lvf_window_solve(lvf_window* w, const lvf_solver_options* o, lvf_solver_summ
   } else {
     LVF_TRY(problem_configure(w->prob));
   }
+  LVF_TRY(window_attach_lidar(w));
   const auto t_configured = now();
   LVF_TRY(lvf_problem_solve(w->prob, o, summary));
   const auto t_solved = now();
