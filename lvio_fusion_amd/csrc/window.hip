@@ -12,15 +12,22 @@
 //   good_imu frame after a good_imu frame              -> ImuError                                            :143-161
 //   no IMU block and < 20 near visual blocks           -> PoseGraphError(last, k, 100, 0) / PoseError(k, 100, 0)  :163-178
 // ("near" = !Camera::Far: depth in cam0 <= 50 baselines, include/lvio_fusion/visual/camera.h:38-41) — in frame order, features
-// by ascending landmark id (features_left is a std::map keyed by landmark id), uploads them with one copy per array and runs
-// the device LM loop; results are read back into the host mirror.
+// by ascending landmark id (features_left is a std::map keyed by landmark id), uploads them and runs the device LM loop; results
+// are read back into the host mirror.
+//
+// This file is the host side: lvf_window, the mirror's bookkeeping, the C entries and the tick.  The kernels are in window_kernels.hip,
+// what the two share (table records, argument blocks) in window_args.hpp.  A tick (lvf_window_solve) is: ensure_objects (state and
+// batches, created once); the assembly by ONE of two strategies — assemble_device (resident tables, k_da_*) or assemble_host (the host
+// walks the features) — which share every step but the classification (stage_state, imu_pairs / shape_imu_batch, weak_prior /
+// shape_prior_batch, ensure_visual / set_visual_counts); configure_problem; the solve with enqueue_read_back riding behind its last
+// iteration; apply_read_back into the mirror.  begin_assembly is the one place where a strategy drops what the other left behind.
 #include <algorithm>
 #include <chrono>
 #include <iterator>
 #include <map>
 #include <unordered_map>
 #include "host_se3.hpp"
-#include "lvf_internal.hpp"
+#include "window_args.hpp"
 
 namespace lvf {
 struct alignas(64) LmHot { double right_ob[2]; double pw[3]; int64_t birth_kf; int bpos; int slot; int fixed; int pad; };
@@ -58,8 +65,7 @@ struct lvf_window {
     double left_ob[2], right_ob[2], inv_depth = 0.0;
     bool fixed = false;                                  // birth frame left the window: world point frozen
     double pw[3] = {0, 0, 0};
-    int slot = -1;                                       // dense index in the current assembly (-1: not in the problem)
-    bool alive = true;                                   // false: a free entry of `lms` (indices are STABLE: Obs::lm and the device tables keep them)
+    bool alive = true;                                  // false: a free entry of `lms` (indices are STABLE: Obs::lm and the device tables keep them)
   };
   lvf_ctx* ctx = nullptr;
   lvf_camera left, right;
@@ -106,7 +112,9 @@ struct lvf_window {
   lvf_batch* lidar = nullptr;
   bool lidar_dirty = false;
   // assembly of the last solve
-  std::vector<int> slot_lm;                              // dense landmark slot -> index into lms
+  enum class Assembler { none, host, device };
+  Assembler assembled_by = Assembler::none;              // who made the block lists that sit in the batches (see begin_assembly)
+  std::vector<int> slot_lm;                              // dense landmark slot -> index into lms (host assembly; the device's table is d_slot_lm)
   int n_tc = 0, n_tf = 0, n_po = 0, n_imu = 0, n_prior = 0, n_lm_problem = 0;
   ~lvf_window() {
     if (prob) lvf_problem_destroy(prob);
@@ -133,8 +141,6 @@ static void to_world(const lvf_camera& right, const double rob[2], double inv_de
   hse3::rotate(birth_pose, pb, r);
   for (int k = 0; k < 3; ++k) pw[k] = r[k] + birth_pose[4 + k];
 }
-template <typename T>
-static int put(DevBuf<T>& buf, const std::vector<T>& v, hipStream_t s) { return buf.assign(v.data(), v.size(), s); }
 
 // Keeps the host mirror bounded over a long run (the reference removes a landmark once its last observation is gone:
 // Landmark::RemoveObservation / Map::RemoveLandmark): landmarks no active keyframe observes any more are dropped and Obs::lm is
@@ -148,7 +154,7 @@ static void prune(lvf_window* w) {
     lvf_window::Lm& l = w->lms[i];
     if (l.alive && !seen[i]) {                 // the entry becomes free; nothing is moved, so every index held elsewhere stays valid
       w->lm_index.erase(l.id);
-      l.alive = false; l.fixed = false; l.slot = -1;
+      l.alive = false; l.fixed = false;
       w->mark_lm((int)i);
       w->lm_free.push_back((int)i);
       --w->n_lm_live;
@@ -161,31 +167,26 @@ static void prune(lvf_window* w) {
   }
 }
 
-// landmark->ToWorld() (src/lvio_fusion/src/landmark.cpp:15-19) for every landmark of the mirror: frozen points as stored, live ones
-// from their birth keyframe's CURRENT pose and inverse depth.  lm_birth_pos[i] = position of the birth keyframe in kfs (-1: not active).
-// Rk[9 k] = rotation of keyframe k (row-major), Rk[9 n_kf] = rotation of the right camera's extrinsic (same construction as in
-// landmarks_to_world: the device-side assembly multiplies with exactly these matrices)
+// the rotation of a unit quaternion, row-major
+static void rot_of(const double q[4], double R[9]) {
+  double e0[3] = {1, 0, 0}, e1[3] = {0, 1, 0}, e2[3] = {0, 0, 1}, c0[3], c1[3], c2[3];
+  hse3::rotate(q, e0, c0); hse3::rotate(q, e1, c1); hse3::rotate(q, e2, c2);
+  R[0] = c0[0]; R[1] = c1[0]; R[2] = c2[0]; R[3] = c0[1]; R[4] = c1[1]; R[5] = c2[1]; R[6] = c0[2]; R[7] = c1[2]; R[8] = c2[2];
+}
+// Rk[9 k] = rotation of keyframe k, Rk[9 n_kf] = rotation of the right camera's extrinsic: the matrices both landmarks_to_world and the
+// device-side assembly (FrameDev::R, DaArgs::Re) multiply with
 static void landmarks_to_world_prepare(const lvf_window* w, double* Rk) {
   const int n_kf = (int)w->kfs.size();
-  auto rot_of = [](const double q[4], double R[9]) {
-    double e0[3] = {1, 0, 0}, e1[3] = {0, 1, 0}, e2[3] = {0, 0, 1}, c0[3], c1[3], c2[3];
-    hse3::rotate(q, e0, c0); hse3::rotate(q, e1, c1); hse3::rotate(q, e2, c2);
-    R[0] = c0[0]; R[1] = c1[0]; R[2] = c2[0]; R[3] = c0[1]; R[4] = c1[1]; R[5] = c2[1]; R[6] = c0[2]; R[7] = c1[2]; R[8] = c2[2];
-  };
   for (int k = 0; k < n_kf; ++k) rot_of(w->kfs[k].pose, Rk + (size_t)9 * k);
   rot_of(w->right.extrinsic, Rk + (size_t)9 * n_kf);
 }
+// landmark->ToWorld() (src/lvio_fusion/src/landmark.cpp:15-19) for every landmark of the mirror: frozen points as stored, live ones
+// from their birth keyframe's CURRENT pose and inverse depth.  lm_birth_pos[i] = position of the birth keyframe in kfs (-1: not active).
 static void landmarks_to_world(const lvf_window* w, std::vector<double>& lm_pw, std::vector<int>& lm_birth_pos) {
   const int n_kf = (int)w->kfs.size();
-  auto rot_of = [](const double q[4], double R[9]) {
-    double e0[3] = {1, 0, 0}, e1[3] = {0, 1, 0}, e2[3] = {0, 0, 1}, c0[3], c1[3], c2[3];
-    hse3::rotate(q, e0, c0); hse3::rotate(q, e1, c1); hse3::rotate(q, e2, c2);
-    R[0] = c0[0]; R[1] = c1[0]; R[2] = c2[0]; R[3] = c0[1]; R[4] = c1[1]; R[5] = c2[1]; R[6] = c0[2]; R[7] = c1[2]; R[8] = c2[2];
-  };
-  std::vector<double> Rk((size_t)9 * n_kf);
-  for (int k = 0; k < n_kf; ++k) rot_of(w->kfs[k].pose, &Rk[(size_t)9 * k]);
-  double Re[9];
-  rot_of(w->right.extrinsic, Re);
+  std::vector<double> Rk((size_t)9 * n_kf + 9);
+  landmarks_to_world_prepare(w, Rk.data());
+  const double* Re = &Rk[(size_t)9 * n_kf];
   const double* te = w->right.extrinsic + 4;
   const size_t nl = w->lms.size();
   lm_pw.assign((size_t)3 * nl, 0.0);
@@ -232,299 +233,6 @@ static void landmarks_hot(const lvf_window* w, std::vector<LmHot>& hot) {
   }
 }
 
-// ================================================================================================ device-side assembly
-// The block lists of a tick assembled ON THE DEVICE from resident tables, so that the host neither walks ~10^5 features nor uploads
-// ~4 MB of lists per tick:
-//   feature arena   obs_lm[i] (landmark INDEX, stable: lvf_window::lms entries never move), obs_xy[i]; one segment per keyframe, in
-//                   BuildProblem's order (ascending landmark id); only new / changed keyframes are uploaded
-//   landmark table  LmDev[nl] (first observation, inverse depth, birth keyframe id, frozen world point) — re-sent every tick (64 B each)
-//   frame table     FrameDev[n_kf] (id, segment, rotation + translation for Landmark::ToWorld, the Camera::Far row) — every tick
-// k_da_classify : one thread per feature -> block type (BuildProblem's rules), per-workgroup and per-keyframe counts, landmarks in use
-// k_da_scan     : one workgroup: output offsets per workgroup and type (features keep their order: keyframe by keyframe, ascending
-//                 landmark id), dense landmark slots (ascending landmark index), inverse depths into the state
-// k_da_emit     : one thread per feature -> its block's SoA entries
-// The host reads back 4 + 2 n_kf counters (block totals, TwoFrame blocks and near visual blocks per keyframe) for the work list, the
-// IMU / prior decisions and the launch shapes.
-struct LmDev { double right_ob[2]; double pw[3]; double inv_depth; long long birth_kf; int fixed; int alive; };
-// w_tc: the weight backend.cpp:123 hands TwoCameraReprojectionError::Create for a landmark born in this frame, `5 * frame->weights.visual` — a FLOAT
-// product (adapt/weights.h:10 declares the weights float), widened to double by the call: (double)(5.0f * (float)w_visual)
-struct FrameDev { long long id; int start, cnt; long long arena_off; double zrow[3], zoff; double R[9], t[3]; double w_tc; };
-static_assert(sizeof(LmDev) == 64 && sizeof(FrameDev) % 8 == 0, "device table records");
-constexpr int kDaMaxKf = 64;
-struct DaArgs {
-  int n_kf, total, nl, n_wg;
-  const FrameDev* frames; const int32_t* obs_lm; const double2* obs_xy; const LmDev* lm;
-  double Re[9], te[3], fx, fy, cx, cy, far_z;      // right camera (Landmark::ToWorld goes through it), Camera::Far threshold
-  unsigned char* cls; unsigned char* used; int* wgcnt; int* wgbase; int* slot; int* slot_lm; int* counts;   // counts: [0..3] tc, tf, po, n_lm | tf per kf [64] | near per kf [64]
-  double* state_invd; double* lm_invd_out;
-  double2 *tc_l, *tc_r; int32_t *tc_lm, *tc_kf; double* tc_w;
-  double2 *tf_f, *tf_o; int32_t *tf_lm, *tf_k1, *tf_k2;
-  double2* po_o; double* po_pw; int32_t *po_kf, *po_pi;
-};
-// frame of global feature index g (frames' segments concatenated); s_start[n_kf] = total
-__device__ __forceinline__ int da_frame_of(const int* s_start, int n_kf, int g) {
-  int lo = 0, hi = n_kf - 1;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_start[mid] <= g) lo = mid; else hi = mid - 1; }
-  return lo;
-}
-__device__ __forceinline__ int da_birth_pos(const long long* s_id, int n_kf, long long id) {
-  int lo = 0, hi = n_kf - 1;
-  while (lo <= hi) { const int mid = (lo + hi) >> 1; if (s_id[mid] == id) return mid; if (s_id[mid] < id) lo = mid + 1; else hi = mid - 1; }
-  return -1;
-}
-// Landmark::ToWorld (landmark.cpp:15-19) with the matrices the host expanded (same operation order as landmarks_to_world)
-__device__ __forceinline__ void da_to_world(const DaArgs& a, const LmDev& L, const FrameDev& B, double pw[3]) {
-  const double d = 1.0 / L.inv_depth;
-  const double ps[3] = {(L.right_ob[0] - a.cx) * d / a.fx, (L.right_ob[1] - a.cy) * d / a.fy, d};
-  const double pb[3] = {a.Re[0] * ps[0] + a.Re[1] * ps[1] + a.Re[2] * ps[2] + a.te[0], a.Re[3] * ps[0] + a.Re[4] * ps[1] + a.Re[5] * ps[2] + a.te[1],
-                        a.Re[6] * ps[0] + a.Re[7] * ps[1] + a.Re[8] * ps[2] + a.te[2]};
-  pw[0] = B.R[0] * pb[0] + B.R[1] * pb[1] + B.R[2] * pb[2] + B.t[0];
-  pw[1] = B.R[3] * pb[0] + B.R[4] * pb[1] + B.R[5] * pb[2] + B.t[1];
-  pw[2] = B.R[6] * pb[0] + B.R[7] * pb[1] + B.R[8] * pb[2] + B.t[2];
-}
-__global__ __launch_bounds__(256) void k_da_classify(DaArgs a) {
-  __shared__ int s_start[kDaMaxKf + 1];
-  __shared__ long long s_id[kDaMaxKf];
-  __shared__ int s_cnt[3], s_tf[kDaMaxKf], s_near[kDaMaxKf];
-  const int tid = threadIdx.x, g = blockIdx.x * 256 + tid;
-  if (tid < a.n_kf) { s_start[tid] = a.frames[tid].start; s_id[tid] = a.frames[tid].id; s_tf[tid] = 0; s_near[tid] = 0; }
-  if (tid == 0) s_start[a.n_kf] = a.total;
-  if (tid < 3) s_cnt[tid] = 0;
-  __syncthreads();
-  if (g < a.total) {
-    const int k = da_frame_of(s_start, a.n_kf, g);
-    const FrameDev F = a.frames[k];
-    const int lm = a.obs_lm[F.arena_off + (g - F.start)];
-    const LmDev L = a.lm[lm];
-    int c = 0;                                       // 0 none / 1 TwoCamera / 2 TwoFrame / 3 PoseOnly
-    if (L.birth_kf == F.id) c = 1;
-    else {
-      const int bpos = da_birth_pos(s_id, a.n_kf, L.birth_kf);
-      double pw[3];
-      if (bpos < 0) { if (L.fixed) { c = 3; pw[0] = L.pw[0]; pw[1] = L.pw[1]; pw[2] = L.pw[2]; } }
-      else { c = 2; da_to_world(a, L, a.frames[bpos], pw); }
-      if (c && !(F.zrow[0] * pw[0] + F.zrow[1] * pw[1] + F.zrow[2] * pw[2] + F.zoff > a.far_z)) atomicAdd(&s_near[k], 1);      // !Camera::Far
-      if (c == 2) atomicAdd(&s_tf[k], 1);
-    }
-    a.cls[g] = (unsigned char)c;
-    if (c) atomicAdd(&s_cnt[c - 1], 1);
-    if (c == 1 || c == 2) a.used[lm] = 1;
-  }
-  __syncthreads();
-  if (tid < 3) a.wgcnt[3 * blockIdx.x + tid] = s_cnt[tid];
-  if (tid < a.n_kf) {
-    if (s_tf[tid]) atomicAdd(&a.counts[4 + tid], s_tf[tid]);
-    if (s_near[tid]) atomicAdd(&a.counts[4 + kDaMaxKf + tid], s_near[tid]);
-  }
-}
-__global__ __launch_bounds__(1024) void k_da_scan(DaArgs a) {
-  // One workgroup, two barriers per 16 k landmarks: the scans run inside waves (shuffles), a Hillis-Steele scan of 1024 LDS entries
-  // (20 workgroup barriers each, 16 waves) and a per-thread walk over runs of 64-byte landmark records made this launch 35 us.
-  __shared__ int s_cnt[16 * 16];                    // used landmarks per (chunk, wave) of a pass, then their exclusive prefix
-  __shared__ int s_total;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  // (1) exclusive scan of the per-workgroup block counts: wave t takes type t, 64 workgroups at a time with a running carry
-  if (wv < 3) {
-    int carry = 0;
-    for (int sb = 0; sb < a.n_wg; sb += 8 * 64) {      // 512 workgroups per pass, their counts requested up front
-      int v[8];
-#pragma unroll
-      for (int g = 0; g < 8; ++g) { const int i = sb + 64 * g + lane; const int t = a.wgcnt[3 * min(i, a.n_wg - 1) + wv]; v[g] = i < a.n_wg ? t : 0; }
-#pragma unroll
-      for (int g = 0; g < 8; ++g) {
-        const int i = sb + 64 * g + lane;
-        const int inc = wave_incl_scan(v[g]);
-        if (i < a.n_wg) a.wgbase[3 * i + wv] = carry + inc - v[g];
-        carry += __shfl(inc, 63);
-      }
-    }
-    if (lane == 0) a.counts[wv] = carry;
-  }
-  // (2) dense landmark slots in ascending landmark index (thread = landmark: coalesced; rank = ballot prefix + wave prefix + chunk prefix).
-  // 16 k landmarks per pass, the `used` flags and inverse depths of a pass requested up front (a load inside the per-1024 loop is waited
-  // for before the next one is issued)
-  constexpr int kG = 16;
-  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-  int total = 0;
-  for (int sb = 0; sb < a.nl; sb += kG * 1024) {
-    unsigned ubits = 0;
-    double invd[kG];
-#pragma unroll
-    for (int g = 0; g < kG; ++g) {
-      const int l = sb + g * 1024 + tid, lc = min(l, a.nl - 1);
-      const unsigned char u = a.used[lc];                // (read unconditionally: behind `l < a.nl &&` each of the 16 loads sat in its own branch and was waited for there)
-      ubits |= ((l < a.nl) & (u != 0)) ? (1u << g) : 0u;
-      invd[g] = a.lm[lc].inv_depth;
-    }
-    int rank[kG];
-#pragma unroll
-    for (int g = 0; g < kG; ++g) {
-      const unsigned long long m = __ballot((ubits >> g) & 1u);
-      rank[g] = __popcll(m & below);
-      if (lane == 0) s_cnt[g * 16 + wv] = __popcll(m);
-    }
-    __syncthreads();
-    if (wv == 0) {
-      int carry = 0;
-#pragma unroll
-      for (int base = 0; base < kG * 16; base += 64) {
-        const int v = s_cnt[base + lane];
-        const int inc = wave_incl_scan(v);
-        s_cnt[base + lane] = carry + inc - v;
-        carry += __shfl(inc, 63);
-      }
-      if (lane == 0) s_total = carry;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int g = 0; g < kG; ++g) {
-      const int l = sb + g * 1024 + tid;
-      if (l < a.nl) {
-        a.lm_invd_out[l] = invd[g];
-        if ((ubits >> g) & 1u) { const int at = total + s_cnt[g * 16 + wv] + rank[g]; a.slot[l] = at; a.slot_lm[at] = l; a.state_invd[at] = invd[g]; }
-        else a.slot[l] = -1;
-      }
-    }
-    total += s_total;
-    __syncthreads();
-  }
-  if (tid == 0) a.counts[3] = total;
-}
-__global__ __launch_bounds__(256) void k_da_emit(DaArgs a) {
-  __shared__ int s_start[kDaMaxKf + 1];
-  __shared__ long long s_id[kDaMaxKf];
-  __shared__ int s_wave[4][3];
-  const int tid = threadIdx.x, g = blockIdx.x * 256 + tid, lane = tid & 63, wv = tid >> 6;
-  if (tid < a.n_kf) { s_start[tid] = a.frames[tid].start; s_id[tid] = a.frames[tid].id; }
-  if (tid == 0) s_start[a.n_kf] = a.total;
-  const int c = g < a.total ? a.cls[g] : 0;
-  // rank of this feature among the workgroup's features of the same type, in feature order
-  int rank = 0;
-  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-#pragma unroll
-  for (int t = 1; t <= 3; ++t) {
-    const unsigned long long m = __ballot(c == t);
-    if (c == t) rank = __popcll(m & below);
-    if (lane == 0) s_wave[wv][t - 1] = __popcll(m);
-  }
-  __syncthreads();
-  if (!c) return;
-  int idx = a.wgbase[3 * blockIdx.x + (c - 1)] + rank;
-  for (int w = 0; w < wv; ++w) idx += s_wave[w][c - 1];
-  const int k = da_frame_of(s_start, a.n_kf, g);
-  const FrameDev F = a.frames[k];
-  const long long i = F.arena_off + (g - F.start);
-  const int lm = a.obs_lm[i];
-  const double2 ob = a.obs_xy[i];
-  const LmDev L = a.lm[lm];
-  if (c == 1) {
-    a.tc_l[idx] = ob; a.tc_r[idx] = make_double2(L.right_ob[0], L.right_ob[1]); a.tc_lm[idx] = a.slot[lm]; a.tc_kf[idx] = k; a.tc_w[idx] = F.w_tc;
-  } else if (c == 2) {
-    a.tf_f[idx] = make_double2(L.right_ob[0], L.right_ob[1]); a.tf_o[idx] = ob; a.tf_lm[idx] = a.slot[lm];
-    a.tf_k1[idx] = da_birth_pos(s_id, a.n_kf, L.birth_kf); a.tf_k2[idx] = k;
-  } else {
-    a.po_o[idx] = ob; a.po_pw[3 * idx] = L.pw[0]; a.po_pw[3 * idx + 1] = L.pw[1]; a.po_pw[3 * idx + 2] = L.pw[2]; a.po_kf[idx] = k; a.po_pi[idx] = idx;
-  }
-}
-// after the solve: the landmarks' inverse depths back into landmark-index order (the host mirror is indexed that way)
-// ... and into the resident landmark table, which the next tick's assembly reads
-__global__ __launch_bounds__(256) void k_da_scatter_invd(int n_lm, const int* __restrict__ slot_lm, const double* __restrict__ state_invd, double* __restrict__ lm_invd_out,
-                                                         LmDev* __restrict__ lmtab) {
-  const int s = blockIdx.x * 256 + threadIdx.x;
-  if (s < n_lm) { const int l = slot_lm[s]; const double v = state_invd[s]; lm_invd_out[l] = v; lmtab[l].inv_depth = v; }
-}
-
-// the read-back mirror of k_window_unpack's plain segments: device arrays -> one contiguous staging block (then ONE device-to-host copy
-// instead of five, each a submission of its own)
-struct PackArgs { unsigned char* stage; int n_segs; const unsigned char* src[8]; size_t off[8]; unsigned words[8]; };
-__global__ __launch_bounds__(256) void k_window_pack(PackArgs a) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    if (k >= a.n_segs) break;
-    const uint4* src = reinterpret_cast<const uint4*>(a.src[k]);
-    uint4* dst = reinterpret_cast<uint4*>(a.stage + a.off[k]);
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < a.words[k]; i += gridDim.x * 256) dst[i] = src[i];
-  }
-}
-
-// flags[i] = 1 iff |residual_i| > max_err  (residual pairs of a PoseOnly pass with unit weights = pixel errors)
-__global__ __launch_bounds__(256) void k_flag_outliers(int n, const double2* __restrict__ res, double max_err, uint8_t* __restrict__ flags) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const double2 r = res[i];
-  flags[i] = sqrt(r.x * r.x + r.y * r.y) > max_err ? 1 : 0;      // Vector2d::norm() > 10 (backend.cpp:239)
-}
-
-// ---- the tick's upload: ONE host-to-device copy of a packed staging buffer, unpacked on the device.
-// The block lists used to go up as ~25 separate copies; each is a blit launch of its own (~5 us) behind ~10 us of submission latency,
-// and together they kept the GPU waiting for 0.33 ms per tick.  The host now writes one 48-byte record per block —
-//   TwoCamera {left ob, right ob, landmark slot, keyframe}   TwoFrame {first ob, ob, landmark slot, k1, k2}   PoseOnly {ob, pw, keyframe, table row}
-// — into one pinned buffer, followed by the small plain arrays (state, IMU pre-integrations and indices, priors); k_window_unpack turns
-// the records into the batches' SoA arrays and copies the plain segments to their buffers.
-struct TcRec { double l[2], r[2]; int32_t lm, kf; double w; };      // w: the block's weight (two_camera_weight)
-struct TfRec { double f[2], o[2]; int32_t lm, k1, k2, pad0; };
-struct PoRec { double o[2], pw[3]; int32_t kf, pi; };
-static_assert(sizeof(TcRec) == 48 && sizeof(TfRec) == 48 && sizeof(PoRec) == 48, "staging records are 48 bytes");
-constexpr int kMaxSegs = 96;            // (the whole UnpackArgs block stays under the 4 KB kernel-argument limit)
-struct UnpackArgs {
-  const unsigned char* stage;
-  int ntc, ntf, npo; size_t off_tc, off_tf, off_po;
-  double2 *tc_l, *tc_r; int32_t *tc_lm, *tc_kf; double* tc_w;
-  double2 *tf_f, *tf_o; int32_t *tf_lm, *tf_k1, *tf_k2;
-  double2* po_o; double* po_pw; int32_t *po_kf, *po_pi;
-  int n_segs; unsigned char* seg_dst[kMaxSegs]; size_t seg_off[kMaxSegs]; unsigned seg_words[kMaxSegs];   // 16-byte words (sizes are padded up)
-  int g_tc, g_tf, g_po, g_seg;
-  unsigned char* zero_dst[2]; unsigned zero_words[2];      // buffers cleared by the same launch (16-byte words)
-  // changed entries of the resident landmark table: record j (64 bytes at rec_off + 64 j) goes to entry idx[j] (int32 at idx_off + 4 j)
-  int n_lm_dirty; size_t lm_idx_off, lm_rec_off; unsigned char* lmtab;
-};
-__global__ __launch_bounds__(256) void k_window_unpack(UnpackArgs a) {
-  int b = blockIdx.x;
-  const int t = threadIdx.x;
-  if (b < a.g_tc) {
-    const int i = b * 256 + t;
-    if (i < a.ntc) { const TcRec r = reinterpret_cast<const TcRec*>(a.stage + a.off_tc)[i]; a.tc_l[i] = make_double2(r.l[0], r.l[1]); a.tc_r[i] = make_double2(r.r[0], r.r[1]); a.tc_lm[i] = r.lm; a.tc_kf[i] = r.kf; if (a.tc_w) a.tc_w[i] = r.w; }
-    return;
-  }
-  b -= a.g_tc;
-  if (b < a.g_tf) {
-    const int i = b * 256 + t;
-    if (i < a.ntf) {
-      const TfRec r = reinterpret_cast<const TfRec*>(a.stage + a.off_tf)[i];
-      a.tf_f[i] = make_double2(r.f[0], r.f[1]); a.tf_o[i] = make_double2(r.o[0], r.o[1]); a.tf_lm[i] = r.lm; a.tf_k1[i] = r.k1; a.tf_k2[i] = r.k2;
-    }
-    return;
-  }
-  b -= a.g_tf;
-  if (b < a.g_po) {
-    const int i = b * 256 + t;
-    if (i < a.npo) {
-      const PoRec r = reinterpret_cast<const PoRec*>(a.stage + a.off_po)[i];
-      a.po_o[i] = make_double2(r.o[0], r.o[1]); a.po_pw[3 * i] = r.pw[0]; a.po_pw[3 * i + 1] = r.pw[1]; a.po_pw[3 * i + 2] = r.pw[2]; a.po_kf[i] = r.kf; a.po_pi[i] = r.pi;
-    }
-    return;
-  }
-  b -= a.g_po;
-  // plain segments: workgroup b strides over every segment (static indices only: no scratch)
-#pragma unroll
-  for (int k = 0; k < kMaxSegs; ++k) {
-    if (k >= a.n_segs) break;
-    const uint4* src = reinterpret_cast<const uint4*>(a.stage + a.seg_off[k]);
-    uint4* dst = reinterpret_cast<uint4*>(a.seg_dst[k]);
-    for (unsigned i = (unsigned)b * 256 + t; i < a.seg_words[k]; i += (unsigned)a.g_seg * 256) dst[i] = src[i];
-  }
-  {
-    const int32_t* idx = reinterpret_cast<const int32_t*>(a.stage + a.lm_idx_off);
-    const uint4* rec = reinterpret_cast<const uint4*>(a.stage + a.lm_rec_off);
-    for (unsigned i = (unsigned)b * 256 + t; i < 4u * (unsigned)a.n_lm_dirty; i += (unsigned)a.g_seg * 256)
-      reinterpret_cast<uint4*>(a.lmtab)[4 * (size_t)idx[i >> 2] + (i & 3)] = rec[i];
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    uint4* dst = reinterpret_cast<uint4*>(a.zero_dst[k]);
-    for (unsigned i = (unsigned)b * 256 + t; i < a.zero_words[k]; i += (unsigned)a.g_seg * 256) dst[i] = make_uint4(0, 0, 0, 0);
-  }
-}
 
 }  // namespace lvf
 
@@ -719,9 +427,9 @@ int lvf_window_counts(const lvf_window* w, int32_t* counts8) {
   return LVF_OK;
 }
 
-
-// lvf_window_solve with the block lists assembled on the device (see "device-side assembly" above).
 }  // extern "C"
+
+// ================================================================================================ the tick (lvf_window_solve)
 namespace lvf { int lidar_pose_assemble(lvf_ctx* ctx, int n_kf, lvf_batch* const* seg, lvf_batch** dst); }      // solver_lidar.hip
 // the window's lidar planes -> its problem, behind the assembly of the other blocks (a window that never had a segment does nothing here)
 static int window_attach_lidar(lvf_window* w) {
@@ -737,26 +445,255 @@ static int window_attach_lidar(lvf_window* w) {
   }
   return lvf_problem_set_lidar_planes(w->prob, w->lidar->n ? w->lidar : nullptr);
 }
-static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_solver_summary* summary) {
-  lvf_ctx* ctx = w->ctx;
-  hipStream_t s = ctx->stream;
-  const int n_kf = (int)w->kfs.size();
-  static const bool timing = getenv("LVF_WINDOW_TIMING") != nullptr;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const auto t_begin = now();
-  const size_t nl = w->lms.size();
-  // ---- persistent device objects
-  if (!w->st) {
-    LVF_TRY(lvf_state_create(ctx, 0, 0, &w->st));
-    const double z2[2] = {0, 0}; const int32_t z = 0; const double id7[7] = {0, 0, 0, 1, 0, 0, 0};
-    LVF_TRY(lvf_two_camera_create(ctx, &w->left, &w->right, 0, z2, z2, &z, &z, &w->tc));
-    LVF_TRY(lvf_two_frame_create(ctx, &w->left, &w->right, 0, z2, z2, &z, &z, &z, &w->tf));
-    LVF_TRY(lvf_pose_only_create(ctx, &w->left, 0, z2, &z, &z, 0, id7, &w->po));
-    LVF_TRY(lvf_imu_create(ctx, 0, nullptr, nullptr, nullptr, &w->imu));
-    LVF_TRY(lvf_pose_prior_create(ctx, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &w->prior));
+
+using Clock = std::chrono::steady_clock;
+static double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+static bool window_timing() { static const bool on = getenv("LVF_WINDOW_TIMING") != nullptr; return on; }
+
+// every segment of a staging block starts on a 16-byte boundary: k_window_unpack / k_window_pack copy 16-byte words (and every destination
+// has two spare elements for the last word)
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// Writes a tick's upload into the pinned staging block from `start` on and builds the UnpackArgs that distribute it on the device.
+struct StageWriter {
+  unsigned char* base; size_t cap, cur; UnpackArgs ua{}; bool overflow = false;
+  StageWriter(const HostPin<unsigned char>& h, size_t start) : base(h.p), cap(h.cap), cur(start) {}
+  // room that no plain segment describes (the landmark table's dirty records); *off = its place in the block
+  unsigned char* raw(size_t bytes, size_t* off) { *off = cur; cur += up16(bytes); return base + *off; }
+  // `bytes` that k_window_unpack copies to `dst`; returns where the host writes them
+  unsigned char* seg(void* dst, size_t bytes) {
+    size_t off;
+    unsigned char* at = raw(bytes, &off);
+    if (bytes && ua.n_segs == kMaxSegs) overflow = true;
+    else if (bytes) { ua.seg_dst[ua.n_segs] = static_cast<unsigned char*>(dst); ua.seg_off[ua.n_segs] = off; ua.seg_words[ua.n_segs] = (unsigned)((bytes + 15) / 16); ++ua.n_segs; }
+    return at;
   }
+  template <typename T> T* seg_of(T* dst, size_t count) { return reinterpret_cast<T*>(seg(dst, count * sizeof(T))); }
+  template <typename T> void put(T* dst, const std::vector<T>& v) { if (!v.empty()) std::memcpy(seg(dst, v.size() * sizeof(T)), v.data(), v.size() * sizeof(T)); }
+  bool fits() const { return !overflow && cur <= cap; }
+};
+// the read-back's counterpart over PackArgs: device arrays -> one staging block; seg returns the segment's place in it
+struct PackWriter {
+  PackArgs pa{}; size_t cur = 0;
+  size_t seg(const void* src, size_t bytes) {
+    const size_t off = cur;
+    if (bytes) { pa.src[pa.n_segs] = static_cast<const unsigned char*>(src); pa.off[pa.n_segs] = off; pa.words[pa.n_segs] = (unsigned)((bytes + 15) / 16); ++pa.n_segs; }
+    cur += up16(bytes);
+    return off;
+  }
+};
+
+// The one row of the world -> cam0 transform of a frame that Camera::Far needs:
+// z_cam(pw) = zrow . pw + zoff  with  pc = R_e^-1 (R_wc^-1 pw + t_inv) + t_e_inv   (inv_e: the inverse of the left camera's extrinsic)
+static void frame_far_row(const double inv_e[7], const double pose[7], double zrow[3], double* zoff) {
+  double inv_pose[7];
+  hse3::inv(pose, inv_pose);
+  double ex[3] = {1, 0, 0}, ey[3] = {0, 1, 0}, ez[3] = {0, 0, 1}, c0[3], c1[3], c2[3], t[3], r[3];
+  hse3::rotate(inv_pose, ex, r); hse3::rotate(inv_e, r, c0);
+  hse3::rotate(inv_pose, ey, r); hse3::rotate(inv_e, r, c1);
+  hse3::rotate(inv_pose, ez, r); hse3::rotate(inv_e, r, c2);
+  zrow[0] = c0[2]; zrow[1] = c1[2]; zrow[2] = c2[2];
+  hse3::rotate(inv_e, inv_pose + 4, t);
+  *zoff = t[2] + inv_e[6];
+}
+
+// ---- steps both assembly strategies take
+
+// persistent device objects: created once (empty), re-filled every tick through grow-only buffers
+static int ensure_objects(lvf_window* w) {
+  if (w->st) return LVF_OK;
+  lvf_ctx* ctx = w->ctx;
+  LVF_TRY(lvf_state_create(ctx, 0, 0, &w->st));
+  const double z2[2] = {0, 0}; const int32_t z = 0; const double id7[7] = {0, 0, 0, 1, 0, 0, 0};
+  LVF_TRY(lvf_two_camera_create(ctx, &w->left, &w->right, 0, z2, z2, &z, &z, &w->tc));
+  LVF_TRY(lvf_two_frame_create(ctx, &w->left, &w->right, 0, z2, z2, &z, &z, &z, &w->tf));
+  LVF_TRY(lvf_pose_only_create(ctx, &w->left, 0, z2, &z, &z, 0, id7, &w->po));
+  LVF_TRY(lvf_imu_create(ctx, 0, nullptr, nullptr, nullptr, &w->imu));
+  LVF_TRY(lvf_pose_prior_create(ctx, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &w->prior));
+  return LVF_OK;
+}
+
+// The hand-over between the strategies.  A window made for device assembly takes the host walk while it holds more than kDaMaxKf
+// keyframes and comes back when it has slid below, so each strategy may find the other's residue:
+//   device -> host : the resident landmark table misses the inverse depths this tick solves and the changes the host walk does not
+//                    track, and the cached ImuError information matrices (sq_prev / sq_ver) describe a batch this tick overwrites
+//   host -> device : the host's slot table (lvf_window_debug_blocks then reads the device's, d_slot_lm)
+// The feature arena needs nothing: Kf::d_dirty is kept by the mirror's entries whichever strategy runs.
+static void begin_assembly(lvf_window* w, lvf_window::Assembler by) {
+  if (by == lvf_window::Assembler::host) { w->lmtab_valid = false; w->sq_valid = false; }
+  else w->slot_lm.clear();
+  w->assembled_by = by;
+}
+
+// poses | vel | ba | bg | w_visual of the mirror -> the state, by keyframe position.  The inverse depths go by dense landmark slot, which only
+// the assembly knows: the state gets room for `inv_depth_capacity` of them and the caller fills them.
+static int stage_state(lvf_window* w, StageWriter& sw, size_t inv_depth_capacity) {
+  lvf_state* st = w->st;
+  const size_t n_kf = w->kfs.size();
+  st->n_kf = (int)n_kf;
+  LVF_TRY(st->poses.ensure(7 * n_kf + 2)); LVF_TRY(st->vel.ensure(3 * n_kf + 2)); LVF_TRY(st->ba.ensure(3 * n_kf + 2)); LVF_TRY(st->bg.ensure(3 * n_kf + 2));
+  LVF_TRY(st->w_visual.ensure(n_kf + 2)); LVF_TRY(st->inv_depth.ensure(inv_depth_capacity + 2));
+  st->poses.n = 7 * n_kf; st->vel.n = st->ba.n = st->bg.n = 3 * n_kf; st->w_visual.n = n_kf;
+  double *sp = sw.seg_of(st->poses.p, 7 * n_kf), *sv = sw.seg_of(st->vel.p, 3 * n_kf), *sa = sw.seg_of(st->ba.p, 3 * n_kf), *sg = sw.seg_of(st->bg.p, 3 * n_kf),
+         *sv_w = sw.seg_of(st->w_visual.p, n_kf);
+  for (size_t k = 0; k < n_kf; ++k) {
+    const lvf_window::Kf& f = w->kfs[k];
+    std::memcpy(&sp[7 * k], f.pose, 56); std::memcpy(&sv[3 * k], f.vel, 24); std::memcpy(&sa[3 * k], f.ba, 24); std::memcpy(&sg[3 * k], f.bg, 24);
+    sv_w[k] = f.w_visual;
+  }
+  return LVF_OK;
+}
+
+// ImuError blocks (backend.cpp:141-153): both frames good, a pre-integration on the later one.  j ascends.
+static void imu_pairs(const lvf_window* w, std::vector<int32_t>& i, std::vector<int32_t>& j) {
+  for (int k = 1; k < (int)w->kfs.size(); ++k)
+    if (w->kfs[k].good_imu && w->kfs[k - 1].good_imu && w->kfs[k].has_pre) { i.push_back(k - 1); j.push_back(k); }
+}
+// the IMU batch for these pairs: sizes, and the pre-integrations and indices into the upload.  The information matrices are the caller's
+// launch (launch_imu_sqrt_info, or the cached form behind imu_cache_sources).
+static int shape_imu_batch(lvf_window* w, StageWriter& sw, const std::vector<int32_t>& imu_i, const std::vector<int32_t>& imu_j) {
+  static_assert(sizeof(lvf_preint) == 467 * 8, "lvf_preint is 467 doubles");
+  lvf_batch* b = w->imu;
+  const size_t ni = imu_j.size();
+  LVF_TRY(b->pre.ensure(467 * ni + 2)); LVF_TRY(b->idx_a.ensure(ni + 4)); LVF_TRY(b->idx_b.ensure(ni + 4));
+  b->pre.n = 467 * ni; b->idx_a.n = b->idx_b.n = ni;
+  if (ni) {
+    lvf_preint* dst = reinterpret_cast<lvf_preint*>(sw.seg(b->pre.p, 467 * ni * 8));
+    for (size_t f = 0; f < ni; ++f) dst[f] = w->kfs[imu_j[f]].pre;
+    sw.put(b->idx_a.p, imu_i); sw.put(b->idx_b.p, imu_j);
+  }
+  b->host_kf1 = imu_i; b->host_kf2 = imu_j;
+  LVF_TRY(b->sqrt_info.ensure((size_t)225 * ni)); LVF_TRY(b->res.ensure((size_t)15 * ni));
+  for (int q = 0; q < 8; ++q) LVF_TRY(b->jac[q].ensure((size_t)15 * b->block_size[q] * ni));
+  b->n = (int)ni; b->min_n_kf = (int)w->kfs.size(); b->min_n_lm = 0; b->evaluated = false;
+  w->n_imu = (int)ni;
+  return LVF_OK;
+}
+
+// Weak-constraint priors (backend.cpp:163-178): a frame without an ImuError block whose near visual blocks (!Camera::Far) number fewer than
+// the threshold gets PoseGraphError(previous, k, weight, v), the first frame PoseError(k, weight, v).
+struct PriorLists { std::vector<double> t, wt, v; std::vector<int32_t> a, b; };
+static int weak_prior(const lvf_window* w, int k, bool has_imu_block, int near_count, PriorLists& pl) {
+  if (has_imu_block || near_count >= w->opt.weak_visual_threshold) return LVF_OK;
+  const lvf_window::Kf& f = w->kfs[k];
+  double t7[7] = {0, 0, 0, 0, 0, 0, 0};
+  if (k > 0) { LVF_TRY(lvf_relative_rpyxyz(w->kfs[k - 1].pose, f.pose, t7)); pl.a.push_back(k - 1); }
+  else { std::memcpy(t7, f.pose, 56); pl.a.push_back(-1); }
+  pl.b.push_back(k); pl.t.insert(pl.t.end(), t7, t7 + 7); pl.wt.push_back(w->opt.prior_weight); pl.v.push_back(w->opt.prior_v);
+  return LVF_OK;
+}
+static int shape_prior_batch(lvf_window* w, StageWriter& sw, const PriorLists& pl) {
+  lvf_batch* b = w->prior;
+  const size_t np_ = pl.b.size();
+  LVF_TRY(b->idx_a.ensure(np_ + 4)); LVF_TRY(b->idx_b.ensure(np_ + 4)); LVF_TRY(b->table.ensure(7 * np_ + 2)); LVF_TRY(b->ob_a.ensure(np_ + 2)); LVF_TRY(b->ob_b.ensure(np_ + 2));
+  b->idx_a.n = b->idx_b.n = np_; b->table.n = 7 * np_; b->ob_a.n = b->ob_b.n = np_;
+  sw.put(b->idx_a.p, pl.a); sw.put(b->idx_b.p, pl.b); sw.put(b->table.p, pl.t); sw.put(b->ob_a.p, pl.wt); sw.put(b->ob_b.p, pl.v);
+  LVF_TRY(b->res.ensure(6 * np_)); LVF_TRY(b->jac[0].ensure(42 * np_)); LVF_TRY(b->jac[1].ensure(42 * np_));
+  b->n = (int)np_; b->min_n_kf = (int)w->kfs.size(); b->min_n_lm = 0; b->evaluated = false;
+  b->host_kf1 = pl.a; b->host_kf2 = pl.b;
+  w->n_prior = (int)np_;
+  return LVF_OK;
+}
+
+// room in the three visual batches (the device strategy asks for upper bounds ahead of its counters, the host walk for what it counted)
+static int ensure_visual(lvf_window* w, size_t cap_tc, size_t cap_tf, size_t cap_po) {
+  lvf_batch *tc = w->tc, *tf = w->tf, *po = w->po;
+  LVF_TRY(tc->ob_a.ensure(2 * cap_tc + 2)); LVF_TRY(tc->ob_b.ensure(2 * cap_tc + 2)); LVF_TRY(tc->idx_a.ensure(cap_tc + 2)); LVF_TRY(tc->idx_b.ensure(cap_tc + 2)); LVF_TRY(tc->wblk.ensure(cap_tc + 2));
+  LVF_TRY(tf->ob_a.ensure(2 * cap_tf + 2)); LVF_TRY(tf->ob_b.ensure(2 * cap_tf + 2)); LVF_TRY(tf->idx_a.ensure(cap_tf + 2)); LVF_TRY(tf->idx_b.ensure(cap_tf + 2)); LVF_TRY(tf->idx_c.ensure(cap_tf + 2));
+  LVF_TRY(po->ob_a.ensure(2 * cap_po + 2)); LVF_TRY(po->idx_a.ensure(cap_po + 2)); LVF_TRY(po->idx_b.ensure(cap_po + 2)); LVF_TRY(po->table.ensure(3 * cap_po + 2));
+  return LVF_OK;
+}
+// what this tick's assembly came to: element counts and flags of the visual batches, the state's landmarks, the window's counters.
+// Kf::sort_unique keeps one observation per (keyframe, landmark) and both strategies emit frame by frame: TwoFrame and PoseOnly are sorted
+// by current keyframe, kf2_counts[k] = TwoFrame blocks of keyframe k.
+static void set_visual_counts(lvf_window* w, size_t ntc, size_t ntf, size_t npo, int n_lm, std::vector<int32_t>&& kf2_counts) {
+  const int n_kf = (int)w->kfs.size();
+  lvf_batch *tc = w->tc, *tf = w->tf, *po = w->po;
+  auto shape = [n_kf](lvf_batch* b, size_t n, int nlm) { b->n = (int)n; b->min_n_kf = n_kf; b->min_n_lm = nlm; b->evaluated = false; };
+  w->n_lm_problem = n_lm; w->n_tc = (int)ntc; w->n_tf = (int)ntf; w->n_po = (int)npo;
+  w->st->n_lm = n_lm; w->st->inv_depth.n = n_lm;
+  tc->ob_a.n = tc->ob_b.n = 2 * ntc; tc->idx_a.n = tc->idx_b.n = tc->wblk.n = ntc;
+  shape(tc, ntc, n_lm);
+  tf->ob_a.n = tf->ob_b.n = 2 * ntf; tf->idx_a.n = tf->idx_b.n = tf->idx_c.n = ntf;
+  shape(tf, ntf, n_lm);
+  tf->sorted_by_kf = true; tf->host_kf1.clear(); tf->host_kf2.clear(); tf->host_lm.clear(); tf->unique_lk2_known = true; tf->kf2_counts = std::move(kf2_counts);
+  po->ob_a.n = 2 * npo; po->idx_a.n = po->idx_b.n = npo; po->table.n = 3 * npo;
+  shape(po, npo, 0); po->n_table = (int)npo; po->sorted_by_kf = true;
+}
+
+static int configure_problem(lvf_window* w) {
+  if (!w->prob) {
+    LVF_TRY(lvf_problem_create(w->ctx, w->st, w->tc, w->tf, w->po, w->imu, &w->prob));
+    LVF_TRY(lvf_problem_set_pose_priors(w->prob, w->prior));
+  } else {
+    LVF_TRY(problem_configure(w->prob));
+  }
+  return window_attach_lidar(w);
+}
+
+// ---- the read-back: poses, velocities, biases by keyframe position and the inverse depths, gathered on the device into one block
+// (k_window_pack) and copied with ONE device-to-host copy.  Where the inverse depths come from is the strategy's:
+//   host walk        st->inv_depth, by dense slot (lvf_window::slot_lm translates)
+//   device assembly  d_lm_invd_out, by landmark index, behind k_da_scatter_invd (which also writes them into the resident landmark table)
+struct ReadBack { lvf_window* w; bool by_landmark; size_t off[5]; };
+// (the tail of lvf_problem_solve_then: enqueued behind the last iteration and ahead of the wait that ends the solve)
+static int enqueue_read_back(void* user) {
+  ReadBack& rb = *static_cast<ReadBack*>(user);
+  lvf_window* w = rb.w; lvf_state* st = w->st; hipStream_t s = w->ctx->stream;
+  const size_t n_kf = w->kfs.size(), n_lm = (size_t)w->n_lm_problem, nl = w->lms.size();
+  if (rb.by_landmark && n_lm)
+    hipLaunchKernelGGL(k_da_scatter_invd, dim3((unsigned)((n_lm + 255) / 256)), dim3(256), 0, s, (int)n_lm, w->d_slot_lm.p, st->inv_depth.p, w->d_lm_invd_out.p, reinterpret_cast<LmDev*>(w->d_lmtab.p));
+  PackWriter pw;
+  rb.off[0] = pw.seg(st->poses.p, 7 * n_kf * 8); rb.off[1] = pw.seg(st->vel.p, 3 * n_kf * 8); rb.off[2] = pw.seg(st->ba.p, 3 * n_kf * 8); rb.off[3] = pw.seg(st->bg.p, 3 * n_kf * 8);
+  rb.off[4] = rb.by_landmark ? pw.seg(w->d_lm_invd_out.p, nl * 8) : pw.seg(st->inv_depth.p, n_lm * 8);
+  LVF_TRY(w->d_stage.ensure(pw.cur + 16)); LVF_TRY(w->h_state.reserve(pw.cur / 8 + 2));
+  pw.pa.stage = w->d_stage.p;
+  hipLaunchKernelGGL(k_window_pack, dim3(32), dim3(256), 0, s, pw.pa);
+  LVF_HIP(hipGetLastError());
+  LVF_HIP(hipMemcpyAsync(w->h_state.p, w->d_stage.p, pw.cur, hipMemcpyDeviceToHost, s));
+  return LVF_OK;
+}
+// ... into the mirror (frame->pose, Vw, biases, landmark->inv_depth), once the copy has arrived
+static void apply_read_back(lvf_window* w, const ReadBack& rb) {
+  const double *poses = w->h_state.p + rb.off[0] / 8, *vel = w->h_state.p + rb.off[1] / 8, *ba = w->h_state.p + rb.off[2] / 8, *bg = w->h_state.p + rb.off[3] / 8,
+               *invd = w->h_state.p + rb.off[4] / 8;
+  for (size_t k = 0; k < w->kfs.size(); ++k) {
+    lvf_window::Kf& f = w->kfs[k];
+    std::memcpy(f.pose, &poses[7 * k], 56);
+    if (f.good_imu) { std::memcpy(f.vel, &vel[3 * k], 24); std::memcpy(f.ba, &ba[3 * k], 24); std::memcpy(f.bg, &bg[3 * k], 24); }
+  }
+  if (rb.by_landmark) { for (size_t i = 0; i < w->lms.size(); ++i) if (w->lms[i].alive) w->lms[i].inv_depth = invd[i]; }
+  else for (size_t l = 0; l < w->slot_lm.size(); ++l) w->lms[w->slot_lm[l]].inv_depth = invd[l];
+}
+
+// ---- strategy 1: the block lists assembled on the device (window_args.hpp describes the tables and the three kernels)
+
+// Where each ImuError factor's information matrix sits in what the previous tick left in the IMU batch (-1: not there, factor it): slot f
+// of `sq_prev` holds sqrt_info of the pre-integration version sq_ver[f].  Swaps the batch's matrices into sq_prev, so it runs ahead of
+// shape_imu_batch; launch_imu_sqrt_info_cached then copies what is found there and factors the rest.
+static int imu_cache_sources(lvf_window* w, StageWriter& sw, const std::vector<int32_t>& imu_j) {
+  const size_t ni = imu_j.size();
+  if (!ni) { w->sq_ver.clear(); return LVF_OK; }
+  LVF_TRY(w->d_sq_src.ensure(ni + 4));
+  int32_t* src = sw.seg_of(w->d_sq_src.p, ni);
+  std::vector<unsigned> ver(ni);
+  if (!w->sq_valid) w->sq_ver.clear();            // (a tick that failed after the swap below, or the host walk, left nothing to reuse)
+  for (size_t f = 0; f < ni; ++f) {
+    ver[f] = w->kfs[imu_j[f]].pre_ver;
+    src[f] = -1;
+    for (size_t g = 0; g < w->sq_ver.size(); ++g) if (w->sq_ver[g] == ver[f]) { src[f] = (int32_t)g; break; }
+  }
+  w->imu->sqrt_info.swap(w->sq_prev);             // last tick's matrices become the source; the batch gets the other buffer
+  w->sq_ver = std::move(ver);
+  w->sq_valid = false;                            // until this tick's matrices are on their way (assemble_device)
+  return LVF_OK;
+}
+
+static int assemble_device(lvf_window* w, char* timing_note, size_t note_len) {
+  hipStream_t s = w->ctx->stream;
+  const int n_kf = (int)w->kfs.size();
+  const auto t_begin = Clock::now();
+  const size_t nl = w->lms.size();
   lvf_state* st = w->st;
   // ---- feature arena: every frame owns a segment; new / changed frames are (re)sent, a frame that outgrew its segment moves to the
   // end, and when the end is reached everything is laid out again from the start
@@ -777,7 +714,7 @@ static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_s
   }
   for (lvf_window::Kf& f : w->kfs)
     if (f.d_cap < f.obs.size()) { f.d_off = w->arena_end; f.d_cap = f.obs.size() + f.obs.size() / 4 + 64; w->arena_end += f.d_cap; }
-  // ---- staging: frame table | landmark table | state | dirty feature segments (one copy, one unpack launch)
+  // ---- staging: frame table | landmark table | state | IMU | dirty feature segments (one copy, one unpack launch)
   size_t dirty_obs = 0; int dirty_frames = 0;
   for (const lvf_window::Kf& f : w->kfs) if (f.d_dirty) { dirty_obs += f.obs.size(); ++dirty_frames; }
   const bool direct_segments = 2 * dirty_frames + 16 > kMaxSegs;      // (a full re-layout of a long window: copy those segments one by one)
@@ -785,45 +722,26 @@ static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_s
                              up16((size_t)n_kf * 467 * 8) + (size_t)n_kf * 16 + 64;
   LVF_TRY(w->h_stage.reserve(stage_bound));
   LVF_TRY(w->d_stage.ensure(stage_bound));
-  unsigned char* hs = w->h_stage.p;
-  UnpackArgs ua{};
-  size_t cur = 0;
-  auto seg = [&](void* dst, size_t bytes) -> unsigned char* {
-    unsigned char* at = hs + cur;
-    if (bytes) { ua.seg_dst[ua.n_segs] = static_cast<unsigned char*>(dst); ua.seg_off[ua.n_segs] = cur; ua.seg_words[ua.n_segs] = (unsigned)((bytes + 15) / 16); ++ua.n_segs; }
-    cur += up16(bytes);
-    return at;
-  };
+  StageWriter sw(w->h_stage, 0);
   const unsigned char* lmtab_before = w->d_lmtab.p;
   LVF_TRY(w->d_frames.ensure((size_t)n_kf * sizeof(FrameDev) + 16)); LVF_TRY(w->d_lmtab.ensure(nl * sizeof(LmDev) + 16));
   if (w->d_lmtab.p != lmtab_before) w->lmtab_valid = false;          // re-allocated: the resident table is gone
-  // frame table (also what the IMU / prior decisions below need of a frame)
+  // frame table
   std::vector<double> Rk((size_t)9 * n_kf + 9);
   landmarks_to_world_prepare(w, Rk.data());
   double inv_e[7];
   hse3::inv(w->left.extrinsic, inv_e);
-  FrameDev* fd = reinterpret_cast<FrameDev*>(seg(w->d_frames.p, (size_t)n_kf * sizeof(FrameDev)));
-  {
-    int start = 0;
-    for (int k = 0; k < n_kf; ++k) {
-      const lvf_window::Kf& f = w->kfs[k];
-      FrameDev& d = fd[k];
-      d.id = f.id; d.start = start; d.cnt = (int)f.obs.size(); d.arena_off = (long long)f.d_off;
-      start += d.cnt;
-      double inv_pose[7];
-      hse3::inv(f.pose, inv_pose);
-      double ex[3] = {1, 0, 0}, ey[3] = {0, 1, 0}, ez[3] = {0, 0, 1}, c0[3], c1[3], c2[3], t[3], r[3];
-      hse3::rotate(inv_pose, ex, r); hse3::rotate(inv_e, r, c0);
-      hse3::rotate(inv_pose, ey, r); hse3::rotate(inv_e, r, c1);
-      hse3::rotate(inv_pose, ez, r); hse3::rotate(inv_e, r, c2);
-      d.zrow[0] = c0[2]; d.zrow[1] = c1[2]; d.zrow[2] = c2[2];
-      hse3::rotate(inv_e, inv_pose + 4, t);
-      d.zoff = t[2] + inv_e[6];
-      std::memcpy(d.R, &Rk[(size_t)9 * k], 72); std::memcpy(d.t, f.pose + 4, 24);
-      d.w_tc = two_camera_weight(f.w_visual);
-    }
+  FrameDev* fd = reinterpret_cast<FrameDev*>(sw.seg(w->d_frames.p, (size_t)n_kf * sizeof(FrameDev)));
+  for (int k = 0, start = 0; k < n_kf; ++k) {
+    const lvf_window::Kf& f = w->kfs[k];
+    FrameDev& d = fd[k];
+    d.id = f.id; d.start = start; d.cnt = (int)f.obs.size(); d.arena_off = (long long)f.d_off;
+    start += d.cnt;
+    frame_far_row(inv_e, f.pose, d.zrow, &d.zoff);
+    std::memcpy(d.R, &Rk[(size_t)9 * k], 72); std::memcpy(d.t, f.pose + 4, 24);
+    d.w_tc = two_camera_weight(f.w_visual);
   }
-  // landmark table: all of it after a (re)allocation or a tick on the host path, otherwise only what add_landmark / slide / prune touched
+  // landmark table: all of it after a (re)allocation or a tick of the host walk, otherwise only what add_landmark / slide / prune touched
   {
     auto fill = [&](LmDev& d, const lvf_window::Lm& l) {
       d.right_ob[0] = l.right_ob[0]; d.right_ob[1] = l.right_ob[1]; d.pw[0] = l.pw[0]; d.pw[1] = l.pw[1]; d.pw[2] = l.pw[2];
@@ -832,72 +750,26 @@ static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_s
     const bool resident = w->lmtab_valid;
     w->lmtab_valid = false;                    // (set again once this tick has gone through: an error below leaves the table to be re-sent)
     if (!resident) {
-      LmDev* ld = reinterpret_cast<LmDev*>(seg(w->d_lmtab.p, nl * sizeof(LmDev)));
+      LmDev* ld = reinterpret_cast<LmDev*>(sw.seg(w->d_lmtab.p, nl * sizeof(LmDev)));
       for (size_t i = 0; i < nl; ++i) fill(ld[i], w->lms[i]);
     } else if (!w->lm_dirty.empty()) {
       const size_t nd = w->lm_dirty.size();
-      ua.n_lm_dirty = (int)nd; ua.lmtab = w->d_lmtab.p;
-      ua.lm_idx_off = cur;
-      int32_t* di = reinterpret_cast<int32_t*>(hs + cur); cur += up16(nd * 4);
-      ua.lm_rec_off = cur;
-      LmDev* dr = reinterpret_cast<LmDev*>(hs + cur); cur += nd * sizeof(LmDev);
+      sw.ua.n_lm_dirty = (int)nd; sw.ua.lmtab = w->d_lmtab.p;
+      int32_t* di = reinterpret_cast<int32_t*>(sw.raw(nd * 4, &sw.ua.lm_idx_off));
+      LmDev* dr = reinterpret_cast<LmDev*>(sw.raw(nd * sizeof(LmDev), &sw.ua.lm_rec_off));
       for (size_t j = 0; j < nd; ++j) { di[j] = w->lm_dirty[j]; fill(dr[j], w->lms[w->lm_dirty[j]]); }
     }
     for (int i : w->lm_dirty) w->lm_dirty_flag[i] = 0;
     w->lm_dirty.clear();
   }
-  // state (the inverse depths are filled on the device, by slot)
-  st->n_kf = n_kf;
-  LVF_TRY(st->poses.ensure((size_t)7 * n_kf + 2)); LVF_TRY(st->vel.ensure((size_t)3 * n_kf + 2)); LVF_TRY(st->ba.ensure((size_t)3 * n_kf + 2)); LVF_TRY(st->bg.ensure((size_t)3 * n_kf + 2));
-  LVF_TRY(st->w_visual.ensure((size_t)n_kf + 2)); LVF_TRY(st->inv_depth.ensure(nl + 2));
-  st->poses.n = (size_t)7 * n_kf; st->vel.n = st->ba.n = st->bg.n = (size_t)3 * n_kf; st->w_visual.n = n_kf;
-  {
-    double* sp = reinterpret_cast<double*>(seg(st->poses.p, (size_t)7 * n_kf * 8));
-    double* sv = reinterpret_cast<double*>(seg(st->vel.p, (size_t)3 * n_kf * 8));
-    double* sa = reinterpret_cast<double*>(seg(st->ba.p, (size_t)3 * n_kf * 8));
-    double* sg = reinterpret_cast<double*>(seg(st->bg.p, (size_t)3 * n_kf * 8));
-    double* sw = reinterpret_cast<double*>(seg(st->w_visual.p, (size_t)n_kf * 8));
-    for (int k = 0; k < n_kf; ++k) {
-      const lvf_window::Kf& f = w->kfs[k];
-      std::memcpy(&sp[(size_t)7 * k], f.pose, 56); std::memcpy(&sv[(size_t)3 * k], f.vel, 24); std::memcpy(&sa[(size_t)3 * k], f.ba, 24);
-      std::memcpy(&sg[(size_t)3 * k], f.bg, 24); sw[k] = f.w_visual;
-    }
-  }
-  // ImuError blocks (backend.cpp:141-153: both frames good, a pre-integration on the later one) do not depend on the assembly: their
-  // pre-integrations ride in this upload and their information matrices are factored while the host waits for the assembly's counters
+  // state: the inverse depths are filled on the device, by slot (k_da_scan)
+  LVF_TRY(stage_state(w, sw, nl));
+  // the ImuError blocks do not depend on the assembly: their pre-integrations ride in this upload and their information matrices are
+  // factored while the host waits for the assembly's counters
   std::vector<int32_t> imu_i, imu_j;
-  {
-    for (int k = 1; k < n_kf; ++k)
-      if (w->kfs[k].good_imu && w->kfs[k - 1].good_imu && w->kfs[k].has_pre) { imu_i.push_back(k - 1); imu_j.push_back(k); }
-    lvf_batch* b = w->imu;
-    const size_t ni = imu_i.size();
-    LVF_TRY(b->pre.ensure(467 * ni + 2)); LVF_TRY(b->idx_a.ensure(ni + 4)); LVF_TRY(b->idx_b.ensure(ni + 4));
-    b->pre.n = 467 * ni; b->idx_a.n = b->idx_b.n = ni;
-    if (ni) {
-      static_assert(sizeof(lvf_preint) == 467 * 8, "lvf_preint is 467 doubles");
-      lvf_preint* dst = reinterpret_cast<lvf_preint*>(seg(b->pre.p, 467 * ni * 8));
-      for (size_t f = 0; f < ni; ++f) dst[f] = w->kfs[imu_j[f]].pre;
-      std::memcpy(seg(b->idx_a.p, ni * 4), imu_i.data(), ni * 4); std::memcpy(seg(b->idx_b.p, ni * 4), imu_j.data(), ni * 4);
-      // where each factor's information matrix sits in what the previous tick left (-1: not there, factor it)
-      LVF_TRY(w->d_sq_src.ensure(ni + 4));
-      int32_t* src = reinterpret_cast<int32_t*>(seg(w->d_sq_src.p, ni * 4));
-      std::vector<unsigned> ver(ni);
-      if (!w->sq_valid) w->sq_ver.clear();            // (a tick that failed after the swap below, or the host-assembly path, left nothing to reuse)
-      for (size_t f = 0; f < ni; ++f) {
-        ver[f] = w->kfs[imu_j[f]].pre_ver;
-        src[f] = -1;
-        for (size_t g = 0; g < w->sq_ver.size(); ++g) if (w->sq_ver[g] == ver[f]) { src[f] = (int32_t)g; break; }
-      }
-      b->sqrt_info.swap(w->sq_prev);                 // last tick's matrices become the source; the batch gets the other buffer
-      w->sq_ver = std::move(ver);
-      w->sq_valid = false;                           // until this tick's matrices are on their way (below)
-    } else w->sq_ver.clear();
-    b->host_kf1 = imu_i; b->host_kf2 = imu_j;
-    LVF_TRY(b->sqrt_info.ensure((size_t)225 * ni)); LVF_TRY(b->res.ensure((size_t)15 * ni));
-    for (int q = 0; q < 8; ++q) LVF_TRY(b->jac[q].ensure((size_t)15 * b->block_size[q] * ni));
-    b->n = (int)ni; b->min_n_kf = n_kf; b->min_n_lm = 0; b->evaluated = false;
-    w->n_imu = (int)ni;
-  }
+  imu_pairs(w, imu_i, imu_j);
+  LVF_TRY(imu_cache_sources(w, sw, imu_j));
+  LVF_TRY(shape_imu_batch(w, sw, imu_i, imu_j));
   // dirty feature segments
   for (lvf_window::Kf& f : w->kfs) {
     if (!f.d_dirty) continue;
@@ -906,7 +778,7 @@ static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_s
       int32_t* dl; double* dx;
       std::vector<int32_t> tl; std::vector<double> tx;
       if (direct_segments) { tl.resize(c); tx.resize(2 * c); dl = tl.data(); dx = tx.data(); }
-      else { dl = reinterpret_cast<int32_t*>(seg(w->d_obs_lm.p + f.d_off, c * 4)); dx = reinterpret_cast<double*>(seg(w->d_obs_xy.p + 2 * f.d_off, c * 16)); }
+      else { dl = sw.seg_of(w->d_obs_lm.p + f.d_off, c); dx = sw.seg_of(w->d_obs_xy.p + 2 * f.d_off, 2 * c); }
       for (size_t j = 0; j < c; ++j) { dl[j] = f.obs[j].lm; dx[2 * j] = f.obs[j].ob[0]; dx[2 * j + 1] = f.obs[j].ob[1]; }
       if (direct_segments) {
         LVF_HIP(hipMemcpyAsync(w->d_obs_lm.p + f.d_off, dl, c * 4, hipMemcpyHostToDevice, s));
@@ -916,9 +788,10 @@ static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_s
     }
     f.d_dirty = false;
   }
-  LVF_REQUIRE(cur <= w->h_stage.cap && ua.n_segs <= kMaxSegs, "lvf_window_solve: staging overflow");
-  const auto t_staged = now();
-  LVF_HIP(hipMemcpyAsync(w->d_stage.p, hs, cur, hipMemcpyHostToDevice, s));
+  LVF_REQUIRE(sw.fits(), "lvf_window_solve: staging overflow");
+  const auto t_staged = Clock::now();
+  LVF_HIP(hipMemcpyAsync(w->d_stage.p, sw.base, sw.cur, hipMemcpyHostToDevice, s));
+  UnpackArgs& ua = sw.ua;
   ua.stage = w->d_stage.p; ua.g_seg = 64;
   // (the assembly's `used` flags and counters are cleared by the unpack launch: two fill launches less)
   LVF_TRY(w->d_used.ensure(nl + 32)); LVF_TRY(w->d_counts.ensure(4 + 2 * kDaMaxKf));
@@ -930,9 +803,7 @@ static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_s
   LVF_TRY(w->d_cls.ensure(n_obs + 16)); LVF_TRY(w->d_wgcnt.ensure((size_t)3 * n_wg + 4)); LVF_TRY(w->d_wgbase.ensure((size_t)3 * n_wg + 4));
   LVF_TRY(w->d_slot.ensure(nl + 4)); LVF_TRY(w->d_slot_lm.ensure(nl + 4)); LVF_TRY(w->d_lm_invd_out.ensure(nl + 4));
   LVF_TRY(w->h_counts.reserve(4 + 2 * kDaMaxKf));
-  LVF_TRY(w->tc->ob_a.ensure(2 * std::min(n_obs, nl) + 2)); LVF_TRY(w->tc->ob_b.ensure(2 * std::min(n_obs, nl) + 2)); LVF_TRY(w->tc->idx_a.ensure(std::min(n_obs, nl) + 2)); LVF_TRY(w->tc->idx_b.ensure(std::min(n_obs, nl) + 2)); LVF_TRY(w->tc->wblk.ensure(std::min(n_obs, nl) + 2));
-  LVF_TRY(w->tf->ob_a.ensure(2 * n_obs + 2)); LVF_TRY(w->tf->ob_b.ensure(2 * n_obs + 2)); LVF_TRY(w->tf->idx_a.ensure(n_obs + 2)); LVF_TRY(w->tf->idx_b.ensure(n_obs + 2)); LVF_TRY(w->tf->idx_c.ensure(n_obs + 2));
-  LVF_TRY(w->po->ob_a.ensure(2 * n_obs + 2)); LVF_TRY(w->po->idx_a.ensure(n_obs + 2)); LVF_TRY(w->po->idx_b.ensure(n_obs + 2)); LVF_TRY(w->po->table.ensure(3 * n_obs + 2));
+  LVF_TRY(ensure_visual(w, std::min(n_obs, nl), n_obs, n_obs));      // upper bounds: one TwoCamera block per landmark at most
   DaArgs da{};
   da.n_kf = n_kf; da.total = (int)n_obs; da.nl = (int)nl; da.n_wg = n_wg;
   da.frames = reinterpret_cast<const FrameDev*>(w->d_frames.p); da.obs_lm = w->d_obs_lm.p; da.obs_xy = reinterpret_cast<const double2*>(w->d_obs_xy.p);
@@ -948,152 +819,47 @@ static int window_solve_device(lvf_window* w, const lvf_solver_options* o, lvf_s
   hipLaunchKernelGGL(k_da_scan, dim3(1), dim3(1024), 0, s, da);
   if (n_wg) hipLaunchKernelGGL(k_da_emit, dim3(n_wg), dim3(256), 0, s, da);
   LVF_HIP(hipGetLastError());
+  // the counter event: the host waits for the counters' copy, not for the work queued after it
   LVF_HIP(hipMemcpyAsync(w->h_counts.p, w->d_counts.p, (4 + 2 * kDaMaxKf) * sizeof(int), hipMemcpyDeviceToHost, s));
   if (!w->ev_counts) LVF_HIP(hipEventCreateWithFlags(&w->ev_counts, hipEventDisableTiming));
   LVF_HIP(hipEventRecord(w->ev_counts, s));
   if (w->n_imu) { LVF_TRY(launch_imu_sqrt_info_cached(w->imu, w->d_sq_src.p, w->sq_prev.p)); w->sq_valid = true; }      // runs while the host reads the counters and configures the problem
   LVF_HIP(hipEventSynchronize(w->ev_counts));
-  const int* hc = w->h_counts.p;
-  const size_t ntc = (size_t)hc[0], ntf = (size_t)hc[1], npo = (size_t)hc[2];
-  const int n_lm = hc[3];
-  const auto t_assembled = now();
-  // ---- weak-constraint priors (backend.cpp:164-178): frames without an ImuError block whose near-feature count is below the threshold
-  std::vector<double> pr_t, pr_w, pr_v;
-  std::vector<int32_t> pr_a, pr_b, kf2_counts(n_kf, 0);
-  {
-    size_t fi = 0;                                   // imu_j is ascending
-    for (int k = 0; k < n_kf; ++k) {
-      lvf_window::Kf& f = w->kfs[k];
-      kf2_counts[k] = hc[4 + k];
-      const bool imu_block = fi < imu_j.size() && imu_j[fi] == k;
-      if (imu_block) ++fi;
-      if (!imu_block && hc[4 + kDaMaxKf + k] < w->opt.weak_visual_threshold) {
-        double t7[7] = {0, 0, 0, 0, 0, 0, 0};
-        if (k > 0) { LVF_TRY(lvf_relative_rpyxyz(w->kfs[k - 1].pose, f.pose, t7)); pr_a.push_back(k - 1); }
-        else { std::memcpy(t7, f.pose, 56); pr_a.push_back(-1); }
-        pr_b.push_back(k); pr_t.insert(pr_t.end(), t7, t7 + 7); pr_w.push_back(w->opt.prior_weight); pr_v.push_back(w->opt.prior_v);
-      }
-    }
+  const int* hc = w->h_counts.p;       // [0..3] tc, tf, po, n_lm | TwoFrame blocks per keyframe | near visual blocks per keyframe
+  const auto t_assembled = Clock::now();
+  // ---- priors, decided with the near counts k_da_classify made
+  PriorLists pl;
+  size_t fi = 0;
+  for (int k = 0; k < n_kf; ++k) {
+    const bool imu_block = fi < imu_j.size() && imu_j[fi] == k;
+    if (imu_block) ++fi;
+    LVF_TRY(weak_prior(w, k, imu_block, hc[4 + kDaMaxKf + k], pl));
   }
-  w->n_lm_problem = n_lm;
-  w->n_tc = (int)ntc; w->n_tf = (int)ntf; w->n_po = (int)npo; w->n_prior = (int)pr_b.size();
-  st->n_lm = n_lm; st->inv_depth.n = n_lm;
-  auto idx_ok = [](lvf_batch* b, int n, int nkf, int nlm) { b->n = n; b->min_n_kf = nkf; b->min_n_lm = nlm; b->evaluated = false; };
-  w->tc->ob_a.n = w->tc->ob_b.n = 2 * ntc; w->tc->idx_a.n = w->tc->idx_b.n = w->tc->wblk.n = ntc;
-  idx_ok(w->tc, w->n_tc, n_kf, n_lm);
-  w->tf->ob_a.n = w->tf->ob_b.n = 2 * ntf; w->tf->idx_a.n = w->tf->idx_b.n = w->tf->idx_c.n = ntf;
-  idx_ok(w->tf, w->n_tf, n_kf, n_lm);
-  w->tf->sorted_by_kf = true; w->tf->host_kf1.clear(); w->tf->host_kf2.clear(); w->tf->host_lm.clear(); w->tf->unique_lk2_known = true; w->tf->kf2_counts = std::move(kf2_counts);
-  w->po->ob_a.n = 2 * npo; w->po->idx_a.n = w->po->idx_b.n = npo; w->po->table.n = 3 * npo;
-  idx_ok(w->po, w->n_po, n_kf, 0); w->po->n_table = w->n_po; w->po->sorted_by_kf = true;
+  set_visual_counts(w, (size_t)hc[0], (size_t)hc[1], (size_t)hc[2], hc[3], std::vector<int32_t>(hc + 4, hc + 4 + n_kf));
   // second (small) staged upload: the priors
-  {
-    UnpackArgs ub{};
-    size_t at = 0;
-    auto seg2 = [&](void* dst, size_t bytes) -> unsigned char* {
-      unsigned char* pp = hs + at;
-      if (bytes) { ub.seg_dst[ub.n_segs] = static_cast<unsigned char*>(dst); ub.seg_off[ub.n_segs] = at; ub.seg_words[ub.n_segs] = (unsigned)((bytes + 15) / 16); ++ub.n_segs; }
-      at += up16(bytes);
-      return pp;
-    };
-    LVF_TRY(w->h_stage.reserve(16 * 64 + (size_t)n_kf * 128 + 4096));      // (grow-only: the first copy above has completed)
-    hs = w->h_stage.p;
-    lvf_batch* b = w->prior;
-    const size_t np_ = (size_t)w->n_prior;
-    LVF_TRY(b->idx_a.ensure(np_ + 4)); LVF_TRY(b->idx_b.ensure(np_ + 4)); LVF_TRY(b->table.ensure(7 * np_ + 2)); LVF_TRY(b->ob_a.ensure(np_ + 2)); LVF_TRY(b->ob_b.ensure(np_ + 2));
-    b->idx_a.n = b->idx_b.n = np_; b->table.n = 7 * np_; b->ob_a.n = b->ob_b.n = np_;
-    if (np_) {
-      std::memcpy(seg2(b->idx_a.p, np_ * 4), pr_a.data(), np_ * 4); std::memcpy(seg2(b->idx_b.p, np_ * 4), pr_b.data(), np_ * 4);
-      std::memcpy(seg2(b->table.p, 7 * np_ * 8), pr_t.data(), 7 * np_ * 8);
-      std::memcpy(seg2(b->ob_a.p, np_ * 8), pr_w.data(), np_ * 8); std::memcpy(seg2(b->ob_b.p, np_ * 8), pr_v.data(), np_ * 8);
-    }
-    LVF_TRY(b->res.ensure((size_t)6 * w->n_prior)); LVF_TRY(b->jac[0].ensure((size_t)42 * w->n_prior)); LVF_TRY(b->jac[1].ensure((size_t)42 * w->n_prior));
-    idx_ok(b, w->n_prior, n_kf, 0);
-    b->host_kf1 = pr_a; b->host_kf2 = pr_b;
-    if (ub.n_segs) {
-      LVF_TRY(w->d_stage.ensure(at + 16));
-      LVF_HIP(hipMemcpyAsync(w->d_stage.p, hs, at, hipMemcpyHostToDevice, s));
-      ub.stage = w->d_stage.p; ub.g_seg = 8;
-      hipLaunchKernelGGL(k_window_unpack, dim3(ub.g_seg), dim3(256), 0, s, ub);
-      LVF_HIP(hipGetLastError());
-    }
-  }
-  const auto t_uploaded = now();
-  if (!w->prob) {
-    LVF_TRY(lvf_problem_create(ctx, st, w->tc, w->tf, w->po, w->imu, &w->prob));
-    LVF_TRY(lvf_problem_set_pose_priors(w->prob, w->prior));
-  } else {
-    LVF_TRY(problem_configure(w->prob));
-  }
-  LVF_TRY(window_attach_lidar(w));
-  const auto t_configured = now();
-  // ---- solve, with the read-back (poses, velocities, biases by keyframe position; inverse depths in landmark-index order) enqueued
-  // behind the last iteration and ahead of the wait that ends the solve: ONE stream wait per tick for both
-  size_t offs[5];
-  struct PackCtx { lvf_window* w; lvf_state* st; hipStream_t s; int n_kf, n_lm; size_t nl; size_t* offs; };
-  PackCtx pc{w, st, s, n_kf, n_lm, nl, offs};
-  auto pack_tail = [](void* u) -> int {
-    PackCtx& c = *static_cast<PackCtx*>(u);
-    lvf_window* w = c.w; lvf_state* st = c.st; hipStream_t s = c.s;
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    if (c.n_lm) hipLaunchKernelGGL(k_da_scatter_invd, dim3((c.n_lm + 255) / 256), dim3(256), 0, s, c.n_lm, w->d_slot_lm.p, st->inv_depth.p, w->d_lm_invd_out.p, reinterpret_cast<LmDev*>(w->d_lmtab.p));
-    PackArgs pa{};
-    size_t at = 0;
-    auto segp = [&](const void* src, size_t bytes, int slot) {
-      c.offs[slot] = at;
-      if (bytes) { pa.src[pa.n_segs] = static_cast<const unsigned char*>(src); pa.off[pa.n_segs] = at; pa.words[pa.n_segs] = (unsigned)((bytes + 15) / 16); ++pa.n_segs; }
-      at += up16(bytes);
-    };
-    segp(st->poses.p, (size_t)7 * c.n_kf * 8, 0); segp(st->vel.p, (size_t)3 * c.n_kf * 8, 1); segp(st->ba.p, (size_t)3 * c.n_kf * 8, 2); segp(st->bg.p, (size_t)3 * c.n_kf * 8, 3);
-    segp(w->d_lm_invd_out.p, c.nl * 8, 4);
-    LVF_TRY(w->d_stage.ensure(at + 16)); LVF_TRY(w->h_state.reserve(at / 8 + 2));
-    pa.stage = w->d_stage.p;
-    hipLaunchKernelGGL(k_window_pack, dim3(32), dim3(256), 0, s, pa);
+  LVF_TRY(w->h_stage.reserve(16 * 64 + (size_t)n_kf * 128 + 4096));      // (grow-only: the first copy above has completed)
+  StageWriter sp(w->h_stage, 0);
+  LVF_TRY(shape_prior_batch(w, sp, pl));
+  LVF_REQUIRE(sp.fits(), "lvf_window_solve: staging overflow");
+  if (sp.ua.n_segs) {
+    LVF_TRY(w->d_stage.ensure(sp.cur + 16));
+    LVF_HIP(hipMemcpyAsync(w->d_stage.p, sp.base, sp.cur, hipMemcpyHostToDevice, s));
+    sp.ua.stage = w->d_stage.p; sp.ua.g_seg = 8;
+    hipLaunchKernelGGL(k_window_unpack, dim3(sp.ua.g_seg), dim3(256), 0, s, sp.ua);
     LVF_HIP(hipGetLastError());
-    LVF_HIP(hipMemcpyAsync(w->h_state.p, w->d_stage.p, at, hipMemcpyDeviceToHost, s));
-    return LVF_OK;
-  };
-  LVF_TRY(lvf_problem_solve_then(w->prob, o, summary, pack_tail, &pc));      // (the wait for the control block also covers the copy above: same stream, enqueued first)
-  if (o->max_num_iterations <= 0) LVF_HIP(hipStreamSynchronize(s));            // (no iteration, no control block to wait for)
-  const auto t_solved = now();
-  {
-    const double *poses = w->h_state.p + offs[0] / 8, *vel = w->h_state.p + offs[1] / 8, *ba = w->h_state.p + offs[2] / 8, *bg = w->h_state.p + offs[3] / 8,
-                 *invd = w->h_state.p + offs[4] / 8;
-    for (int k = 0; k < n_kf; ++k) {
-      lvf_window::Kf& f = w->kfs[k];
-      std::memcpy(f.pose, &poses[(size_t)7 * k], 56);
-      if (f.good_imu) { std::memcpy(f.vel, &vel[(size_t)3 * k], 24); std::memcpy(f.ba, &ba[(size_t)3 * k], 24); std::memcpy(f.bg, &bg[(size_t)3 * k], 24); }
-    }
-    for (size_t i = 0; i < nl; ++i) if (w->lms[i].alive) w->lms[i].inv_depth = invd[i];
   }
-  w->slot_lm.clear();
-  w->lmtab_valid = true;
-  if (timing)
-    std::fprintf(stderr, "lvf_window_solve (device assembly): host tables %.3f ms (%zu bytes staged), upload + assembly + counters %.3f ms, small uploads %.3f ms, configure %.3f ms, solve %.3f ms (%d its), read-back %.3f ms\n",
-                 ms(t_begin, t_staged), cur, ms(t_staged, t_assembled), ms(t_assembled, t_uploaded), ms(t_uploaded, t_configured), ms(t_configured, t_solved), summary->num_iterations, ms(t_solved, now()));
+  if (timing_note)
+    std::snprintf(timing_note, note_len, " (device assembly): host tables %.3f ms (%zu bytes staged), upload + assembly + counters %.3f ms, small uploads %.3f ms", ms_between(t_begin, t_staged),
+                  sw.cur, ms_between(t_staged, t_assembled), ms_between(t_assembled, Clock::now()));
   return LVF_OK;
 }
 
-extern "C" {
-int lvf_window_solve(lvf_window* w, const lvf_solver_options* o, lvf_solver_summary* summary) {
-  LVF_REQUIRE(w && o && summary, "lvf_window_solve: null argument");
-  LVF_REQUIRE(!w->kfs.empty(), "lvf_window_solve: empty window");
-  lvf_ctx* ctx = w->ctx;
-  LVF_TRY(lvf::enter(ctx));
-  static const bool host_asm = getenv("LVF_WINDOW_HOST_ASM") != nullptr;
-  if (w->opt.device_assembly && !host_asm && (int)w->kfs.size() <= lvf::kDaMaxKf) return window_solve_device(w, o, summary);
-  hipStream_t s = ctx->stream;
+// ---- strategy 2: the host walks the features in BuildProblem's order and writes the block lists as 48-byte records into ONE pinned
+// staging buffer (see TcRec / TfRec / PoRec), the plain segments behind them
+static int assemble_host(lvf_window* w, char* timing_note, size_t note_len) {
+  hipStream_t s = w->ctx->stream;
   const int n_kf = (int)w->kfs.size();
-  w->lmtab_valid = false;                     // (host-side assembly: the device-resident landmark table, if any, goes stale)
-  static const bool timing = getenv("LVF_WINDOW_TIMING") != nullptr;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-  const auto t_begin = now();
-  // ---- assemble the block lists in BuildProblem's order, as 48-byte records in ONE pinned staging buffer (see k_window_unpack)
-  std::vector<double> pr_t, pr_w, pr_v;
-  std::vector<int32_t> imu_i, imu_j, pr_a, pr_b;
-  std::vector<lvf_preint> imu_pre;
-  w->slot_lm.clear();
+  const auto t_begin = Clock::now();
   // landmark->ToWorld() once per live landmark per tick (the reference recomputes it per feature) with the keyframe rotations
   // expanded once, and per frame the one row of the world->cam0 transform that Camera::Far needs
   std::vector<LmHot>& hot = w->hot;
@@ -1103,7 +869,6 @@ int lvf_window_solve(lvf_window* w, const lvf_solver_options* o, lvf_solver_summ
   const double far_z = w->opt.baseline * 50.0;
   size_t n_obs = 0;
   for (const lvf_window::Kf& f : w->kfs) n_obs += f.obs.size();
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
   // record regions sized by their upper bounds: one TwoCamera block per live landmark at most, every other feature one TwoFrame or
   // PoseOnly block; the PoseOnly region comes last so that the copy ends where its data ends
   const size_t cap_tc = std::min(n_obs, w->lms.size());
@@ -1127,29 +892,24 @@ int lvf_window_solve(lvf_window* w, const lvf_solver_options* o, lvf_solver_summ
     tc_sent = ntc; tf_sent = ntf;
     return LVF_OK;
   };
+  std::vector<int32_t> imu_i, imu_j;
+  imu_pairs(w, imu_i, imu_j);
+  PriorLists pl;
+  size_t fi = 0;
+  w->slot_lm.clear();                                  // dense slots in the order the walk first meets a landmark
+  auto slot_of =[&](LmHot& l, int lm) { if (l.slot < 0) { l.slot = (int)w->slot_lm.size(); w->slot_lm.push_back(lm); } return l.slot; };
   for (int k = 0; k < n_kf; ++k) {
     if (chunked && (k == n_kf / 3 || k == (2 * n_kf) / 3)) LVF_TRY(send_records());
     lvf_window::Kf& f = w->kfs[k];
     f.sort_unique();
-    // z_cam(pw) = zrow . pw + zoff  with  pc = R_e^-1 (R_wc^-1 pw + t_inv) + t_e_inv
-    double inv_pose[7], zrow[3], zoff;
-    hse3::inv(f.pose, inv_pose);
-    {
-      double ex[3] = {1, 0, 0}, ey[3] = {0, 1, 0}, ez[3] = {0, 0, 1}, c0[3], c1[3], c2[3], t[3], r[3];
-      hse3::rotate(inv_pose, ex, r); hse3::rotate(inv_e, r, c0);
-      hse3::rotate(inv_pose, ey, r); hse3::rotate(inv_e, r, c1);
-      hse3::rotate(inv_pose, ez, r); hse3::rotate(inv_e, r, c2);
-      zrow[0] = c0[2]; zrow[1] = c1[2]; zrow[2] = c2[2];
-      hse3::rotate(inv_e, inv_pose + 4, t);
-      zoff = t[2] + inv_e[6];
-    }
+    double zrow[3], zoff;
+    frame_far_row(inv_e, f.pose, zrow, &zoff);
     int near_visual = 0;
     for (const lvf_window::Obs& ob : f.obs) {
       LmHot& l = hot[ob.lm];
       if (l.birth_kf == f.id) {
-        if (l.slot < 0) { l.slot = (int)w->slot_lm.size(); w->slot_lm.push_back(ob.lm); }
         TcRec& r = tcr[ntc++];
-        r.l[0] = ob.ob[0]; r.l[1] = ob.ob[1]; r.r[0] = l.right_ob[0]; r.r[1] = l.right_ob[1]; r.lm = l.slot; r.kf = k; r.w = two_camera_weight(f.w_visual);
+        r.l[0] = ob.ob[0]; r.l[1] = ob.ob[1]; r.r[0] = l.right_ob[0]; r.r[1] = l.right_ob[1]; r.lm = slot_of(l, ob.lm); r.kf = k; r.w = two_camera_weight(f.w_visual);
         continue;
       }
       const double* pw = l.pw;
@@ -1160,118 +920,35 @@ int lvf_window_solve(lvf_window* w, const lvf_solver_options* o, lvf_solver_summ
         r.o[0] = ob.ob[0]; r.o[1] = ob.ob[1]; r.pw[0] = pw[0]; r.pw[1] = pw[1]; r.pw[2] = pw[2]; r.kf = k; r.pi = (int)npo;
         ++npo;
       } else {
-        if (l.slot < 0) { l.slot = (int)w->slot_lm.size(); w->slot_lm.push_back(ob.lm); }
         TfRec& r = tfr[ntf];
-        r.f[0] = l.right_ob[0]; r.f[1] = l.right_ob[1]; r.o[0] = ob.ob[0]; r.o[1] = ob.ob[1]; r.lm = l.slot; r.k1 = bpos; r.k2 = k;
+        r.f[0] = l.right_ob[0]; r.f[1] = l.right_ob[1]; r.o[0] = ob.ob[0]; r.o[1] = ob.ob[1]; r.lm = slot_of(l, ob.lm); r.k1 = bpos; r.k2 = k;
         ++kf2_counts[k];
         ++ntf;
       }
       if (!(zrow[0] * pw[0] + zrow[1] * pw[1] + zrow[2] * pw[2] + zoff > far_z)) ++near_visual;   // !Camera::Far
     }
-    bool imu_block = false;
-    if (f.good_imu && k > 0 && w->kfs[k - 1].good_imu && f.has_pre) {
-      imu_pre.push_back(f.pre); imu_i.push_back(k - 1); imu_j.push_back(k);
-      imu_block = true;
-    }
-    if (!imu_block && near_visual < w->opt.weak_visual_threshold) {
-      double t7[7] = {0, 0, 0, 0, 0, 0, 0};
-      if (k > 0) { LVF_TRY(lvf_relative_rpyxyz(w->kfs[k - 1].pose, f.pose, t7)); pr_a.push_back(k - 1); }
-      else { std::memcpy(t7, f.pose, 56); pr_a.push_back(-1); }
-      pr_b.push_back(k); pr_t.insert(pr_t.end(), t7, t7 + 7); pr_w.push_back(w->opt.prior_weight); pr_v.push_back(w->opt.prior_v);
-    }
+    const bool imu_block = fi < imu_j.size() && imu_j[fi] == k;
+    if (imu_block) ++fi;
+    LVF_TRY(weak_prior(w, k, imu_block, near_visual, pl));
   }
-  for (size_t i = 0; i < hot.size(); ++i) w->lms[i].slot = hot[i].slot;
   LVF_REQUIRE(ntc <= cap_tc, "lvf_window_solve: more TwoCamera blocks than live landmarks (%zu > %zu)", ntc, cap_tc);
   const int n_lm = (int)w->slot_lm.size();
-  w->n_lm_problem = n_lm;
-  w->n_tc = (int)ntc; w->n_tf = (int)ntf; w->n_po = (int)npo; w->n_imu = (int)imu_i.size(); w->n_prior = (int)pr_b.size();
-
-  const auto t_assembled = now();
-  // ---- persistent device objects: created once (empty), re-filled every tick through grow-only buffers
-  if (!w->st) {
-    LVF_TRY(lvf_state_create(ctx, 0, 0, &w->st));
-    const double z2[2] = {0, 0}; const int32_t z = 0; const double id7[7] = {0, 0, 0, 1, 0, 0, 0};
-    LVF_TRY(lvf_two_camera_create(ctx, &w->left, &w->right, 0, z2, z2, &z, &z, &w->tc));
-    LVF_TRY(lvf_two_frame_create(ctx, &w->left, &w->right, 0, z2, z2, &z, &z, &z, &w->tf));
-    LVF_TRY(lvf_pose_only_create(ctx, &w->left, 0, z2, &z, &z, 0, id7, &w->po));
-    LVF_TRY(lvf_imu_create(ctx, 0, nullptr, nullptr, nullptr, &w->imu));
-    LVF_TRY(lvf_pose_prior_create(ctx, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &w->prior));
-  }
-  lvf_state* st = w->st;
-  st->n_kf = n_kf; st->n_lm = n_lm;
-  // the read-back staging of the state (filled after the solve)
-  const size_t o_pose = 0, o_vel = (size_t)7 * n_kf, o_ba = o_vel + (size_t)3 * n_kf, o_bg = o_ba + (size_t)3 * n_kf, o_wv = o_bg + (size_t)3 * n_kf,
-               o_invd = o_wv + n_kf;
-  LVF_TRY(w->h_state.reserve(o_invd + n_lm));
-  double *poses = w->h_state.p + o_pose, *vel = w->h_state.p + o_vel, *ba = w->h_state.p + o_ba, *bg = w->h_state.p + o_bg, *invd = w->h_state.p + o_invd;
-  // the plain segments behind the PoseOnly records: state, IMU, priors.  Every destination gets two spare elements: segments are
-  // copied in 16-byte words.
-  UnpackArgs ua{};
-  size_t cur = up16(off_po + npo * 48);
-  auto seg = [&](void* dst, size_t bytes) -> unsigned char* {
-    unsigned char* at = hs + cur;
-    if (bytes) { ua.seg_dst[ua.n_segs] = static_cast<unsigned char*>(dst); ua.seg_off[ua.n_segs] = cur; ua.seg_words[ua.n_segs] = (unsigned)((bytes + 15) / 16); ++ua.n_segs; }
-    cur += up16(bytes);
-    return at;
-  };
-  auto idx_ok = [](lvf_batch* b, int n, int nkf, int nlm) { b->n = n; b->min_n_kf = nkf; b->min_n_lm = nlm; b->evaluated = false; };
-  LVF_TRY(st->poses.ensure((size_t)7 * n_kf + 2)); LVF_TRY(st->vel.ensure((size_t)3 * n_kf + 2)); LVF_TRY(st->ba.ensure((size_t)3 * n_kf + 2)); LVF_TRY(st->bg.ensure((size_t)3 * n_kf + 2));
-  LVF_TRY(st->w_visual.ensure((size_t)n_kf + 2)); LVF_TRY(st->inv_depth.ensure((size_t)n_lm + 2));
-  st->poses.n = (size_t)7 * n_kf; st->vel.n = st->ba.n = st->bg.n = (size_t)3 * n_kf; st->w_visual.n = n_kf; st->inv_depth.n = n_lm;
-  {
-    double* sp = reinterpret_cast<double*>(seg(st->poses.p, (size_t)7 * n_kf * 8));
-    double* sv = reinterpret_cast<double*>(seg(st->vel.p, (size_t)3 * n_kf * 8));
-    double* sa = reinterpret_cast<double*>(seg(st->ba.p, (size_t)3 * n_kf * 8));
-    double* sg = reinterpret_cast<double*>(seg(st->bg.p, (size_t)3 * n_kf * 8));
-    double* sw = reinterpret_cast<double*>(seg(st->w_visual.p, (size_t)n_kf * 8));
-    double* si = reinterpret_cast<double*>(seg(st->inv_depth.p, (size_t)n_lm * 8));
-    for (int k = 0; k < n_kf; ++k) {
-      const lvf_window::Kf& f = w->kfs[k];
-      std::memcpy(&sp[(size_t)7 * k], f.pose, 56); std::memcpy(&sv[(size_t)3 * k], f.vel, 24); std::memcpy(&sa[(size_t)3 * k], f.ba, 24);
-      std::memcpy(&sg[(size_t)3 * k], f.bg, 24); sw[k] = f.w_visual;
-    }
-    for (int l = 0; l < n_lm; ++l) si[l] = w->lms[w->slot_lm[l]].inv_depth;
-  }
-  // block arrays (filled by the unpack kernel from the records)
-  LVF_TRY(w->tc->ob_a.ensure(2 * ntc)); LVF_TRY(w->tc->ob_b.ensure(2 * ntc)); LVF_TRY(w->tc->idx_a.ensure(ntc)); LVF_TRY(w->tc->idx_b.ensure(ntc)); LVF_TRY(w->tc->wblk.ensure(ntc));
-  idx_ok(w->tc, w->n_tc, n_kf, n_lm);
-  LVF_TRY(w->tf->ob_a.ensure(2 * ntf)); LVF_TRY(w->tf->ob_b.ensure(2 * ntf)); LVF_TRY(w->tf->idx_a.ensure(ntf)); LVF_TRY(w->tf->idx_b.ensure(ntf)); LVF_TRY(w->tf->idx_c.ensure(ntf));
-  idx_ok(w->tf, w->n_tf, n_kf, n_lm);
-  w->tf->sorted_by_kf = true; w->tf->host_kf1.clear(); w->tf->host_kf2.clear(); w->tf->host_lm.clear(); w->tf->unique_lk2_known = true; w->tf->kf2_counts = std::move(kf2_counts);   // Kf::sort_unique keeps one observation per (keyframe, landmark); assembled frame by frame: sorted by current keyframe
-  LVF_TRY(w->po->ob_a.ensure(2 * npo)); LVF_TRY(w->po->idx_a.ensure(npo)); LVF_TRY(w->po->idx_b.ensure(npo)); LVF_TRY(w->po->table.ensure(3 * npo));
-  idx_ok(w->po, w->n_po, n_kf, 0); w->po->n_table = w->n_po; w->po->sorted_by_kf = true;
-  {
-    lvf_batch* b = w->imu;
-    const size_t ni = (size_t)w->n_imu;
-    LVF_TRY(b->pre.ensure(467 * ni + 2)); LVF_TRY(b->idx_a.ensure(ni + 4)); LVF_TRY(b->idx_b.ensure(ni + 4));
-    b->pre.n = 467 * ni; b->idx_a.n = b->idx_b.n = ni;
-    if (ni) {
-      std::memcpy(seg(b->pre.p, 467 * ni * 8), imu_pre.data(), 467 * ni * 8);
-      std::memcpy(seg(b->idx_a.p, ni * 4), imu_i.data(), ni * 4); std::memcpy(seg(b->idx_b.p, ni * 4), imu_j.data(), ni * 4);
-    }
-    b->host_kf1 = imu_i; b->host_kf2 = imu_j;
-    LVF_TRY(b->sqrt_info.ensure((size_t)225 * w->n_imu)); LVF_TRY(b->res.ensure((size_t)15 * w->n_imu));
-    for (int q = 0; q < 8; ++q) LVF_TRY(b->jac[q].ensure((size_t)15 * b->block_size[q] * w->n_imu));
-    idx_ok(b, w->n_imu, n_kf, 0);
-  }
-  {
-    lvf_batch* b = w->prior;
-    const size_t np_ = (size_t)w->n_prior;
-    LVF_TRY(b->idx_a.ensure(np_ + 4)); LVF_TRY(b->idx_b.ensure(np_ + 4)); LVF_TRY(b->table.ensure(7 * np_ + 2)); LVF_TRY(b->ob_a.ensure(np_ + 2)); LVF_TRY(b->ob_b.ensure(np_ + 2));
-    b->idx_a.n = b->idx_b.n = np_; b->table.n = 7 * np_; b->ob_a.n = b->ob_b.n = np_;
-    if (np_) {
-      std::memcpy(seg(b->idx_a.p, np_ * 4), pr_a.data(), np_ * 4); std::memcpy(seg(b->idx_b.p, np_ * 4), pr_b.data(), np_ * 4);
-      std::memcpy(seg(b->table.p, 7 * np_ * 8), pr_t.data(), 7 * np_ * 8);
-      std::memcpy(seg(b->ob_a.p, np_ * 8), pr_w.data(), np_ * 8); std::memcpy(seg(b->ob_b.p, np_ * 8), pr_v.data(), np_ * 8);
-    }
-    LVF_TRY(b->res.ensure((size_t)6 * w->n_prior)); LVF_TRY(b->jac[0].ensure((size_t)42 * w->n_prior)); LVF_TRY(b->jac[1].ensure((size_t)42 * w->n_prior));
-    idx_ok(b, w->n_prior, n_kf, 0);
-    b->host_kf1 = pr_a; b->host_kf2 = pr_b;
-  }
-  LVF_REQUIRE(cur <= w->h_stage.cap && ua.n_segs <= kMaxSegs, "lvf_window_solve: staging overflow");
-  // the rest of the records, then the PoseOnly records and the plain segments in one copy; one unpack launch
+  const auto t_assembled = Clock::now();
+  // the plain segments behind the PoseOnly records: state (with the inverse depths, by slot), IMU, priors
+  StageWriter sw(w->h_stage, up16(off_po + npo * 48));
+  LVF_TRY(stage_state(w, sw, (size_t)n_lm));
+  double* si = sw.seg_of(w->st->inv_depth.p, (size_t)n_lm);
+  for (int l = 0; l < n_lm; ++l) si[l] = w->lms[w->slot_lm[l]].inv_depth;
+  LVF_TRY(ensure_visual(w, ntc, ntf, npo));
+  set_visual_counts(w, ntc, ntf, npo, n_lm, std::move(kf2_counts));
+  LVF_TRY(shape_imu_batch(w, sw, imu_i, imu_j));
+  LVF_TRY(shape_prior_batch(w, sw, pl));
+  LVF_REQUIRE(sw.fits(), "lvf_window_solve: staging overflow");
+  // the rest of the records, then the PoseOnly records and the plain segments in one copy; one unpack launch: its record half fills the
+  // batches' SoA arrays
   LVF_TRY(send_records());
-  if (cur > off_po) LVF_HIP(hipMemcpyAsync(w->d_stage.p + off_po, hs + off_po, cur - off_po, hipMemcpyHostToDevice, s));
+  if (sw.cur > off_po) LVF_HIP(hipMemcpyAsync(w->d_stage.p + off_po, hs + off_po, sw.cur - off_po, hipMemcpyHostToDevice, s));
+  UnpackArgs& ua = sw.ua;
   ua.stage = w->d_stage.p; ua.ntc = (int)ntc; ua.ntf = (int)ntf; ua.npo = (int)npo; ua.off_tc = off_tc; ua.off_tf = off_tf; ua.off_po = off_po;
   ua.tc_l = reinterpret_cast<double2*>(w->tc->ob_a.p); ua.tc_r = reinterpret_cast<double2*>(w->tc->ob_b.p); ua.tc_lm = w->tc->idx_a.p; ua.tc_kf = w->tc->idx_b.p; ua.tc_w = w->tc->wblk.p;
   ua.tf_f = reinterpret_cast<double2*>(w->tf->ob_a.p); ua.tf_o = reinterpret_cast<double2*>(w->tf->ob_b.p); ua.tf_lm = w->tf->idx_a.p; ua.tf_k1 = w->tf->idx_b.p; ua.tf_k2 = w->tf->idx_c.p;
@@ -1279,49 +956,39 @@ int lvf_window_solve(lvf_window* w, const lvf_solver_options* o, lvf_solver_summ
   ua.g_tc = (int)((ntc + 255) / 256); ua.g_tf = (int)((ntf + 255) / 256); ua.g_po = (int)((npo + 255) / 256); ua.g_seg = 64;
   hipLaunchKernelGGL(k_window_unpack, dim3(ua.g_tc + ua.g_tf + ua.g_po + ua.g_seg), dim3(256), 0, s, ua);
   LVF_HIP(hipGetLastError());
-  if (w->n_imu) LVF_TRY(launch_imu_sqrt_info(w->imu));
-  w->sq_valid = false;                               // (this path factors every pair: nothing is tracked for the cached form)
-  const auto t_uploaded = now();
-  if (!w->prob) {
-    LVF_TRY(lvf_problem_create(ctx, st, w->tc, w->tf, w->po, w->imu, &w->prob));
-    LVF_TRY(lvf_problem_set_pose_priors(w->prob, w->prior));
-  } else {
-    LVF_TRY(problem_configure(w->prob));
-  }
-  LVF_TRY(window_attach_lidar(w));
-  const auto t_configured = now();
-  LVF_TRY(lvf_problem_solve(w->prob, o, summary));
-  const auto t_solved = now();
-  // ---- read the solution back into the host mirror (frame->pose, Vw, biases, landmark->inv_depth): gathered on the device, one copy
-  {
-    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    PackArgs pa{};
-    size_t at = 0;
-    size_t offs[5];
-    auto seg = [&](const void* src, size_t bytes, int slot) {
-      offs[slot] = at;
-      if (bytes) { pa.src[pa.n_segs] = static_cast<const unsigned char*>(src); pa.off[pa.n_segs] = at; pa.words[pa.n_segs] = (unsigned)((bytes + 15) / 16); ++pa.n_segs; }
-      at += up16(bytes);
-    };
-    seg(st->poses.p, (size_t)7 * n_kf * 8, 0); seg(st->vel.p, (size_t)3 * n_kf * 8, 1); seg(st->ba.p, (size_t)3 * n_kf * 8, 2); seg(st->bg.p, (size_t)3 * n_kf * 8, 3);
-    seg(st->inv_depth.p, (size_t)n_lm * 8, 4);
-    LVF_TRY(w->d_stage.ensure(at + 16)); LVF_TRY(w->h_state.reserve(at / 8 + 2));
-    pa.stage = w->d_stage.p;
-    hipLaunchKernelGGL(k_window_pack, dim3(32), dim3(256), 0, s, pa);
-    LVF_HIP(hipGetLastError());
-    LVF_HIP(hipMemcpyAsync(w->h_state.p, w->d_stage.p, at, hipMemcpyDeviceToHost, s));
-    LVF_HIP(hipStreamSynchronize(s));
-    poses = w->h_state.p + offs[0] / 8; vel = w->h_state.p + offs[1] / 8; ba = w->h_state.p + offs[2] / 8; bg = w->h_state.p + offs[3] / 8; invd = w->h_state.p + offs[4] / 8;
-  }
-  for (int k = 0; k < n_kf; ++k) {
-    lvf_window::Kf& f = w->kfs[k];
-    std::memcpy(f.pose, &poses[(size_t)7 * k], 56);
-    if (f.good_imu) { std::memcpy(f.vel, &vel[(size_t)3 * k], 24); std::memcpy(f.ba, &ba[(size_t)3 * k], 24); std::memcpy(f.bg, &bg[(size_t)3 * k], 24); }
-  }
-  for (int l = 0; l < n_lm; ++l) w->lms[w->slot_lm[l]].inv_depth = invd[l];
-  if (timing)
-    std::fprintf(stderr, "lvf_window_solve: assemble %.3f ms, upload %.3f ms, configure %.3f ms, solve %.3f ms (%d its), read-back %.3f ms\n", ms(t_begin, t_assembled),
-                 ms(t_assembled, t_uploaded), ms(t_uploaded, t_configured), ms(t_configured, t_solved), summary->num_iterations, ms(t_solved, now()));
+  if (w->n_imu) LVF_TRY(launch_imu_sqrt_info(w->imu));      // (this strategy factors every pair: nothing is tracked for the cached form)
+  if (timing_note)
+    std::snprintf(timing_note, note_len, ": assemble %.3f ms, upload %.3f ms", ms_between(t_begin, t_assembled), ms_between(t_assembled, Clock::now()));
+  return LVF_OK;
+}
+
+extern "C" {
+int lvf_window_solve(lvf_window* w, const lvf_solver_options* o, lvf_solver_summary* summary) {
+  LVF_REQUIRE(w && o && summary, "lvf_window_solve: null argument");
+  LVF_REQUIRE(!w->kfs.empty(), "lvf_window_solve: empty window");
+  LVF_TRY(lvf::enter(w->ctx));
+  using Assembler = lvf_window::Assembler;
+  static const bool host_asm = getenv("LVF_WINDOW_HOST_ASM") != nullptr;
+  const Assembler by = w->opt.device_assembly && !host_asm && (int)w->kfs.size() <= kDaMaxKf ? Assembler::device : Assembler::host;
+  char note[256] = "";
+  char* timing_note = window_timing() ? note : nullptr;
+  LVF_TRY(ensure_objects(w));
+  // the block lists, the state, the IMU and prior batches: assembled, uploaded, the batches shaped
+  begin_assembly(w, by);
+  LVF_TRY(by == Assembler::device ? assemble_device(w, timing_note, sizeof note) : assemble_host(w, timing_note, sizeof note));
+  const auto t_uploaded = Clock::now();
+  LVF_TRY(configure_problem(w));
+  const auto t_configured = Clock::now();
+  // solve, with the read-back enqueued behind the last iteration and ahead of the wait that ends the solve: ONE stream wait per tick for both
+  ReadBack rb{w, by == Assembler::device, {0, 0, 0, 0, 0}};
+  LVF_TRY(lvf_problem_solve_then(w->prob, o, summary, enqueue_read_back, &rb));      // (the wait for the control block also covers the read-back's copy: same stream, enqueued first)
+  if (o->max_num_iterations <= 0) LVF_HIP(hipStreamSynchronize(w->ctx->stream));       // (no iteration, no control block to wait for; lvf_window_marginal relies on this)
+  const auto t_solved = Clock::now();
+  apply_read_back(w, rb);
+  if (by == Assembler::device) w->lmtab_valid = true;      // the resident landmark table holds what this tick solved (k_da_scatter_invd)
+  if (timing_note)
+    std::fprintf(stderr, "lvf_window_solve%s, configure %.3f ms, solve %.3f ms (%d its), read-back %.3f ms\n", note, ms_between(t_uploaded, t_configured),
+                 ms_between(t_configured, t_solved), summary->num_iterations, ms_between(t_solved, Clock::now()));
   return LVF_OK;
 }
 
@@ -1427,17 +1094,16 @@ int lvf_window_debug_blocks(lvf_window* w, int kind, int capacity, int64_t* ids,
   if (kind == 1) { LVF_TRY(get_i(b->idx_b, ib, m)); LVF_TRY(get_d(b->table, tab, (size_t)3 * b->n_table)); }
   if (kind == 3) { LVF_TRY(get_i(b->idx_a, ia, m)); LVF_TRY(get_i(b->idx_b, ib, m)); }
   if (kind == 4) { LVF_TRY(get_i(b->idx_a, ia, m)); LVF_TRY(get_i(b->idx_b, ib, m)); LVF_TRY(get_d(b->ob_a, oa, m)); LVF_TRY(get_d(b->ob_b, ob, m)); }
-  const bool need_slots = kind == 0 || kind == 2;
-  if (need_slots && (int)w->slot_lm.size() != w->n_lm_problem) {      // device assembly: the slot table lives on the device
-    slot_lm.resize((size_t)w->n_lm_problem);
-    if (w->n_lm_problem) LVF_HIP(hipMemcpyAsync(slot_lm.data(), w->d_slot_lm.p, (size_t)w->n_lm_problem * 4, hipMemcpyDeviceToHost, s));
+  // dense landmark slot -> landmark index, from where the strategy that assembled these lists left it
+  if (kind == 0 || kind == 2) {
+    if (w->assembled_by == lvf_window::Assembler::device) {
+      slot_lm.resize((size_t)w->n_lm_problem);
+      if (w->n_lm_problem) LVF_HIP(hipMemcpyAsync(slot_lm.data(), w->d_slot_lm.p, (size_t)w->n_lm_problem * 4, hipMemcpyDeviceToHost, s));
+    } else slot_lm.assign(w->slot_lm.begin(), w->slot_lm.end());
   }
   LVF_HIP(hipStreamSynchronize(s));
-  const std::vector<int>* sl = nullptr;
-  std::vector<int> sl_copy;
-  if (need_slots) { if (slot_lm.empty() && (int)w->slot_lm.size() == w->n_lm_problem) sl = &w->slot_lm; else { sl_copy.assign(slot_lm.begin(), slot_lm.end()); sl = &sl_copy; } }
   auto kf_id = [&](int pos) -> int64_t { return (pos >= 0 && pos < n_kf) ? w->kfs[pos].id : -1; };
-  auto lm_id = [&](int slot) -> int64_t { return (sl && slot >= 0 && slot < (int)sl->size()) ? w->lms[(*sl)[slot]].id : -1; };
+  auto lm_id = [&](int slot) -> int64_t { return (slot >= 0 && slot < (int)slot_lm.size()) ? w->lms[slot_lm[slot]].id : -1; };
   auto wv = [&](int pos) { return (pos >= 0 && pos < n_kf) ? w->kfs[pos].w_visual : 0.0; };
   for (int i = 0; i < m; ++i) {
     int64_t* I = ids + 3 * (size_t)i; double* V = vals + 8 * (size_t)i;

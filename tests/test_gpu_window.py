@@ -166,6 +166,101 @@ def test_ticks_match_from_scratch_assembly(oracle, with_imu, weak_thr, device_as
     win.close(); ctx.close()
 
 
+def test_window_crosses_the_device_assembly_limit_and_back(oracle):
+    """A window made with device_assembly=True assembles on the device only while it holds at most 64 keyframes (kDaMaxKf); above that it
+    takes the host walk, and it comes back once it has slid below.  The strategy is selected BY THE KEYFRAME COUNT ALONE and nothing the
+    API reports names it, so the crossing is pinned against a twin made with device_assembly=False (always the host walk) that is fed the
+    same drive: solves at 63, 64 (device), 65, 66 (host) keyframes without sliding, four more keyframes and a re-integrated IMU pair while
+    the host walk owns the window, a slide to 60 keyframes, and two more solves — the first back on the device must send the whole landmark
+    table again and factor every ImuError information matrix again (the host ticks tracked neither), the second runs resident.  At every
+    solve: the same census, the same block lists (which blocks, in which order, on which landmarks / keyframes, with which observations
+    and weights), and states that agree within the bounds test_ticks_match_from_scratch_assembly holds a window to.  The frozen world
+    point of a PoseOnly block is Landmark::ToWorld of the two windows' own solved states at the slide — R(pose) (ray / inv_depth) + t with
+    inv_depth within 1e-6 and the pose within assert_parity's 1e-6 of each other — so it is compared to 3e-6 of the largest coordinate."""
+    from lvio_fusion_amd import api
+    from tests import window_replay as wr
+    N, GROW_TO, KEEP = 70, 66, 60
+    cfg = syn.config4_window(n_kf=N, n_lm=70, n_prewindow=0, seed=606, imu_samples=4, p_geom=0.2)
+    tc, tf = cfg["tc"], cfg["tf"]
+    assert len(tc["lm_idx"]) + len(tf["lm_idx"]) < 500
+    pre = [oracle.imu_preintegrate(f["samples"], f["acc0"], f["gyr0"], f["ba"], f["bg"], syn.IMU_NOISE) for f in cfg["imu"]]
+    ctx = api.Context(0)
+    wins = [api.Window(ctx, cfg["cam0"], cfg["cam1"], baseline=syn.baseline(), device_assembly=d) for d in (True, False)]
+    opt = api.default_solver_options(); opt.max_num_iterations = 2
+    ids = {"kf": [], "lm": set()}
+
+    def add_keyframe(t):
+        for win in wins:
+            win.add_keyframe(100 + t, cfg["poses"][t], cfg["w_kf"][t])
+            win.set_imu(100 + t, cfg["vel"][t], cfg["ba"][t], cfg["bg"][t], pre[t - 1] if t > 0 else None)
+            for i in np.nonzero(tc["kf_idx"] == t)[0]:
+                win.add_landmark(5000 + int(tc["lm_idx"][i]), 100 + t, tc["left_ob"][i], tc["right_ob"][i], cfg["inv_depth"][tc["lm_idx"][i]])
+            for i in np.nonzero(tf["kf2_idx"] == t)[0]:
+                win.add_observation(5000 + int(tf["lm_idx"][i]), 100 + t, tf["ob"][i])
+        ids["kf"].append(100 + t)
+        ids["lm"].update(5000 + int(l) for l in tc["lm_idx"][tc["kf_idx"] == t])
+
+    seen = dict(po=0, tf=0, imu=0)
+
+    def solve_and_compare(what):
+        for win in wins:
+            win.solve(opt)
+        dev, host = wins
+        cd, ch = dev.counts(), host.counts()
+        assert cd == ch, f"{what}: census {cd} vs {ch}"
+        ld, lh = wr.window_lists(dev), wr.window_lists(host)
+        for kind in wr.KINDS:
+            g, h = ld[kind], lh[kind]
+            assert g["ids"].shape == h["ids"].shape and np.array_equal(g["ids"], h["ids"]), f"{what} {kind}: block set / order / indices"
+            if kind in ("TwoCamera", "TwoFrame"):
+                assert np.array_equal(g["vals"][:, :5], h["vals"][:, :5]), f"{what} {kind}: weight / observations"
+            elif kind == "PoseOnly":
+                assert np.array_equal(g["vals"][:, :3], h["vals"][:, :3]), f"{what} {kind}: weight / observation"
+                if len(h["ids"]):
+                    assert np.abs(g["vals"][:, 5:8] - h["vals"][:, 5:8]).max() <= 3e-6 * np.abs(h["vals"][:, 5:8]).max(), f"{what} {kind}: frozen world point"
+            elif kind in ("PoseGraphError", "PoseError"):
+                assert np.array_equal(g["vals"][:, :2], h["vals"][:, :2]), f"{what} {kind}: prior weight / v"
+        for k in ids["kf"]:
+            assert_parity(dev.pose(k), host.pose(k), f"{what} pose {k}")
+            assert_parity(dev.imu(k)[0], host.imu(k)[0], f"{what} vel {k}")
+        for l in sorted(ids["lm"]):
+            a, b = dev.inv_depth(l), host.inv_depth(l)
+            assert abs(a - b) <= 1e-6 * abs(b), f"{what} inverse depth {l}"
+        assert cd["kf"] == len(ids["kf"]) and cd["imu"] == cd["kf"] - 1
+        seen["po"] += cd["po"]; seen["tf"] += cd["tf"]; seen["imu"] += cd["imu"]
+
+    for t in range(GROW_TO):
+        add_keyframe(t)
+        if t + 1 >= 63:
+            solve_and_compare(f"{t + 1} keyframes")         # 63, 64: device assembly; 65, 66: the host walk
+    for t in range(GROW_TO, N):
+        add_keyframe(t)
+    # an older pair that stays in the window is re-integrated while the host walk owns it (Repropagate after a bias change): back on the
+    # device its information matrix must not come from what the device path cached before the crossing
+    f39 = cfg["imu"][39]
+    noise2 = {k: 2.0 * v for k, v in syn.IMU_NOISE.items()} if isinstance(syn.IMU_NOISE, dict) else tuple(2.0 * x for x in syn.IMU_NOISE)
+    pre39 = oracle.imu_preintegrate(f39["samples"], f39["acc0"], f39["gyr0"], f39["ba"], f39["bg"], noise2)
+    for win in wins:
+        v, a, g = win.imu(100 + 40)
+        win.set_imu(100 + 40, v, a, g, pre39)
+    first = N - KEEP
+    for win in wins:
+        win.slide(100 + first)
+    ids["kf"] = ids["kf"][first:]
+    born = {5000 + int(l): int(k) for l, k in zip(tc["lm_idx"], tc["kf_idx"])}
+    last_seen = dict(born)
+    for l, k in zip(tf["lm_idx"], tf["kf2_idx"]):
+        last_seen[5000 + int(l)] = max(last_seen[5000 + int(l)], int(k))
+    ids["lm"] = {l for l in ids["lm"] if last_seen[l] >= first}            # (the slide prunes landmarks nobody in the window observes)
+    solve_and_compare("back at 60 keyframes")
+    solve_and_compare("resident again")
+    assert seen["po"] > 0 and seen["tf"] > 0 and seen["imu"] > 0
+    assert wins[0].counts()["lm_known"] == len(ids["lm"])
+    for win in wins:
+        win.close()
+    ctx.close()
+
+
 def test_reject_outliers_matches_the_reference_gate(oracle):
     """Backend::Optimize's outlier rejection (backend.cpp:229-245): features that are not their landmark's first observation and whose
     unit-weight reprojection error exceeds 10 px are removed; the device gate must pick exactly the set the oracle's PoseOnly residuals
