@@ -790,7 +790,7 @@ int dc_tail_run(lvf_ctx* ctx, const DcTailPlan& plan, hipStream_t q, const float
   if (plan.two_streams) LVF_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));
   return LVF_OK;
 }
-// out = a new cloud of n points: pose * in[0 .. n)  (Sensor2Robot, association.cpp:236-247)
+// out = a new cloud of n points: pose * in[0 .. n)  (Sensor2Robot, association.cpp:236-247; lvf_cloud_transform is this behind its argument checks)
 int transform_points(lvf_ctx* ctx, const float4* in, int n, const double* pose, lvf_cloud** out) {
   lvf_cloud* c = nullptr;
   LVF_TRY(new_cloud(ctx, n, &c));
@@ -837,12 +837,7 @@ int lvf_cloud_download(const lvf_cloud* c, float* xyzi) {
 int lvf_cloud_transform(const lvf_cloud* in, const double* pose, lvf_cloud** out) {
   LVF_REQUIRE(in && pose && out, "lvf_cloud_transform: null argument");
   LVF_TRY(lvf::enter(in->ctx));
-  lvf_cloud* c = nullptr;
-  LVF_TRY(new_cloud(in->ctx, in->n, &c));
-  if (in->n) hipLaunchKernelGGL(k_cloud_transform, dim3(gridc(in->n)), dim3(kC), 0, in->ctx->stream, in->n, in->pts.p, tf_arg(pose), c->pts.p);
-  LVF_HIP(hipGetLastError());
-  *out = c;
-  return LVF_OK;
+  return transform_points(in->ctx, in->pts.p, in->n, pose, out);
 }
 
 int lvf_cloud_concat(lvf_ctx* ctx, const lvf_cloud* const* parts, int n_parts, lvf_cloud** out) {

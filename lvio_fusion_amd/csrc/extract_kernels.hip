@@ -18,6 +18,8 @@
 // Float arithmetic follows the reference's float/double promotions; sin/cos of the two constant angles and the start/end
 // orientations are taken on the HOST; every atan2 of floats — host or device — is cr_atan2f (cr_math.hpp: correctly rounded, one
 // operation sequence for both sides), sqrtf is IEEE on both: the per-pixel decisions are reproducible bit for bit.
+// Host side: extract_entry picks extract_device_counted (default: counts on the device, one stream wait per scan) or extract_host_counted (fallback and
+// A/B: counts read back stage by stage).  Both run the shared stages — ScanUpload, RangeImage, PickArrays, the taps, emit_features — and state only their own scans, tail and waits.
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
@@ -217,7 +219,7 @@ __device__ __forceinline__ float ori_first_half(float x, float y, OriP o, bool& 
   return ori;
 }
 // FindStartEndAngle (projection.cpp:42-56): the reference's float / double promotions, for the host-counted path on the host and for the
-// device-counted one in a one-thread launch
+// device-counted one in every thread that needs them (ori_of)
 __host__ __device__ inline OriP find_start_end(const float4 first, const float4 last, double cycle) {
   OriP o;
   float start = -cr_atan2f(first.y, first.x);
@@ -236,23 +238,17 @@ __device__ __forceinline__ OriP ori_of(const OriSrc& src) {
   const float4 unit = make_float4(1, 0, 0, 0);
   return find_start_end(m ? src.filtered[0] : unit, m ? src.filtered[m - 1] : unit, src.cycle);
 }
-__global__ __launch_bounds__(kE) void k_ex_latch(int m, const int* __restrict__ m_dev, const float4* __restrict__ seg, OriP o, const OriSrc op,
-                                                 int* __restrict__ latch) {
+__global__ __launch_bounds__(kE) void k_ex_latch(int m, const float4* __restrict__ seg, OriP o, int* __restrict__ latch) {
   const int i = blockIdx.x * kE + threadIdx.x;
-  if (m_dev) m = min(m, *m_dev);
   if (i >= m) return;
-  if (op.m_dev) o = ori_of(op);
   bool l;
   (void)ori_first_half(seg[i].x, seg[i].y, o, l);
   latch[i] = l ? 1 : 0;
 }
 __device__ __forceinline__ void reltime_body(const int i, float4* __restrict__ seg, const OriP o, const int* __restrict__ latch_before);
-__global__ __launch_bounds__(kE) void k_ex_reltime(int m, const int* __restrict__ m_dev, float4* __restrict__ seg, OriP o, const OriSrc op,
-                                                   const int* __restrict__ latch_before) {
+__global__ __launch_bounds__(kE) void k_ex_reltime(int m, float4* __restrict__ seg, OriP o, const int* __restrict__ latch_before) {
   const int i = blockIdx.x * kE + threadIdx.x;
-  if (m_dev) m = min(m, *m_dev);
   if (i >= m) return;
-  if (op.m_dev) o = ori_of(op);
   reltime_body(i, seg, o, latch_before);
 }
 __device__ __forceinline__ void reltime_body(const int i, float4* __restrict__ seg, const OriP o, const int* __restrict__ latch_before) {
@@ -273,11 +269,10 @@ __device__ __forceinline__ void reltime_body(const int i, float4* __restrict__ s
 // CalculateSmoothness + ExtractFeatures' sector test for segmented point k
 __device__ __forceinline__ void pick_body(const int k, const int m, int Cn, const float* __restrict__ rg, const int* __restrict__ seg_ground, const int* __restrict__ seg_row,
                                           const int* __restrict__ pixpos, int* __restrict__ pick_ground, int* __restrict__ pick_surf, float* __restrict__ curv_out);
-__global__ __launch_bounds__(kE) void k_ex_pick(int m, const int* __restrict__ m_dev, int Cn, const float4* __restrict__ seg, const float* __restrict__ rg, const int* __restrict__ seg_ground,
+__global__ __launch_bounds__(kE) void k_ex_pick(int m, int Cn, const float4* __restrict__ seg, const float* __restrict__ rg, const int* __restrict__ seg_ground,
                                                 const int* __restrict__ seg_row, const int* __restrict__ pixpos /* exclusive prefix over pixels */,
                                                 int* __restrict__ pick_ground, int* __restrict__ pick_surf, float* __restrict__ curv_out) {
   const int k = blockIdx.x * kE + threadIdx.x;
-  if (m_dev) m = min(m, *m_dev);
   if (k >= m) return;
   pick_body(k, m, Cn, rg, seg_ground, seg_row, pixpos, pick_ground, pick_surf, curv_out);
 }
@@ -391,63 +386,141 @@ using namespace lvf;
 
 // what lvf_lidar_extract_edges adds to a chain (null: exactly lvf_lidar_extract[_deskewed]'s launches)
 struct EdgeReq { lvf_edge_params prm; lvf_cloud** sharp_out; lvf_cloud** less_out; lvf_edge_extract_debug* dbg; };
-// pick_sharp and pick_less are the two halves of ONE block (pick_less = pick_sharp + capacity): one memset clears both
-static int launch_edge_pick(hipStream_t s, int cap_m, const int* m_dev, int R, int Cn, const float* curv, const int* seg_ground, const int* pixpos, const lvf_edge_params& e,
-                            int* pick_sharp, int* pick_less) {
-  LVF_HIP(hipMemsetAsync(pick_sharp, 0, (size_t)(pick_less - pick_sharp) * 8, s));      // both flag arrays: halves of one block, pick_less behind pick_sharp
-  const EdgePickP E{e.edge_threshold, e.n_sharp, e.n_less_sharp, Cn / 6 + 8};
-  hipLaunchKernelGGL(k_ex_edge_pick, dim3(R * 6), dim3(64), (size_t)4 * E.cap, s, cap_m, m_dev, Cn, curv, seg_ground, pixpos, E, pick_sharp, pick_less);
-  LVF_HIP(hipGetLastError());
-  return LVF_OK;
-}
 
 static std::atomic<int> g_extract_host_counts{[] { const char* e = std::getenv("LVF_EXTRACT_HOST_COUNTS"); return (e && e[0] == '1') ? 1 : 0; }()};
 static std::atomic<int> g_extract_fallbacks{0};      // scans the device-counted path handed to the host-counted one (lvf_debug_extract_fallbacks)
 
-// The host-counted path (rounds 2-4; kept as the fallback of the device-counted one and as its reference in the tests): every stage reads its
-// output count back before the next one is sized — 13 stream waits per scan.
-// dk (here and in the device-counted path; null: none, exactly lvf_lidar_extract's launches): the deskew of the two pick clouds, in place, where
+// ---- the stages of FeatureAssociation::Process, written once.  The two paths below state where the counts live, which scan / compaction and which
+// PCL tail they call and when they wait; the rest is one of these.  A stage enqueues on the stream it is given and waits for nothing, the two taps excepted.
+struct ExStamps {      // LVF_EXTRACT_TIMING (device-counted path): the upload enqueued, the last launch enqueued; us() = microseconds since the call began
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double upload = 0.0, enq = 0.0;
+  double us() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+};
+// Preprocess' front: the raw scan on the device, packed to float4, and the NaN + range gate as one flag per point
+struct ScanUpload {
+  DevBuf<float> src; DevBuf<float4> packed; DevBuf<int> flags;
+  HostPin<float> stage;      // (pooled pinned staging)
+  StreamWaitGuard guard;     // declared AFTER `stage`: every path out — the error returns too — waits for the copy before the block returns to the pool
+  explicit ScanUpload(hipStream_t s) : guard(s) {}
+  int run(hipStream_t s, const float* points, int n, int stride_floats, const ExP& P, ExStamps* st) {
+    LVF_TRY(src.upload_staged(points, (size_t)n * stride_floats, s, stage)); LVF_TRY(packed.alloc(std::max(n, 1))); LVF_TRY(flags.alloc(std::max(n, 1)));
+    if (st) st->upload = st->us();
+    if (n) hipLaunchKernelGGL(k_ex_preflag, dim3(gride(n)), dim3(kE), 0, s, n, src.p, stride_floats, P.min2, P.max2, packed.p, flags.p);
+    LVF_HIP(hipGetLastError());
+    return LVF_OK;
+  }
+};
+// ImageProjection::Process up to the flag of every pixel that belongs to the segmented cloud (the caller scans `flags` into `pos`)
+struct RangeImage {
+  int npix = 0;
+  DevBuf<int> pixel_src, size, parent, flags, pos, label; DevBuf<unsigned long long> rows; DevBuf<float4> full; DevBuf<float> range; DevBuf<signed char> ground;
+  int alloc(int n) {
+    npix = n; LVF_TRY(pixel_src.alloc(npix)); LVF_TRY(size.alloc(npix)); LVF_TRY(rows.alloc(npix)); LVF_TRY(parent.alloc(npix)); LVF_TRY(flags.alloc(npix));
+    LVF_TRY(pos.alloc((size_t)npix + 1)); LVF_TRY(label.alloc(npix)); LVF_TRY(full.alloc(npix)); LVF_TRY(range.alloc(npix)); LVF_TRY(ground.alloc(npix));
+    return LVF_OK;
+  }
+  // what does not depend on the scan: pixel_src = -1, size = 0, rows = 0 (the next hipGetLastError on the way looks at this launch too)
+  void clear(hipStream_t s) { hipLaunchKernelGGL(k_ex_clear, dim3(gride(npix)), dim3(kE), 0, s, npix, pixel_src.p, size.p, rows.p); }
+  // the filtered cloud: cap_m points at the most, m_dev (null: exactly cap_m) their count on the device
+  int build(hipStream_t s, int cap_m, const int* m_dev, const float4* filtered, const ExP& P) {
+    if (cap_m) hipLaunchKernelGGL(k_ex_project, dim3(gride(cap_m)), dim3(kE), 0, s, cap_m, m_dev, filtered, P, pixel_src.p);
+    hipLaunchKernelGGL(k_ex_fill, dim3(gride(npix)), dim3(kE), 0, s, npix, filtered, P, pixel_src.p, full.p, range.p);
+    hipLaunchKernelGGL(k_ex_ground, dim3(gride(npix)), dim3(kE), 0, s, npix, full.p, range.p, P, ground.p, parent.p);
+    hipLaunchKernelGGL(k_ex_union, dim3(gride(npix)), dim3(kE), 0, s, npix, range.p, P, parent.p);
+    hipLaunchKernelGGL(k_ex_stats, dim3(gride(npix)), dim3(kE), 0, s, npix, P.Cn, parent.p, size.p, rows.p);
+    hipLaunchKernelGGL(k_ex_segflag, dim3(gride(npix)), dim3(kE), 0, s, npix, parent.p, size.p, rows.p, ground.p, flags.p, label.p);
+    LVF_HIP(hipGetLastError());
+    return LVF_OK;
+  }
+};
+// what AdjustDistortion, CalculateSmoothness and the picks keep per segmented point; pick_e: the sharp and less-sharp flags, the two halves of ONE block
+struct PickArrays {
+  DevBuf<float4> seg; DevBuf<float> seg_range, curv; DevBuf<int> seg_ground, seg_row, latch, latch_pos, pick_g, pick_s, pick_both;
+  int* pick_e[2] = {nullptr, nullptr};
+  int alloc(int mm, bool edges) {
+    LVF_TRY(seg.alloc(mm)); LVF_TRY(seg_range.alloc(mm)); LVF_TRY(curv.alloc(mm)); LVF_TRY(seg_ground.alloc(mm)); LVF_TRY(seg_row.alloc(mm));
+    LVF_TRY(latch.alloc(mm)); LVF_TRY(latch_pos.alloc((size_t)mm + 1)); LVF_TRY(pick_g.alloc(mm)); LVF_TRY(pick_s.alloc(mm));
+    if (edges) { LVF_TRY(pick_both.alloc((size_t)2 * mm)); pick_e[0] = pick_both.p; pick_e[1] = pick_both.p + mm; }
+    return LVF_OK;
+  }
+  // the edge picks of cap_m segmented points at the most (m_dev, null: exactly cap_m, their count on the device) into pick_e; one memset clears both halves
+  int edge_pick(hipStream_t s, int cap_m, const int* m_dev, const ExP& P, const int* pixpos, const lvf_edge_params& e) {
+    LVF_HIP(hipMemsetAsync(pick_e[0], 0, (size_t)(pick_e[1] - pick_e[0]) * 8, s));
+    const EdgePickP E{e.edge_threshold, e.n_sharp, e.n_less_sharp, P.Cn / 6 + 8};
+    hipLaunchKernelGGL(k_ex_edge_pick, dim3(P.R * 6), dim3(64), (size_t)4 * E.cap, s, cap_m, m_dev, P.Cn, curv.p, seg_ground.p, pixpos, E, pick_e[0], pick_e[1]);
+    LVF_HIP(hipGetLastError());
+    return LVF_OK;
+  }
+};
+struct Pts { const float4* p; int n; };      // points on the device, their count on the host
+static Pts pts_of(const lvf_cloud* c) { return c ? Pts{c->pts.p, c->n} : Pts{nullptr, 0}; }
+// lvf_lidar_extract_debug.  m, num: filtered and segmented points; g, f: the ground and surf picks.  Five copies, one wait.
+static int tap_debug(hipStream_t s, lvf_lidar_extract_debug* dbg, const RangeImage& im, int m, int num, Pts g, Pts f) {
+  dbg->n_filtered = m; dbg->n_segmented = num; dbg->n_ground_raw = g.n; dbg->n_surf_raw = f.n;
+  if (dbg->label_mat) LVF_HIP(hipMemcpyAsync(dbg->label_mat, im.label.p, (size_t)4 * im.npix, hipMemcpyDeviceToHost, s));
+  if (dbg->ground_mat) LVF_HIP(hipMemcpyAsync(dbg->ground_mat, im.ground.p, (size_t)im.npix, hipMemcpyDeviceToHost, s));
+  if (dbg->range_mat) LVF_HIP(hipMemcpyAsync(dbg->range_mat, im.range.p, (size_t)4 * im.npix, hipMemcpyDeviceToHost, s));
+  if (dbg->ground_raw && g.n) LVF_HIP(hipMemcpyAsync(dbg->ground_raw, g.p, (size_t)16 * g.n, hipMemcpyDeviceToHost, s));
+  if (dbg->surf_raw && f.n) LVF_HIP(hipMemcpyAsync(dbg->surf_raw, f.p, (size_t)16 * f.n, hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipStreamSynchronize(s));
+  return LVF_OK;
+}
+// lvf_edge_extract_debug.  num: segmented points; sharp, less: the RAW picks.  Five copies, one wait.
+static int tap_edge_debug(hipStream_t s, lvf_edge_extract_debug* ed, int num, const PickArrays& pk, Pts sharp, Pts less) {
+  ed->n_sharp_raw = sharp.n; ed->n_less_sharp_raw = less.n;
+  if (ed->sharp_raw && sharp.n) LVF_HIP(hipMemcpyAsync(ed->sharp_raw, sharp.p, (size_t)16 * sharp.n, hipMemcpyDeviceToHost, s));
+  if (ed->less_sharp_raw && less.n) LVF_HIP(hipMemcpyAsync(ed->less_sharp_raw, less.p, (size_t)16 * less.n, hipMemcpyDeviceToHost, s));
+  if (ed->curvature && num) LVF_HIP(hipMemcpyAsync(ed->curvature, pk.curv.p, (size_t)4 * num, hipMemcpyDeviceToHost, s));
+  if (ed->sharp_flags && num) LVF_HIP(hipMemcpyAsync(ed->sharp_flags, pk.pick_e[0], (size_t)4 * num, hipMemcpyDeviceToHost, s));
+  if (ed->less_sharp_flags && num) LVF_HIP(hipMemcpyAsync(ed->less_sharp_flags, pk.pick_e[1], (size_t)4 * num, hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipStreamSynchronize(s));
+  return LVF_OK;
+}
+// Sensor2Robot (association.cpp:236-247) of ground, surf and — with er — sharp, less sharp, each sized exactly and consumed on the context's stream.
+// An output exists only when all do: what was created goes again when a later one fails.
+static int emit_features(lvf_ctx* ctx, const double* extrinsic7, const Pts* f, lvf_cloud** ground_out, lvf_cloud** surf_out, const EdgeReq* er) {
+  lvf_cloud** const out[4] = {ground_out, surf_out, er ? er->sharp_out : nullptr, er ? er->less_out : nullptr};
+  for (int k = 0; k < (er ? 4 : 2); ++k) {
+    const int rc = transform_points(ctx, f[k].p, f[k].n, extrinsic7, out[k]);
+    if (rc == LVF_OK) continue;
+    while (k--) { lvf_cloud_destroy(*out[k]); *out[k] = nullptr; }
+    return rc;
+  }
+  return LVF_OK;
+}
+
+// The host-counted path (the fallback of the device-counted one, the A/B path, and its reference in the tests): every stage reads its output count back
+// before the next one is sized (device_exclusive_scan_i32 / compact_points: 13 stream waits per scan), the start / end orientations are taken on the
+// host, the PCL tail is the lvf_cloud_* entry points on device clouds.
+// dk (here and in the device-counted path; null: none, exactly lvf_lidar_extract's launches): the deskew of the pick clouds where
 // AdjustDistortion's TODO stands — nothing between that line and the PCL tail reads a coordinate (association.cpp:144-208)
 static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7, const ExP& P,
-                                const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg, const EdgeReq* er = nullptr) {
+                                const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg, const EdgeReq* er) {
   hipStream_t s = ctx->stream;
   const int npix = P.R * P.Cn;
   // ---- Preprocess
   lvf_cloud* filtered = nullptr;
   {
-    DevBuf<float> src; DevBuf<float4> packed; DevBuf<int> flags;
-    HostPin<float> stage;                // (pooled pinned staging)
-    StreamWaitGuard stage_guard(s);      // every path out of this scope — the error returns too — waits for the copy before the block returns to the pool
-    LVF_TRY(src.upload_staged(points, (size_t)n * stride_floats, s, stage)); LVF_TRY(packed.alloc(std::max(n, 1))); LVF_TRY(flags.alloc(std::max(n, 1)));
-    if (n) hipLaunchKernelGGL(k_ex_preflag, dim3(gride(n)), dim3(kE), 0, s, n, src.p, stride_floats, P.min2, P.max2, packed.p, flags.p);
-    LVF_HIP(hipGetLastError());
-    LVF_TRY(compact_points(ctx, packed.p, n, flags.p, &filtered));
+    ScanUpload up(s);
+    LVF_TRY(up.run(s, points, n, stride_floats, P, nullptr));
+    LVF_TRY(compact_points(ctx, up.packed.p, n, up.flags.p, &filtered));
   }
   struct Guard { lvf_cloud* c[12]; int k = 0; ~Guard() { for (int i = 0; i < k; ++i) if (c[i]) lvf_cloud_destroy(c[i]); } void add(lvf_cloud* x) { c[k++] = x; } } guard;
   guard.add(filtered);
   const int m = filtered->n;
   // ---- projection, ground, segmentation
-  DevBuf<int> pixel_src, parent, size, flags, pos, label; DevBuf<unsigned long long> rows; DevBuf<float4> full; DevBuf<float> range; DevBuf<signed char> ground;
-  LVF_TRY(pixel_src.alloc(npix)); LVF_TRY(parent.alloc(npix)); LVF_TRY(size.alloc(npix)); LVF_TRY(flags.alloc(npix)); LVF_TRY(pos.alloc((size_t)npix + 1));
-  LVF_TRY(label.alloc(npix)); LVF_TRY(rows.alloc(npix)); LVF_TRY(full.alloc(npix)); LVF_TRY(range.alloc(npix)); LVF_TRY(ground.alloc(npix));
-  LVF_HIP(hipMemsetAsync(pixel_src.p, 0xff, (size_t)4 * npix, s));      // -1
-  LVF_HIP(hipMemsetAsync(size.p, 0, (size_t)4 * npix, s));
-  LVF_HIP(hipMemsetAsync(rows.p, 0, (size_t)8 * npix, s));
-  if (m) hipLaunchKernelGGL(k_ex_project, dim3(gride(m)), dim3(kE), 0, s, m, (const int*)nullptr, filtered->pts.p, P, pixel_src.p);
-  hipLaunchKernelGGL(k_ex_fill, dim3(gride(npix)), dim3(kE), 0, s, npix, filtered->pts.p, P, pixel_src.p, full.p, range.p);
-  hipLaunchKernelGGL(k_ex_ground, dim3(gride(npix)), dim3(kE), 0, s, npix, full.p, range.p, P, ground.p, parent.p);
-  hipLaunchKernelGGL(k_ex_union, dim3(gride(npix)), dim3(kE), 0, s, npix, range.p, P, parent.p);
-  hipLaunchKernelGGL(k_ex_stats, dim3(gride(npix)), dim3(kE), 0, s, npix, P.Cn, parent.p, size.p, rows.p);
-  hipLaunchKernelGGL(k_ex_segflag, dim3(gride(npix)), dim3(kE), 0, s, npix, parent.p, size.p, rows.p, ground.p, flags.p, label.p);
-  LVF_HIP(hipGetLastError());
-  LVF_TRY(device_exclusive_scan_i32(ctx, flags.p, npix, pos.p));
+  RangeImage im;
+  LVF_TRY(im.alloc(npix)); im.clear(s);
+  LVF_TRY(im.build(s, m, nullptr, filtered->pts.p, P));
+  LVF_TRY(device_exclusive_scan_i32(ctx, im.flags.p, npix, im.pos.p));
   int num = 0;
   float4 ends[2] = {make_float4(1, 0, 0, 0), make_float4(1, 0, 0, 0)};
   {
     // three small read-backs, one wait, through the context's pinned mailbox (lvf::read_back's reason)
     LVF_TRY(ctx->mailbox.reserve(4096));
     char* mb = ctx->mailbox.p;
-    LVF_HIP(hipMemcpyAsync(mb, pos.p + npix, sizeof(int), hipMemcpyDeviceToHost, s));
+    LVF_HIP(hipMemcpyAsync(mb, im.pos.p + npix, sizeof(int), hipMemcpyDeviceToHost, s));
     if (m) {
       LVF_HIP(hipMemcpyAsync(mb + 16, filtered->pts.p, sizeof(float4), hipMemcpyDeviceToHost, s));
       LVF_HIP(hipMemcpyAsync(mb + 32, filtered->pts.p + (m - 1), sizeof(float4), hipMemcpyDeviceToHost, s));
@@ -456,160 +529,111 @@ static int extract_host_counted(lvf_ctx* ctx, const float* points, int n, int st
     std::memcpy(&num, mb, sizeof(int));
     if (m) { std::memcpy(&ends[0], mb + 16, sizeof(float4)); std::memcpy(&ends[1], mb + 32, sizeof(float4)); }
   }
+  // ---- AdjustDistortion, CalculateSmoothness, ExtractFeatures' picks
   const OriP o = find_start_end(ends[0], ends[1], prm->cycle_time);      // FindStartEndAngle (projection.cpp:42-56)
-  DevBuf<float4> seg; DevBuf<float> seg_range, curv; DevBuf<int> seg_ground, seg_row, latch, latch_pos, pick_g, pick_s;
-  const int mm = std::max(num, 1);
-  LVF_TRY(seg.alloc(mm)); LVF_TRY(seg_range.alloc(mm)); LVF_TRY(curv.alloc(mm)); LVF_TRY(seg_ground.alloc(mm)); LVF_TRY(seg_row.alloc(mm));
-  LVF_TRY(latch.alloc(mm)); LVF_TRY(latch_pos.alloc((size_t)mm + 1)); LVF_TRY(pick_g.alloc(mm)); LVF_TRY(pick_s.alloc(mm));
-  lvf_cloud *g_raw = nullptr, *s_raw = nullptr;
+  PickArrays pk;
+  LVF_TRY(pk.alloc(std::max(num, 1), er != nullptr));
   if (num) {
-    hipLaunchKernelGGL(k_ex_segemit, dim3(gride(npix)), dim3(kE), 0, s, npix, P.Cn, flags.p, pos.p, full.p, range.p, ground.p, seg.p, seg_range.p, seg_ground.p, seg_row.p);
-    hipLaunchKernelGGL(k_ex_latch, dim3(gride(num)), dim3(kE), 0, s, num, (const int*)nullptr, seg.p, o, OriSrc{nullptr, nullptr, 0.0}, latch.p);
+    hipLaunchKernelGGL(k_ex_segemit, dim3(gride(npix)), dim3(kE), 0, s, npix, P.Cn, im.flags.p, im.pos.p, im.full.p, im.range.p, im.ground.p, pk.seg.p, pk.seg_range.p, pk.seg_ground.p, pk.seg_row.p);
+    hipLaunchKernelGGL(k_ex_latch, dim3(gride(num)), dim3(kE), 0, s, num, pk.seg.p, o, pk.latch.p);
     LVF_HIP(hipGetLastError());
-    LVF_TRY(device_exclusive_scan_i32(ctx, latch.p, num, latch_pos.p));
-    hipLaunchKernelGGL(k_ex_pick, dim3(gride(num)), dim3(kE), 0, s, num, (const int*)nullptr, P.Cn, seg.p, seg_range.p, seg_ground.p, seg_row.p, pos.p, pick_g.p, pick_s.p, curv.p);
-    hipLaunchKernelGGL(k_ex_reltime, dim3(gride(num)), dim3(kE), 0, s, num, (const int*)nullptr, seg.p, o, OriSrc{nullptr, nullptr, 0.0}, latch_pos.p);
+    LVF_TRY(device_exclusive_scan_i32(ctx, pk.latch.p, num, pk.latch_pos.p));
+    hipLaunchKernelGGL(k_ex_pick, dim3(gride(num)), dim3(kE), 0, s, num, P.Cn, pk.seg.p, pk.seg_range.p, pk.seg_ground.p, pk.seg_row.p, im.pos.p, pk.pick_g.p, pk.pick_s.p, pk.curv.p);
+    hipLaunchKernelGGL(k_ex_reltime, dim3(gride(num)), dim3(kE), 0, s, num, pk.seg.p, o, pk.latch_pos.p);
     LVF_HIP(hipGetLastError());
   }
-  LVF_TRY(compact_points(ctx, seg.p, num, pick_g.p, &g_raw)); guard.add(g_raw);
-  LVF_TRY(compact_points(ctx, seg.p, num, pick_s.p, &s_raw)); guard.add(s_raw);
+  lvf_cloud *g_raw = nullptr, *s_raw = nullptr;
+  LVF_TRY(compact_points(ctx, pk.seg.p, num, pk.pick_g.p, &g_raw)); guard.add(g_raw);
+  LVF_TRY(compact_points(ctx, pk.seg.p, num, pk.pick_s.p, &s_raw)); guard.add(s_raw);
   lvf_cloud* e_raw[2] = {nullptr, nullptr};      // sharp, less sharp: the raw picks
   if (er) {
-    DevBuf<int> pick_both;                       // sharp flags | less-sharp flags
-    LVF_TRY(pick_both.alloc((size_t)2 * mm));
-    int* const pick_e[2] = {pick_both.p, pick_both.p + mm};
-    LVF_TRY(launch_edge_pick(s, num, nullptr, P.R, P.Cn, curv.p, seg_ground.p, pos.p, er->prm, pick_e[0], pick_e[1]));
-    for (int k = 0; k < 2; ++k) { LVF_TRY(compact_points(ctx, seg.p, num, pick_e[k], &e_raw[k])); guard.add(e_raw[k]); }
-    if (lvf_edge_extract_debug* ed = er->dbg) {
-      ed->n_sharp_raw = e_raw[0]->n; ed->n_less_sharp_raw = e_raw[1]->n;
-      if (ed->sharp_raw && e_raw[0]->n) LVF_HIP(hipMemcpyAsync(ed->sharp_raw, e_raw[0]->pts.p, (size_t)16 * e_raw[0]->n, hipMemcpyDeviceToHost, s));
-      if (ed->less_sharp_raw && e_raw[1]->n) LVF_HIP(hipMemcpyAsync(ed->less_sharp_raw, e_raw[1]->pts.p, (size_t)16 * e_raw[1]->n, hipMemcpyDeviceToHost, s));
-      if (ed->curvature && num) LVF_HIP(hipMemcpyAsync(ed->curvature, curv.p, (size_t)4 * num, hipMemcpyDeviceToHost, s));
-      if (ed->sharp_flags && num) LVF_HIP(hipMemcpyAsync(ed->sharp_flags, pick_e[0], (size_t)4 * num, hipMemcpyDeviceToHost, s));
-      if (ed->less_sharp_flags && num) LVF_HIP(hipMemcpyAsync(ed->less_sharp_flags, pick_e[1], (size_t)4 * num, hipMemcpyDeviceToHost, s));
-      LVF_HIP(hipStreamSynchronize(s));
-    }
-    if (dk) for (int k = 0; k < 2; ++k) LVF_TRY(deskew_launch(s, e_raw[k]->n, nullptr, e_raw[k]->pts.p, e_raw[k]->pts.p, *dk));
+    LVF_TRY(pk.edge_pick(s, num, nullptr, P, im.pos.p, er->prm));
+    for (int k = 0; k < 2; ++k) { LVF_TRY(compact_points(ctx, pk.seg.p, num, pk.pick_e[k], &e_raw[k])); guard.add(e_raw[k]); }
+    if (er->dbg) LVF_TRY(tap_edge_debug(s, er->dbg, num, pk, pts_of(e_raw[0]), pts_of(e_raw[1])));      // the tap keeps the RAW picks: it and its wait come before ...
+    if (dk) for (lvf_cloud* c : e_raw) LVF_TRY(deskew_launch(s, c->n, nullptr, c->pts.p, c->pts.p, *dk));      // ... the deskew, in place
   }
-  if (dk) {
-    LVF_TRY(deskew_launch(s, g_raw->n, nullptr, g_raw->pts.p, g_raw->pts.p, *dk));
-    LVF_TRY(deskew_launch(s, s_raw->n, nullptr, s_raw->pts.p, s_raw->pts.p, *dk));
-  }
-  if (dbg) {
-    dbg->n_filtered = m; dbg->n_segmented = num; dbg->n_ground_raw = g_raw->n; dbg->n_surf_raw = s_raw->n;
-    if (dbg->label_mat) LVF_HIP(hipMemcpyAsync(dbg->label_mat, label.p, (size_t)4 * npix, hipMemcpyDeviceToHost, s));
-    if (dbg->ground_mat) LVF_HIP(hipMemcpyAsync(dbg->ground_mat, ground.p, (size_t)npix, hipMemcpyDeviceToHost, s));
-    if (dbg->range_mat) LVF_HIP(hipMemcpyAsync(dbg->range_mat, range.p, (size_t)4 * npix, hipMemcpyDeviceToHost, s));
-    if (dbg->ground_raw && g_raw->n) LVF_HIP(hipMemcpyAsync(dbg->ground_raw, g_raw->pts.p, (size_t)16 * g_raw->n, hipMemcpyDeviceToHost, s));
-    if (dbg->surf_raw && s_raw->n) LVF_HIP(hipMemcpyAsync(dbg->surf_raw, s_raw->pts.p, (size_t)16 * s_raw->n, hipMemcpyDeviceToHost, s));
-    LVF_HIP(hipStreamSynchronize(s));
-  }
+  if (dk) for (lvf_cloud* c : {g_raw, s_raw}) LVF_TRY(deskew_launch(s, c->n, nullptr, c->pts.p, c->pts.p, *dk));
+  if (dbg) LVF_TRY(tap_debug(s, dbg, im, m, num, pts_of(g_raw), pts_of(s_raw)));
   // ---- the PCL tail (association.cpp:210-234) on device clouds
   lvf_cloud *sv = nullptr, *sr = nullptr, *gv = nullptr, *gp = nullptr;
   LVF_TRY(lvf_cloud_voxel_filter(s_raw, 2 * prm->resolution, &sv)); guard.add(sv);
   LVF_TRY(lvf_cloud_radius_outlier_filter(sv, 4 * prm->resolution, 4, &sr)); guard.add(sr);
   LVF_TRY(lvf_cloud_voxel_filter(g_raw, 2 * prm->resolution, &gv)); guard.add(gv);
   LVF_TRY(lvf_cloud_segment_plane(gv, 0.1f * prm->resolution, 100, prm->ransac_seed, &gp, nullptr, nullptr)); guard.add(gp);
-  LVF_TRY(lvf_cloud_transform(gp, extrinsic7, ground_out));
-  int rc = lvf_cloud_transform(sr, extrinsic7, surf_out);
-  if (rc == LVF_OK && er) rc = lvf_cloud_transform(e_raw[0], extrinsic7, er->sharp_out);
-  if (rc == LVF_OK && er) rc = lvf_cloud_transform(e_raw[1], extrinsic7, er->less_out);
-  if (rc != LVF_OK) {
-    lvf_cloud_destroy(*ground_out); *ground_out = nullptr;
-    if (*surf_out) { lvf_cloud_destroy(*surf_out); *surf_out = nullptr; }
-    if (er && *er->sharp_out) { lvf_cloud_destroy(*er->sharp_out); *er->sharp_out = nullptr; }
-    return rc;
-  }
+  const Pts f[4] = {pts_of(gp), pts_of(sr), pts_of(e_raw[0]), pts_of(e_raw[1])};
+  LVF_TRY(emit_features(ctx, extrinsic7, f, ground_out, surf_out, er));
   LVF_HIP(hipStreamSynchronize(s));
   return LVF_OK;
 }
+// waits for the side stream on every way out, the error returns too: declared AFTER every buffer that stream touches, so none goes back to the pool under it
+struct SideGuard { lvf_ctx* c; ~SideGuard() { if (c->stream2) (void)hipStreamSynchronize(c->stream2); } };
 
-// The device-counted path: ONE stream wait per scan.  Every intermediate cloud is a buffer of the raw scan's (or the range image's) capacity
-// with its count in device memory; launches are sized by the capacity and read the count; scans / compactions are one launch each
-// (device_scan1); the start / end orientations are taken by a one-thread launch with the host's arithmetic; the PCL tail is dc_pcl_tail.
-// The counts (and the tail's verdict) come back in one read before the two extrinsic transforms, which are then sized exactly.
-// *done = false: a scan outside what the path was sized for (the tail's a-priori bounds) — the caller takes the host-counted path.
+// The device-counted path: counts on the device, ONE stream wait per scan.  Every intermediate cloud is a buffer of the raw scan's (or the range
+// image's) capacity with its count in device memory; launches are sized by the capacity and read the count; scans / compactions are one launch each
+// (device_scan1); every thread that needs the start / end orientations takes them itself with the host's arithmetic (ori_of); the PCL tail is
+// dc_tail_*, its ground half on the side stream.  The counts (and the tail's verdict) come back in one read before the extrinsic transforms, then sized exactly.
+// *done = false: a scan outside what the path was sized for (the tail's a-priori bounds) — the caller takes the host-counted path; no output exists.
 // (Deskewed picks may leave the range gate's ball the tail's plan is sized from.  The tail derives its voxel keys and its radius grid from the
 // MEASURED box of what it is given and raises its verdict when they do not fit the plan: such a scan goes through the host-counted path.)
 static int extract_device_counted(lvf_ctx* ctx, const float* points, int n, int stride_floats, const lvf_lidar_params* prm, const double* extrinsic7, const ExP& P,
-                                  const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg, bool* done, const EdgeReq* er = nullptr) {
+                                  const DeskewP* dk, lvf_cloud** ground_out, lvf_cloud** surf_out, lvf_lidar_extract_debug* dbg, bool* done, const EdgeReq* er) {
   hipStream_t s = ctx->stream;
   *done = false;
   static const bool timing = std::getenv("LVF_EXTRACT_TIMING") != nullptr;
-  const auto t_in = std::chrono::steady_clock::now();
-  auto us_since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
+  ExStamps st;
   const int npix = P.R * P.Cn;
   const int capseg = std::min(npix, n);               // a segmented point is a pixel AND a filtered point
   DevBuf<ExDev> exd;
   LVF_TRY(exd.alloc(1));
   ExDev* ex = exd.p;
   // ---- what does not depend on the scan goes first: it runs while the host is still preparing the upload
-  DevBuf<int> pixel_src, size; DevBuf<unsigned long long> rows;
-  LVF_TRY(pixel_src.alloc(npix)); LVF_TRY(size.alloc(npix)); LVF_TRY(rows.alloc(npix));
-  hipLaunchKernelGGL(k_ex_clear, dim3(gride(npix)), dim3(kE), 0, s, npix, pixel_src.p, size.p, rows.p);
+  RangeImage im;
+  LVF_TRY(im.alloc(npix)); im.clear(s);
   DevBuf<unsigned char> tail_state;
-  std::shared_ptr<void> tail_keep;      // the tail's scratch: alive until this function has waited for the streams (declared before the guard below)
-  struct SideGuard { lvf_ctx* c; ~SideGuard() { if (c->stream2) (void)hipStreamSynchronize(c->stream2); } } side_guard{ctx};      // an error return must not release scratch the side stream still uses
+  std::shared_ptr<void> tail_keep;      // the tail's scratch.  These two are declared before everything that waits (`up`, `side_guard`): they outlive every wait
   DcTailPlan plan;
   LVF_TRY(dc_tail_begin(ctx, capseg, prm->resolution, prm->max_range, tail_state, tail_keep, &plan));
   if (!plan.supported) return LVF_OK;
   // ---- Preprocess
-  DevBuf<float> src; DevBuf<float4> packed, filtered; DevBuf<int> pflags;
-  HostPin<float> stage;                // (pooled pinned staging)
-  StreamWaitGuard stage_guard(s);      // every path out — the error returns too — waits for the copy before the block returns to the pool
-  LVF_TRY(src.upload_staged(points, (size_t)n * stride_floats, s, stage)); LVF_TRY(packed.alloc(n)); LVF_TRY(pflags.alloc(n)); LVF_TRY(filtered.alloc(n));
-  const double us_upload = us_since(t_in);
-  hipLaunchKernelGGL(k_ex_preflag, dim3(gride(n)), dim3(kE), 0, s, n, src.p, stride_floats, P.min2, P.max2, packed.p, pflags.p);
-  LVF_HIP(hipGetLastError());
-  LVF_TRY(device_scan1(ctx, pflags.p, n, nullptr, nullptr, &ex->cnt[0], packed.p, filtered.p));
+  DevBuf<float4> filtered;
+  LVF_TRY(filtered.alloc(n));
+  ScanUpload up(s);
+  LVF_TRY(up.run(s, points, n, stride_floats, P, &st));
+  LVF_TRY(device_scan1(ctx, up.flags.p, n, nullptr, nullptr, &ex->cnt[0], up.packed.p, filtered.p));
   const int* m_dev = &ex->cnt[0];
   // ---- projection, ground, segmentation
-  DevBuf<int> parent, flags, pos, label; DevBuf<float4> full; DevBuf<float> range; DevBuf<signed char> ground;
-  LVF_TRY(parent.alloc(npix)); LVF_TRY(flags.alloc(npix)); LVF_TRY(pos.alloc((size_t)npix + 1));
-  LVF_TRY(label.alloc(npix)); LVF_TRY(full.alloc(npix)); LVF_TRY(range.alloc(npix)); LVF_TRY(ground.alloc(npix));
-  hipLaunchKernelGGL(k_ex_project, dim3(gride(n)), dim3(kE), 0, s, n, m_dev, filtered.p, P, pixel_src.p);
-  hipLaunchKernelGGL(k_ex_fill, dim3(gride(npix)), dim3(kE), 0, s, npix, filtered.p, P, pixel_src.p, full.p, range.p);
-  hipLaunchKernelGGL(k_ex_ground, dim3(gride(npix)), dim3(kE), 0, s, npix, full.p, range.p, P, ground.p, parent.p);
-  hipLaunchKernelGGL(k_ex_union, dim3(gride(npix)), dim3(kE), 0, s, npix, range.p, P, parent.p);
-  hipLaunchKernelGGL(k_ex_stats, dim3(gride(npix)), dim3(kE), 0, s, npix, P.Cn, parent.p, size.p, rows.p);
-  hipLaunchKernelGGL(k_ex_segflag, dim3(gride(npix)), dim3(kE), 0, s, npix, parent.p, size.p, rows.p, ground.p, flags.p, label.p);
-  LVF_HIP(hipGetLastError());
-  LVF_TRY(device_scan1(ctx, flags.p, npix, nullptr, pos.p, &ex->cnt[1], nullptr, nullptr));
+  LVF_TRY(im.build(s, n, m_dev, filtered.p, P));
+  LVF_TRY(device_scan1(ctx, im.flags.p, npix, nullptr, im.pos.p, &ex->cnt[1], nullptr, nullptr));
   const int* num_dev = &ex->cnt[1];
   // ---- AdjustDistortion, CalculateSmoothness, ExtractFeatures' picks
-  DevBuf<float4> seg, g_raw, s_raw; DevBuf<float> seg_range, curv; DevBuf<int> seg_ground, seg_row, latch, latch_pos, pick_g, pick_s;
+  PickArrays pk; DevBuf<float4> g_raw, s_raw;
   const int mm = std::max(capseg, 1);
-  LVF_TRY(seg.alloc(mm)); LVF_TRY(seg_range.alloc(mm)); LVF_TRY(curv.alloc(mm)); LVF_TRY(seg_ground.alloc(mm)); LVF_TRY(seg_row.alloc(mm));
-  LVF_TRY(latch.alloc(mm)); LVF_TRY(latch_pos.alloc((size_t)mm + 1)); LVF_TRY(pick_g.alloc(mm)); LVF_TRY(pick_s.alloc(mm));
-  LVF_TRY(g_raw.alloc(mm)); LVF_TRY(s_raw.alloc(mm));
+  LVF_TRY(pk.alloc(mm, er != nullptr)); LVF_TRY(g_raw.alloc(mm)); LVF_TRY(s_raw.alloc(mm));
   const OriSrc op{filtered.p, m_dev, prm->cycle_time};      // (start / end orientations: every thread of the two launches below takes them itself)
-  hipLaunchKernelGGL(k_ex_segemit_latch, dim3(gride(npix)), dim3(kE), 0, s, npix, P.Cn, flags.p, pos.p, full.p, range.p, ground.p, seg.p, seg_range.p, seg_ground.p, seg_row.p, op,
-                     latch.p);
+  hipLaunchKernelGGL(k_ex_segemit_latch, dim3(gride(npix)), dim3(kE), 0, s, npix, P.Cn, im.flags.p, im.pos.p, im.full.p, im.range.p, im.ground.p, pk.seg.p, pk.seg_range.p,
+                     pk.seg_ground.p, pk.seg_row.p, op, pk.latch.p);
   LVF_HIP(hipGetLastError());
-  LVF_TRY(device_scan1(ctx, latch.p, capseg, num_dev, latch_pos.p, nullptr, nullptr, nullptr));
-  hipLaunchKernelGGL(k_ex_pick_reltime, dim3(gride(capseg)), dim3(kE), 0, s, capseg, num_dev, P.Cn, seg.p, seg_range.p, seg_ground.p, seg_row.p, pos.p, pick_g.p, pick_s.p, curv.p, op,
-                     latch_pos.p);
+  LVF_TRY(device_scan1(ctx, pk.latch.p, capseg, num_dev, pk.latch_pos.p, nullptr, nullptr, nullptr));
+  hipLaunchKernelGGL(k_ex_pick_reltime, dim3(gride(capseg)), dim3(kE), 0, s, capseg, num_dev, P.Cn, pk.seg.p, pk.seg_range.p, pk.seg_ground.p, pk.seg_row.p, im.pos.p, pk.pick_g.p,
+                     pk.pick_s.p, pk.curv.p, op, pk.latch_pos.p);
   LVF_HIP(hipGetLastError());
   // ---- the picks' compactions and the PCL tail (association.cpp:210-234): the ground half on the side stream, the surf half on this one
   hipStream_t q = s;
   DevBuf<float4> surf_pre, ground_pre;
-  SideGuard side_fork_guard{ctx};      // declared AFTER every buffer the side stream touches (seg, pick_g, g_raw, ground_pre ...): on an error return it waits for stream2 before they go back to the pool
+  SideGuard side_guard{ctx};            // behind pk (seg, pick_g), g_raw, ground_pre and the tail's scratch: destroyed — stream2 waited for — before any of them
   LVF_TRY(dc_tail_fork(ctx, plan, &q));
-  LVF_TRY(device_scan1_on(ctx, q, plan.lane_ground, pick_g.p, capseg, num_dev, nullptr, &ex->cnt[2], seg.p, g_raw.p));
+  LVF_TRY(device_scan1_on(ctx, q, plan.lane_ground, pk.pick_g.p, capseg, num_dev, nullptr, &ex->cnt[2], pk.seg.p, g_raw.p));
   if (dk) LVF_TRY(deskew_launch(q, capseg, &ex->cnt[2], g_raw.p, g_raw.p, *dk));      // (each on the stream of its compaction: no wait is added)
-  LVF_TRY(device_scan1_on(ctx, s, 0, pick_s.p, capseg, num_dev, nullptr, &ex->cnt[3], seg.p, s_raw.p));
+  LVF_TRY(device_scan1_on(ctx, s, 0, pk.pick_s.p, capseg, num_dev, nullptr, &ex->cnt[3], pk.seg.p, s_raw.p));
   if (dk) LVF_TRY(deskew_launch(s, capseg, &ex->cnt[3], s_raw.p, s_raw.p, *dk));
   LVF_TRY(dc_tail_run(ctx, plan, q, s_raw.p, &ex->cnt[3], g_raw.p, &ex->cnt[2], (unsigned long long)prm->ransac_seed, tail_state, tail_keep, surf_pre, ground_pre));
   // ---- the edge picks, behind the tails on this stream (nothing of lvf_lidar_extract's chain waits for them): flags, two compactions, the deskew
-  DevBuf<int> pick_both; DevBuf<float4> e_raw[2], e_dk[2];      // pick_both: sharp flags | less-sharp flags
-  int* pick_e[2] = {nullptr, nullptr};
+  DevBuf<float4> e_raw[2], e_dk[2];
   if (er) {
-    LVF_TRY(pick_both.alloc((size_t)2 * mm));
-    pick_e[0] = pick_both.p; pick_e[1] = pick_both.p + mm;
     for (int k = 0; k < 2; ++k) { LVF_TRY(e_raw[k].alloc(mm)); if (dk) LVF_TRY(e_dk[k].alloc(mm)); }
-    LVF_TRY(launch_edge_pick(s, capseg, num_dev, P.R, P.Cn, curv.p, seg_ground.p, pos.p, er->prm, pick_e[0], pick_e[1]));
+    LVF_TRY(pk.edge_pick(s, capseg, num_dev, P, im.pos.p, er->prm));
     for (int k = 0; k < 2; ++k) {
-      LVF_TRY(device_scan1_on(ctx, s, 0, pick_e[k], capseg, num_dev, nullptr, &ex->cnt[4 + k], seg.p, e_raw[k].p));
+      LVF_TRY(device_scan1_on(ctx, s, 0, pk.pick_e[k], capseg, num_dev, nullptr, &ex->cnt[4 + k], pk.seg.p, e_raw[k].p));
       if (dk) LVF_TRY(deskew_launch(s, capseg, &ex->cnt[4 + k], e_raw[k].p, e_dk[k].p, *dk));      // (out of place: the tap keeps the raw picks)
     }
   }
@@ -620,43 +644,17 @@ static int extract_device_counted(lvf_ctx* ctx, const float* points, int n, int 
     char* mb = ctx->mailbox.p;
     LVF_HIP(hipMemcpyAsync(mb, ex->cnt, sizeof(hc), hipMemcpyDeviceToHost, s));
     LVF_HIP(hipMemcpyAsync(mb + 64, tail_state.p + dc_state_counts_offset(), sizeof(ht), hipMemcpyDeviceToHost, s));
-    const double us_enq = us_since(t_in);
+    st.enq = st.us();
     LVF_HIP(hipStreamSynchronize(s));
-    stage_guard.dismiss();             // the upload has been waited for: no second full stream wait when this scope ends (the transforms below are consumed on the same stream)
-    if (timing) std::fprintf(stderr, "extract: upload enqueued at %.1f us, all launches enqueued at %.1f us, stream drained at %.1f us\n", us_upload, us_enq, us_since(t_in));
+    up.guard.dismiss();                // the upload has been waited for: no second full stream wait when this scope ends (the transforms below are consumed on the same stream)
+    if (timing) std::fprintf(stderr, "extract: upload enqueued at %.1f us, all launches enqueued at %.1f us, stream drained at %.1f us\n", st.upload, st.enq, st.us());
     std::memcpy(hc, mb, sizeof(hc)); std::memcpy(ht, mb + 64, sizeof(ht));
   }
   if (ht[4] != 0) return LVF_OK;                        // outside the tail's a-priori bounds: the host-counted path decides (and reports)
-  if (dbg) {
-    dbg->n_filtered = hc[0]; dbg->n_segmented = hc[1]; dbg->n_ground_raw = hc[2]; dbg->n_surf_raw = hc[3];
-    if (dbg->label_mat) LVF_HIP(hipMemcpyAsync(dbg->label_mat, label.p, (size_t)4 * npix, hipMemcpyDeviceToHost, s));
-    if (dbg->ground_mat) LVF_HIP(hipMemcpyAsync(dbg->ground_mat, ground.p, (size_t)npix, hipMemcpyDeviceToHost, s));
-    if (dbg->range_mat) LVF_HIP(hipMemcpyAsync(dbg->range_mat, range.p, (size_t)4 * npix, hipMemcpyDeviceToHost, s));
-    if (dbg->ground_raw && hc[2]) LVF_HIP(hipMemcpyAsync(dbg->ground_raw, g_raw.p, (size_t)16 * hc[2], hipMemcpyDeviceToHost, s));
-    if (dbg->surf_raw && hc[3]) LVF_HIP(hipMemcpyAsync(dbg->surf_raw, s_raw.p, (size_t)16 * hc[3], hipMemcpyDeviceToHost, s));
-    LVF_HIP(hipStreamSynchronize(s));
-  }
-  if (er && er->dbg) {
-    lvf_edge_extract_debug* ed = er->dbg;
-    ed->n_sharp_raw = hc[4]; ed->n_less_sharp_raw = hc[5];
-    if (ed->sharp_raw && hc[4]) LVF_HIP(hipMemcpyAsync(ed->sharp_raw, e_raw[0].p, (size_t)16 * hc[4], hipMemcpyDeviceToHost, s));
-    if (ed->less_sharp_raw && hc[5]) LVF_HIP(hipMemcpyAsync(ed->less_sharp_raw, e_raw[1].p, (size_t)16 * hc[5], hipMemcpyDeviceToHost, s));
-    if (ed->curvature && hc[1]) LVF_HIP(hipMemcpyAsync(ed->curvature, curv.p, (size_t)4 * hc[1], hipMemcpyDeviceToHost, s));
-    if (ed->sharp_flags && hc[1]) LVF_HIP(hipMemcpyAsync(ed->sharp_flags, pick_e[0], (size_t)4 * hc[1], hipMemcpyDeviceToHost, s));
-    if (ed->less_sharp_flags && hc[1]) LVF_HIP(hipMemcpyAsync(ed->less_sharp_flags, pick_e[1], (size_t)4 * hc[1], hipMemcpyDeviceToHost, s));
-    LVF_HIP(hipStreamSynchronize(s));
-  }
-  // ---- Sensor2Robot (association.cpp:236-247), sized exactly; consumed on the same stream, nothing to wait for
-  LVF_TRY(transform_points(ctx, ground_pre.p, ht[3], extrinsic7, ground_out));
-  int rc = transform_points(ctx, surf_pre.p, ht[1], extrinsic7, surf_out);
-  if (rc == LVF_OK && er) rc = transform_points(ctx, (dk ? e_dk[0] : e_raw[0]).p, hc[4], extrinsic7, er->sharp_out);
-  if (rc == LVF_OK && er) rc = transform_points(ctx, (dk ? e_dk[1] : e_raw[1]).p, hc[5], extrinsic7, er->less_out);
-  if (rc != LVF_OK) {
-    lvf_cloud_destroy(*ground_out); *ground_out = nullptr;
-    if (*surf_out) { lvf_cloud_destroy(*surf_out); *surf_out = nullptr; }
-    if (er && *er->sharp_out) { lvf_cloud_destroy(*er->sharp_out); *er->sharp_out = nullptr; }
-    return rc;
-  }
+  if (dbg) LVF_TRY(tap_debug(s, dbg, im, hc[0], hc[1], {g_raw.p, hc[2]}, {s_raw.p, hc[3]}));
+  if (er && er->dbg) LVF_TRY(tap_edge_debug(s, er->dbg, hc[1], pk, {e_raw[0].p, hc[4]}, {e_raw[1].p, hc[5]}));
+  const Pts f[4] = {{ground_pre.p, ht[3]}, {surf_pre.p, ht[1]}, {(dk ? e_dk[0] : e_raw[0]).p, hc[4]}, {(dk ? e_dk[1] : e_raw[1]).p, hc[5]}};
+  LVF_TRY(emit_features(ctx, extrinsic7, f, ground_out, surf_out, er));
   *done = true;
   return LVF_OK;
 }

@@ -113,6 +113,37 @@ def scan_full(seed):
     return a
 
 
+def fast_drive(velocity=(650.0, 585.0, 520.0)):
+    """3 keyframes 0.1 s apart at a constant heading and a constant world-frame velocity that is large on all three axes: 1015 m/s, 105 m across
+    one 0.1036 s sweep.  Chosen on the CPU from oracle.lidar_extract's picks of scan600(31) pushed through deskew_ref.deskew about the middle
+    keyframe: the deskewed ground picks then span 324 x 142 x 201 = 9.2e6 = 2^23.1 voxels of 0.4 m and the surf picks 217 x 90 x 139 = 2^21.4 —
+    the ground box is past the 2^22 keys that two 11-bit digit passes sort (a factor 2.2) and within lvf_cloud_voxel_filter's 2^26 (a factor 7.3);
+    600 m/s gives 2^22.8 and 700 m/s 2^23.4, so the case does not sit at an edge.  Positions stay within 130 m."""
+    stamps = 0.1 * np.arange(3)
+    q = syn.quat_from_ypr(np.array([0.4]), np.array([0.0]), np.array([0.0])).reshape(4)
+    return stamps, np.stack([np.concatenate([q, np.asarray(velocity, np.float64) * t]) for t in stamps])
+
+
+def tail_digit_passes(max_range, resolution):
+    """the digit passes the device-counted tail enqueues, derived as dc_tail_begin derives them: coordinates in [-max_range, max_range], voxels of
+    2 * resolution (a float32), two cells of slack for the rounding at the ends, 11 bits per pass"""
+    leaf = float(np.float32(2) * np.float32(resolution))
+    span = np.floor(float(max_range) / leaf) - np.floor(-float(max_range) / leaf) + 1.0 + 2.0
+    bits = 1
+    while float(1 << bits) < span ** 3:
+        bits += 1
+    return (bits + 10) // 11
+
+
+def voxel_cells(picks, resolution):
+    """the voxel box of a pick cloud in float32, as k_dc_bounds and lvf_cloud_voxel_filter compute it: per axis
+    floor(hi * inv_leaf) - floor(lo * inv_leaf) + 1 with inv_leaf = 1 / (2 * resolution); the product"""
+    inv_leaf = np.float32(1.0) / (np.float32(2) * np.float32(resolution))
+    lo, hi = picks[:, :3].min(0), picks[:, :3].max(0)
+    assert lo.dtype == np.float32
+    return int(np.prod(np.floor(hi * inv_leaf).astype(np.int64) - np.floor(lo * inv_leaf).astype(np.int64) + 1))
+
+
 def drive(speed=15.0, yaw_rate=0.3, seed=3):
     """the extraction tests' trajectory: 3 keyframes 0.1 s apart"""
     return trajectory(3, dt=0.1, speed=speed, yaw_rate=yaw_rate, seed=seed)

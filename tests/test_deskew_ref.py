@@ -143,3 +143,19 @@ def test_cloud_edge_cases_of_the_restatement():
     _, d, _ = dr.point_times(c2[:, 3], 0.0, dc.CYCLE)
     p2, _ = dr.deskew(c2, stamps, poses, 0.1, dr.compute_pose(stamps, poses, [0.1 - 0.5 * dc.CYCLE + float(d[0])])[0], dc.CYCLE, E)
     assert np.abs(p2 - c2[:, :3]).max() <= 1e-12
+
+
+def test_fast_drive_sits_inside_the_hand_over_window(oracle):
+    """deskew_cases.fast_drive is chosen on the CPU: the oracle's picks of the 600-firing scan, deskewed by the restatement, must need more voxel
+    keys than the digit passes planned for (max_range 30, resolution 0.2) sort — so the device-counted tail raises its verdict — and fewer than
+    lvf_cloud_voxel_filter's 2^26 — so the host-counted path finishes — with a factor two to spare on either side (test_gpu_deskew.py's
+    test_tail_verdict_hands_the_scan_over asserts the window itself on the device's own picks)"""
+    ref = oracle.lidar_extract(dc.scan600(31), syn.lidar_extrinsic(), horizon_scan=600)
+    stamps, poses = dc.fast_drive()
+    passes = dc.tail_digit_passes(30.0, 0.2)
+    assert passes == 2
+    cells = [dc.voxel_cells(dr.deskew(ref[key], stamps, poses, stamps[1], poses[1], dc.CYCLE, syn.lidar_extrinsic())[1], 0.2) for key in ("ground_raw", "surf_raw")]
+    print("deskewed boxes: 2^%.2f (ground), 2^%.2f (surf) voxels; displacement across one sweep %.1f m" %
+          (np.log2(cells[0]), np.log2(cells[1]), np.linalg.norm((poses[2, 4:] - poses[0, 4:]) / 0.2) * dc.CYCLE))
+    assert 2 << (11 * passes) < max(cells) < (1 << 26) // 2
+    assert np.abs(poses[:, 4:]).max() <= 1e3

@@ -306,6 +306,51 @@ def test_extract_count_paths_agree(ctx, name, speed, yaw_rate):
         assert len(out[False][1][0]) > 50 and len(out[False][1][1]) > 50
 
 
+@pytest.mark.parametrize("call", ["deskewed", "edges"])
+def test_tail_verdict_hands_the_scan_over(ctx, call):
+    """The hand-over AFTER the launch chain ran: the plan is accepted (max_range = 30, resolution = 0.2: two digit passes), but the sweep is deskewed
+    along deskew_cases.fast_drive, so the MEASURED voxel box of the ground picks needs more key bits than the enqueued passes sort — the tail
+    raises its verdict (kDcErrBits), the device-counted path returns with every output still null and the host-counted path, whose voxel filter
+    accepts the box, produces the result.  In device mode the fall-back counter moves by exactly 1, in host mode by 0, and both modes give the
+    same clouds and the same taps bit for bit."""
+    from lvio_fusion_amd import api
+    scan, E = dc.scan600(31), syn.lidar_extrinsic()
+    stamps, poses = dc.fast_drive()
+    out, moved = {}, {}
+    for host in (False, True):
+        tr = api.Trajectory(ctx, stamps, poses)
+        was = api.extract_host_counts(ctx, host)
+        fell = api.extract_fallbacks(ctx)
+        try:
+            if call == "deskewed":
+                res = api.lidar_extract_deskewed(ctx, scan, E, tr, stamps[1], poses[1], params=api.lidar_params(**PRM600), debug=True)
+            else:
+                res = api.lidar_extract_edges(ctx, scan, E, api.edge_params(), tr, stamps[1], poses[1], params=api.lidar_params(**PRM600), debug=True)
+            moved[host] = api.extract_fallbacks(ctx) - fell
+        finally:
+            api.extract_host_counts(ctx, was)
+        out[host] = [c.download() for c in res[:-1]], res[-1]
+        for h in res[:-1] + (tr,):
+            h.close()
+    # the conditions of the case, on the deskewed picks the call itself returned
+    prm = api.lidar_params(**PRM600)
+    passes = dc.tail_digit_passes(prm.max_range, prm.resolution)
+    limit = 1 << (11 * passes)
+    cells = {key: dc.voxel_cells(out[False][1][key], prm.resolution) for key in ("ground_raw", "surf_raw")}
+    print("%s: %d digit passes sort 2^%d keys; measured boxes %r (2^%.2f, 2^%.2f); counter moved by %r" %
+          (call, passes, 11 * passes, cells, np.log2(cells["ground_raw"]), np.log2(cells["surf_raw"]), moved))
+    assert all(len(out[False][1][key]) > 5000 for key in cells)
+    assert max(cells.values()) > limit, "the measured box fits the enqueued digit passes: nothing to hand over"
+    assert max(cells.values()) <= 1 << 26, "lvf_cloud_voxel_filter would refuse the box"
+    assert moved == {False: 1, True: 0}
+    for a, b in zip(out[False][0], out[True][0]):
+        assert a.shape == b.shape and np.array_equal(bits(a), bits(b))
+    assert len(out[False][0]) == (2 if call == "deskewed" else 4) and sorted(out[False][1]) == sorted(out[True][1])
+    for key, a in out[False][1].items():
+        b = out[True][1][key]
+        assert np.shape(a) == np.shape(b) and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes(), key
+
+
 def test_extract_one_pose_equals_plain(ctx):
     scan, kw = scan_case("az600_31")
     stamps, poses = dc.drive()

@@ -135,17 +135,24 @@ def test_extract_feeds_scan_matching(ctx):
 def test_parameters_outside_the_device_counted_path(ctx):
     """The device-counted path sizes the voxel keys and the radius grid from max_range / resolution BEFORE it sees a point; parameters beyond
     what it can size (here: 2^26 voxels) go through the host-counted path without the caller noticing — and parameters inside it, but
-    unusual (a wide range gate, a coarse resolution), still give the host-counted path's clouds bit for bit."""
+    unusual (a wide range gate, a coarse resolution), still give the host-counted path's clouds bit for bit.
+    The fall-back counter says which path produced a result.  It moves by exactly 1 for max_range = 400, resolution = 0.05 in device mode: the a-priori
+    voxel span is (2 * 4000 + 3)^3 ~ 5e11 > 2^26, the plan is refused.  It stays for the other three: max_range = 60 gives 303^3 ~ 2.8e7 <= 2^26
+    voxels, a radius grid of 151^3 <= 2^22 cells and a capacity of 38 400 <= 2^18 points, and the remaining two are smaller.  Host mode never enters
+    the device-counted path: 0."""
     from lvio_fusion_amd import api
     ext = syn.lidar_extrinsic()
     scan = syn.raw_scan(seed=21)[::3]
-    for kw in (dict(max_range=400.0, resolution=0.05), dict(max_range=60.0, min_range=1.0), dict(resolution=0.5), dict(ground_rows=40, num_scans=64)):
+    for kw, handed_over in ((dict(max_range=400.0, resolution=0.05), 1), (dict(max_range=60.0, min_range=1.0), 0), (dict(resolution=0.5), 0),
+                            (dict(ground_rows=40, num_scans=64), 0)):
         prm = api.lidar_params(**kw)
         out = {}
         for host in (False, True):
             was = api.extract_host_counts(ctx, host)
+            fell = api.extract_fallbacks(ctx)
             try:
                 g, s = api.lidar_extract(ctx, scan, ext, params=prm)
+                assert api.extract_fallbacks(ctx) - fell == (0 if host else handed_over), (kw, host)
                 out[host] = (g.download(), s.download())
                 g.close(); s.close()
             finally:
