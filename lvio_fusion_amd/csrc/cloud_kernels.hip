@@ -8,7 +8,9 @@
 //   pcl::RadiusOutlierRemoval<PointI> (r = 4 x resolution, min 4)  association.cpp:217-221          -> lvf_cloud_radius_outlier_filter
 //   FeatureAssociation::SegmentGround: pcl::SACSegmentation(SACMODEL_PLANE, SAC_RANSAC, 100 its, thr 0.1 x resolution,
 //        optimize coefficients) + ExtractIndices               association.cpp:249-268               -> lvf_cloud_segment_plane
-// All HBM-streaming or small-grid work: one thread per point, counting sorts, prefix-sum compaction.
+// All HBM-streaming or small-grid work: one thread per point, counting sorts, prefix-sum compaction.  RadiusOutlierRemoval and SegmentGround are one launch
+// chain each (RadiusChain, PlaneChain) for their entry points and for the feature extraction's tail (dc_tail_*); what a filter derives from a cloud's box is
+// stated once for host and device (voxel_grid_of, radius_grid_of, moment_shift_of); scan_compact alone picks between the one-launch and the three-launch scan.
 //
 // DECLARED upstream semantics (PCL is un-vendored; restated in oracle/cloud.h):
 //   VoxelGrid: inverse_leaf = 1/leaf (float); min_b = floor(min * inverse_leaf), div_b = max_b - min_b + 1; a point's voxel
@@ -114,10 +116,11 @@ static int cloud_bounds(const lvf_cloud* c, float lo[3], float hi[3]) {
 
 // ---------------------------------------------------------------------------------------------- voxel grid
 struct VoxP { float inv_leaf; int minb[3]; int div[3]; };
+__host__ __device__ __forceinline__ float voxel_coord(float x, float inv_leaf) { return floorf(x * inv_leaf); }      // (of a point and of the grid's corners alike)
 __device__ __forceinline__ int voxel_of(const float4 p, const VoxP v) {
-  const int i = (int)(floorf(p.x * v.inv_leaf) - (float)v.minb[0]);
-  const int j = (int)(floorf(p.y * v.inv_leaf) - (float)v.minb[1]);
-  const int k = (int)(floorf(p.z * v.inv_leaf) - (float)v.minb[2]);
+  const int i = (int)(voxel_coord(p.x, v.inv_leaf) - (float)v.minb[0]);
+  const int j = (int)(voxel_coord(p.y, v.inv_leaf) - (float)v.minb[1]);
+  const int k = (int)(voxel_coord(p.z, v.inv_leaf) - (float)v.minb[2]);
   return i + j * v.div[0] + k * v.div[0] * v.div[1];
 }
 // (n_dev / vp, here and below: the count / the parameters as an earlier launch left them on the device — the device-counted pipeline of
@@ -384,14 +387,62 @@ __host__ __device__ inline bool refit_plane(const MomI& hm, int shift, float co[
   co[0] = (float)nv[0]; co[1] = (float)nv[1]; co[2] = (float)nv[2]; co[3] = (float)(-(nv[0] * cx + nv[1] * cy + nv[2] * cz));
   return true;
 }
-// state of the device-counted PCL tail (dc_pcl_tail below): everything a launch leaves for the next one
+// ---------------------------------------------------------------------------------------------- box arithmetic
+// What the filters derive from a cloud's bounding box (lo, hi), stated ONCE for the host (the entry points that read the box back, the tail's a-priori
+// plan) and for the last workgroup of k_dc_bounds.  IEEE +, -, *, /, floor only and no contraction (the pragma at the top of the file): the host and
+// the device produce the same bits, as with sample3, smallest_eigvec3 and refit_plane above.
+// VoxelGrid's origin, dimensions and key width.  ok: 0 < ncell <= kVoxMaxCells — PCL refuses larger grids too ("Leaf size is too small for the input
+// dataset. Integer indices would overflow."); the caller refuses in its own words, and bits is 1 then.
+constexpr long long kVoxMaxCells = 1ll << 26;
+struct VoxGrid { VoxP v; long long ncell; int bits; bool ok; };
+__host__ __device__ inline VoxGrid voxel_grid_of(const float lo[3], const float hi[3], float inv_leaf) {
+  VoxGrid g; g.v.inv_leaf = inv_leaf; g.ncell = 1;
+  for (int k = 0; k < 3; ++k) {
+    g.v.minb[k] = (int)voxel_coord(lo[k], inv_leaf);
+    const int maxb = (int)voxel_coord(hi[k], inv_leaf);
+    g.v.div[k] = maxb - g.v.minb[k] + 1;
+    g.ncell *= g.v.div[k];
+  }
+  g.ok = g.ncell > 0 && g.ncell <= kVoxMaxCells;
+  g.bits = 1;
+  while (g.ok && (1ll << g.bits) < g.ncell) ++g.bits;
+  return g;
+}
+// RadiusOutlierRemoval's grid: cells strictly larger than the radius (the 27-cell stencil is exhaustive), enlarged by 1.5 until at most max_cells of
+// them cover the box — bigger cells stay correct, only slower; the kept points do not depend on the cell size
+__host__ __device__ inline GridC radius_grid_of(const float lo[3], const float hi[3], float radius, long long max_cells) {
+  float cell = radius * 1.0001f;
+  int d[3];
+  for (;;) {
+    long long t = 1;
+    for (int k = 0; k < 3; ++k) { d[k] = (int)floorf((hi[k] - lo[k]) / cell) + 1; t *= d[k]; }
+    if (t <= max_cells) break;
+    cell *= 1.5f;
+  }
+  GridC g; g.ox = lo[0]; g.oy = lo[1]; g.oz = lo[2]; g.inv_cell = 1.0f / cell; g.nx = d[0]; g.ny = d[1]; g.nz = d[2];
+  return g;
+}
+// the plane fit's moment scale 2^shift: |coordinate| < 2^e  =>  |x y| 2^shift < 2^60
+__host__ __device__ inline int moment_shift_of(const float lo[3], const float hi[3]) {
+  float maxabs = 0.0f;
+  for (int k = 0; k < 3; ++k) maxabs = fmaxf(maxabs, fmaxf(fabsf(lo[k]), fabsf(hi[k])));
+  int e2 = 0;
+  (void)frexpf(maxabs, &e2);
+  return 60 - 2 * (e2 > 0 ? e2 : 0);
+}
+
+// State block of a launch chain that keeps its counts on the device (the tail and the radius / plane chains below): everything a launch leaves for
+// the next one.  cnt[], bounds[] and tick[] are addressed by slot.  The tail's slots are named here; an entry point owns its block alone: k_dc_init
+// plants the host-known count of its input in cnt[kCntGiven], its result lands in cnt[kCntGiven + 1] and its box in slot kBoxGiven.
 constexpr int kDcErrBounds = 1, kDcErrVoxel = 2, kDcErrBits = 4;
+constexpr int kCntSurfVox = 0, kCntSurf = 1, kCntGroundVox = 2, kCntGround = 3;      // points after: surf voxel grid, surf radius filter (= the surf features), ground voxel grid, ground plane (= the ground features)
+constexpr int kBoxSurfRaw = 0, kBoxSurfVox = 1, kBoxGroundRaw = 2, kBoxGroundVox = 3, kCntGiven = 2, kBoxGiven = 0;
 struct DcState {
-  int cnt[4];                 // points after: surf voxel grid, surf radius filter (= the surf features), ground voxel grid, ground plane (= the ground features)
+  int cnt[4];                 // point counts (dc_state_counts_offset: the extraction reads cnt[4], err back)
   int err;                    // kDcErr* bits: the host re-runs the scan through the host-counted path
   int ransac_used;
-  int tick[6];                // arrival counters of the launches whose LAST workgroup finishes the job (4 bounds passes, the moment pass)
-  unsigned bounds[4][6];      // ordered-uint min xyz | max xyz of: surf picks, surf voxels, ground picks, ground voxels
+  int tick[6];                // arrival counters of the launches whose LAST workgroup finishes the job ([slot]: a bounds pass, [4]: the moment pass)
+  unsigned bounds[4][6];      // [slot]: ordered-uint min xyz | max xyz
   VoxP vox[2];
   SortP sortp[2];
   GridC grid;
@@ -468,44 +519,47 @@ static int new_cloud(lvf_ctx* ctx, int n, lvf_cloud** out) {
   *out = c;
   return LVF_OK;
 }
-// out (a NEW cloud) = the flagged points of pts[0..n), input order preserved — shared with extract_kernels.hip
-// (device_scan1's tiles read every earlier tile's sum: fine for thousands of tiles, not for a 30 M-cell grid — beyond this the three-launch scan)
+// How far the one-launch scan (device_scan1) reaches: its tiles read every earlier tile's sum — fine for thousands of tiles, not for a 30 M-cell grid.
+// Beyond it: the three-launch scan, and the radius filter sizes its grid on the host.
 constexpr int kScan1Max = 1 << 22;
-static int scan_i32(lvf_ctx* ctx, const int* in, int n, int* pos) {
-  if (n <= kScan1Max) return device_scan1(ctx, in, n, nullptr, pos, nullptr, nullptr, nullptr);
-  return device_exclusive_scan_i32(ctx, in, n, pos);
-}
-int compact_points(lvf_ctx* ctx, const float4* pts, int n, const int* flags_dev, lvf_cloud** out) {
-  if (n > kScan1Max) {
-    hipStream_t s = ctx->stream;
-    DevBuf<int> pos;
-    LVF_TRY(pos.alloc((size_t)n + 1));
-    LVF_TRY(device_exclusive_scan_i32(ctx, flags_dev, n, pos.p));
-    int total = 0;
-    LVF_TRY(read_back(ctx, &total, pos.p + n, sizeof(int)));
-    LVF_TRY(new_cloud(ctx, total, out));
-    if (total) hipLaunchKernelGGL(k_compact, dim3(gridc(n)), dim3(kC), 0, s, n, pts, flags_dev, pos.p, (*out)->pts.p);
-    LVF_HIP(hipGetLastError());
-    LVF_HIP(hipStreamSynchronize(s));
+static bool scan1_reaches(int n) { return n <= kScan1Max; }
+struct ReadBlock { void* host = nullptr; const void* dev = nullptr; size_t bytes = 0; };
+// The scan and the compaction of everything in this file that is counted by the host, and the ONE place that picks between the two scans.
+// Without `out`: pos[0 .. n] = the exclusive scan of flags[0 .. n).  With `out`: a NEW cloud = the flagged points of pts[0 .. n), input order preserved.
+// Within device_scan1's reach that is ONE launch (scan + compaction into a block of the input's capacity) and ONE wait: the count lands in *total_dev and
+// comes back inside `rb`, the block the caller wants back anyway (an entry point's state; without one, a word of this function's own).  Beyond: rb, the
+// three scan launches, the count, a block of exactly that size, the compaction launch, a second wait.
+static int scan_compact(lvf_ctx* ctx, const int* flags, int n, int* pos, const float4* pts, int* total_dev, ReadBlock rb, lvf_cloud** out) {
+  if (!out) return scan1_reaches(n) ? device_scan1(ctx, flags, n, nullptr, pos, nullptr, nullptr, nullptr) : device_exclusive_scan_i32(ctx, flags, n, pos);
+  DevBuf<int> own; int total = 0; lvf_cloud* c = nullptr;
+  if (!scan1_reaches(n)) {
+    LVF_TRY(read_back(ctx, rb.host, rb.dev, rb.bytes));
+    LVF_TRY(own.alloc((size_t)n + 1));
+    LVF_TRY(device_exclusive_scan_i32(ctx, flags, n, own.p));
+    LVF_TRY(read_back(ctx, &total, own.p + n, sizeof(int)));
+    LVF_TRY(new_cloud(ctx, total, &c));
+    if (total) hipLaunchKernelGGL(k_compact, dim3(gridc(n)), dim3(kC), 0, ctx->stream, n, pts, flags, own.p, c->pts.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { delete c; return ::lvf::hip_fail(e, "k_compact", __FILE__, __LINE__); }
+    *out = c;
     return LVF_OK;
   }
-  // ONE launch (device_scan1: scan + compaction) into a block of the input's capacity, then the count comes back (round 4: three scan launches,
-  // the count, a block of exactly that size, the compaction launch, a second wait)
-  lvf_cloud* c = nullptr;
   LVF_TRY(new_cloud(ctx, n, &c));
-  DevBuf<int> total_dev;
-  int rc = total_dev.alloc(1);
-  if (rc == LVF_OK) rc = device_scan1(ctx, flags_dev, n, nullptr, nullptr, total_dev.p, pts, c->pts.p);
-  int total = 0;
-  if (rc == LVF_OK) rc = read_back(ctx, &total, total_dev.p, sizeof(int));
+  int rc = LVF_OK;
+  if (!total_dev) { rc = own.alloc(1); total_dev = own.p; rb = ReadBlock{&total, own.p, sizeof(int)}; }
+  if (rc == LVF_OK) rc = device_scan1(ctx, flags, n, nullptr, nullptr, total_dev, pts, c->pts.p);
+  if (rc == LVF_OK) rc = read_back(ctx, rb.host, rb.dev, rb.bytes);
   if (rc != LVF_OK) { delete c; return rc; }
+  total = *reinterpret_cast<const int*>(static_cast<const char*>(rb.host) + (reinterpret_cast<const char*>(total_dev) - static_cast<const char*>(rb.dev)));
   c->n = total; c->pts.n = (size_t)total;
   *out = c;
   return LVF_OK;
 }
-// out = the flagged points of `in`, input order preserved
-static int compact_cloud(const lvf_cloud* in, const int* flags_dev, lvf_cloud** out) {
-  return compact_points(in->ctx, in->pts.p, in->n, flags_dev, out);
+static int scan_i32(lvf_ctx* ctx, const int* in, int n, int* pos) { return scan_compact(ctx, in, n, pos, nullptr, nullptr, ReadBlock{}, nullptr); }
+// (shared with extract_kernels.hip)
+int compact_points(lvf_ctx* ctx, const float4* pts, int n, const int* flags_dev, lvf_cloud** out) {
+  return scan_compact(ctx, flags_dev, n, nullptr, pts, nullptr, ReadBlock{}, out);
 }
 
 // ============================================================================================== the PCL tail with the counts on the device
@@ -516,17 +570,18 @@ static int compact_cloud(const lvf_cloud* in, const int* flags_dev, lvf_cloud** 
 // launches — the voxel grid's origin and dimensions, the sort's digit split, the radius grid, RANSAC's bookkeeping, the least-squares refit —
 // is computed by the LAST workgroup of the launch that produces its inputs (arrival counter behind a fence) or by a one-thread launch, with
 // the same arithmetic.  Results are the host-counted path's bit for bit (tests/test_gpu_extract.py runs both).
-__global__ void k_dc_init(DcState* __restrict__ st, int* __restrict__ ransac_counts, int n_ransac, int cnt2) {
+__global__ void k_dc_init(DcState* __restrict__ st, int* __restrict__ ransac_counts, int n_ransac, int n_given) {
   const int t = threadIdx.x;
   for (int i = t; i < n_ransac; i += blockDim.x) ransac_counts[i] = 0;
-  if (t < 4) st->cnt[t] = t == 2 ? cnt2 : 0;          // (cnt2: lvf_cloud_segment_plane enters the chain at the plane fit with a host-known count)
+  if (t < 4) st->cnt[t] = t == kCntGiven ? n_given : 0;          // (n_given: an entry point's chain starts from a host-known count; the tail passes 0)
   if (t < 6) st->tick[t] = 0;
   if (t < 24) st->bounds[t / 6][t % 6] = (t % 6) < 3 ? 0xffffffffu : 0u;
   if (t < 19) st->mom.v[t] = 0ull;
   if (t == 0) { st->err = 0; st->ransac_used = 0; st->grid_ncell = 1; st->plane[0].valid = 0; st->plane[1].valid = 0; }
 }
 // what the last workgroup of a bounds pass derives from the box
-constexpr int kDcBoundsBlocks = 64;      // (arrival atomics on one address: a few dozen workgroups, not hundreds)
+constexpr int kDcBoundsBlocks = 64;      // (arrival atomics on one address: a few dozen workgroups, not hundreds — kCapBlocks for an entry point's cloud beyond 2^18 points)
+static int dc_bounds_blocks(int n, bool entry) { return std::min(entry && n > (1 << 18) ? kCapBlocks : kDcBoundsBlocks, gridc(n)); }
 struct DcSetup {
   int mode;          // 0: voxel grid `which` (VoxP + the sort's SortP), 1: the radius filter's grid, 2: the plane fit's moment scale
   int slot;          // bounds[slot], tick[slot]
@@ -573,40 +628,19 @@ __global__ __launch_bounds__(kC) void k_dc_bounds(int cap, const int* __restrict
   }
   if (n > 0 && !finite) atomicOr(&st->err, kDcErrBounds);
   const bool live = n > 0 && finite;
-  if (su.mode == 0) {                                  // lvf_cloud_voxel_filter's host arithmetic
-    VoxP v; v.inv_leaf = su.f0;
-    long long ncell = 1;
-    for (int k = 0; k < 3; ++k) {
-      v.minb[k] = live ? (int)floorf(lo[k] * v.inv_leaf) : 0;
-      const int maxb = live ? (int)floorf(hi[k] * v.inv_leaf) : 0;
-      v.div[k] = maxb - v.minb[k] + 1;
-      ncell *= v.div[k];
-    }
-    if (live && !(ncell > 0 && ncell <= (1ll << 26))) { atomicOr(&st->err, kDcErrVoxel); ncell = 1; }
-    int bits = 1;
-    while ((1ll << bits) < ncell) ++bits;
+  if (!live) for (int k = 0; k < 3; ++k) lo[k] = hi[k] = 0.0f;      // (no box: one voxel / one cell at the origin, the widest moment scale)
+  if (su.mode == 0) {
+    const VoxGrid vg = voxel_grid_of(lo, hi, su.f0);
+    if (!vg.ok) atomicOr(&st->err, kDcErrVoxel);
+    int bits = vg.bits;
     if (bits > kSortMaxDigitBits * su.i0) { atomicOr(&st->err, kDcErrBits); bits = kSortMaxDigitBits * su.i0; }
     SortP sp; sp.n = live ? n : 0; sp.bits = bits; sp.db = (bits + su.i0 - 1) / su.i0; sp.nbins = 1 << sp.db;
-    st->vox[su.which] = v; st->sortp[su.which] = sp;
-  } else if (su.mode == 1) {                           // lvf_cloud_radius_outlier_filter's
-    float cell = su.f0 * 1.0001f;
-    int d[3] = {1, 1, 1};
-    if (live) {
-      for (;;) {
-        long long t = 1;
-        for (int k = 0; k < 3; ++k) { d[k] = (int)floorf((hi[k] - lo[k]) / cell) + 1; t *= d[k]; }
-        if (t <= (long long)su.i0) break;
-        cell *= 1.5f;                                  // bigger cells stay correct, only slower
-      }
-    }
-    GridC g; g.ox = live ? lo[0] : 0.0f; g.oy = live ? lo[1] : 0.0f; g.oz = live ? lo[2] : 0.0f; g.inv_cell = 1.0f / cell; g.nx = d[0]; g.ny = d[1]; g.nz = d[2];
-    st->grid = g; st->grid_ncell = d[0] * d[1] * d[2];
-  } else {                                             // lvf_cloud_segment_plane's: |coordinate| < 2^e  =>  |x y| 2^shift < 2^60
-    float maxabs = 0.0f;
-    if (live) for (int k = 0; k < 3; ++k) maxabs = fmaxf(maxabs, fmaxf(fabsf(lo[k]), fabsf(hi[k])));
-    int e2 = 0;
-    (void)frexpf(maxabs, &e2);
-    const int shift = 60 - 2 * max(e2, 0);
+    st->vox[su.which] = vg.v; st->sortp[su.which] = sp;
+  } else if (su.mode == 1) {
+    const GridC g = radius_grid_of(lo, hi, su.f0, su.i0);
+    st->grid = g; st->grid_ncell = g.nx * g.ny * g.nz;
+  } else {
+    const int shift = moment_shift_of(lo, hi);
     st->plane[0].mom_shift = shift; st->plane[0].mom_scale = ldexp(1.0, shift);
   }
 }
@@ -662,8 +696,7 @@ static int dc_voxel_filters(lvf_ctx* ctx, DcState* st, int n_jobs, DcVoxelJob* j
   }
   for (int k = 0; k < n_jobs; ++k) {
     const DcVoxelJob& J = jobs[k];
-    DcSetup su; su.mode = 0; su.slot = J.slot; su.which = J.which; su.f0 = 1.0f / leaf; su.i0 = passes;
-    hipLaunchKernelGGL(k_dc_bounds, dim3(std::min(kDcBoundsBlocks, gridc(cap))), dim3(kC), 0, J.q, cap, J.n_in, J.in, st, su);
+    hipLaunchKernelGGL(k_dc_bounds, dim3(dc_bounds_blocks(cap, false)), dim3(kC), 0, J.q, cap, J.n_in, J.in, st, DcSetup{0, J.slot, J.which, 1.0f / leaf, passes});
   }
   for (int k = 0; k < n_jobs; ++k) {
     const DcVoxelJob& J = jobs[k];
@@ -688,6 +721,52 @@ static int dc_voxel_filters(lvf_ctx* ctx, DcState* st, int n_jobs, DcVoxelJob* j
   return LVF_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- the radius chain and the plane chain
+// RadiusOutlierRemoval and SegmentGround, each as ONE launch chain for the entry points and the tail: in = (pts, *n_dev <= cap), what a launch leaves
+// for the next in the state block `st` (box and arrival counter: `slot`), out = flags[i]: point i stays.  A chain is enqueued on q step by step: a
+// caller with two chains on two streams enqueues step k of both before step k + 1 (dc_tail_run; see device_sort_pairs_u32_dc_multi).  What differs
+// between the callers is a member, not a branch: the launch shapes (bounds_blocks, grid_cells), where the count is, which slots are theirs.
+constexpr int kChainSteps = 5;
+struct RadiusTmp { DevBuf<int> cell_of, counts2, start, flags; DevBuf<float4> sorted; };      // counts2: the grid's counts | cursor (one block, cleared by the caller)
+struct RadiusChain {
+  hipStream_t q; int lane;      // (lane: of the one-launch scan over the cells)
+  const float4* pts; int cap; const int* n_dev;
+  DcState* st; int slot;        // st == nullptr: the host sized the grid (g, grid_cells = its cells) and knows the count (cap); on the context's stream only
+  float radius; int min_neighbors, grid_cells, bounds_blocks; GridC g;
+  RadiusTmp* t;
+  int step(lvf_ctx* ctx, int k) const {
+    const GridC* gp = st ? &st->grid : nullptr;
+    int* counts = t->counts2.p; int* cursor = t->counts2.p + grid_cells;
+    const dim3 per_point(gridc(cap)), tb(kC);
+    if (k == 0 && st) hipLaunchKernelGGL(k_dc_bounds, dim3(bounds_blocks), tb, 0, q, cap, n_dev, pts, st, DcSetup{1, slot, 0, radius, grid_cells});      // (its last workgroup fits the grid into grid_cells)
+    if (k == 1) hipLaunchKernelGGL(k_grid_count, per_point, tb, 0, q, cap, n_dev, pts, g, gp, t->cell_of.p, counts);
+    if (k == 2) return st ? device_scan1_on(ctx, q, lane, counts, grid_cells, &st->grid_ncell, t->start.p, nullptr, nullptr, nullptr) : scan_i32(ctx, counts, grid_cells, t->start.p);
+    if (k == 3) hipLaunchKernelGGL(k_grid_scatter, per_point, tb, 0, q, cap, n_dev, pts, t->cell_of.p, t->start.p, cursor, t->sorted.p);
+    if (k == 4) hipLaunchKernelGGL(k_radius_count, per_point, tb, 0, q, cap, n_dev, pts, g, gp, t->start.p, t->sorted.p, radius * radius, min_neighbors, t->flags.p);
+    LVF_HIP(hipGetLastError());
+    return LVF_OK;
+  }
+};
+// (the moment scale by the last workgroup of the bounds pass, RANSAC's bookkeeping and the winner by a one-thread launch, the refit by the last workgroup of the first inlier pass)
+struct PlaneTmp { DevBuf<int> ransac_counts, flags; };      // ransac_counts: cleared by k_dc_init
+struct PlaneChain {
+  hipStream_t q;
+  const float4* pts; int cap; const int* n_dev;
+  DcState* st; int slot;
+  float thr; int max_iterations; unsigned long long seed; int bounds_blocks;
+  PlaneTmp* t;
+  int step(lvf_ctx*, int k) const {
+    const dim3 bb(bounds_blocks), tb(kC);
+    if (k == 0) hipLaunchKernelGGL(k_dc_bounds, bb, tb, 0, q, cap, n_dev, pts, st, DcSetup{2, slot, 0, 0.0f, 0});
+    if (k == 1) hipLaunchKernelGGL(k_ransac_count, dim3(std::min(gridc(cap), 8), max_iterations), tb, 0, q, cap, n_dev, pts, seed, thr, t->ransac_counts.p);
+    if (k == 2) hipLaunchKernelGGL(k_ransac_pick, dim3(1), dim3(64), 0, q, n_dev, cap, pts, t->ransac_counts.p, max_iterations, seed, st);
+    if (k == 3 || k == 4)      // [3] the winning hypothesis' inliers and their moments, [4] the inliers of the plane re-fitted to them
+      hipLaunchKernelGGL(k_plane_inliers, bb, tb, 0, q, cap, n_dev, pts, 0.0f, 0.0f, 0.0f, 0.0f, &st->plane[k - 3], thr, t->flags.p, k == 3 ? &st->mom : nullptr, 0.0, k == 3 ? st : nullptr);
+    LVF_HIP(hipGetLastError());
+    return LVF_OK;
+  }
+};
+
 // The tail.  surf_raw / ground_raw: the picks (capacity `cap`, counts on the device).  Picks that come straight from Preprocess' range gate
 // lie within max_range of the origin (centroids stay inside), which sizes the plan — the voxel keys' width, the radius grid's cells — BEFORE
 // anything is measured.  Deskewed picks may lie outside that ball: the grids themselves are laid over the MEASURED box
@@ -698,11 +777,7 @@ static int dc_voxel_filters(lvf_ctx* ctx, DcState* st, int n_jobs, DcVoxelJob* j
 // Scratch of BOTH chains lives in `keep` until the caller has waited for the stream (the pool hands a released block to the next allocation
 // in HOST order, which is only safe on one stream).  On return (nothing waited for): surf_out / ground_out hold the features before the
 // extrinsic transform, st->cnt their counts (and the two intermediate ones), st->err the verdict.
-struct DcTailKeep {
-  DevBuf<int> ransac_counts, cell_of, counts2, start, flags_s, flags_g;
-  DevBuf<float4> sv, gv, sorted;
-  DcVoxelTmp vs, vg;
-};
+struct DcTailKeep { DevBuf<float4> sv, gv; DcVoxelTmp vs, vg; RadiusTmp radius; PlaneTmp plane; };
 // begin: the a-priori bounds (plan->supported = false when the scan's parameters are outside them: nothing is launched), the state block and its
 // clears — enqueued by the caller ahead of everything that depends on the scan, so they run while the host prepares the upload
 int dc_tail_begin(lvf_ctx* ctx, int cap, float resolution, float max_range, DevBuf<unsigned char>& state, std::shared_ptr<void>& keep_out, DcTailPlan* plan) {
@@ -711,14 +786,16 @@ int dc_tail_begin(lvf_ctx* ctx, int cap, float resolution, float max_range, DevB
   plan->cap = cap;
   plan->leaf = 2 * resolution; plan->radius = 4 * resolution; plan->thr = 0.1f * resolution;
   plan->max_iterations = 100; plan->min_neighbors = 4;
-  // a-priori widths: coordinates in [-max_range, max_range]
-  const double span_v = std::floor((double)max_range / plan->leaf) - std::floor(-(double)max_range / plan->leaf) + 1.0 + 2.0;      // (+2: float rounding of p * inv_leaf at the ends)
+  // a-priori widths: the grids of the box [-max_range, max_range]^3, with two voxels / one cell of slack per axis (deskewed picks may lie a little outside)
+  if (!(std::fabs(max_range) / plan->leaf < 1e6f)) return LVF_OK;      // (neither NaN nor past what an int index holds; far beyond the limits below)
+  const float lo[3] = {-max_range, -max_range, -max_range}, hi[3] = {max_range, max_range, max_range};
+  const double span_v = voxel_grid_of(lo, hi, 1.0f / plan->leaf).v.div[0] + 2.0;
   const double ncell_v = span_v * span_v * span_v;
-  if (!(ncell_v > 0 && ncell_v <= (double)(1ll << 26))) return LVF_OK;
+  if (!(ncell_v > 0 && ncell_v <= (double)kVoxMaxCells)) return LVF_OK;
   int bits = 1;
   while ((double)(1ll << bits) < ncell_v) ++bits;
   plan->passes = (bits + kSortMaxDigitBits - 1) / kSortMaxDigitBits;
-  const double span_g = std::floor(2.0 * max_range / (plan->radius * 1.0001f)) + 2.0;
+  const double span_g = radius_grid_of(lo, hi, plan->radius, std::numeric_limits<long long>::max()).nx + 1.0;
   const double ncell_g = span_g * span_g * span_g;
   if (!(ncell_g <= (double)(1 << 22)) || cap <= 0 || cap > (1 << 18)) return LVF_OK;
   plan->grid_cells = (int)ncell_g;
@@ -729,10 +806,10 @@ int dc_tail_begin(lvf_ctx* ctx, int cap, float resolution, float max_range, DevB
   keep_out = keep;
   DcTailKeep& K = *keep;
   LVF_TRY(state.alloc(sizeof(DcState)));
-  LVF_TRY(K.ransac_counts.alloc(plan->max_iterations));
-  LVF_TRY(K.counts2.alloc((size_t)2 * plan->grid_cells));
-  hipLaunchKernelGGL(k_dc_init, dim3(1), dim3(64), 0, s, reinterpret_cast<DcState*>(state.p), K.ransac_counts.p, plan->max_iterations, 0);
-  LVF_HIP(hipMemsetAsync(K.counts2.p, 0, (size_t)8 * plan->grid_cells, s));      // the radius grid's counts | cursor (one block, one clear)
+  LVF_TRY(K.plane.ransac_counts.alloc(plan->max_iterations));
+  LVF_TRY(K.radius.counts2.alloc((size_t)2 * plan->grid_cells));
+  hipLaunchKernelGGL(k_dc_init, dim3(1), dim3(64), 0, s, reinterpret_cast<DcState*>(state.p), K.plane.ransac_counts.p, plan->max_iterations, 0);
+  LVF_HIP(hipMemsetAsync(K.radius.counts2.p, 0, (size_t)8 * plan->grid_cells, s));      // the radius grid's counts | cursor (one block, one clear)
   LVF_HIP(hipGetLastError());
   plan->supported = true;
   return LVF_OK;
@@ -756,36 +833,19 @@ int dc_tail_run(lvf_ctx* ctx, const DcTailPlan& plan, hipStream_t q, const float
   LVF_TRY(surf_out.alloc(cap)); LVF_TRY(ground_out.alloc(cap));
   LVF_TRY(K.sv.alloc(cap)); LVF_TRY(K.gv.alloc(cap));
   // ---- both VoxelGrids (2 res), surf on the context's stream and ground on the side stream                 association.cpp:210-215,222-224
-  {
-    DcVoxelJob jobs[2] = {{q, lane_g, 1, 2, ground_raw, n_ground_raw, &K.vg, K.gv.p, &st->cnt[2]}, {s, 0, 0, 0, surf_raw, n_surf_raw, &K.vs, K.sv.p, &st->cnt[0]}};
-    LVF_TRY(dc_voxel_filters(ctx, st, 2, jobs, cap, plan.leaf, plan.passes));
-  }
-  // ---- ground: SegmentGround (RANSAC plane, 100 its, 0.1 res)  association.cpp:225-234,249-268 | surf: RadiusOutlierRemoval(4 res, 4)  :217-221
-  // (launch by launch in turn, as above)
-  const int grid_cells = plan.grid_cells;
-  DevBuf<int>& rcounts = K.ransac_counts;              // (cleared by k_dc_init)
-  LVF_TRY(K.flags_g.alloc(cap));
-  LVF_TRY(K.cell_of.alloc(cap)); LVF_TRY(K.start.alloc((size_t)grid_cells + 1)); LVF_TRY(K.flags_s.alloc(cap)); LVF_TRY(K.sorted.alloc(cap));
-  int* counts = K.counts2.p; int* cursor = K.counts2.p + grid_cells;      // (cleared by dc_tail_begin)
-  const int* n_gv = &st->cnt[2]; const int* n_sv = &st->cnt[0];
-  const int gb = std::min(kDcBoundsBlocks, gridc(cap));
-  DcSetup sug; sug.mode = 2; sug.slot = 3; sug.which = 0; sug.f0 = 0.0f; sug.i0 = 0;
-  DcSetup sus; sus.mode = 1; sus.slot = 1; sus.which = 0; sus.f0 = plan.radius; sus.i0 = grid_cells;
-  hipLaunchKernelGGL(k_dc_bounds, dim3(gb), dim3(kC), 0, q, cap, n_gv, K.gv.p, st, sug);
-  hipLaunchKernelGGL(k_dc_bounds, dim3(gb), dim3(kC), 0, s, cap, n_sv, K.sv.p, st, sus);
-  hipLaunchKernelGGL(k_ransac_count, dim3(std::min(gridc(cap), 8), plan.max_iterations), dim3(kC), 0, q, cap, n_gv, K.gv.p, seed, plan.thr, rcounts.p);
-  hipLaunchKernelGGL(k_grid_count, dim3(gridc(cap)), dim3(kC), 0, s, cap, n_sv, K.sv.p, GridC{}, &st->grid, K.cell_of.p, counts);
-  hipLaunchKernelGGL(k_ransac_pick, dim3(1), dim3(64), 0, q, n_gv, cap, K.gv.p, rcounts.p, plan.max_iterations, seed, st);
-  LVF_HIP(hipGetLastError());
-  LVF_TRY(device_scan1_on(ctx, s, 0, counts, grid_cells, &st->grid_ncell, K.start.p, nullptr, nullptr, nullptr));
-  hipLaunchKernelGGL(k_plane_inliers, dim3(gb), dim3(kC), 0, q, cap, n_gv, K.gv.p, 0.0f, 0.0f, 0.0f, 0.0f, &st->plane[0], plan.thr, K.flags_g.p, &st->mom, 0.0, st);
-  hipLaunchKernelGGL(k_grid_scatter, dim3(gridc(cap)), dim3(kC), 0, s, cap, n_sv, K.sv.p, K.cell_of.p, K.start.p, cursor, K.sorted.p);
-  hipLaunchKernelGGL(k_plane_inliers, dim3(gb), dim3(kC), 0, q, cap, n_gv, K.gv.p, 0.0f, 0.0f, 0.0f, 0.0f, &st->plane[1], plan.thr, K.flags_g.p, (MomI*)nullptr, 0.0, (DcState*)nullptr);
-  hipLaunchKernelGGL(k_radius_count, dim3(gridc(cap)), dim3(kC), 0, s, cap, n_sv, K.sv.p, GridC{}, &st->grid, K.start.p, K.sorted.p, plan.radius * plan.radius, plan.min_neighbors,
-                     K.flags_s.p);
-  LVF_HIP(hipGetLastError());
-  LVF_TRY(device_scan1_on(ctx, q, lane_g, K.flags_g.p, cap, n_gv, nullptr, &st->cnt[3], K.gv.p, ground_out.p));
-  LVF_TRY(device_scan1_on(ctx, s, 0, K.flags_s.p, cap, n_sv, nullptr, &st->cnt[1], K.sv.p, surf_out.p));
+  DcVoxelJob jobs[2] = {{q, lane_g, 1, kBoxGroundRaw, ground_raw, n_ground_raw, &K.vg, K.gv.p, &st->cnt[kCntGroundVox]}, {s, 0, 0, kBoxSurfRaw, surf_raw, n_surf_raw, &K.vs, K.sv.p, &st->cnt[kCntSurfVox]}};
+  LVF_TRY(dc_voxel_filters(ctx, st, 2, jobs, cap, plan.leaf, plan.passes));
+  // ---- ground: SegmentGround (RANSAC plane, 100 its, 0.1 res)  association.cpp:225-234,249-268 | surf: RadiusOutlierRemoval(4 res, 4)  :217-221 — step by step in turn, as above
+  RadiusTmp& R = K.radius; PlaneTmp& P = K.plane;
+  LVF_TRY(P.flags.alloc(cap));
+  LVF_TRY(R.cell_of.alloc(cap)); LVF_TRY(R.start.alloc((size_t)plan.grid_cells + 1)); LVF_TRY(R.flags.alloc(cap)); LVF_TRY(R.sorted.alloc(cap));
+  const int* n_gv = &st->cnt[kCntGroundVox]; const int* n_sv = &st->cnt[kCntSurfVox];
+  const int gb = dc_bounds_blocks(cap, false);      // (ransac_counts and counts2: allocated and cleared by dc_tail_begin)
+  const PlaneChain ground{q, K.gv.p, cap, n_gv, st, kBoxGroundVox, plan.thr, plan.max_iterations, seed, gb, &P};
+  const RadiusChain surf{s, 0, K.sv.p, cap, n_sv, st, kBoxSurfVox, plan.radius, plan.min_neighbors, plan.grid_cells, gb, GridC{}, &R};
+  for (int k = 0; k < kChainSteps; ++k) { LVF_TRY(ground.step(ctx, k)); LVF_TRY(surf.step(ctx, k)); }
+  LVF_TRY(device_scan1_on(ctx, q, lane_g, P.flags.p, cap, n_gv, nullptr, &st->cnt[kCntGround], K.gv.p, ground_out.p));
+  LVF_TRY(device_scan1_on(ctx, s, 0, R.flags.p, cap, n_sv, nullptr, &st->cnt[kCntSurf], K.sv.p, surf_out.p));
   if (plan.two_streams) LVF_HIP(hipEventRecord(ctx->ev_join, q));
   if (plan.two_streams) LVF_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));
   return LVF_OK;
@@ -896,25 +956,14 @@ int lvf_cloud_voxel_filter(const lvf_cloud* in, float leaf, lvf_cloud** out) {
   hipStream_t s = ctx->stream;
   float lo[3], hi[3];
   LVF_TRY(cloud_bounds(in, lo, hi));
-  VoxP v;
-  v.inv_leaf = 1.0f / leaf;
-  long long ncell = 1;
-  for (int k = 0; k < 3; ++k) {
-    v.minb[k] = (int)std::floor(lo[k] * v.inv_leaf);
-    const int maxb = (int)std::floor(hi[k] * v.inv_leaf);
-    v.div[k] = maxb - v.minb[k] + 1;
-    ncell *= v.div[k];
-  }
-  // PCL refuses such grids too ("Leaf size is too small for the input dataset. Integer indices would overflow.")
-  LVF_REQUIRE(ncell > 0 && ncell <= (1ll << 26), "lvf_cloud_voxel_filter: %lld voxels: leaf size too small for the cloud's extent", ncell);
+  const VoxGrid vg = voxel_grid_of(lo, hi, 1.0f / leaf);
+  LVF_REQUIRE(vg.ok, "lvf_cloud_voxel_filter: %lld voxels: leaf size too small for the cloud's extent", vg.ncell);
   DevBuf<int> flags, pos, val, order; DevBuf<unsigned> key, key_sorted;
   LVF_TRY(flags.alloc(in->n)); LVF_TRY(pos.alloc((size_t)in->n + 1));
   LVF_TRY(key.alloc(in->n)); LVF_TRY(key_sorted.alloc(in->n)); LVF_TRY(val.alloc(in->n)); LVF_TRY(order.alloc(in->n));
-  hipLaunchKernelGGL(k_voxel_key, dim3(gridc(in->n)), dim3(kC), 0, s, in->n, (const int*)nullptr, in->pts.p, v, (const VoxP*)nullptr, key.p, val.p);
+  hipLaunchKernelGGL(k_voxel_key, dim3(gridc(in->n)), dim3(kC), 0, s, in->n, (const int*)nullptr, in->pts.p, vg.v, (const VoxP*)nullptr, key.p, val.p);
   LVF_HIP(hipGetLastError());
-  int bits = 1;
-  while ((1ll << bits) < ncell) ++bits;
-  LVF_TRY(device_sort_pairs_u32(ctx, key.p, key_sorted.p, val.p, order.p, in->n, bits));      // stable: ascending input index inside a voxel
+  LVF_TRY(device_sort_pairs_u32(ctx, key.p, key_sorted.p, val.p, order.p, in->n, vg.bits));      // stable: ascending input index inside a voxel
   hipLaunchKernelGGL(k_voxel_heads, dim3(gridc(in->n)), dim3(kC), 0, s, in->n, (const int*)nullptr, key_sorted.p, flags.p);
   LVF_TRY(scan_i32(ctx, flags.p, in->n, pos.p));
   int total = 0;
@@ -934,61 +983,29 @@ int lvf_cloud_radius_outlier_filter(const lvf_cloud* in, float radius, int min_n
   lvf_ctx* ctx = in->ctx;
   LVF_TRY(lvf::enter(ctx));
   if (in->n == 0) return new_cloud(ctx, 0, out);
-  hipStream_t s = ctx->stream;
-  const int n = in->n;
-  if (n <= kScan1Max) {
-    // One launch chain and ONE wait (round 4: the bounding box came back first, to size the grid).  The grid arrays are sized by the cloud — 8
-    // cells per point, at least 64 k — and the last workgroup of the bounds pass fits the grid into them (cell = radius, enlarged by 1.5 until
-    // it fits: bigger cells stay correct, only slower; the kept points do not depend on the cell size).
-    const int grid_cells = (int)std::min<long long>(1ll << 22, std::max<long long>(1ll << 16, 8ll * n));
-    DevBuf<unsigned char> state; DevBuf<int> cell_of, counts2, start, flags; DevBuf<float4> sorted;
+  hipStream_t s = ctx->stream; const int n = in->n;
+  RadiusTmp t; DevBuf<unsigned char> state;
+  RadiusChain ch{s, 0, in->pts.p, n, nullptr, nullptr, kBoxGiven, radius, min_neighbors, 0, dc_bounds_blocks(n, true), GridC{}, &t};
+  if (scan1_reaches(n)) {
+    // One launch chain and ONE wait (round 4: the bounding box came back first, to size the grid).  The grid arrays are sized by the cloud — 8 cells
+    // per point, at least 64 k — and the last workgroup of the bounds pass fits the grid into them.
+    ch.grid_cells = (int)std::min<long long>(1ll << 22, std::max<long long>(1ll << 16, 8ll * n));
     LVF_TRY(state.alloc(sizeof(DcState)));
-    LVF_TRY(cell_of.alloc(n)); LVF_TRY(counts2.alloc((size_t)2 * grid_cells)); LVF_TRY(start.alloc((size_t)grid_cells + 1)); LVF_TRY(flags.alloc(n)); LVF_TRY(sorted.alloc(n));
-    DcState* st = reinterpret_cast<DcState*>(state.p);
-    const int* n_dev = &st->cnt[2];
-    int* counts = counts2.p; int* cursor = counts2.p + grid_cells;
-    hipLaunchKernelGGL(k_dc_init, dim3(1), dim3(64), 0, s, st, (int*)nullptr, 0, n);
-    LVF_HIP(hipMemsetAsync(counts2.p, 0, (size_t)8 * grid_cells, s));
-    DcSetup su; su.mode = 1; su.slot = 1; su.which = 0; su.f0 = radius; su.i0 = grid_cells;
-    hipLaunchKernelGGL(k_dc_bounds, dim3(std::min(n > (1 << 18) ? kCapBlocks : kDcBoundsBlocks, gridc(n))), dim3(kC), 0, s, n, n_dev, in->pts.p, st, su);
-    hipLaunchKernelGGL(k_grid_count, dim3(gridc(n)), dim3(kC), 0, s, n, n_dev, in->pts.p, GridC{}, &st->grid, cell_of.p, counts);
-    LVF_HIP(hipGetLastError());
-    LVF_TRY(device_scan1(ctx, counts, grid_cells, &st->grid_ncell, start.p, nullptr, nullptr, nullptr));
-    hipLaunchKernelGGL(k_grid_scatter, dim3(gridc(n)), dim3(kC), 0, s, n, n_dev, in->pts.p, cell_of.p, start.p, cursor, sorted.p);
-    hipLaunchKernelGGL(k_radius_count, dim3(gridc(n)), dim3(kC), 0, s, n, n_dev, in->pts.p, GridC{}, &st->grid, start.p, sorted.p, radius * radius, min_neighbors, flags.p);
-    LVF_HIP(hipGetLastError());
-    lvf_cloud* c = nullptr;
-    LVF_TRY(new_cloud(ctx, n, &c));
-    int h[5] = {0, 0, 0, 0, 0};                       // cnt[4], err
-    int rc = device_scan1(ctx, flags.p, n, nullptr, nullptr, &st->cnt[3], in->pts.p, c->pts.p);
-    if (rc == LVF_OK) rc = read_back(ctx, h, state.p + offsetof(DcState, cnt), sizeof(h));
-    if (rc != LVF_OK) { delete c; return rc; }
-    if (h[4] & kDcErrBounds) { delete c; set_error("cloud has non-finite coordinates"); return LVF_ERR_INVALID; }
-    c->n = h[3]; c->pts.n = (size_t)h[3];
-    *out = c;
-    return LVF_OK;
+    ch.st = reinterpret_cast<DcState*>(state.p); ch.n_dev = &ch.st->cnt[kCntGiven];
+    hipLaunchKernelGGL(k_dc_init, dim3(1), dim3(64), 0, s, ch.st, (int*)nullptr, 0, n);
+  } else {      // beyond the one-launch scan's reach: the box comes back and the host lays the grid over it
+    float lo[3], hi[3];
+    LVF_TRY(cloud_bounds(in, lo, hi));
+    ch.g = radius_grid_of(lo, hi, radius, 1ll << 25);
+    ch.grid_cells = ch.g.nx * ch.g.ny * ch.g.nz;
   }
-  float lo[3], hi[3];
-  LVF_TRY(cloud_bounds(in, lo, hi));
-  float cell = radius * 1.0001f;               // strictly larger than the radius: the 27-cell stencil is exhaustive
-  auto dims = [&](float c, int d[3]) { long long t = 1; for (int k = 0; k < 3; ++k) { d[k] = (int)std::floor((hi[k] - lo[k]) / c) + 1; t *= d[k]; } return t; };
-  int d[3];
-  while (dims(cell, d) > (1ll << 25)) cell *= 1.5f;   // bigger cells stay correct, only slower
-  const int ncell = d[0] * d[1] * d[2];
-  const GridC g{lo[0], lo[1], lo[2], 1.0f / cell, d[0], d[1], d[2]};
-  DevBuf<int> cell_of, counts2, start, flags;
-  DevBuf<float4> sorted;
-  LVF_TRY(cell_of.alloc(in->n)); LVF_TRY(counts2.alloc((size_t)2 * ncell)); LVF_TRY(start.alloc((size_t)ncell + 1));
-  LVF_TRY(flags.alloc(in->n)); LVF_TRY(sorted.alloc(in->n));
-  struct { int* p; } counts{counts2.p}, cursor{counts2.p + ncell};      // (one block, one clear)
-  LVF_HIP(hipMemsetAsync(counts2.p, 0, (size_t)8 * ncell, s));
-  hipLaunchKernelGGL(k_grid_count, dim3(gridc(in->n)), dim3(kC), 0, s, in->n, (const int*)nullptr, in->pts.p, g, (const GridC*)nullptr, cell_of.p, counts.p);
-  LVF_HIP(hipGetLastError());
-  LVF_TRY(scan_i32(ctx, counts.p, ncell, start.p));
-  hipLaunchKernelGGL(k_grid_scatter, dim3(gridc(in->n)), dim3(kC), 0, s, in->n, (const int*)nullptr, in->pts.p, cell_of.p, start.p, cursor.p, sorted.p);
-  hipLaunchKernelGGL(k_radius_count, dim3(gridc(in->n)), dim3(kC), 0, s, in->n, (const int*)nullptr, in->pts.p, g, (const GridC*)nullptr, start.p, sorted.p, radius * radius, min_neighbors, flags.p);
-  LVF_HIP(hipGetLastError());
-  return compact_cloud(in, flags.p, out);
+  LVF_TRY(t.cell_of.alloc(n)); LVF_TRY(t.counts2.alloc((size_t)2 * ch.grid_cells)); LVF_TRY(t.start.alloc((size_t)ch.grid_cells + 1)); LVF_TRY(t.flags.alloc(n)); LVF_TRY(t.sorted.alloc(n));
+  LVF_HIP(hipMemsetAsync(t.counts2.p, 0, (size_t)8 * ch.grid_cells, s));
+  for (int k = 0; k < kChainSteps; ++k) LVF_TRY(ch.step(ctx, k));
+  int h[5] = {0, 0, 0, 0, 0};                       // cnt[4], err
+  LVF_TRY(scan_compact(ctx, t.flags.p, n, nullptr, in->pts.p, ch.st ? &ch.st->cnt[kCntGiven + 1] : nullptr, ch.st ? ReadBlock{h, state.p + offsetof(DcState, cnt), sizeof(h)} : ReadBlock{}, out));
+  if (h[4] & kDcErrBounds) { delete *out; *out = nullptr; set_error("cloud has non-finite coordinates"); return LVF_ERR_INVALID; }
+  return LVF_OK;
 }
 
 int lvf_cloud_segment_plane(const lvf_cloud* in, float distance_threshold, int max_iterations, uint64_t seed, lvf_cloud** out, double* coefficients4,
@@ -1000,39 +1017,21 @@ int lvf_cloud_segment_plane(const lvf_cloud* in, float distance_threshold, int m
   if (coefficients4) for (int k = 0; k < 4; ++k) coefficients4[k] = 0.0;
   if (iterations_used) *iterations_used = 0;
   if (in->n < 3) return new_cloud(ctx, 0, out);          // SACSegmentation cannot fit a model: no inliers
-  hipStream_t s = ctx->stream;
-  const int n = in->n;
+  hipStream_t s = ctx->stream; const int n = in->n;
   // One launch chain and ONE wait (round 4: five — the bounding box for the moment scale, the hypothesis counts, the winner's three points, the
-  // moments, the inlier count — with RANSAC's bookkeeping and the refit on the host in between).  The chain is the ground half of the feature
-  // extraction's tail: the moment scale by the last workgroup of the bounds pass, pcl::RandomSampleConsensus' bookkeeping and the winning plane
-  // by a one-thread launch (k_ransac_pick), the least-squares refit by the last workgroup of the first inlier pass, the inliers' compaction by
-  // device_scan1 — the host arithmetic of round 4, on the device.
-  DevBuf<unsigned char> state; DevBuf<int> counts, flags;
-  LVF_TRY(state.alloc(sizeof(DcState))); LVF_TRY(counts.alloc(max_iterations)); LVF_TRY(flags.alloc(n));
+  // moments, the inlier count — with RANSAC's bookkeeping and the refit on the host in between)
+  DevBuf<unsigned char> state; PlaneTmp t;
+  LVF_TRY(state.alloc(sizeof(DcState))); LVF_TRY(t.ransac_counts.alloc(max_iterations)); LVF_TRY(t.flags.alloc(n));
   DcState* st = reinterpret_cast<DcState*>(state.p);
-  const int* n_dev = &st->cnt[2];
-  hipLaunchKernelGGL(k_dc_init, dim3(1), dim3(64), 0, s, st, counts.p, max_iterations, n);
-  DcSetup su; su.mode = 2; su.slot = 3; su.which = 0; su.f0 = 0.0f; su.i0 = 0;
-  const int gb = std::min(n > (1 << 18) ? kCapBlocks : kDcBoundsBlocks, gridc(n));
-  hipLaunchKernelGGL(k_dc_bounds, dim3(gb), dim3(kC), 0, s, n, n_dev, in->pts.p, st, su);
-  hipLaunchKernelGGL(k_ransac_count, dim3(std::min(gridc(n), 8), max_iterations), dim3(kC), 0, s, n, n_dev, in->pts.p, (unsigned long long)seed, distance_threshold, counts.p);
-  hipLaunchKernelGGL(k_ransac_pick, dim3(1), dim3(64), 0, s, n_dev, n, in->pts.p, counts.p, max_iterations, (unsigned long long)seed, st);
-  hipLaunchKernelGGL(k_plane_inliers, dim3(gb), dim3(kC), 0, s, n, n_dev, in->pts.p, 0.0f, 0.0f, 0.0f, 0.0f, &st->plane[0], distance_threshold, flags.p, &st->mom, 0.0, st);
-  hipLaunchKernelGGL(k_plane_inliers, dim3(gb), dim3(kC), 0, s, n, n_dev, in->pts.p, 0.0f, 0.0f, 0.0f, 0.0f, &st->plane[1], distance_threshold, flags.p, (MomI*)nullptr, 0.0, (DcState*)nullptr);
-  LVF_HIP(hipGetLastError());
-  lvf_cloud* c = nullptr;
-  LVF_TRY(new_cloud(ctx, n, &c));
+  hipLaunchKernelGGL(k_dc_init, dim3(1), dim3(64), 0, s, st, t.ransac_counts.p, max_iterations, n);
+  const PlaneChain ch{s, in->pts.p, n, &st->cnt[kCntGiven], st, kBoxGiven, distance_threshold, max_iterations, (unsigned long long)seed, dc_bounds_blocks(n, true), &t};
+  for (int k = 0; k < kChainSteps; ++k) LVF_TRY(ch.step(ctx, k));
   DcState h;
-  int rc = n <= kScan1Max ? device_scan1(ctx, flags.p, n, nullptr, nullptr, &st->cnt[3], in->pts.p, c->pts.p) : LVF_OK;
   static_assert(sizeof(DcState) <= 4096, "DcState comes back through the context's mailbox");
-  if (rc == LVF_OK) rc = read_back(ctx, &h, st, sizeof(DcState));
-  if (rc != LVF_OK) { delete c; return rc; }
-  if (h.err & kDcErrBounds) { delete c; set_error("cloud has non-finite coordinates"); return LVF_ERR_INVALID; }
+  LVF_TRY(scan_compact(ctx, t.flags.p, n, nullptr, in->pts.p, &st->cnt[kCntGiven + 1], ReadBlock{&h, st, sizeof(DcState)}, out));
+  if (h.err & kDcErrBounds) { delete *out; *out = nullptr; set_error("cloud has non-finite coordinates"); return LVF_ERR_INVALID; }
   if (iterations_used) *iterations_used = h.ransac_used;
   if (coefficients4) for (int q = 0; q < 4; ++q) coefficients4[q] = h.plane[1].valid ? (double)h.plane[1].co[q] : 0.0;
-  if (n > kScan1Max) { delete c; return compact_cloud(in, flags.p, out); }      // (beyond the one-launch scan: the three-launch compaction)
-  c->n = h.cnt[3]; c->pts.n = (size_t)h.cnt[3];
-  *out = c;
   return LVF_OK;
 }
 

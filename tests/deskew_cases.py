@@ -126,9 +126,9 @@ def fast_drive(velocity=(650.0, 585.0, 520.0)):
 
 def tail_digit_passes(max_range, resolution):
     """the digit passes the device-counted tail enqueues, derived as dc_tail_begin derives them: coordinates in [-max_range, max_range], voxels of
-    2 * resolution (a float32), two cells of slack for the rounding at the ends, 11 bits per pass"""
-    leaf = float(np.float32(2) * np.float32(resolution))
-    span = np.floor(float(max_range) / leaf) - np.floor(-float(max_range) / leaf) + 1.0 + 2.0
+    2 * resolution, in float32 like the voxel box below, two cells of slack, 11 bits per pass"""
+    inv_leaf = np.float32(1) / (np.float32(2) * np.float32(resolution))
+    span = float(np.floor(np.float32(max_range) * inv_leaf)) - float(np.floor(-np.float32(max_range) * inv_leaf)) + 1.0 + 2.0
     bits = 1
     while float(1 << bits) < span ** 3:
         bits += 1

@@ -173,13 +173,15 @@ def test_stable_pair_sort(ctx, n, key_bits):
     assert np.array_equal(ko, keys[order])
 
 
-def test_radius_filter_on_millions_of_points(ctx):
-    """The one-launch scan / compaction (device_scan1) with thousands of tiles: a 3 M-point cloud = a dense lattice (every point has its 6 axis
-    neighbours within the radius: kept) with isolated points sprinkled through the input (removed).  The output must be the lattice points in
-    input order, bit for bit."""
+@pytest.mark.parametrize("side", [143, 162])
+def test_radius_filter_on_millions_of_points(ctx, side):
+    """The scan / compaction with thousands of tiles on either side of the one-launch scan's limit of 2^22 points: a cloud = a dense lattice of
+    side^3 points, spacing 0.1 (every point has its 6 axis neighbours within the radius: kept), with isolated points sprinkled through the input
+    (removed).  143^3 = 2 924 207 takes the one-launch scan (device_scan1) for the grid and the compaction; 162^3 = 4 251 528 > 2^22, the first
+    cubic lattice beyond it, takes the grid sized on the host, its 12 M-cell start array through the three-launch scan, and the three-launch
+    compaction.  The output must be the lattice points in input order, bit for bit."""
     from lvio_fusion_amd import api
     rng = np.random.default_rng(5)
-    side = 143                                              # 143^3 = 2 924 207 lattice points, spacing 0.1
     g = (np.arange(side, dtype=np.float32) * np.float32(0.1))
     lat = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
     n_out = 2000                                            # a 50 x 40 sheet of points 1 m apart, 20 m above the lattice
@@ -196,3 +198,33 @@ def test_radius_filter_on_millions_of_points(ctx):
     assert got.shape == (len(lat), 4)
     assert np.array_equal(got.view(np.uint32), pts[~mask].view(np.uint32))
     out.close(); cl.close()
+
+
+@pytest.mark.parametrize("n", [50000, (1 << 22) + 1])
+def test_segment_plane_on_a_sheet_in_clutter(ctx, oracle, n):
+    """SegmentGround on either side of the one-launch scan's limit of 2^22 points, on one input family: a sheet of points at z = 0 (x = 0.25 i - 100,
+    y = 0.25 j - 60: exact floats) with clutter 1 to 3 m above it scattered through the input.  n = 2^22 + 1 (a 1943 x 1943 sheet) compacts the
+    inliers by the three-launch scan, n = 50 000 (a 211 x 211 sheet) by device_scan1.  Iterations, plane and inliers equal the oracle's, as in
+    test_segment_plane_parity."""
+    from lvio_fusion_amd import api
+    side = 1943 if n > (1 << 22) else 211
+    rng = np.random.default_rng(n)
+    i, j = np.divmod(np.arange(side * side), side)
+    n_clutter = n - side * side
+    pts = np.zeros((n, 4), np.float32)
+    mask = np.zeros(n, bool); mask[np.sort(rng.choice(n, n_clutter, replace=False))] = True
+    pts[~mask, 0] = np.float32(0.25) * i.astype(np.float32) - np.float32(100.0)
+    pts[~mask, 1] = np.float32(0.25) * j.astype(np.float32) - np.float32(60.0)
+    pts[mask, 0] = rng.uniform(-100, 100, n_clutter); pts[mask, 1] = rng.uniform(-60, 100, n_clutter); pts[mask, 2] = rng.uniform(1, 3, n_clutter)
+    pts[:, 3] = np.arange(n, dtype=np.float32) % 251
+    cl = api.Cloud(ctx, pts)
+    for seed in (12345, 99):
+        inl, co, it = cl.segment_plane(0.05, 100, seed)
+        mask_ref, co_ref, it_ref = oracle.segment_plane(pts, 0.05, 100, seed)
+        assert it == it_ref
+        assert np.array_equal(np.asarray(co, np.float64), np.asarray(co_ref, np.float64))
+        got = inl.download()
+        assert np.array_equal(got, pts[mask_ref > 0])
+        assert np.array_equal(mask_ref > 0, ~mask)              # the sheet, and nothing of the clutter
+        inl.close()
+    cl.close()
