@@ -806,14 +806,16 @@ int lvf_optical_flow(const lvf_image* prev_img, const lvf_image* next_img, int n
  * (:240-242), optical_flow(left, right) (:245), triangulate (utility.cpp:7-18; one-sided Jacobi SVD of the 4x4 in fp64) with the inverse
  * extrinsics and Pixel2Sensor of both pixels (:255).  status [n]: 0 = lost by the flow, 1 = landmark accepted, 2 = tracked but
  * Robot2Sensor_0(pb).z <= 0 (:256).  inv_depth [n] = 1 / Robot2Sensor_1(pb).z — camera ONE, as :258 has it; p_robot [n][3] = pb.  Both are
- * zero where status == 0.  What lvf_window_add_landmark takes: (kps_left, kps_right, inv_depth) of the points with status 1. */
+ * zero where status == 0.  What lvf_window_add_landmark takes: (kps_left, kps_right, inv_depth) of the points with status 1.
+ * A non-finite camera field or extrinsic returns LVF_ERR_INVALID before anything is launched. */
 int lvf_stereo_triangulate(const lvf_image* left, const lvf_image* right, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n,
                            const float* kps_left, float* kps_right, uint8_t* status, double* inv_depth, double* p_robot, const lvf_flow_options* opt);
 /* The numeric part of Frontend::TrackLastFrame (frontend.cpp:163-256): predictions = World2Pixel(pw[i], current_pose) (:168-170), optical_flow
  * (last, current, kps_last, predictions) (:189), deviation = prediction - tracked minus its mean over the tracked points (:195-212), class
  * per point cls [n]: 0 lost, 1 far (Camera::Far, camera.h:38-41), 2 near (!remove_moving_points or |deviation| < 30, :220), 3 moving;
  * *num_good = far + near if that exceeds num_features_tracking_bad, else 0 (:236).  kps_current [n][2] = the tracked pixels; predictions
- * [n][2] may be NULL.  What lvf_window_add_observation takes: kps_current of the points of class 1 or 2 when *num_good > 0. */
+ * [n][2] may be NULL.  What lvf_window_add_observation takes: kps_current of the points of class 1 or 2 when *num_good > 0.
+ * A non-finite camera field, extrinsic or current_pose returns LVF_ERR_INVALID before anything is launched. */
 int lvf_track_last_frame(const lvf_image* last, const lvf_image* current, const lvf_camera* cam0, double baseline, const double* current_pose, int n,
                          const double* pw, const float* kps_last, int remove_moving_points, int num_features_tracking_bad, float* kps_current,
                          float* predictions, uint8_t* cls, int* num_good, const lvf_flow_options* opt);
@@ -901,7 +903,8 @@ int lvf_orb_download_level(lvf_orb* orb, int level, int* width, int* height, uin
  * (< num_levels) with |angle_last - angle| < 15 (no wrap-around, as the reference) and |p - pt_last| < 31 * scale_factors_[level] (the
  * fp64 running product of the float scale_factor, local_map.h:26-31); Hamming 2-NN, ties to the lower (level, index); accepted iff >= 2
  * candidates, best < 50 and float(best) < 0.8f * float(second).  match [n_cur] = index into last_* or -1; best / second [n_cur] (may be
- * NULL) = the two distances, -1 where there is no such candidate.  The keyframe loop and the map insertion stay with the caller. */
+ * NULL) = the two distances, -1 where there is no such candidate.  The keyframe loop and the map insertion stay with the caller.
+ * A non-finite camera field, extrinsic or last_pose returns LVF_ERR_INVALID before anything is launched. */
 int lvf_orb_search(lvf_ctx* ctx, const lvf_orb_options* opt, const lvf_camera* cam0, const double* last_pose, int n_last, const float* last_pt,
                    const int32_t* last_octave, const float* last_angle, const uint8_t* last_desc, int n_cur, const double* cur_pw,
                    const int32_t* cur_octave, const float* cur_angle, const uint8_t* cur_desc, const uint8_t* skip, int32_t* match, int32_t* best,
@@ -1056,7 +1059,8 @@ int lvf_lidar_depth_query(const lvf_lidar_depth* depth, const lvf_camera* cam0, 
  * feature iff its LiDAR status is 1 AND either the stereo status is 1 and Robot2Sensor_0(p_robot_stereo).z > far_factor * baseline
  * (far_factor == 0: always), or the stereo status is not 1 and replace_lost is set.  A replaced feature gets status 1, source 2 and the
  * LiDAR kps_right / inv_depth / p_robot; every other feature keeps exactly what lvf_stereo_triangulate writes, source [n] = 1 where its
- * status is 1, else 0.  `depth` belongs to the images' context. */
+ * status is 1, else 0.  `depth` belongs to the images' context.  A non-finite camera field or extrinsic returns LVF_ERR_INVALID before
+ * anything is launched. */
 int lvf_stereo_triangulate_lidar(const lvf_image* left, const lvf_image* right, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n,
                                  const float* kps_left, float* kps_right, uint8_t* status, double* inv_depth, double* p_robot, const lvf_flow_options* opt,
                                  const lvf_lidar_depth* depth, uint8_t* source);

@@ -30,17 +30,10 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line) {
   return LVF_ERR_HIP;
 }
 
-// host-side rotation of the (constant) camera extrinsic; mirrors derive_pose
-static void host_rot(const double q[4], double R[9]) {
-  const double s = 1.0 / std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const double x = s * q[0], y = s * q[1], z = s * q[2], w = s * q[3];
-  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-  R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-  R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
+// the solver's derived form of the (constant) camera; the rotation is camera_dev.hpp's and mirrors derive_pose
 void make_camd(const lvf_camera& c, CamD& d) {
   d.fx = c.fx; d.fy = c.fy; d.cx = c.cx; d.cy = c.cy;
-  host_rot(c.extrinsic, d.Re);
+  rot_of_quat(c.extrinsic, d.Re);
   for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) d.E[3 * i + j] = d.Re[3 * j + i];
   for (int i = 0; i < 3; ++i) {
     d.te[i] = c.extrinsic[4 + i];

@@ -15,13 +15,13 @@
 // narrowed window counts stamps there.  Any other point — and every point of a sweep that spans more knots than the stage holds — takes a
 // binary search over the whole array: the bracket is the same, so is every operation after it.  The point count may live on the device
 // (n_dev: the extraction's picks), the launch then covers the capacity.
+#pragma clang fp contract(off)      // ahead of the includes: the unit's semantics are contraction-free, shared inline chains included
+
 #include "host_se3.hpp"
 #include "lvf_internal.hpp"
 
 #include <cfloat>
 #include <cmath>
-
-#pragma clang fp contract(off)
 
 struct lvf_trajectory {
   lvf_ctx* ctx = nullptr;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kD) void k_traj_pose(int m, const double* __restric
   o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3]; o[4] = p[0]; o[5] = p[1]; o[6] = p[2];
 }
 
-__device__ __forceinline__ void rt_apply(const DeskewRt& M, const double v[3], double o[3]) {
+__device__ __forceinline__ void rt_apply(const Rigid& M, const double v[3], double o[3]) {
   o[0] = ((M.R[0] * v[0] + M.R[1] * v[1]) + M.R[2] * v[2]) + M.t[0];
   o[1] = ((M.R[3] * v[0] + M.R[4] * v[1]) + M.R[5] * v[2]) + M.t[1];
   o[2] = ((M.R[6] * v[0] + M.R[7] * v[1]) + M.R[8] * v[2]) + M.t[2];
@@ -135,25 +135,12 @@ __global__ __launch_bounds__(kD) void k_deskew(int cap, const int* __restrict__ 
 
 namespace {
 
-bool finite_n(const double* v, int n) {
-  for (int k = 0; k < n; ++k) if (!std::isfinite(v[k])) return false;
-  return true;
-}
-// a pose argument: finite, the quaternion not zero and its squared norm finite; out = the pose with its quaternion normalised (the SE3d constructor's)
-int check_pose(const char* who, const char* what, const double* in, double out[7]) {
-  LVF_REQUIRE(finite_n(in, 7), "%s: non-finite %s", who, what);
-  const double n2 = in[0] * in[0] + in[1] * in[1] + in[2] * in[2] + in[3] * in[3];
-  LVF_REQUIRE(n2 > 0.0 && std::isfinite(n2), "%s: the quaternion of %s is zero or not normalisable", who, what);
-  for (int k = 0; k < 7; ++k) out[k] = in[k];
-  hse3::normalize4(out);
-  return LVF_OK;
-}
-void rt_of(const double T[7], DeskewRt* M) {
-  const double x = T[0], y = T[1], z = T[2], w = T[3];
-  const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-                       2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
-  for (int k = 0; k < 9; ++k) M->R[k] = R[k];
-  for (int k = 0; k < 3; ++k) M->t[k] = T[4 + k];
+// the matrix form of a pose whose quaternion hse3 has ALREADY normalised: normalising again (make_rigid) would move the last bit
+Rigid rigid_of_unit(const double T[7]) {
+  Rigid M;
+  unit_quat_matrix(T[0], T[1], T[2], T[3], M.R);
+  for (int k = 0; k < 3; ++k) M.t[k] = T[4 + k];
+  return M;
 }
 // the knot's row goes up; the device array grows by re-uploading the host copy (contents are not preserved across a growth)
 int upload_knots(lvf_trajectory* tr, int first, int count) {
@@ -182,7 +169,7 @@ int deskew_prepare(const char* who, lvf_ctx* ctx, const lvf_trajectory* tr, doub
   if (!*active) return LVF_OK;
   double Ei[7], Tfi[7], A[7];
   hse3::inv(E, Ei); hse3::inv(Tf, Tfi); hse3::mul(Ei, Tfi, A);
-  rt_of(E, &P->E); rt_of(A, &P->A);
+  P->E = rigid_of_unit(E); P->A = rigid_of_unit(A);
   P->knots = tr->dev.p; P->n = tr->n;
   P->t0 = frame_time - 0.5 * cycle_time;
   P->t_lo = frame_time - 0.75 * cycle_time; P->t_hi = frame_time + 0.75 * cycle_time;

@@ -14,7 +14,7 @@
 #include <cmath>
 
 namespace {
-using lvf::DevBuf;
+using lvf::DevBuf; using lvf::Pinhole; using lvf::Rigid; using lvf::grid_of; using lvf::refl101;
 
 constexpr int kMaxLevels = 8;        // pyramid levels an image can hold (max_level <= 7)
 constexpr int kMaxWin = 21;          // 7 pixels per lane x 64 lanes >= win^2
@@ -38,14 +38,6 @@ struct lvf_image {
 };
 
 namespace {
-
-__device__ __forceinline__ int refl101(int i, int n) {      // BORDER_REFLECT_101, any i
-  if (n == 1) return 0;
-  const int m = 2 * (n - 1);
-  int r = i % m;
-  if (r < 0) r += m;
-  return r >= n ? m - r : r;
-}
 
 // level L+1 from level L: separable [1 4 6 4 1] decimation, reflect-101, (sum + 128) >> 8
 __global__ void __launch_bounds__(kT) k_klt_pyr_down(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh) {
@@ -210,28 +202,17 @@ __global__ void __launch_bounds__(kFlowBlock) k_klt_flow(int n, const KltLevel* 
   }
 }
 
-// ---- geometry (fp64, one thread per feature) ------------------------------------------------------------------------------------------------
-struct KCam { double fx, fy, cx, cy, R[9], t[3]; };      // R, t: sensor -> robot (the extrinsic)
-struct KPose { double R[9], t[3]; };                     // body -> world
-
-__device__ __forceinline__ void robot2sensor(const KCam& c, const double pb[3], double pc[3]) {      // sensor.h:36-39
-  const double d[3] = {pb[0] - c.t[0], pb[1] - c.t[1], pb[2] - c.t[2]};
-  pc[0] = c.R[0] * d[0] + c.R[3] * d[1] + c.R[6] * d[2];
-  pc[1] = c.R[1] * d[0] + c.R[4] * d[1] + c.R[7] * d[2];
-  pc[2] = c.R[2] * d[0] + c.R[5] * d[1] + c.R[8] * d[2];
-}
-
+// ---- geometry (fp64, one thread per feature; the camera chains are camera_dev.hpp's) ----------------------------------------------------------
 // local_map.cpp:240-242: the left pixel at depth 50 * baseline, seen by camera 1
-__global__ void __launch_bounds__(kT) k_klt_stereo_predict(int n, const float2* __restrict__ left, float2* __restrict__ right, KCam c0, KCam c1, double depth) {
+__global__ void __launch_bounds__(kT) k_klt_stereo_predict(int n, const float2* __restrict__ left, float2* __restrict__ right, Pinhole c0, Pinhole c1, double depth) {
   const int i = blockIdx.x * kT + threadIdx.x;
   if (i >= n) return;
   const float2 kp = left[i];
-  const double ps[3] = {((double)kp.x - c0.cx) * depth / c0.fx, ((double)kp.y - c0.cy) * depth / c0.fy, depth};
-  const double pb[3] = {c0.R[0] * ps[0] + c0.R[1] * ps[1] + c0.R[2] * ps[2] + c0.t[0], c0.R[3] * ps[0] + c0.R[4] * ps[1] + c0.R[5] * ps[2] + c0.t[1],
-                        c0.R[6] * ps[0] + c0.R[7] * ps[1] + c0.R[8] * ps[2] + c0.t[2]};
-  double pc[3];
+  double ps[3], pb[3], pc[3];
+  pixel2sensor(c0, (double)kp.x, (double)kp.y, depth, ps);
+  sensor2robot(c0, ps, pb);
   robot2sensor(c1, pb, pc);
-  right[i] = make_float2((float)(c1.fx * pc[0] / pc[2] + c1.cx), (float)(c1.fy * pc[1] / pc[2] + c1.cy));
+  right[i] = sensor2pixel(c1, pc);
 }
 
 // one Hestenes rotation of columns P, Q of the 4x4 pair (A, V); column-major a[4 * col + row], all indices compile-time
@@ -258,15 +239,17 @@ __device__ __forceinline__ bool jacobi_rotate(double (&a)[16], double (&v)[16]) 
 // singular value comes from a one-sided Jacobi SVD of the 4x4 DLT matrix itself (A^T A is never formed: it would square the condition number).
 // status: in = the flow's (0 / 1); out = 0 lost, 1 accepted, 2 tracked but behind camera 0.
 __global__ void __launch_bounds__(kT) k_klt_dlt(int n, const float2* __restrict__ left, const float2* __restrict__ right, uint8_t* __restrict__ status,
-                                                 double* __restrict__ inv_depth, double* __restrict__ p_robot, KCam c0, KCam c1) {
+                                                 double* __restrict__ inv_depth, double* __restrict__ p_robot, Pinhole c0, Pinhole c1) {
   const int i = blockIdx.x * kT + threadIdx.x;
   if (i >= n) return;
   double out_inv = 0.0, pb[3] = {0.0, 0.0, 0.0};
   uint8_t st = status[i];
   if (st) {
     const float2 kl = left[i], kr = right[i];
-    const double x0 = ((double)kl.x - c0.cx) / c0.fx, y0 = ((double)kl.y - c0.cy) / c0.fy;      // Pixel2Sensor, depth 1
-    const double x1 = ((double)kr.x - c1.cx) / c1.fx, y1 = ((double)kr.y - c1.cy) / c1.fy;
+    double n0[3], n1[3];                                                                        // Pixel2Sensor, depth 1
+    pixel2sensor(c0, (double)kl.x, (double)kl.y, 1.0, n0);
+    pixel2sensor(c1, (double)kr.x, (double)kr.y, 1.0, n1);
+    const double x0 = n0[0], y0 = n0[1], x1 = n1[0], y1 = n1[1];
     // P = extrinsic.inverse().matrix3x4() = [R^T | -R^T t]; row r of P: (R[r], R[3 + r], R[6 + r], m[r])
     const double m0[3] = {-(c0.R[0] * c0.t[0] + c0.R[3] * c0.t[1] + c0.R[6] * c0.t[2]), -(c0.R[1] * c0.t[0] + c0.R[4] * c0.t[1] + c0.R[7] * c0.t[2]),
                           -(c0.R[2] * c0.t[0] + c0.R[5] * c0.t[1] + c0.R[8] * c0.t[2])};
@@ -308,14 +291,13 @@ __global__ void __launch_bounds__(kT) k_klt_dlt(int n, const float2* __restrict_
 
 // frontend.cpp:168-170: World2Pixel(pw, current pose); also the depth in camera 0 that Camera::Far tests (camera.h:38-41)
 __global__ void __launch_bounds__(kT) k_klt_track_predict(int n, const double* __restrict__ pw, float2* __restrict__ pred, float2* __restrict__ cur, double* __restrict__ z,
-                                                           KCam c0, KPose T) {
+                                                           Pinhole c0, Rigid T) {      // T: body -> world
   const int i = blockIdx.x * kT + threadIdx.x;
   if (i >= n) return;
-  const double d[3] = {pw[3 * i] - T.t[0], pw[3 * i + 1] - T.t[1], pw[3 * i + 2] - T.t[2]};
-  const double pb[3] = {T.R[0] * d[0] + T.R[3] * d[1] + T.R[6] * d[2], T.R[1] * d[0] + T.R[4] * d[1] + T.R[7] * d[2], T.R[2] * d[0] + T.R[5] * d[1] + T.R[8] * d[2]};
-  double pc[3];
+  double pb[3], pc[3];
+  world2robot(T, pw + 3 * i, pb);
   robot2sensor(c0, pb, pc);
-  const float2 px = make_float2((float)(c0.fx * pc[0] / pc[2] + c0.cx), (float)(c0.fy * pc[1] / pc[2] + c0.cy));
+  const float2 px = sensor2pixel(c0, pc);
   pred[i] = px; cur[i] = px;                                 // kps_current = kps_perdict (frontend.cpp:188)
   z[i] = pc[2];
 }
@@ -362,26 +344,6 @@ __global__ void __launch_bounds__(kT) k_klt_track_classify(int n, const float2* 
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------------
-void rot_of(const double* q, double R[9]) {      // (of q / |q|, as Sophus holds it)
-  const double inv = 1.0 / std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const double x = q[0] * inv, y = q[1] * inv, z = q[2] * inv, w = q[3] * inv;
-  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
-  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
-}
-KCam make_cam(const lvf_camera* c) {
-  KCam k;
-  k.fx = c->fx; k.fy = c->fy; k.cx = c->cx; k.cy = c->cy;
-  rot_of(c->extrinsic, k.R);
-  for (int i = 0; i < 3; ++i) k.t[i] = c->extrinsic[4 + i];
-  return k;
-}
-bool cam_ok(const lvf_camera* c) {
-  if (!c || !(c->fx != 0.0) || !(c->fy != 0.0)) return false;
-  const double* q = c->extrinsic;
-  return q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] > 0.0;
-}
-
 int check_flow(const char* who, const lvf_image* a, const lvf_image* b, int n, const lvf_flow_options* o) {
   LVF_REQUIRE(a && b, "%s: null image", who);
   LVF_REQUIRE(a->ctx == b->ctx, "%s: the images belong to different contexts", who);
@@ -404,7 +366,43 @@ void launch_flow(hipStream_t s, const lvf_image* a, const lvf_image* b, int n, c
   hipLaunchKernelGGL(k_klt_flow, dim3((n + per - 1) / per), dim3(kFlowBlock), 0, s, n, a->table.p, b->table.p, prev, next, status, fb, P);
 }
 
-inline int grid_of(size_t n) { return (int)((n + kT - 1) / kT); }
+// lvf_stereo_triangulate and lvf_stereo_triangulate_lidar: the 50-baseline prediction, the flow and the DLT, then — with a projected sweep —
+// the LiDAR query and the merge (lidar_depth_kernels.hip) behind them; the downloads and ONE wait.  depth == nullptr: no merge, no source.
+int stereo_chain(const char* who, const lvf_image* left, const lvf_image* right, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n,
+                 const float* kps_left, float* kps_right, uint8_t* status, double* inv_depth, double* p_robot, const lvf_flow_options* opt, const lvf_lidar_depth* depth,
+                 uint8_t* source) {
+  lvf_flow_options o;
+  if (opt) o = *opt; else lvf_flow_options_default(&o);
+  LVF_TRY(check_flow(who, left, right, n, &o));
+  LVF_TRY(lvf::check_camera(who, cam0));
+  LVF_TRY(lvf::check_camera(who, cam1));
+  LVF_REQUIRE(baseline > 0.0, "%s: baseline must be > 0", who);
+  if (depth) LVF_TRY(lvf::lidar_depth_check(who, depth, left->ctx, cam0, cam1));
+  if (n == 0) return LVF_OK;
+  LVF_REQUIRE(kps_left && kps_right && status && inv_depth && p_robot && (!depth || source), "%s: null point arrays", who);
+  lvf_ctx* ctx = left->ctx;
+  LVF_TRY(lvf::enter(ctx));
+  hipStream_t s = ctx->stream;
+  const Pinhole c0 = lvf::make_pinhole(*cam0), c1 = lvf::make_pinhole(*cam1);
+  DevBuf<float2> p, q; DevBuf<uint8_t> st, src; DevBuf<double> inv, pb;
+  lvf::StreamWaitGuard wait(s);                  // (an error below: what is queued ends before the buffers go)
+  LVF_TRY(p.upload(reinterpret_cast<const float2*>(kps_left), n, s));
+  LVF_TRY(q.alloc(n)); LVF_TRY(st.alloc(n)); LVF_TRY(inv.alloc(n)); LVF_TRY(pb.alloc((size_t)3 * n));
+  if (depth) LVF_TRY(src.alloc(n));
+  hipLaunchKernelGGL(k_klt_stereo_predict, dim3(grid_of(n)), dim3(kT), 0, s, n, p.p, q.p, c0, c1, baseline * 50);
+  launch_flow(s, left, right, n, p.p, q.p, st.p, (float*)nullptr, &o);
+  hipLaunchKernelGGL(k_klt_dlt, dim3(grid_of(n)), dim3(kT), 0, s, n, p.p, q.p, st.p, inv.p, pb.p, c0, c1);
+  LVF_HIP(hipGetLastError());
+  if (depth) LVF_TRY(lvf::lidar_depth_merge_queue(depth, c0, c1, baseline, n, p.p, q.p, st.p, inv.p, pb.p, src.p));
+  LVF_HIP(hipMemcpyAsync(kps_right, q.p, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipMemcpyAsync(status, st.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipMemcpyAsync(inv_depth, inv.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipMemcpyAsync(p_robot, pb.p, (size_t)3 * n * 8, hipMemcpyDeviceToHost, s));
+  if (depth) LVF_HIP(hipMemcpyAsync(source, src.p, (size_t)n, hipMemcpyDeviceToHost, s));
+  LVF_HIP(hipStreamSynchronize(s));
+  wait.dismiss();
+  return LVF_OK;
+}
 
 }  // namespace
 
@@ -524,70 +522,16 @@ int lvf_optical_flow(const lvf_image* prev_img, const lvf_image* next_img, int n
   return LVF_OK;
 }
 
-// (lvf_stereo_triangulate_lidar below queues the SAME three launches with the same arguments — the 50-baseline prediction included — and says so
-// in its contract; a change to this chain is a change to that one.  tests/test_gpu_lidar_depth.py compares the two byte for byte.)
 int lvf_stereo_triangulate(const lvf_image* left, const lvf_image* right, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n,
                            const float* kps_left, float* kps_right, uint8_t* status, double* inv_depth, double* p_robot, const lvf_flow_options* opt) {
-  lvf_flow_options o;
-  if (opt) o = *opt; else lvf_flow_options_default(&o);
-  LVF_TRY(check_flow("lvf_stereo_triangulate", left, right, n, &o));
-  LVF_REQUIRE(cam_ok(cam0) && cam_ok(cam1), "lvf_stereo_triangulate: bad camera (null, zero focal length or zero extrinsic quaternion)");
-  LVF_REQUIRE(baseline > 0.0, "lvf_stereo_triangulate: baseline must be > 0");
-  if (n == 0) return LVF_OK;
-  LVF_REQUIRE(kps_left && kps_right && status && inv_depth && p_robot, "lvf_stereo_triangulate: null point arrays");
-  lvf_ctx* ctx = left->ctx;
-  LVF_TRY(lvf::enter(ctx));
-  hipStream_t s = ctx->stream;
-  const KCam c0 = make_cam(cam0), c1 = make_cam(cam1);
-  DevBuf<float2> p, q; DevBuf<uint8_t> st; DevBuf<double> inv, pb;
-  LVF_TRY(p.upload(reinterpret_cast<const float2*>(kps_left), n, s));
-  LVF_TRY(q.alloc(n)); LVF_TRY(st.alloc(n)); LVF_TRY(inv.alloc(n)); LVF_TRY(pb.alloc((size_t)3 * n));
-  hipLaunchKernelGGL(k_klt_stereo_predict, dim3(grid_of(n)), dim3(kT), 0, s, n, p.p, q.p, c0, c1, baseline * 50);
-  launch_flow(s, left, right, n, p.p, q.p, st.p, (float*)nullptr, &o);
-  hipLaunchKernelGGL(k_klt_dlt, dim3(grid_of(n)), dim3(kT), 0, s, n, p.p, q.p, st.p, inv.p, pb.p, c0, c1);
-  LVF_HIP(hipGetLastError());
-  LVF_HIP(hipMemcpyAsync(kps_right, q.p, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, s));
-  LVF_HIP(hipMemcpyAsync(status, st.p, (size_t)n, hipMemcpyDeviceToHost, s));
-  LVF_HIP(hipMemcpyAsync(inv_depth, inv.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  LVF_HIP(hipMemcpyAsync(p_robot, pb.p, (size_t)3 * n * 8, hipMemcpyDeviceToHost, s));
-  LVF_HIP(hipStreamSynchronize(s));
-  return LVF_OK;
+  return stereo_chain("lvf_stereo_triangulate", left, right, cam0, cam1, baseline, n, kps_left, kps_right, status, inv_depth, p_robot, opt, nullptr, nullptr);
 }
 
-// lvf_stereo_triangulate's launch chain, restated launch for launch (keep the two in step), then the LiDAR query and the merge
-// (lidar_depth_kernels.hip) behind it: one wait
 int lvf_stereo_triangulate_lidar(const lvf_image* left, const lvf_image* right, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n,
                                  const float* kps_left, float* kps_right, uint8_t* status, double* inv_depth, double* p_robot, const lvf_flow_options* opt,
                                  const lvf_lidar_depth* depth, uint8_t* source) {
-  lvf_flow_options o;
-  if (opt) o = *opt; else lvf_flow_options_default(&o);
-  LVF_TRY(check_flow("lvf_stereo_triangulate_lidar", left, right, n, &o));
-  LVF_REQUIRE(cam_ok(cam0) && cam_ok(cam1), "lvf_stereo_triangulate_lidar: bad camera (null, zero focal length or zero extrinsic quaternion)");
-  LVF_REQUIRE(baseline > 0.0, "lvf_stereo_triangulate_lidar: baseline must be > 0");
-  LVF_TRY(lvf::lidar_depth_check("lvf_stereo_triangulate_lidar", depth, left->ctx, cam0, cam1));
-  if (n == 0) return LVF_OK;
-  LVF_REQUIRE(kps_left && kps_right && status && inv_depth && p_robot && source, "lvf_stereo_triangulate_lidar: null point arrays");
-  lvf_ctx* ctx = left->ctx;
-  LVF_TRY(lvf::enter(ctx));
-  hipStream_t s = ctx->stream;
-  const KCam c0 = make_cam(cam0), c1 = make_cam(cam1);
-  DevBuf<float2> p, q; DevBuf<uint8_t> st, src; DevBuf<double> inv, pb;
-  LVF_TRY(p.upload(reinterpret_cast<const float2*>(kps_left), n, s));
-  LVF_TRY(q.alloc(n)); LVF_TRY(st.alloc(n)); LVF_TRY(src.alloc(n)); LVF_TRY(inv.alloc(n)); LVF_TRY(pb.alloc((size_t)3 * n));
-  lvf::StreamWaitGuard wait(s);                  // (an error below: what is queued ends before the buffers go)
-  hipLaunchKernelGGL(k_klt_stereo_predict, dim3(grid_of(n)), dim3(kT), 0, s, n, p.p, q.p, c0, c1, baseline * 50);
-  launch_flow(s, left, right, n, p.p, q.p, st.p, (float*)nullptr, &o);
-  hipLaunchKernelGGL(k_klt_dlt, dim3(grid_of(n)), dim3(kT), 0, s, n, p.p, q.p, st.p, inv.p, pb.p, c0, c1);
-  LVF_HIP(hipGetLastError());
-  LVF_TRY(lvf::lidar_depth_merge_queue(depth, cam0, cam1, baseline, n, p.p, q.p, st.p, inv.p, pb.p, src.p));
-  LVF_HIP(hipMemcpyAsync(kps_right, q.p, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, s));
-  LVF_HIP(hipMemcpyAsync(status, st.p, (size_t)n, hipMemcpyDeviceToHost, s));
-  LVF_HIP(hipMemcpyAsync(inv_depth, inv.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  LVF_HIP(hipMemcpyAsync(p_robot, pb.p, (size_t)3 * n * 8, hipMemcpyDeviceToHost, s));
-  LVF_HIP(hipMemcpyAsync(source, src.p, (size_t)n, hipMemcpyDeviceToHost, s));
-  LVF_HIP(hipStreamSynchronize(s));
-  wait.dismiss();
-  return LVF_OK;
+  LVF_REQUIRE(depth, "lvf_stereo_triangulate_lidar: null lvf_lidar_depth");
+  return stereo_chain("lvf_stereo_triangulate_lidar", left, right, cam0, cam1, baseline, n, kps_left, kps_right, status, inv_depth, p_robot, opt, depth, source);
 }
 
 int lvf_track_last_frame(const lvf_image* last, const lvf_image* current, const lvf_camera* cam0, double baseline, const double* current_pose, int n,
@@ -596,19 +540,16 @@ int lvf_track_last_frame(const lvf_image* last, const lvf_image* current, const 
   lvf_flow_options o;
   if (opt) o = *opt; else lvf_flow_options_default(&o);
   LVF_TRY(check_flow("lvf_track_last_frame", last, current, n, &o));
-  LVF_REQUIRE(cam_ok(cam0), "lvf_track_last_frame: bad camera (null, zero focal length or zero extrinsic quaternion)");
+  LVF_TRY(lvf::check_camera("lvf_track_last_frame", cam0));
   LVF_REQUIRE(baseline > 0.0 && current_pose && num_good, "lvf_track_last_frame: bad argument");
-  LVF_REQUIRE(current_pose[0] * current_pose[0] + current_pose[1] * current_pose[1] + current_pose[2] * current_pose[2] + current_pose[3] * current_pose[3] > 0.0,
-              "lvf_track_last_frame: zero pose quaternion");
+  LVF_TRY(lvf::check_pose("lvf_track_last_frame", "the current pose", current_pose, nullptr));
   if (n == 0) { *num_good = 0; return LVF_OK; }
   LVF_REQUIRE(pw && kps_last && kps_current && cls, "lvf_track_last_frame: null point arrays");
   lvf_ctx* ctx = last->ctx;
   LVF_TRY(lvf::enter(ctx));
   hipStream_t s = ctx->stream;
-  const KCam c0 = make_cam(cam0);
-  KPose T;
-  rot_of(current_pose, T.R);
-  for (int i = 0; i < 3; ++i) T.t[i] = current_pose[4 + i];
+  const Pinhole c0 = lvf::make_pinhole(*cam0);
+  const Rigid T = lvf::make_rigid(current_pose);      // body -> world
   DevBuf<float2> p, pred, q; DevBuf<uint8_t> st, cl; DevBuf<double> w, z; DevBuf<int> good;
   LVF_TRY(p.upload(reinterpret_cast<const float2*>(kps_last), n, s));
   LVF_TRY(w.upload(pw, (size_t)3 * n, s));

@@ -24,11 +24,11 @@
 //   k_ld_merge      one thread per feature: LiDAR replaces the stereo result where the rule of lvf_stereo_triangulate_lidar says so.
 //                   At most 66 bytes read and 42 written per feature.
 // lvf_lidar_depth_create queues memset -> project -> scan -> fill and waits for nothing (the record array is sized by the cloud).
+#pragma clang fp contract(off)      // ahead of the includes: camera_dev.hpp's chains are compiled contraction-free here, as the restatement states them
+
 #include "lvf_internal.hpp"
 
 #include <cmath>
-
-#pragma clang fp contract(off)
 
 namespace lvf {
 
@@ -38,10 +38,9 @@ constexpr int kLdMaxCells = 1 << 22;
 struct LdRecord { float u, v, z; int src; };
 static_assert(sizeof(LdRecord) == 16 && sizeof(LdRecord) == sizeof(lvf_lidar_depth_record), "a record is one 16-byte load");
 
-struct LdCam { double fx, fy, cx, cy, R[9], t[3]; };      // R, t: sensor -> robot
 struct LdGrid { int width, height, shift, ncx, ncy, cells; };
 struct LdProjP { double M[12], fx, fy, cx, cy, min_depth, max_depth; LdGrid g; };
-struct LdQueryP { LdGrid g; LdCam c0, c1; double cell, radius, r2, min_depth, max_depth, max_spread, min_det, max_extrapolation; };
+struct LdQueryP { LdGrid g; Pinhole c0, c1; double cell, radius, r2, min_depth, max_depth, max_spread, min_det, max_extrapolation; };
 
 __device__ __forceinline__ int ld_cell_of(const LdRecord& r, const LdGrid& g) { return ((int)r.v >> g.shift) * g.ncx + ((int)r.u >> g.shift); }
 
@@ -209,17 +208,13 @@ __global__ __launch_bounds__(kLdQueryBlock) void k_ld_query(int n, const float2*
     else {
       st = 1;
       out_depth = d;
-      const LdCam& c0 = P.c0;
-      const LdCam& c1 = P.c1;
-      const double ps[3] = {(u0 - c0.cx) * d / c0.fx, (v0 - c0.cy) * d / c0.fy, d};                       // Pixel2Sensor_0 (camera.h:51-57)
-      pb[0] = ((c0.R[0] * ps[0] + c0.R[1] * ps[1]) + c0.R[2] * ps[2]) + c0.t[0];                          // Sensor2Robot_0
-      pb[1] = ((c0.R[3] * ps[0] + c0.R[4] * ps[1]) + c0.R[5] * ps[2]) + c0.t[1];
-      pb[2] = ((c0.R[6] * ps[0] + c0.R[7] * ps[1]) + c0.R[8] * ps[2]) + c0.t[2];
-      const double e[3] = {pb[0] - c1.t[0], pb[1] - c1.t[1], pb[2] - c1.t[2]};                            // Robot2Sensor_1 (sensor.h:36-39)
-      const double s1[3] = {(c1.R[0] * e[0] + c1.R[3] * e[1]) + c1.R[6] * e[2], (c1.R[1] * e[0] + c1.R[4] * e[1]) + c1.R[7] * e[2],
-                            (c1.R[2] * e[0] + c1.R[5] * e[1]) + c1.R[8] * e[2]};
+      double ps[3], r[3], s1[3];
+      pixel2sensor(P.c0, u0, v0, d, ps);
+      sensor2robot(P.c0, ps, r);
+      pb[0] = r[0]; pb[1] = r[1]; pb[2] = r[2];      // (through a local: handing out the result array itself moves the register allocation)
+      robot2sensor(P.c1, r, s1);
       out_inv = 1.0 / s1[2];                                                                              // local_map.cpp:258: camera ONE
-      out_right = make_float2((float)(c1.fx * s1[0] / s1[2] + c1.cx), (float)(c1.fy * s1[1] / s1[2] + c1.cy));
+      out_right = sensor2pixel(P.c1, s1);
     }
   }
   if (lane == 0) {
@@ -233,16 +228,16 @@ __global__ __launch_bounds__(kLdQueryBlock) void k_ld_query(int n, const float2*
 __global__ __launch_bounds__(kLdThreads) void k_ld_merge(int n, float2* __restrict__ right, uint8_t* __restrict__ status, double* __restrict__ inv_depth,
                                                           double* __restrict__ p_robot, uint8_t* __restrict__ source, const uint8_t* __restrict__ l_status,
                                                           const double* __restrict__ l_inv, const double* __restrict__ l_pb, const float2* __restrict__ l_right,
-                                                          const LdCam c0, double far_depth, int always_far, int replace_lost) {
+                                                          const Pinhole c0, double far_depth, int always_far, int replace_lost) {
   const int i = blockIdx.x * kLdThreads + threadIdx.x;
   if (i >= n) return;
   const uint8_t st = status[i];
   bool replace = false;
   if (l_status[i] == 1) {
     if (st == 1) {
-      const double e[3] = {p_robot[3 * i] - c0.t[0], p_robot[3 * i + 1] - c0.t[1], p_robot[3 * i + 2] - c0.t[2]};
-      const double z0 = (c0.R[2] * e[0] + c0.R[5] * e[1]) + c0.R[8] * e[2];                               // Robot2Sensor_0(pb).z
-      replace = always_far || z0 > far_depth;
+      double s0[3];
+      robot2sensor(c0, p_robot + 3 * i, s0);                                                              // (only the z row survives)
+      replace = always_far || s0[2] > far_depth;
     } else {
       replace = replace_lost != 0;
     }
@@ -270,28 +265,6 @@ struct lvf_lidar_depth {
 namespace lvf {
 namespace {
 
-void ld_rot_of(const double* q, double R[9]) {      // (of q / |q|, as Sophus holds it; the operation order tests/lidar_depth_ref.py states)
-  const double inv = 1.0 / std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-  const double x = q[0] * inv, y = q[1] * inv, z = q[2] * inv, w = q[3] * inv;
-  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - z * w); R[2] = 2.0 * (x * z + y * w);
-  R[3] = 2.0 * (x * y + z * w); R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - x * w);
-  R[6] = 2.0 * (x * z - y * w); R[7] = 2.0 * (y * z + x * w); R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-LdCam ld_cam(const lvf_camera* c) {
-  LdCam k;
-  k.fx = c->fx; k.fy = c->fy; k.cx = c->cx; k.cy = c->cy;
-  ld_rot_of(c->extrinsic, k.R);
-  for (int i = 0; i < 3; ++i) k.t[i] = c->extrinsic[4 + i];
-  return k;
-}
-bool ld_cam_ok(const lvf_camera* c) {
-  if (!c) return false;
-  for (double v : {c->fx, c->fy, c->cx, c->cy}) if (!std::isfinite(v)) return false;
-  for (int i = 0; i < 7; ++i) if (!std::isfinite(c->extrinsic[i])) return false;
-  const double* q = c->extrinsic;
-  return c->fx != 0.0 && c->fy != 0.0 && q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] > 0.0;
-}
-
 int ld_check_options(const char* who, const lvf_lidar_depth_options& o) {
   LVF_REQUIRE(o.cell == 4 || o.cell == 8 || o.cell == 16 || o.cell == 32, "%s: cell %d is not 4, 8, 16 or 32", who, o.cell);
   LVF_REQUIRE(o.radius > 0.0 && o.radius <= 64.0, "%s: radius %g outside (0, 64]", who, o.radius);
@@ -304,17 +277,15 @@ int ld_check_options(const char* who, const lvf_lidar_depth_options& o) {
   return LVF_OK;
 }
 
-inline unsigned ld_grid_of(int n, int per) { return (unsigned)(((long long)n + per - 1) / per); }
-
 // the query's launch on device arrays; nothing waits
-int ld_launch_query(const lvf_lidar_depth* d, const lvf_camera* cam0, const lvf_camera* cam1, int n, const float2* kps, uint8_t* status, double* depth, double* inv_depth,
+int ld_launch_query(const lvf_lidar_depth* d, const Pinhole& c0, const Pinhole& c1, int n, const float2* kps, uint8_t* status, double* depth, double* inv_depth,
                     double* p_robot, float2* right) {
   LdQueryP P;
-  P.g = d->g; P.c0 = ld_cam(cam0); P.c1 = ld_cam(cam1);
+  P.g = d->g; P.c0 = c0; P.c1 = c1;
   P.cell = (double)d->opt.cell; P.radius = d->opt.radius; P.r2 = d->opt.radius * d->opt.radius;
   P.min_depth = d->opt.min_depth; P.max_depth = d->opt.max_depth; P.max_spread = d->opt.max_spread; P.min_det = d->opt.min_det;
   P.max_extrapolation = d->opt.max_extrapolation;
-  hipLaunchKernelGGL(k_ld_query, dim3(ld_grid_of(n, kLdQueryBlock / 64)), dim3(kLdQueryBlock), 0, d->ctx->stream, n, kps, (const LdRecord*)d->rec.p, (const int*)d->start.p,
+  hipLaunchKernelGGL(k_ld_query, dim3(grid_of(n, kLdQueryBlock / 64)), dim3(kLdQueryBlock), 0, d->ctx->stream, n, kps, (const LdRecord*)d->rec.p, (const int*)d->start.p,
                      status, depth, inv_depth, p_robot, right, P);
   LVF_HIP(hipGetLastError());
   return LVF_OK;
@@ -325,18 +296,19 @@ int ld_launch_query(const lvf_lidar_depth* d, const lvf_camera* cam0, const lvf_
 int lidar_depth_check(const char* who, const lvf_lidar_depth* d, lvf_ctx* ctx, const lvf_camera* cam0, const lvf_camera* cam1) {
   LVF_REQUIRE(d, "%s: null lvf_lidar_depth", who);
   LVF_REQUIRE(!ctx || d->ctx == ctx, "%s: the projected sweep belongs to another context", who);
-  LVF_REQUIRE(ld_cam_ok(cam0) && ld_cam_ok(cam1), "%s: bad camera (null, non-finite, zero focal length or zero extrinsic quaternion)", who);
+  LVF_TRY(check_camera(who, cam0));
+  LVF_TRY(check_camera(who, cam1));
   LVF_REQUIRE(cam0->fx == d->fx && cam0->fy == d->fy && cam0->cx == d->cx && cam0->cy == d->cy, "%s: cam0's intrinsics are not the ones the sweep was projected with", who);
   return LVF_OK;
 }
 
-int lidar_depth_merge_queue(const lvf_lidar_depth* d, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n, const float2* left, float2* right,
-                            uint8_t* status, double* inv_depth, double* p_robot, uint8_t* source) {
+int lidar_depth_merge_queue(const lvf_lidar_depth* d, const Pinhole& c0, const Pinhole& c1, double baseline, int n, const float2* left, float2* right, uint8_t* status,
+                            double* inv_depth, double* p_robot, uint8_t* source) {
   DevBuf<uint8_t> l_st; DevBuf<double> l_depth, l_inv, l_pb; DevBuf<float2> l_right;
   LVF_TRY(l_st.alloc(n)); LVF_TRY(l_depth.alloc(n)); LVF_TRY(l_inv.alloc(n)); LVF_TRY(l_pb.alloc((size_t)3 * n)); LVF_TRY(l_right.alloc(n));
-  LVF_TRY(ld_launch_query(d, cam0, cam1, n, left, l_st.p, l_depth.p, l_inv.p, l_pb.p, l_right.p));
-  hipLaunchKernelGGL(k_ld_merge, dim3(ld_grid_of(n, kLdThreads)), dim3(kLdThreads), 0, d->ctx->stream, n, right, status, inv_depth, p_robot, source,
-                     (const uint8_t*)l_st.p, (const double*)l_inv.p, (const double*)l_pb.p, (const float2*)l_right.p, ld_cam(cam0), d->opt.far_factor * baseline,
+  LVF_TRY(ld_launch_query(d, c0, c1, n, left, l_st.p, l_depth.p, l_inv.p, l_pb.p, l_right.p));
+  hipLaunchKernelGGL(k_ld_merge, dim3(grid_of(n, kLdThreads)), dim3(kLdThreads), 0, d->ctx->stream, n, right, status, inv_depth, p_robot, source,
+                     (const uint8_t*)l_st.p, (const double*)l_inv.p, (const double*)l_pb.p, (const float2*)l_right.p, c0, d->opt.far_factor * baseline,
                      d->opt.far_factor == 0.0 ? 1 : 0, d->opt.replace_lost);
   LVF_HIP(hipGetLastError());
   // (the scratch goes back to the context's pool, whose reuse is ordered on the same stream)
@@ -359,7 +331,7 @@ int lvf_lidar_depth_create(lvf_ctx* ctx, const lvf_cloud* cloud, const lvf_camer
                            const lvf_lidar_depth_options* opt, lvf_lidar_depth** out) {
   LVF_REQUIRE(ctx && cloud && cam_from_lidar && out, "lvf_lidar_depth_create: null argument");
   LVF_REQUIRE(cloud->ctx == ctx, "lvf_lidar_depth_create: the cloud belongs to another context");
-  LVF_REQUIRE(ld_cam_ok(cam0), "lvf_lidar_depth_create: bad camera (null, non-finite, zero focal length or zero extrinsic quaternion)");
+  LVF_TRY(check_camera("lvf_lidar_depth_create", cam0));
   for (int i = 0; i < 12; ++i) LVF_REQUIRE(std::isfinite(cam_from_lidar[i]), "lvf_lidar_depth_create: cam_from_lidar[%d] is not finite", i);
   std::unique_ptr<lvf_lidar_depth> d(new lvf_lidar_depth());
   if (opt) d->opt = *opt; else lvf_lidar_depth_options_default(&d->opt);
@@ -386,10 +358,10 @@ int lvf_lidar_depth_create(lvf_ctx* ctx, const lvf_cloud* cloud, const lvf_camer
     LdProjP P;
     for (int i = 0; i < 12; ++i) P.M[i] = cam_from_lidar[i];
     P.fx = cam0->fx; P.fy = cam0->fy; P.cx = cam0->cx; P.cy = cam0->cy; P.min_depth = d->opt.min_depth; P.max_depth = d->opt.max_depth; P.g = g;
-    hipLaunchKernelGGL(k_ld_project, dim3(ld_grid_of(n, per)), dim3(kLdThreads), 0, s, n, (const float4*)cloud->pts.p, tmp.p, cursor.p, P);
+    hipLaunchKernelGGL(k_ld_project, dim3(grid_of(n, per)), dim3(kLdThreads), 0, s, n, (const float4*)cloud->pts.p, tmp.p, cursor.p, P);
   }
   hipLaunchKernelGGL(k_ld_scan, dim3(1), dim3(kLdScanThreads), 0, s, (int)m4, reinterpret_cast<int4*>(cursor.p), reinterpret_cast<int4*>(d->start.p));
-  if (n > 0) hipLaunchKernelGGL(k_ld_fill, dim3(ld_grid_of(n, per)), dim3(kLdThreads), 0, s, n, (const LdRecord*)tmp.p, cursor.p, d->rec.p, g);
+  if (n > 0) hipLaunchKernelGGL(k_ld_fill, dim3(grid_of(n, per)), dim3(kLdThreads), 0, s, n, (const LdRecord*)tmp.p, cursor.p, d->rec.p, g);
   LVF_HIP(hipGetLastError());
   if (n == 0) d->kept = 0;
   *out = d.release();
@@ -433,7 +405,7 @@ int lvf_lidar_depth_query(const lvf_lidar_depth* depth, const lvf_camera* cam0, 
   LVF_TRY(p.upload(reinterpret_cast<const float2*>(kps_left), n, s));
   LVF_TRY(q.alloc(n)); LVF_TRY(st.alloc(n)); LVF_TRY(dz.alloc(n)); LVF_TRY(inv.alloc(n)); LVF_TRY(pb.alloc((size_t)3 * n));
   StreamWaitGuard wait(s);                     // (an error below: the upload from the caller's array ends before the buffers go)
-  LVF_TRY(ld_launch_query(depth, cam0, cam1, n, p.p, st.p, dz.p, inv.p, pb.p, q.p));
+  LVF_TRY(ld_launch_query(depth, make_pinhole(*cam0), make_pinhole(*cam1), n, p.p, st.p, dz.p, inv.p, pb.p, q.p));
   LVF_HIP(hipMemcpyAsync(status, st.p, (size_t)n, hipMemcpyDeviceToHost, s));
   LVF_HIP(hipMemcpyAsync(depth_out, dz.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
   LVF_HIP(hipMemcpyAsync(inv_depth, inv.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));

@@ -16,6 +16,7 @@
 
 #include "../../include/lvf.h"
 #include "lvf_math.hpp"
+#include "camera_dev.hpp"
 
 namespace lvf {
 
@@ -527,6 +528,16 @@ __device__ __forceinline__ double wave_sum32(double v[32]) {
   return v[0] + quad_perm<0xB1>(v[0]);                                                                                                            // lanes [1,0,3,2]
 }
 
+__device__ __forceinline__ int refl101(int i, int n) {      // BORDER_REFLECT_101, any i
+  if (n == 1) return 0;
+  const int m = 2 * (n - 1);
+  int r = i % m;
+  if (r < 0) r += m;
+  return r >= n ? m - r : r;
+}
+// workgroups of `per` threads (or items) that cover n
+inline int grid_of(size_t n, int per = 256) { return (int)((n + per - 1) / per); }
+
 // Same-address global atomics serialise in L2 at ~65 ns each (measured), so counters are touched once per RUN of consecutive lanes
 // holding the same key (clouds arrive in scan order: a coarse cell, a segment or a voxel sees long runs): only the head lane of a
 // run issues the atomic, with the run length.  `start` = head lane of this lane's run, `len` = run
@@ -597,11 +608,10 @@ int transform_points(lvf_ctx* ctx, const float4* in, int n, const double* pose, 
 // LiDAR sweep deskew (deskew_kernels.hip): what one launch of k_deskew needs.  A rigid map as a matrix, the trajectory's knots ([n][8]: stamp, q, t)
 // on the device, the knots staged in LDS (k0 .. k0 + nk; nk = 0: every point searches the whole array) and the time window they are exact for.
 constexpr int kDeskewFastKnots = 8;
-struct DeskewRt { double R[9], t[3]; };
 struct DeskewP {
   const double* knots; int n, k0, nk;
   double t_lo, t_hi, t0;             // t0 = frame_time - cycle_time / 2: a point's time is t0 + its offset
-  DeskewRt E, A;                     // E = extrinsic, A = extrinsic^-1 frame_pose^-1
+  Rigid E, A;                        // E = extrinsic, A = extrinsic^-1 frame_pose^-1
 };
 // checks the arguments on the host (LVF_ERR_INVALID, nothing launched) and fills *P.  *active = false: a one-pose trajectory, the deskew is the
 // identity and the caller launches nothing.
@@ -613,8 +623,26 @@ int deskew_launch(hipStream_t q, int cap, const int* n_dev, const float4* in, fl
 // handle, its context (ctx may be null: not compared) and the cameras, on the host (LVF_ERR_INVALID, nothing launched).  lidar_depth_merge_queue:
 // the query of `left` and the merge into the stereo chain's device arrays (all [n]; source [n] is written) on the context's stream; no wait.
 int lidar_depth_check(const char* who, const lvf_lidar_depth* d, lvf_ctx* ctx, const lvf_camera* cam0, const lvf_camera* cam1);
-int lidar_depth_merge_queue(const lvf_lidar_depth* d, const lvf_camera* cam0, const lvf_camera* cam1, double baseline, int n, const float2* left, float2* right,
-                            uint8_t* status, double* inv_depth, double* p_robot, uint8_t* source);
+int lidar_depth_merge_queue(const lvf_lidar_depth* d, const Pinhole& c0, const Pinhole& c1, double baseline, int n, const float2* left, float2* right, uint8_t* status,
+                            double* inv_depth, double* p_robot, uint8_t* source);
+// THE checks of a pose and of a camera argument: LVF_ERR_INVALID with a text that starts with `who`, before anything is launched.
+// A pose [qx, qy, qz, qw, tx, ty, tz]: finite, the quaternion not zero and its squared norm finite; out7 (may be null) = the pose with its
+// quaternion normalised (the SE3d constructor's).
+inline int check_pose(const char* who, const char* what, const double* in, double* out7) {
+  for (int k = 0; k < 7; ++k) LVF_REQUIRE(std::isfinite(in[k]), "%s: non-finite %s", who, what);
+  const double n2 = in[0] * in[0] + in[1] * in[1] + in[2] * in[2] + in[3] * in[3];
+  LVF_REQUIRE(n2 > 0.0 && std::isfinite(n2), "%s: the quaternion of %s is zero or not normalisable", who, what);
+  if (!out7) return LVF_OK;
+  const double s = 1.0 / std::sqrt(n2);
+  for (int k = 0; k < 7; ++k) out7[k] = k < 4 ? in[k] * s : in[k];
+  return LVF_OK;
+}
+inline int check_camera(const char* who, const lvf_camera* c) {
+  LVF_REQUIRE(c, "%s: null camera", who);
+  LVF_REQUIRE(std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) && std::isfinite(c->cy), "%s: non-finite camera intrinsics", who);
+  LVF_REQUIRE(c->fx != 0.0 && c->fy != 0.0, "%s: zero focal length", who);
+  return check_pose(who, "the camera extrinsic", c->extrinsic, nullptr);
+}
 // kernels / launchers implemented in the .hip translation units
 int launch_pose_only(lvf_batch* b, const lvf_state* st, bool want_j);
 int launch_two_frame(lvf_batch* b, const lvf_state* st, bool want_j);

@@ -16,7 +16,7 @@
 #include <vector>
 
 namespace {
-using lvf::DevBuf;
+using lvf::DevBuf; using lvf::Pinhole; using lvf::Rigid; using lvf::grid_of; using lvf::refl101;
 
 constexpr int kOrbMaxLevels = 8;
 constexpr int kT = 256;
@@ -35,16 +35,6 @@ struct OrbLevels { OrbLevel l[kOrbMaxLevels]; int n; unsigned total; };
 // the cell grid of ComputeKeyPointsQuadTree (:383-388) and the quadtree's initial nodes (:165-166) of one level; ncols == 0: the level has no cell
 struct OrbGrid { int ncols, nrows, cw, ch, first, slots, slot_off, n_init, num; float hx; };
 struct OrbGrids { OrbGrid g[kOrbMaxLevels]; int n, total_cells; };
-struct OCam { double fx, fy, cx, cy, R[9], t[3]; };      // R, t: sensor -> robot (the extrinsic)
-struct OPose { double R[9], t[3]; };                     // body -> world
-
-__device__ __forceinline__ int orb_refl101(int i, int n) {      // BORDER_REFLECT_101, any i
-  if (n == 1) return 0;
-  const int m = 2 * (n - 1);
-  int r = i % m;
-  if (r < 0) r += m;
-  return r >= n ? m - r : r;
-}
 
 // level L from level L - 1: cv::resize INTER_LINEAR's fixed-point arithmetic with host tables tx = {index[dw], a1[dw]}, ty = {index[dh], b1[dh]}
 __global__ void __launch_bounds__(kT) k_orb_resize(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh,
@@ -158,9 +148,9 @@ __global__ void __launch_bounds__(kT) k_orb_blur(const uint8_t* __restrict__ src
   const int xc = min(x, w - 1);
   int xs[7];
 #pragma unroll
-  for (int k = 0; k < 7; ++k) xs[k] = orb_refl101(xc + k - 3, w);
+  for (int k = 0; k < 7; ++k) xs[k] = refl101(xc + k - 3, w);
   for (int r = t >> 6; r < kBlurH + 6; r += kT / 64) {
-    const uint8_t* row = src + (size_t)orb_refl101(y0 + r - 3, h) * w;
+    const uint8_t* row = src + (size_t)refl101(y0 + r - 3, h) * w;
     int s = 0;
 #pragma unroll
     for (int k = 0; k < 7; ++k) s += wt[k] * (int)row[xs[k]];
@@ -207,17 +197,17 @@ __global__ void __launch_bounds__(kT) k_orb_brief(int n, const int* __restrict__
 // (distance, level, index): the two smallest keys of the wave are the Hamming 2-NN with the declared tie rule.
 __global__ void __launch_bounds__(kT) k_orb_search(int n_last, const float2* __restrict__ lpt, const int* __restrict__ loct, const float* __restrict__ lang,
                                                    const unsigned long long* __restrict__ ldesc, int n_cur, const double* __restrict__ pw, const int* __restrict__ coct,
-                                                   const float* __restrict__ cang, const unsigned long long* __restrict__ cdesc, const uint8_t* __restrict__ skip, OCam c0,
-                                                   OPose T, const double* __restrict__ radius, int* __restrict__ match, int* __restrict__ best, int* __restrict__ second) {
+                                                   const float* __restrict__ cang, const unsigned long long* __restrict__ cdesc, const uint8_t* __restrict__ skip, Pinhole c0,
+                                                   Rigid T, const double* __restrict__ radius, int* __restrict__ match, int* __restrict__ best, int* __restrict__ second) {
   const int f = blockIdx.x * (kT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (f >= n_cur) return;
   if (skip && skip[f]) return;                                   // (the outputs were preset to -1)
-  const double d[3] = {pw[3 * f] - T.t[0], pw[3 * f + 1] - T.t[1], pw[3 * f + 2] - T.t[2]};
-  const double pb[3] = {T.R[0] * d[0] + T.R[3] * d[1] + T.R[6] * d[2], T.R[1] * d[0] + T.R[4] * d[1] + T.R[7] * d[2], T.R[2] * d[0] + T.R[5] * d[1] + T.R[8] * d[2]};
-  const double e[3] = {pb[0] - c0.t[0], pb[1] - c0.t[1], pb[2] - c0.t[2]};
-  const double pc[3] = {c0.R[0] * e[0] + c0.R[3] * e[1] + c0.R[6] * e[2], c0.R[1] * e[0] + c0.R[4] * e[1] + c0.R[7] * e[2], c0.R[2] * e[0] + c0.R[5] * e[1] + c0.R[8] * e[2]};
+  double pb[3], pc[3];
+  world2robot(T, pw + 3 * f, pb);                                // T: the last keyframe's pose, body -> world
+  robot2sensor(c0, pb, pc);
   if (pc[2] < 0) return;                                         // local_map.cpp:316
-  const float px = (float)(c0.fx * pc[0] / pc[2] + c0.cx), py = (float)(c0.fy * pc[1] / pc[2] + c0.cy);
+  const float2 pix = sensor2pixel(c0, pc);
+  const float px = pix.x, py = pix.y;
   const int o = coct[f];
   const float ca = cang[f];
   const double r0 = radius[o], r1 = radius[min(o + 1, kOrbMaxLevels - 1)];
@@ -507,16 +497,6 @@ __global__ void __launch_bounds__(kT) k_orb_fill(int* __restrict__ p, int n, int
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------------
-inline int grid_of(size_t n) { return (int)((n + kT - 1) / kT); }
-
-void orb_rot_of(const double* q, double R[9]) {      // (of q / |q|, as Sophus holds it)
-  const double inv = 1.0 / std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const double x = q[0] * inv, y = q[1] * inv, z = q[2] * inv, w = q[3] * inv;
-  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
-  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
-}
-
 int check_options(const char* who, const lvf_orb_options* o) {
   LVF_REQUIRE(o->patch_size == 31 && o->edge_threshold == 31, "%s: patch_size and edge_threshold must be 31 (got %d, %d)", who, o->patch_size, o->edge_threshold);
   LVF_REQUIRE(o->num_levels >= 1 && o->num_levels <= kOrbMaxLevels, "%s: num_levels must be in [1, %d]", who, kOrbMaxLevels);
@@ -903,11 +883,9 @@ int lvf_orb_search(lvf_ctx* ctx, const lvf_orb_options* opt, const lvf_camera* c
   if (opt) o = *opt; else lvf_orb_options_default(&o);
   LVF_TRY(check_options("lvf_orb_search", &o));
   if (n_cur == 0) return LVF_OK;
-  LVF_REQUIRE(cam0 && cam0->fx != 0.0 && cam0->fy != 0.0 && last_pose, "lvf_orb_search: bad camera or pose");
-  const double* q = cam0->extrinsic;
-  LVF_REQUIRE(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] > 0.0 &&
-                  last_pose[0] * last_pose[0] + last_pose[1] * last_pose[1] + last_pose[2] * last_pose[2] + last_pose[3] * last_pose[3] > 0.0,
-              "lvf_orb_search: zero quaternion");
+  LVF_TRY(lvf::check_camera("lvf_orb_search", cam0));
+  LVF_REQUIRE(last_pose, "lvf_orb_search: null pose");
+  LVF_TRY(lvf::check_pose("lvf_orb_search", "the last keyframe's pose", last_pose, nullptr));
   LVF_REQUIRE(cur_pw && cur_octave && cur_angle && cur_desc && match, "lvf_orb_search: null current-feature arrays");
   LVF_REQUIRE(n_last == 0 || (last_pt && last_octave && last_angle && last_desc), "lvf_orb_search: null last-feature arrays");
   for (int i = 0; i < n_cur; ++i) LVF_REQUIRE(cur_octave[i] >= 0 && cur_octave[i] < o.num_levels, "lvf_orb_search: current feature %d has octave %d", i, cur_octave[i]);
@@ -918,11 +896,8 @@ int lvf_orb_search(lvf_ctx* ctx, const lvf_orb_options* opt, const lvf_camera* c
     return LVF_OK;
   }
   hipStream_t s = ctx->stream;
-  OCam c0; OPose T;
-  c0.fx = cam0->fx; c0.fy = cam0->fy; c0.cx = cam0->cx; c0.cy = cam0->cy;
-  orb_rot_of(cam0->extrinsic, c0.R);
-  orb_rot_of(last_pose, T.R);
-  for (int i = 0; i < 3; ++i) { c0.t[i] = cam0->extrinsic[4 + i]; T.t[i] = last_pose[4 + i]; }
+  const Pinhole c0 = lvf::make_pinhole(*cam0);
+  const Rigid T = lvf::make_rigid(last_pose);
   double radius[kOrbMaxLevels], sf = 1.0;                        // local_map.h:26-31: double products of the float factor
   for (int L = 0; L < kOrbMaxLevels; ++L) { radius[L] = 31.0 * sf; sf *= (double)o.scale_factor; }
   DevBuf<float2> lp; DevBuf<int> lo, co, out; DevBuf<float> la, ca; DevBuf<unsigned long long> ld, cd; DevBuf<double> pw, rad; DevBuf<uint8_t> sk;

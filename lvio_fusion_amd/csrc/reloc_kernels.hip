@@ -478,16 +478,6 @@ int check_pnp_options(const char* who, const lvf_pnp_options* o) {
   LVF_REQUIRE(std::isfinite(o->huber_a) && o->huber_a >= 0.0, "%s: bad huber_a", who);
   return LVF_OK;
 }
-bool pose_ok(const double* p) {
-  for (int k = 0; k < 7; ++k)
-    if (!std::isfinite(p[k])) return false;
-  return p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3] > 0.0;
-}
-int check_camera(const char* who, const lvf_camera* c) {
-  LVF_REQUIRE(c && std::isfinite(c->fx) && std::isfinite(c->fy) && c->fx != 0.0 && c->fy != 0.0 && std::isfinite(c->cx) && std::isfinite(c->cy) && pose_ok(c->extrinsic),
-              "%s: bad camera", who);
-  return LVF_OK;
-}
 
 // the match, the gate and the compaction, queued on the context's stream: match / best / second / flag are device arrays [nq], list [nq],
 // pos [nq + 1] (pos[nq] = the number of pairs)
@@ -606,7 +596,7 @@ int lvf_pnp_ransac(lvf_ctx* ctx, const lvf_camera* cam0, int n, const double* pw
   LVF_TRY(check_pnp_options("lvf_pnp_ransac", &o));
   LVF_TRY(check_camera("lvf_pnp_ransac", cam0));
   LVF_REQUIRE(n == 0 || (pw && pt), "lvf_pnp_ransac: null correspondence arrays");
-  LVF_REQUIRE(!init_pose7 || pose_ok(init_pose7), "lvf_pnp_ransac: bad initial pose");
+  if (init_pose7) LVF_TRY(lvf::check_pose("lvf_pnp_ransac", "the initial pose", init_pose7, nullptr));
   LVF_REQUIRE(pose7 || n < o.min_matches, "lvf_pnp_ransac: null pose7");
   *score = 0;
   if (summary) std::memset(summary, 0, sizeof(*summary));
@@ -652,7 +642,8 @@ int lvf_relocate_by_image(lvf_ctx* ctx, const lvf_camera* cam0, const double* ol
   LVF_TRY(check_match_options("lvf_relocate_by_image", &mo));
   LVF_TRY(check_pnp_options("lvf_relocate_by_image", &po));
   LVF_TRY(check_camera("lvf_relocate_by_image", cam0));
-  LVF_REQUIRE(pose_ok(old_pose7) && pose_ok(relative_o_c7), "lvf_relocate_by_image: bad pose");
+  LVF_TRY(lvf::check_pose("lvf_relocate_by_image", "the old pose", old_pose7, nullptr));
+  LVF_TRY(lvf::check_pose("lvf_relocate_by_image", "the relative pose", relative_o_c7, nullptr));
   LVF_REQUIRE((n_old == 0 || (old_pw && old_desc)) && (n_cur == 0 || (cur_pt && cur_desc)), "lvf_relocate_by_image: null feature arrays");
   *score = 0;
   if (summary) std::memset(summary, 0, sizeof(*summary));

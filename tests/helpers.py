@@ -21,3 +21,26 @@ def assert_parity(gpu, ref, what=""):
 
 def ocam(oracle, c):
     return oracle.Camera.make(c["fx"], c["fy"], c["cx"], c["cy"], c["extrinsic"])
+
+
+def bad_cameras(cam):
+    """camera dicts the library must refuse: a NaN and an Inf in fx, cx, an extrinsic quaternion component and an extrinsic translation component; then the zero quaternion"""
+    for v in (np.nan, np.inf):
+        yield f"fx = {v}", dict(cam, fx=v)
+        yield f"cx = {v}", dict(cam, cx=v)
+        for k in (1, 5):
+            e = np.array(cam["extrinsic"], np.float64)
+            e[k] = v
+            yield f"extrinsic[{k}] = {v}", dict(cam, extrinsic=e)
+    yield "zero quaternion", dict(cam, extrinsic=np.concatenate([np.zeros(4), cam["extrinsic"][4:]]))
+
+
+def bad_poses(pose):
+    """the same for a pose [qx, qy, qz, qw, tx, ty, tz]"""
+    pose = np.asarray(pose, np.float64)
+    for v in (np.nan, np.inf):
+        for k in (2, 6):
+            p = np.array(pose, np.float64)
+            p[k] = v
+            yield f"pose[{k}] = {v}", p
+    yield "zero quaternion", np.concatenate([np.zeros(4), pose[4:]])

@@ -10,13 +10,14 @@ Rules (the same for optical_flow, stereo_triangulate and track_last_frame):
     within 1 % of min_eig, the final point within 0.02 px of an image edge, a window-bounds test that flips under a 0.02 px shift, or the
     float32 and float64 restatements disagreeing.  Marginal points are at most 5 % of a case, asserted BEFORE the device is looked at."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 from tests import klt_cases as kc
 from tests import klt_ref as kr
-from tests.helpers import assert_parity
+from tests.helpers import assert_parity, bad_cameras, bad_poses
 
 pytestmark = pytest.mark.gpu
 
@@ -208,6 +209,122 @@ def test_stereo_triangulate_parity(ctx, seed, lo):
     for x, y in zip((right, st, inv, pb), again):
         assert np.array_equal(x.view(np.uint8), y.view(np.uint8))
     il.close(); ir.close()
+
+
+# Feature counts around the launch shapes: one wave per feature and four features per workgroup in k_klt_flow (1: one wave of a workgroup, 5: a second
+# workgroup with one wave), 256 threads per workgroup in k_klt_stereo_predict / k_klt_dlt / k_klt_track_predict / k_klt_track_classify (257: one
+# thread into the second workgroup, and the second trip of the classify loop).  Features are independent, so the first n of a case are a case.
+COUNTS = [1, 5, 257]
+
+
+@functools.lru_cache(maxsize=None)
+def stereo_small():
+    """klt_cases.stereo_case(21) with its pyramids of the restatement, built once and shared (never modified)"""
+    c = kc.stereo_case(21)
+    return c, kr.Pyramid(c["left"]), kr.Pyramid(c["right"])
+
+
+@functools.lru_cache(maxsize=None)
+def track_small():
+    c = kc.track_case(31)
+    return c, kr.Pyramid(c["A"]), kr.Pyramid(c["B"])
+
+
+@pytest.mark.parametrize("n", COUNTS)
+def test_stereo_triangulate_feature_counts(ctx, n):
+    """test_stereo_triangulate_parity's rules on the first n features"""
+    from lvio_fusion_amd import api
+    c, L, R = stereo_small()
+    kps = c["kps"][:n]
+    il, ir = images(ctx, c["left"], c["right"])
+    right, st, inv, pb = api.stereo_triangulate(il, ir, c["cam0"], c["cam1"], c["baseline"], kps)
+    assert right.shape == (n, 2) and st.shape == (n,) and inv.shape == (n,) and pb.shape == (n, 3)
+    pred = kr.stereo_predict(c["cam0"], c["cam1"], c["baseline"], kps)
+    compare_flow(f"stereo, first {n}", L, R, kps, pred, right, st)
+    pb_ref, z0, inv_ref = kr.stereo_depth(c["cam0"], c["cam1"], kps, right)        # from the DEVICE's own right pixels, as above
+    t = st > 0
+    assert t.any() and np.abs(z0[t]).min() > 1e-6
+    assert np.array_equal(st[t], np.where(z0[t] > 0, 1, 2)), "depth-sign gate"
+    assert_parity(pb[t], pb_ref[t], "p_robot")
+    assert_parity(inv[t], inv_ref[t], "inv_depth")
+    assert not inv[~t].any() and not pb[~t].any()
+    again = api.stereo_triangulate(il, ir, c["cam0"], c["cam1"], c["baseline"], kps)
+    for x, y in zip((right, st, inv, pb), again):
+        assert x.tobytes() == y.tobytes()
+    il.close(); ir.close()
+
+
+@pytest.mark.parametrize("n", COUNTS)
+def test_track_last_frame_feature_counts(ctx, n):
+    """test_track_last_frame_parity's rules on the first n features (the case with a pose and world points is klt_cases.track_case)"""
+    from lvio_fusion_amd import api
+    c, A, B = track_small()
+    b, pw, prev = c["baseline"], c["pw"][:n], c["prev"][:n]
+    ia, ib = images(ctx, c["A"], c["B"])
+    cur, cls, good, pred = api.track_last_frame(ia, ib, c["cam0"], b, c["pose"], pw, prev)
+    assert cur.shape == (n, 2) and cls.shape == (n,) and pred.shape == (n, 2)
+    assert np.abs(pred.astype(np.float64) - kr.track_predict(c["cam0"], c["pose"], pw)).max() <= 1e-4
+    keep, n64, s64 = compare_flow(f"track, first {n}", A, B, prev, pred, cur, cls)
+    cls_ref, _, norm, z = kr.classify(c["cam0"], b, c["pose"], pw, pred, n64, s64)
+    keep &= ~(np.abs(norm - 30) < 0.05) & ~(np.abs(z - 50 * b) <= 1e-9 * 50 * b)
+    assert np.array_equal(cls[keep], cls_ref[keep])
+    # the count: the restatement's on the device's own tracks, at the default threshold of 20 and with none
+    _, good_own, _, _ = kr.classify(c["cam0"], b, c["pose"], pw, pred, cur, cls > 0)
+    _, count_own, _, _ = kr.classify(c["cam0"], b, c["pose"], pw, pred, cur, cls > 0, num_features_tracking_bad=0)
+    assert good == good_own and count_own >= 1 and (good_own > 0) == (n > 20)
+    again = api.track_last_frame(ia, ib, c["cam0"], b, c["pose"], pw, prev, num_features_tracking_bad=0)
+    assert again[2] == count_own
+    for x, y in zip((cur, cls, pred), (again[0], again[1], again[3])):
+        assert x.tobytes() == y.tobytes()
+    ia.close(); ib.close()
+
+
+# ---- refusals --------------------------------------------------------------------------------------------------------------------------------
+def test_non_finite_cameras_and_poses_are_refused(ctx):
+    """lvf_stereo_triangulate and lvf_track_last_frame: LVF_ERR_INVALID with the entry point's name, nothing written, and the same call works after"""
+    from lvio_fusion_amd import api
+    INVALID = 1
+    L = ctx.L
+    fp, u8, dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)), lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8)), lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    n = 5
+    c, _, _ = stereo_small()
+    il, ir = images(ctx, c["left"], c["right"])
+    kps = np.ascontiguousarray(c["kps"][:n])
+    outs = [np.full((n, 2), 7, np.float32), np.full(n, 7, np.uint8), np.full(n, 7.0), np.full((n, 3), 7.0)]
+
+    def stereo(cam0, cam1):
+        a, b = api.make_camera(cam0), api.make_camera(cam1)
+        return L.lvf_stereo_triangulate(il.h, ir.h, C.byref(a), C.byref(b), C.c_double(c["baseline"]), n, fp(kps), fp(outs[0]), u8(outs[1]), dp(outs[2]), dp(outs[3]), None)
+
+    for what, cams in [(w, (bad, c["cam1"])) for w, bad in bad_cameras(c["cam0"])] + [(w, (c["cam0"], bad)) for w, bad in bad_cameras(c["cam1"])]:
+        assert stereo(*cams) == INVALID, what
+        assert L.lvf_last_error().startswith(b"lvf_stereo_triangulate:"), (what, L.lvf_last_error())
+    assert all((o == 7).all() for o in outs), "a refused call wrote its outputs"
+    assert stereo(c["cam0"], c["cam1"]) == 0
+    want = api.stereo_triangulate(il, ir, c["cam0"], c["cam1"], c["baseline"], kps)
+    for o, w in zip(outs, want):
+        assert o.tobytes() == w.tobytes()
+    il.close(); ir.close()
+
+    t, _, _ = track_small()
+    ia, ib = images(ctx, t["A"], t["B"])
+    prev, pw = np.ascontiguousarray(t["prev"][:n]), np.ascontiguousarray(t["pw"][:n])
+    touts = [np.full((n, 2), 7, np.float32), np.full((n, 2), 7, np.float32), np.full(n, 7, np.uint8)]
+    good = C.c_int32(7)
+
+    def track(cam0, pose):
+        a, p = api.make_camera(cam0), np.ascontiguousarray(pose, np.float64)
+        return L.lvf_track_last_frame(ia.h, ib.h, C.byref(a), C.c_double(t["baseline"]), dp(p), n, dp(pw), fp(prev), 1, 0, fp(touts[0]), fp(touts[1]), u8(touts[2]),
+                                      C.byref(good), None)
+
+    for what, cam0, pose in [(w, bad, t["pose"]) for w, bad in bad_cameras(t["cam0"])] + [(w, t["cam0"], bad) for w, bad in bad_poses(t["pose"])]:
+        assert track(cam0, pose) == INVALID, what
+        assert L.lvf_last_error().startswith(b"lvf_track_last_frame:"), (what, L.lvf_last_error())
+    assert all((o == 7).all() for o in touts) and good.value == 7, "a refused call wrote its outputs"
+    assert track(t["cam0"], t["pose"]) == 0
+    cur, cls, g, pred = api.track_last_frame(ia, ib, t["cam0"], t["baseline"], t["pose"], pw, prev, num_features_tracking_bad=0)
+    assert touts[0].tobytes() == cur.tobytes() and touts[1].tobytes() == pred.tobytes() and touts[2].tobytes() == cls.tobytes() and good.value == g
+    ia.close(); ib.close()
 
 
 # ---- track_last_frame --------------------------------------------------------------------------------------------------------------------------

@@ -6,10 +6,13 @@ The conditions the equalities rest on (no gate comparison within 1e-9 of its thr
 CPU in tests/test_lidar_depth_ref.py on the same inputs: every generated cloud and feature set here comes from the generators of
 tests/lidar_depth_cases.py, and lc.projection_cases() / lc.query_cases() list them all for that test.  The one gate the CPU cannot see, the
 merge's far test on the device's own stereo depths, has its margin asserted in the fused test."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 from tests import lidar_depth_cases as lc, lidar_depth_ref as lr
+from tests.helpers import bad_cameras
 
 pytestmark = pytest.mark.gpu
 
@@ -203,6 +206,74 @@ def test_fused_without_replacement_is_stereo_triangulate(ctx, fused):
     assert np.array_equal(src, (stereo[1] == 1).astype(np.uint8))
     empty = api.stereo_triangulate_lidar(il, ir, f["cam0"], f["cam1"], f["baseline"], np.zeros((0, 2), np.float32), d)
     assert all(len(a) == 0 for a in empty)
+    d.close()
+
+
+# Feature counts around the launch shapes of the chain: four features per workgroup in k_klt_flow and k_ld_query (1, 5), 256 threads per
+# workgroup in k_klt_stereo_predict, k_klt_dlt and k_ld_merge (257).  Features are independent: the first n of the case are a case.
+@pytest.mark.parametrize("n", [1, 5, 257])
+def test_fused_feature_counts(ctx, fused, n):
+    from lvio_fusion_amd import api
+    f, il, ir, cloud, stereo_all = fused
+    kps = f["kps"][:n]
+    stereo = api.stereo_triangulate(il, ir, f["cam0"], f["cam1"], f["baseline"], kps)
+    for g, s in zip(stereo, stereo_all):
+        assert g.tobytes() == s[:n].tobytes()
+    # no replacement: lvf_stereo_triangulate byte for byte
+    d = api.LidarDepth(ctx, cloud, f["cam0"], f["M"], f["width"], f["height"], api.lidar_depth_options(far_factor=1e12, replace_lost=0))
+    right, st, inv, pb, src = api.stereo_triangulate_lidar(il, ir, f["cam0"], f["cam1"], f["baseline"], kps, d)
+    for g, s in zip((right, st, inv, pb), stereo):
+        assert g.tobytes() == s.tobytes()
+    assert np.array_equal(src, (stereo[1] == 1).astype(np.uint8))
+    d.close()
+    # the default options: the merge of its parts
+    o = lr.options()
+    z0, far_depth = lr.robot2sensor(f["cam0"], stereo[3])[stereo[1] == 1, 2], o["far_factor"] * f["baseline"]
+    assert len(z0) == 0 or np.abs(z0 - far_depth).min() > 1e-9 * far_depth
+    d = api.LidarDepth(ctx, cloud, f["cam0"], f["M"], f["width"], f["height"])
+    lidar = d.query(f["cam1"], kps)
+    got = api.stereo_triangulate_lidar(il, ir, f["cam0"], f["cam1"], f["baseline"], kps, d)
+    want = lr.merge(stereo, lidar, f["cam0"], f["baseline"], o)
+    for name, g, w in zip(("kps_right", "status", "inv_depth", "p_robot", "source"), got, want):
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), (n, name)
+    d.close()
+
+
+def test_non_finite_cameras_are_refused(ctx, fused):
+    """lvf_stereo_triangulate_lidar and lvf_lidar_depth_query: LVF_ERR_INVALID with the entry point's name, nothing written, and the same call works after"""
+    from lvio_fusion_amd import api
+    INVALID = 1
+    f, il, ir, cloud, _ = fused
+    L = ctx.L
+    fp, u8, dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)), lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8)), lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    n = 5
+    kps = np.ascontiguousarray(f["kps"][:n], np.float32)
+    d = api.LidarDepth(ctx, cloud, f["cam0"], f["M"], f["width"], f["height"])
+    cams = [(w, (bad, f["cam1"])) for w, bad in bad_cameras(f["cam0"])] + [(w, (f["cam0"], bad)) for w, bad in bad_cameras(f["cam1"])]
+
+    fo = [np.full((n, 2), 7, np.float32), np.full(n, 7, np.uint8), np.full(n, 7.0), np.full((n, 3), 7.0), np.full(n, 7, np.uint8)]
+
+    def fused_call(cam0, cam1):
+        a, b = api.make_camera(cam0), api.make_camera(cam1)
+        return L.lvf_stereo_triangulate_lidar(il.h, ir.h, C.byref(a), C.byref(b), C.c_double(f["baseline"]), n, fp(kps), fp(fo[0]), u8(fo[1]), dp(fo[2]), dp(fo[3]), None, d.h,
+                                              u8(fo[4]))
+
+    qo = [np.full(n, 7, np.uint8), np.full(n, 7.0), np.full(n, 7.0), np.full((n, 3), 7.0), np.full((n, 2), 7, np.float32)]
+
+    def query_call(cam0, cam1):
+        a, b = api.make_camera(cam0), api.make_camera(cam1)
+        return L.lvf_lidar_depth_query(d.h, C.byref(a), C.byref(b), n, fp(kps), u8(qo[0]), dp(qo[1]), dp(qo[2]), dp(qo[3]), fp(qo[4]))
+
+    for call, name, outs in ((fused_call, b"lvf_stereo_triangulate_lidar:", fo), (query_call, b"lvf_lidar_depth_query:", qo)):
+        for what, pair in cams:
+            assert call(*pair) == INVALID, (name, what)
+            assert L.lvf_last_error().startswith(name), (what, L.lvf_last_error())
+        assert all((o == 7).all() for o in outs), "a refused call wrote its outputs"
+        assert call(f["cam0"], f["cam1"]) == 0
+    for o, w in zip(fo, api.stereo_triangulate_lidar(il, ir, f["cam0"], f["cam1"], f["baseline"], kps, d)):
+        assert o.tobytes() == w.tobytes()
+    for o, w in zip(qo, d.query(f["cam1"], kps)):
+        assert o.tobytes() == w.tobytes()
     d.close()
 
 

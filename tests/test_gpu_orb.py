@@ -10,6 +10,7 @@ Rules:
   * search: match / best / second equal on every feature that is not marginal in the restatement (a candidate's |angle difference - 15| or
     |distance - radius| below 1e-3, or |pc.z| < 1e-9); marginal features are at most 2 % of a case, asserted before the device is looked at;
   * two runs are bit-identical."""
+import ctypes as C
 import functools
 
 import numpy as np
@@ -19,6 +20,8 @@ from tests import klt_cases as kc
 from tests import klt_ref as kr
 from tests import orb_cases as oc
 from tests import orb_ref as R
+from tests import reloc_cases as rc
+from tests.helpers import bad_cameras, bad_poses
 
 pytestmark = pytest.mark.gpu
 
@@ -224,6 +227,82 @@ def test_search_parity(ctx):
     pw[::2] = 2 * centre - pw[::2]
     mb, bb, _, _ = run_search(ctx, c, pw=pw)
     assert (mb[::2] == -1).all() and (bb[::2] == -1).all() and np.array_equal(mb[1::2], m[1::2])
+
+
+@functools.lru_cache(maxsize=None)
+def small_search(n_cur, n_last):
+    """n_cur current features of search_case() that the whole case matches, and the n_last last features nearest to their matches (the matches
+    themselves and what competes with them), in index order; with the restatement's result (computed once and shared, never modified)"""
+    c = search_case()
+    A, B = c["A"], c["B"]
+    m_full = R.search(c["opt"], c["cam0"], c["last_pose"], A["pt"], A["octave"], A["angle"], A["desc"], c["pw"], B["octave"], B["angle"], B["desc"])[0]
+    cur = np.nonzero(m_full >= 0)[0][:n_cur]
+    centre = A["pt"][m_full[cur]].astype(np.float64)
+    dist = np.sqrt(((A["pt"].astype(np.float64)[:, None, :] - centre[None]) ** 2).sum(-1)).min(axis=1)
+    last = np.sort(np.argsort(dist, kind="stable")[:n_last])
+    args = (c["cam0"], c["last_pose"], A["pt"][last], A["octave"][last], A["angle"][last], A["desc"][last], c["pw"][cur], B["octave"][cur], B["angle"][cur], B["desc"][cur])
+    return args, R.search(c["opt"], *args)
+
+
+# one wave per current feature, four per workgroup: 1 = a single wave, 5 = a second workgroup with one wave, 4 = exactly one workgroup;
+# the lanes stride the last features by 64: 1, 64 (every lane exactly once) and 65 (lane 0 a second time)
+@pytest.mark.parametrize("n_cur,n_last", [(1, 1), (5, 65), (4, 64)])
+def test_search_small_shapes(ctx, n_cur, n_last):
+    from lvio_fusion_amd import api
+    args, (m, b, s, marg) = small_search(n_cur, n_last)
+    assert len(m) == n_cur and len(args[2]) == n_last and not marg.any()                                         # before the device is looked at
+    assert (b >= 0).all(), "a feature without a candidate tests nothing"
+    assert n_last == 1 or ((m >= 0).sum() >= n_cur - 1 and (s >= 0).sum() >= n_cur - 1), "the shape must exercise the second distance and the ratio gate"
+    dm, db, ds = api.orb_search(ctx, *args)
+    for name, g, w in (("match", dm, m), ("best", db, b), ("second", ds, s)):
+        assert g.dtype == np.int32 and np.array_equal(g, w), (name, g, w)
+    again = api.orb_search(ctx, *args)
+    assert all(np.array_equal(x, y) for x, y in zip((dm, db, ds), again)), "two runs differ"
+
+
+def test_non_finite_cameras_and_poses_are_refused(ctx):
+    """lvf_orb_search and lvf_pnp_ransac: LVF_ERR_INVALID with the entry point's name, nothing written, and the same call works after"""
+    from lvio_fusion_amd import api
+    INVALID = 1
+    L = ctx.L
+    fp, u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)), lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
+    dp, ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)), lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    args, (m, b, s, _) = small_search(5, 65)
+    cam, pose, lpt, loct, lang, ldesc, pw, coct, cang, cdesc = args
+    lpt, lang, cang, pw = (np.ascontiguousarray(lpt, np.float32), np.ascontiguousarray(lang, np.float32), np.ascontiguousarray(cang, np.float32),
+                           np.ascontiguousarray(pw, np.float64))
+    loct, coct, ldesc, cdesc = np.ascontiguousarray(loct, np.int32), np.ascontiguousarray(coct, np.int32), np.ascontiguousarray(ldesc), np.ascontiguousarray(cdesc)
+    outs = [np.full(len(pw), 7, np.int32) for _ in range(3)]
+
+    def search(cam0, last_pose):
+        a, p = api.make_camera(cam0), np.ascontiguousarray(last_pose, np.float64)
+        return L.lvf_orb_search(ctx.h, None, C.byref(a), dp(p), len(lpt), fp(lpt), ip(loct), fp(lang), u8(ldesc), len(pw), dp(pw), ip(coct), fp(cang), u8(cdesc), None,
+                                ip(outs[0]), ip(outs[1]), ip(outs[2]))
+
+    for what, cam0, p in [(w, bad, pose) for w, bad in bad_cameras(cam)] + [(w, cam, bad) for w, bad in bad_poses(pose)]:
+        assert search(cam0, p) == INVALID, what
+        assert L.lvf_last_error().startswith(b"lvf_orb_search:"), (what, L.lvf_last_error())
+    assert all((o == 7).all() for o in outs), "a refused call wrote its outputs"
+    assert search(cam, pose) == 0
+    assert np.array_equal(outs[0], m) and np.array_equal(outs[1], b) and np.array_equal(outs[2], s)
+
+    # lvf_pnp_ransac (strict before this): a scene of tests/reloc_cases.py with its pose as the initial one
+    sc = rc.named_scene("n71_w40")
+    n = len(sc["pw"])
+    pw3, pt, opt = np.ascontiguousarray(sc["pw"], np.float64), np.ascontiguousarray(sc["pt"], np.float32), api.pnp_options(**sc["opt"])
+    out_pose, score, inl = np.full(7, 7.0), C.c_int32(7), np.full(n, 7, np.uint8)
+
+    def pnp(cam0, init):
+        a, i = api.make_camera(cam0), np.ascontiguousarray(init, np.float64)
+        return L.lvf_pnp_ransac(ctx.h, C.byref(a), n, dp(pw3), fp(pt), dp(i), C.byref(opt), dp(out_pose), C.byref(score), u8(inl), None)
+
+    for what, cam0, init in [(w, bad, sc["pose"]) for w, bad in bad_cameras(sc["cam0"])] + [(w, sc["cam0"], bad) for w, bad in bad_poses(sc["pose"])]:
+        assert pnp(cam0, init) == INVALID, what
+        assert L.lvf_last_error().startswith(b"lvf_pnp_ransac:"), (what, L.lvf_last_error())
+    assert (out_pose == 7).all() and score.value == 7 and (inl == 7).all(), "a refused call wrote its outputs"
+    assert pnp(sc["cam0"], sc["pose"]) == 0
+    want = api.pnp_ransac(ctx, sc["cam0"], sc["pw"], sc["pt"], sc["pose"], opt)
+    assert score.value == want["score"] > 0 and inl.tobytes() == want["inlier"].tobytes() and out_pose.tobytes() == want["pose"].tobytes()
 
 
 def test_detect_to_window_chain(ctx):
