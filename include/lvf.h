@@ -1154,6 +1154,64 @@ int lvf_problem_marginal(lvf_problem* p, const lvf_solver_options* o, const int*
 /* The same for the persistent window, by keyframe id: the window's problem is refreshed as lvf_window_solve refreshes it, without iterating. */
 int lvf_window_marginal(lvf_window* w, const lvf_solver_options* o, const int64_t* kf_ids, int n_sel, double* info, double* cov, lvf_marginal_stats* stats);
 
+/* ---- Dense keyframe prior: what marginalising other unknowns leaves on a few keyframes, fed back as a factor.
+ * On n_sel distinct keyframes (1 .. 8), m = 15 n_sel unknowns, per keyframe [rotation 3, translation 3, v 3, ba 3, bg 3] (the order of
+ * lvf_problem_marginal's outputs):
+ *     cost(x) = c0 + eta^T e + 1/2 e^T info e,        e = x [-] x0
+ * x0 [n_sel][16] = {pose 7, v 3, ba 3, bg 3} per keyframe, info [m][m] row-major of which only the lower triangle is read, eta [m] (NULL:
+ * zero).  e is the local coordinate of x at x0 in the solver's parameterisation: with u = q/|q|, u0 = q0/|q0|, d = u (x) u0^-1 (negated if
+ * d.w < 0), the rotation part is atan2(|d.v|, d.w) d.v/|d.v| (so that Plus(q0, e_rot) = q); the other twelve entries are plain differences.
+ * No loss function and no first-estimate Jacobians: e is re-evaluated at every state.  With T the tangent Jacobian of e (the identity at
+ * x = x0, so an info that lvf_problem_marginal / _marginal_prior computed at x0 needs no conversion) the gradient is T^T (info e + eta) and
+ * the Gauss-Newton matrix T^T info T; a constant block gets zero columns.  A zero row / column of info (an absent unknown) is legal and info
+ * may be singular; the caller vouches that [info eta; eta^T 2 c0] is positive semi-definite.  Declared semantics: tests/dense_prior_ref.py.
+ * LVF_ERR_INVALID before anything reaches the device: n_sel outside 1 .. 8, a negative index, a keyframe listed twice, a non-finite entry of
+ * x0, eta, c0 or the lower triangle of info, a zero quaternion in x0.  kf_idx are keyframe POSITIONS in the state / problem. */
+typedef struct lvf_dense_prior lvf_dense_prior;
+int lvf_dense_prior_create(lvf_ctx* ctx, int n_sel, const int32_t* kf_idx, const double* x0, const double* info, const double* eta, double c0,
+                           lvf_dense_prior** out);
+int lvf_dense_prior_destroy(lvf_dense_prior* prior);
+/* keyframes of the prior; what it was created with (any pointer may be NULL) */
+int lvf_dense_prior_size(const lvf_dense_prior* prior);
+int lvf_dense_prior_download(lvf_dense_prior* prior, int32_t* kf_idx, double* x0, double* info, double* eta, double* c0);
+/* Materialised parity mode: cost, gradient [m] and Gauss-Newton matrix [m][m] (row-major, exactly symmetric) at the state, in the prior's own
+ * order.  const_bits (NULL: nothing constant): one byte per keyframe of the state, bit 0 = pose constant, bits 1 .. 3 = v, ba, bg constant.
+ * Any output may be NULL. */
+int lvf_dense_prior_evaluate(lvf_dense_prior* prior, const lvf_state* st, const uint8_t* const_bits, double* cost, double* gradient, double* matrix);
+/* Adds (or with NULL removes) a dense prior on keyframes of the problem (the prior is borrowed).  Every entry that linearises or evaluates
+ * the problem sees it: cost, gradient, lm_iteration, solve, download_reduced, marginal, marginal_prior.  A problem with such a prior runs the
+ * chain a problem with pose priors runs (no fused candidate pass, no table launches), and the (v, ba, bg) blocks of the prior's keyframes stay
+ * in the dense corner of the elimination plan; a change of that set of keyframes configures the problem again (constant flags are kept). */
+int lvf_problem_set_dense_prior(lvf_problem* p, lvf_dense_prior* prior);
+/* lvf_problem_marginal with the reduced right-hand side carried along: for the local model c + g^T eps + 1/2 eps^T H eps of the problem at its
+ * current state (landmarks minimised out; H the undamped Gauss-Newton matrix, g the gradient, c the cost, all with o->huber_a) and the
+ * unknowns of keyframes kfs[n_sel] as the selection s, r the rest,
+ *     info = H_ss - H_sr H_rr^-1 H_rs,      eta = g_s - H_sr H_rr^-1 g_r,      c0 = c - 1/2 g_r^T H_rr^-1 g_r
+ * — with x0 = the selected keyframes' current state exactly the arguments of lvf_dense_prior_create.  m + 1 <= 121 rows ride behind the rest.
+ * Stats, absent unknowns and the soft failure are lvf_problem_marginal's, except that no covariance is formed: a singular SELECTED block is
+ * no failure (an unanchored sub-problem leaves the gauge free), fail only reports the elimination of the rest, and min_pivot_ratio is taken
+ * over the rest's pivots (1 when there is no rest).  Any of info / eta / c0 may be NULL. */
+int lvf_problem_marginal_prior(lvf_problem* p, const lvf_solver_options* o, const int* kfs, int n_sel, double* info, double* eta, double* c0,
+                               lvf_marginal_stats* stats);
+/* The persistent window's dense prior, by keyframe ID (arguments of lvf_dense_prior_create otherwise; n_sel = 0 removes it).  Every
+ * lvf_window_solve and lvf_window_marginal translates the ids to positions and attaches it to the window's problem.  A prior one of whose
+ * keyframes leaves by plain lvf_window_slide is dropped.  LVF_ERR_INVALID, before anything reaches the device: n_sel outside 0 .. 8, a
+ * keyframe that is not in the window or listed twice, a non-finite entry. */
+int lvf_window_set_dense_prior(lvf_window* w, int n_sel, const int64_t* kf_ids, const double* x0, const double* info, const double* eta, double c0);
+/* What the window holds: *n_sel = 0 when there is none; the arrays (each may be NULL) must have room for 8 keyframes' worth. */
+int lvf_window_get_dense_prior(const lvf_window* w, int* n_sel, int64_t* kf_ids, double* x0, double* info, double* eta, double* c0);
+/* lvf_window_slide that keeps what the departing keyframes knew.  With D the keyframes older than first_active_kf_id and s the first kept
+ * one, a sub-problem over D and s is built at the window's current state from every block BuildProblem's rules give for that keyframe list
+ * that touches D: D's TwoCamera, PoseOnly and TwoFrame blocks, D's weak-constraint priors and LiDAR plane sets, the ImuError blocks along D
+ * and into s, and the window's dense prior (which must not sit on keyframes beyond s: LVF_ERR_INVALID).  s contributes no visual block and no
+ * weak-constraint prior of its own: what kept frames observe of D's landmarks lives on as PoseOnly blocks after the slide (the reference's
+ * rule), so no factor is counted twice and none is lost.  lvf_problem_marginal_prior of s in that sub-problem, with o->huber_a and
+ * x0 = s's current state, becomes the window's dense prior; then the window slides as lvf_window_slide does.  No departing keyframe: nothing
+ * happens (LVF_OK); no kept keyframe: LVF_ERR_INVALID.  A soft failure (stats->fail != 0) slides without a prior.  The sub-problem is a second
+ * persistent window owned by this one: its DEVICE buffers only grow; its host mirror (keyframes, observations, the landmark table) is copied
+ * from this window's at every call. */
+int lvf_window_slide_marginalize(lvf_window* w, int64_t first_active_kf_id, const lvf_solver_options* o, lvf_marginal_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -393,6 +393,16 @@ _SIGS = {
     "lvf_marginal_dense": (C.c_int, [_VP, c_double_p, C.c_int, c_int_p, C.c_int, c_double_p, c_double_p, C.POINTER(MarginalStats)]),
     "lvf_problem_marginal": (C.c_int, [_VP, C.POINTER(SolverOptions), c_int_p, C.c_int, c_double_p, c_double_p, C.POINTER(MarginalStats)]),
     "lvf_window_marginal": (C.c_int, [_VP, C.POINTER(SolverOptions), C.POINTER(C.c_int64), C.c_int, c_double_p, c_double_p, C.POINTER(MarginalStats)]),
+    "lvf_dense_prior_create": (C.c_int, [_VP, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p, C.c_double, C.POINTER(_VP)]),
+    "lvf_dense_prior_destroy": (C.c_int, [_VP]),
+    "lvf_dense_prior_size": (C.c_int, [_VP]),
+    "lvf_dense_prior_download": (C.c_int, [_VP, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "lvf_dense_prior_evaluate": (C.c_int, [_VP, _VP, c_u8_p, c_double_p, c_double_p, c_double_p]),
+    "lvf_problem_set_dense_prior": (C.c_int, [_VP, _VP]),
+    "lvf_window_set_dense_prior": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int64), c_double_p, c_double_p, c_double_p, C.c_double]),
+    "lvf_window_get_dense_prior": (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int64), c_double_p, c_double_p, c_double_p, c_double_p]),
+    "lvf_window_slide_marginalize": (C.c_int, [_VP, C.c_int64, C.POINTER(SolverOptions), C.POINTER(MarginalStats)]),
+    "lvf_problem_marginal_prior": (C.c_int, [_VP, C.POINTER(SolverOptions), c_int_p, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(MarginalStats)]),
 }
 
 

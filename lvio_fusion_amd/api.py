@@ -1444,6 +1444,35 @@ class Window:
         _chk(self.ctx.L.lvf_window_marginal(self.h, C.byref(opt), ids.ctypes.data_as(C.POINTER(C.c_int64)), int(ids.size), _dp(info), _dp(cov), C.byref(st)))
         return _marginal_result(info, cov, st)
 
+    def set_dense_prior(self, kf_ids, x0=None, info=None, eta=None, c0=0.0):
+        """the window's dense prior by keyframe id (DensePrior's arrays; lvf_window_set_dense_prior); kf_ids None or empty removes it"""
+        ids = np.zeros(0, np.int64) if kf_ids is None else np.ascontiguousarray(kf_ids, dtype=np.int64).ravel()
+        n = int(ids.size)
+        if n == 0:
+            _chk(self.ctx.L.lvf_window_set_dense_prior(self.h, 0, None, None, None, None, 0.0))
+            return
+        x0, info = _d(x0), _d(info)
+        if n <= 8 and (x0.size != 16 * n or info.shape != (15 * n, 15 * n) or (eta is not None and np.size(eta) != 15 * n)):
+            raise ValueError(f"Window.set_dense_prior: {n} keyframes need x0 [{n}][16], info [{15 * n}][{15 * n}] and eta [{15 * n}]")
+        eta = None if eta is None else _d(eta)
+        _chk(self.ctx.L.lvf_window_set_dense_prior(self.h, n, ids.ctypes.data_as(C.POINTER(C.c_int64)), _dp(x0), _dp(info), None if eta is None else _dp(eta), float(c0)))
+
+    def get_dense_prior(self):
+        """dict(kf_ids, x0 [n][16], info, eta, c0) of the window's dense prior, or None (lvf_window_get_dense_prior)"""
+        n, ids, x0, info, eta, c0 = C.c_int(), np.zeros(8, np.int64), np.zeros((8, 16)), np.zeros(120 * 120), np.zeros(120), C.c_double()
+        _chk(self.ctx.L.lvf_window_get_dense_prior(self.h, C.byref(n), ids.ctypes.data_as(C.POINTER(C.c_int64)), _dp(x0), _dp(info), _dp(eta), C.byref(c0)))
+        k = n.value
+        if k == 0:
+            return None
+        return dict(kf_ids=ids[:k].copy(), x0=x0[:k].copy(), info=info[:225 * k * k].reshape(15 * k, 15 * k).copy(), eta=eta[:15 * k].copy(), c0=c0.value)
+
+    def slide_marginalize(self, first_active_kf, opt):
+        """slide() that leaves what the departing keyframes knew as a dense prior on the first kept one (lvf_window_slide_marginalize);
+        returns the marginalisation's stats (fail != 0: the window slid without a prior)"""
+        st = _lib.MarginalStats()
+        _chk(self.ctx.L.lvf_window_slide_marginalize(self.h, int(first_active_kf), C.byref(opt), C.byref(st)))
+        return dict(fail=int(st.fail), n_present=int(st.n_present), n_absent=int(st.n_absent), min_pivot_ratio=float(st.min_pivot_ratio))
+
     def set_lidar_planes(self, kf_id, p, pa, pb, pc, weight=None, huber_a=None):
         """the plane blocks of keyframe kf_id's sweep (lidar_pose_batch's arrays); replaces that keyframe's set, empty arrays remove it"""
         p, pa, pb, pc = _d(p).reshape(-1, 3), _d(pa).reshape(-1, 3), _d(pb).reshape(-1, 3), _d(pc).reshape(-1, 3)
@@ -1561,6 +1590,45 @@ def marginal_dense(ctx, S, sel):
     return _marginal_result(info, cov, st)
 
 
+class DensePrior:
+    """A dense prior on the 15 tangent unknowns of up to eight keyframes (lvf_dense_prior_create; semantics: tests/dense_prior_ref.py):
+    cost = c0 + eta^T e + 1/2 e^T info e, e = x [-] x0.  kfs: keyframe positions; x0 [n][16] = pose 7, v 3, ba 3, bg 3; info [15 n][15 n]
+    (lower triangle read); eta [15 n] or None."""
+
+    def __init__(self, ctx, kfs, x0, info, eta=None, c0=0.0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        k, x0, info = _i(kfs).ravel(), _d(x0), _d(info)
+        n = int(k.size)
+        if n >= 1 and (x0.size != 16 * n or info.shape != (15 * n, 15 * n) or (eta is not None and np.size(eta) != 15 * n)):
+            raise ValueError(f"DensePrior: {n} keyframes need x0 [{n}][16], info [{15 * n}][{15 * n}] and eta [{15 * n}]")
+        eta = None if eta is None else _d(eta)
+        self.n_sel, self.m = n, 15 * n
+        _chk(ctx.L.lvf_dense_prior_create(ctx.h, n, _ip(k), _dp(x0), _dp(info), None if eta is None else _dp(eta), float(c0), C.byref(self.h)))
+
+    def evaluate(self, state, const_bits=None):
+        """(cost, gradient [m], matrix [m][m]) at `state` (lvf_dense_prior_evaluate); const_bits: one byte per keyframe of the state"""
+        g, H, c = np.empty(self.m), np.empty((self.m, self.m)), C.c_double()
+        cb = None
+        if const_bits is not None:
+            cb = np.ascontiguousarray(const_bits, dtype=np.uint8)
+            if cb.size != state.n_kf:
+                raise ValueError(f"DensePrior.evaluate: const_bits has {cb.size} entries, the state {state.n_kf} keyframes")
+        _chk(self.ctx.L.lvf_dense_prior_evaluate(self.h, state.h, None if cb is None else cb.ctypes.data_as(_lib.c_u8_p), C.byref(c), _dp(g), _dp(H)))
+        return c.value, g, H
+
+    def download(self):
+        """dict(kfs, x0, info, eta, c0) as created"""
+        k, x0, info, eta, c0 = np.empty(self.n_sel, np.int32), np.empty((self.n_sel, 16)), np.empty((self.m, self.m)), np.empty(self.m), C.c_double()
+        _chk(self.ctx.L.lvf_dense_prior_download(self.h, _ip(k), _dp(x0), _dp(info), _dp(eta), C.byref(c0)))
+        return dict(kfs=k, x0=x0, info=info, eta=eta, c0=c0.value)
+
+    def close(self):
+        if self.h:
+            self.ctx.L.lvf_dense_prior_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 def default_solver_options():
     o = SolverOptions()
     _lib.lib().lvf_solver_options_default(C.byref(o))
@@ -1580,6 +1648,10 @@ class Problem:
     def set_lidar_planes(self, batch):
         """adds (None: removes) LiDAR plane blocks on the keyframe poses (lidar_pose_batch / lidar_pose_from_scans); the batch is borrowed"""
         _chk(self.ctx.L.lvf_problem_set_lidar_planes(self.h, batch.h if batch is not None else None))
+
+    def set_dense_prior(self, prior):
+        """adds (None: removes) a DensePrior on keyframes of this problem; the prior is borrowed (lvf_problem_set_dense_prior)"""
+        _chk(self.ctx.L.lvf_problem_set_dense_prior(self.h, prior.h if prior is not None else None))
 
     def set_pose_constant(self, kf, const=True):
         _chk(self.ctx.L.lvf_problem_set_pose_constant(self.h, int(kf), 1 if const else 0))
@@ -1679,6 +1751,17 @@ class Problem:
         info, cov, st = np.empty((m, m)), np.empty((m, m)), _lib.MarginalStats()
         _chk(self.ctx.L.lvf_problem_marginal(self.h, C.byref(opt), _ip(k), int(k.size), _dp(info), _dp(cov), C.byref(st)))
         return _marginal_result(info, cov, st)
+
+    def marginal_prior(self, opt, kfs):
+        """(info [15 n x 15 n], eta [15 n], c0, stats): what minimising the problem's local model at the current state over everything but
+        keyframes `kfs` leaves on them (lvf_problem_marginal_prior) — with x0 = their current state, the arguments of DensePrior.  After a
+        numeric failure (stats["fail"] != 0) info, eta and c0 are None."""
+        k = _i(kfs).ravel()
+        m = 15 * k.size
+        info, eta, c0, st = np.empty((m, m)), np.empty(m), C.c_double(), _lib.MarginalStats()
+        _chk(self.ctx.L.lvf_problem_marginal_prior(self.h, C.byref(opt), _ip(k), int(k.size), _dp(info), _dp(eta), C.byref(c0), C.byref(st)))
+        stats = dict(fail=int(st.fail), n_present=int(st.n_present), n_absent=int(st.n_absent), min_pivot_ratio=float(st.min_pivot_ratio))
+        return (info, eta, c0.value, stats) if st.fail == 0 else (None, None, None, stats)
 
     def close(self):
         if self.h:

@@ -445,6 +445,7 @@ struct lvf_cloud {
 };
 
 struct lvf_problem;
+struct lvf_dense_prior;
 namespace lvf {
 // butterfly inside each group of four lanes on the DPP path (quad_perm, VALU latency): __shfl_xor compiles to ds_bpermute, an LDS
 // round trip of ~120 cycles, and two of them per step WERE the panel solve's dependent chain (11 us per 64 columns)
@@ -558,6 +559,8 @@ __device__ __forceinline__ bool cell_runs(int c, int& start, int& len) {
 // (re)derives a problem's dimensions from its state's CURRENT n_kf / n_lm, grows its work buffers if needed and rebuilds the
 // TwoFrame work list; called by lvf_problem_create and, every tick, by the persistent window (window.hip)
 int problem_configure(lvf_problem* p);
+// the same with the problem's dense prior (borrowed; null: none) replaced first: its keyframes are part of the elimination plan (solver_plan.hip)
+int problem_configure(lvf_problem* p, lvf_dense_prior* prior);
 }  // namespace lvf
 // lvf_problem_solve with a caller's launches enqueued behind the last iteration and ahead of the wait that ends the solve (solver_api.hip).
 // CONTRACT: tail(user) MUST be idempotent — pure enqueues that can be repeated (pack + copy, as window.hip's): it runs once per pass of the

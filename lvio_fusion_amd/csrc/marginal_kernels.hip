@@ -13,6 +13,11 @@
 // the last launch the update of the LAST rest column onto the selected block is still pending: k_marg_tail_update applies it with the same
 // tile product (chol_update_tile).  A non-positive or NaN pivot raises the failure flag (1 + kb, atomicMax); the flag is also every launch's
 // `done` gate, so whatever is enqueued behind a failed step returns at once.  Nothing here waits on another workgroup.
+//
+// lvf_problem_marginal_prior carries the reduced right-hand side along as one more row behind the selection — [rest | padding | selection |
+// rhs] — so the same block steps leave, beside `info`, the information vector eta = g_s - H_sr H_rr^-1 g_r in that row and -g_r^T H_rr^-1 g_r
+// on its diagonal (gathered as 0: the 1e300 the production system keeps there would swallow it).  No covariance is formed there, so a
+// singular selected block is no failure (k_marg_prior_finish).
 #include <vector>
 
 #include "solver_dev.hpp"
@@ -29,18 +34,20 @@ constexpr double kMargRadius = 1e300;     // "undamped": see lvf_problem_margina
 struct MargGather {
   GP<const double> S; int lds; GP<const int> rowmap; GP<const double> diag; size_t dstride;
   GP<const int> src; int ld; GP<double> W, diag0; GP<int> pres, fail;
+  int aug_row;      // src == -2: the right-hand-side row, read from row aug_row of S (lvf_problem_marginal_prior)
 };
 __global__ __launch_bounds__(kMargT) void k_marg_gather(MargGather a) {
   const int r = blockIdx.x;
   const int ua = a.src[r];
-  const bool pa = ua >= 0 && a.diag[(size_t)ua * a.dstride] != 0.0;      // (a NaN diagonal is present: its pivot then fails)
-  const size_t ra = pa ? (size_t)(a.rowmap ? a.rowmap[ua] : ua) : 0;
+  const bool rhs = ua == -2;
+  const bool pa = rhs || (ua >= 0 && a.diag[(size_t)ua * a.dstride] != 0.0);      // (a NaN diagonal is present: its pivot then fails)
+  const size_t ra = rhs ? (size_t)a.aug_row : pa ? (size_t)(a.rowmap ? a.rowmap[ua] : ua) : 0;
   double* row = a.W + (size_t)r * a.ld;
   for (int c = threadIdx.x; c < a.ld; c += kMargT) {
     double v = 0.0;
     if (c == r) {
-      v = pa ? a.S[ra * a.lds + ra] : 1.0;
-      a.diag0[r] = v; a.pres[r] = pa ? 1 : 0;
+      v = rhs ? 0.0 : pa ? a.S[ra * a.lds + ra] : 1.0;
+      a.diag0[r] = v; a.pres[r] = (pa && !rhs) ? 1 : 0;
     } else if (c < r && pa) {
       const int ub = a.src[c];
       if (ub >= 0 && a.diag[(size_t)ub * a.dstride] != 0.0) {
@@ -165,6 +172,48 @@ __global__ __launch_bounds__(kMargFT) void k_marg_finish(MargFinish a) {
   if (tid == 0) { stats[0] = 0.0; stats[1] = n_present; stats[2] = (double)a.d - n_present; stats[3] = mn; }
 }
 
+// ---- finish of lvf_problem_marginal_prior: ONE workgroup.  Trailing block rows R .. R + m - 1 = info, row R + m = -(eta) with
+// -g_r^T H_rr^-1 g_r on its diagonal.  c0 = cost - 1/2 sum_l g_l^2 / Cd_l (the landmarks' share, from what k_prepare left in E's extra
+// column and Cd) + 1/2 of that diagonal.  out = info [m x m] | eta [m] | c0 | {fail, n_present, n_absent, min_pivot_ratio over the rest}.
+struct MargPriorFinish {
+  GP<const double> W; int ld, R, nr, m, d; GP<const int> pres; GP<const double> diag0, Ldiag; GP<const int> fail; GP<double> out;
+  GP<const double> cost; int n_lm, ldE, dp; GP<const double> E, Cd;
+};
+__global__ __launch_bounds__(kMargFT) void k_marg_prior_finish(MargPriorFinish a) {
+  __shared__ double red[kMargFT / 64];
+  const int tid = threadIdx.x, m = a.m, R = a.R;
+  double* const info = a.out; double* const eta = a.out + (size_t)m * m; double* const stats = eta + m + 1;
+  int np = 0;
+  for (int p = tid; p < a.ld; p += kMargFT) np += a.pres[p];
+  const double n_present = marg_block_sum((double)np, red);
+  const int f0 = done_flag_issue(a.fail);
+  if (f0) {
+    if (tid == 0) { stats[0] = (double)f0; stats[1] = n_present; stats[2] = (double)a.d - n_present; stats[3] = 0.0; }
+    return;
+  }
+  const double* T = a.W + (size_t)R * a.ld + R;
+  for (int idx = tid; idx < m * m; idx += kMargFT) {
+    const int i = idx / m, j = idx - i * m;
+    if (j > i) continue;
+    const double o = (a.pres[R + i] && a.pres[R + j]) ? T[(size_t)i * a.ld + j] : 0.0;
+    info[i * m + j] = o; info[j * m + i] = o;
+  }
+  for (int j = tid; j < m; j += kMargFT) eta[j] = a.pres[R + j] ? -T[(size_t)m * a.ld + j] : 0.0;
+  double lm = 0.0;
+  for (int l = tid; l < a.n_lm; l += kMargFT) { const double g = a.E[(size_t)l * a.ldE + a.dp], cd = a.Cd[l]; if (cd > 0.0) lm += g * g / cd; }      // (a landmark no block observes: g = 0, and Cd may be 0)
+  lm = marg_block_sum(lm, red);
+  double c = tid < kStripes ? a.cost[tid] : 0.0;
+  c = marg_block_sum(c, red);
+  double mn = 1.0;
+  for (int p = tid; p < R; p += kMargFT)
+    if (a.pres[p]) { const double l = a.Ldiag[(size_t)(p >> 6) * kNB * kNB + (size_t)(p & 63) * (kNB + 1)]; mn = fmin(mn, l * l / a.diag0[p]); }
+  mn = marg_block_min(mn, red);
+  if (tid == 0) {
+    eta[m] = c - 0.5 * lm + 0.5 * T[(size_t)m * a.ld + m];
+    stats[0] = 0.0; stats[1] = n_present; stats[2] = (double)a.d - n_present; stats[3] = mn;
+  }
+}
+
 // checks a selection of unknowns: 1 <= m <= 120, distinct, in range
 static int check_selection(const char* who, int d, const int* sel, int m) {
   LVF_REQUIRE(d >= 1 && d <= 32768, "%s: %d unknowns (1 .. 32768)", who, d);
@@ -181,11 +230,14 @@ static int check_selection(const char* who, int d, const int* sel, int m) {
 // The device path on a system that is already on the device: S (leading dimension lds, lower triangle) read through rowmap, absence from
 // diag.  Enqueues gather, one block step per 64 rest columns, the tail update and the finish, waits ONCE and downloads 2 m^2 + 4 doubles.
 // The selection has been checked (check_selection).  A numeric failure leaves info / cov untouched.
+// `rhs` (lvf_problem_marginal_prior): the right-hand-side row rides behind the selection and the outputs are info, eta, c0 (no covariance).
+struct MargRhs { int aug_row; const double* cost; int n_lm, ldE, dp; const double *E, *Cd; double *eta, *c0; };
 static int marginal_run(lvf_ctx* ctx, const double* S, int lds, const int* rowmap, const double* diag, size_t dstride, int d, const int* sel, int m,
-                        double* info, double* cov, lvf_marginal_stats* stats) {
+                        double* info, double* cov, lvf_marginal_stats* stats, const MargRhs* rhs = nullptr) {
   hipStream_t q = ctx->stream;
-  const int nrest = d - m, nr = (nrest + kNB - 1) / kNB, R = kNB * nr, ns = (m + kNB - 1) / kNB, nb = nr + ns, ld = kNB * nb;
+  const int nrest = d - m, nr = (nrest + kNB - 1) / kNB, R = kNB * nr, ns = (m + (rhs ? 1 : 0) + kNB - 1) / kNB, nb = nr + ns, ld = kNB * nb;
   std::vector<int> src((size_t)ld, -1);
+  if (rhs) src[(size_t)R + m] = -2;
   {
     std::vector<char> is_sel((size_t)d, 0);
     for (int i = 0; i < m; ++i) { is_sel[sel[i]] = 1; src[(size_t)R + i] = sel[i]; }
@@ -197,11 +249,12 @@ static int marginal_run(lvf_ctx* ctx, const double* S, int lds, const int* rowma
   LVF_TRY(srcd.assign(src.data(), src.size(), q));
   LVF_TRY(W.alloc((size_t)ld * ld)); LVF_TRY(Dinv.alloc((size_t)std::max(nr, 1) * kNB * kNB)); LVF_TRY(Ldiag.alloc((size_t)std::max(nr, 1) * kNB * kNB));
   LVF_TRY(diag0.alloc(ld)); LVF_TRY(pres.alloc(ld)); LVF_TRY(fail.alloc(1));
-  const size_t n_out = 2 * (size_t)m * m + 4;
+  const size_t n_out = rhs ? (size_t)m * m + m + 1 + 4 : 2 * (size_t)m * m + 4;
   LVF_TRY(out.alloc(n_out));
   StreamWaitGuard guard(q);                           // (the buffers above go back to the context's pool only once the stream is idle, on every path out)
   MargGather ga{};
   ga.S = S; ga.lds = lds; ga.rowmap = rowmap; ga.diag = diag; ga.dstride = dstride; ga.src = srcd.p; ga.ld = ld; ga.W = W.p; ga.diag0 = diag0.p; ga.pres = pres.p; ga.fail = fail.p;
+  ga.aug_row = rhs ? rhs->aug_row : -1;
   hipLaunchKernelGGL(k_marg_gather, dim3(ld), dim3(kMargT), 0, q, ga);
   CholArgs ca{};
   ca.Sd = W.p; ca.ld = ld; ca.nb = nb; ca.fail = fail.p; ca.Dinv = Dinv.p; ca.done = fail.p; ca.dbg = nullptr; ca.last_cols = 0; ca.Ldiag = Ldiag.p;
@@ -209,6 +262,24 @@ static int marginal_run(lvf_ctx* ctx, const double* S, int lds, const int* rowma
   TRide tr{}; tr.n = 0;
   for (int kb = 0; kb < nr; ++kb) hipLaunchKernelGGL(k_chol_step, dim3(chol_step_grid(nb, kb)), dim3(kCT), 0, q, ca, kb, gr, tr);
   if (nr > 0) hipLaunchKernelGGL(k_marg_tail_update, dim3(ns * (ns + 1) / 2), dim3(kCT), 0, q, GP<double>(W.p), ld, nr, GP<const int>(fail.p));
+  if (rhs) {
+    MargPriorFinish fp{};
+    fp.W = W.p; fp.ld = ld; fp.R = R; fp.nr = nr; fp.m = m; fp.d = d; fp.pres = pres.p; fp.diag0 = diag0.p; fp.Ldiag = Ldiag.p; fp.fail = fail.p; fp.out = out.p;
+    fp.cost = rhs->cost; fp.n_lm = rhs->n_lm; fp.ldE = rhs->ldE; fp.dp = rhs->dp; fp.E = rhs->E; fp.Cd = rhs->Cd;
+    hipLaunchKernelGGL(k_marg_prior_finish, dim3(1), dim3(kMargFT), 0, q, fp);
+    LVF_HIP(hipGetLastError());
+    std::vector<double> h(n_out);
+    LVF_TRY(copy_down_wait(ctx, h.data(), out.p, n_out * sizeof(double)));
+    guard.dismiss();
+    const double* st = h.data() + (size_t)m * m + m + 1;
+    stats->fail = (int)st[0]; stats->n_present = (int)st[1]; stats->n_absent = (int)st[2]; stats->min_pivot_ratio = st[3];
+    if (stats->fail == 0) {
+      if (info) std::memcpy(info, h.data(), (size_t)m * m * sizeof(double));
+      if (rhs->eta) std::memcpy(rhs->eta, h.data() + (size_t)m * m, (size_t)m * sizeof(double));
+      if (rhs->c0) *rhs->c0 = h[(size_t)m * m + m];
+    }
+    return LVF_OK;
+  }
   MargFinish fa{};
   fa.W = W.p; fa.ld = ld; fa.R = R; fa.nr = nr; fa.m = m; fa.d = d; fa.pres = pres.p; fa.diag0 = diag0.p; fa.Ldiag = Ldiag.p; fa.fail = fail.p; fa.out = out.p;
   const size_t lds_bytes = (size_t)m * (m | 1) * sizeof(double);
@@ -275,6 +346,32 @@ int lvf_problem_marginal(lvf_problem* p, const lvf_solver_options* o, const int*
   LVF_TRY(enqueue_linearize(p, o->huber_a, false));                                        // (marks the accumulators dirty)
   LVF_TRY(enqueue_reduced_system(p, &p->ctl.p->radius, false, false, nullptr));            // (marks S dirty where the chain would add into it)
   return marginal_run(p->ctx, p->S.p, p->ld, p->perm.p, p->B.p, (size_t)p->dpad + 1, p->d, sel.data(), (int)sel.size(), info, cov, stats);
+}
+
+// The same assembly; the right-hand-side row of S (-(gc - E^T Cd^-1 g_rho)) rides behind the selection, the cost comes from the
+// linearisation's stripes (cleared with the accumulators, which the linearisation above finds dirty or clears itself)
+int lvf_problem_marginal_prior(lvf_problem* p, const lvf_solver_options* o, const int* kfs, int n_sel, double* info, double* eta, double* c0,
+                               lvf_marginal_stats* stats) {
+  LVF_REQUIRE(p && o && kfs && stats, "lvf_problem_marginal_prior: null argument");
+  LVF_REQUIRE(n_sel >= 1 && n_sel <= kMargMaxSel / 15, "lvf_problem_marginal_prior: %d keyframes selected (1 .. %d)", n_sel, kMargMaxSel / 15);
+  std::vector<int> sel;
+  for (int i = 0; i < n_sel; ++i) {
+    const int k = kfs[i];
+    LVF_REQUIRE(k >= 0 && k < p->n_kf, "lvf_problem_marginal_prior: keyframe %d out of range (%d keyframes)", k, p->n_kf);
+    for (int t = 0; t < 6; ++t) sel.push_back(6 * k + t);
+    for (int t = 0; t < 9; ++t) sel.push_back(p->dp + 9 * k + t);
+  }
+  LVF_TRY(check_selection("lvf_problem_marginal_prior", p->d, sel.data(), (int)sel.size()));
+  LVF_TRY(lvf::enter(p->ctx));
+  LmCtl c;
+  ctl_from_options(o, kMargRadius, 2.0, 1, false, &c);
+  if (p->last_radius > 0.0) c.last_radius = p->last_radius;
+  LVF_TRY(upload_ctl(p, c));
+  // (the cost stripes start from zero: cleared with the accumulators, or left so by whatever left the accumulators clean)
+  LVF_TRY(enqueue_linearize(p, o->huber_a, false));
+  LVF_TRY(enqueue_reduced_system(p, &p->ctl.p->radius, false, false, nullptr));
+  const MargRhs rhs{p->aug, p->scal.p + SC_COST, p->n_lm, p->ldE, p->dp, p->E.p, p->Cd.p, eta, c0};
+  return marginal_run(p->ctx, p->S.p, p->ld, p->perm.p, p->B.p, (size_t)p->dpad + 1, p->d, sel.data(), (int)sel.size(), info, nullptr, stats, &rhs);      // (the accumulators and the stripes are left dirty and marked so)
 }
 
 }  // extern "C"

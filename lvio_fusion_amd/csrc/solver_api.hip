@@ -28,7 +28,7 @@ static const char* const kStageNames[ST_N] = {"k_zero_multi (only when the accum
 void summary_from_ctl(const lvf_problem* p, const LmCtl& c, lvf_solver_summary* s) {
   std::memset(s, 0, sizeof(*s));
   s->num_residual_blocks = (p->tc ? p->tc->n : 0) + (p->tf ? p->tf->n : 0) + (p->po ? p->po->n : 0) + (p->imu ? p->imu->n : 0) + (p->prior ? p->prior->n : 0) +
-                           (p->lidar ? p->lidar->n : 0);
+                           (p->lidar ? p->lidar->n : 0) + (p->dprior ? 1 : 0);
   s->initial_cost = c.initial_cost; s->final_cost = c.cost; s->num_iterations = c.iter; s->num_successful_steps = c.successes; s->termination = c.termination;
   s->num_unsuccessful_steps = c.rejected; s->termination_reason = c.why; s->hand_over_retries = p->handover_retries;
 }

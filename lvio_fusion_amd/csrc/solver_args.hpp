@@ -59,18 +59,31 @@ constexpr int kFailSparse = 100000, kFailHandover = 300000;
 struct ReducedOverride { int d = 0; DevBuf<double> S, rhs; };
 // (debug_taps.hip: the copy kernel lives in a translation unit of its own, so the kernel units' device code is what it is without the tap)
 int launch_override_reduced(hipStream_t q, int d, int ld, int aug, const int* perm, const double* Sov, const double* rhs, double* S);
+constexpr int kDensePriorMaxKf = 8;
 }
+// A dense prior on the 15 tangent unknowns of n_sel keyframes (solver_dense_prior.hip; declared semantics: tests/dense_prior_ref.py):
+// cost = c0 + eta^T e + 1/2 e^T info e with e = x [-] x0.  kf = the keyframes' positions in the state the prior is evaluated on.
+struct lvf_dense_prior {
+  lvf_ctx* ctx = nullptr;
+  int n_sel = 0, m = 0;
+  double c0 = 0.0;
+  std::vector<int32_t> kf_h;                    // [n_sel]
+  lvf::DevBuf<int> kf;                          // [n_sel]
+  lvf::DevBuf<double> x0, info, eta;            // [n_sel][16] (pose 7, v 3, ba 3, bg 3) | [m][m], the lower triangle is read | [m]
+  lvf::DevBuf<double> out;                      // lvf_dense_prior_evaluate: gradient [m] | matrix [m][m] | 32 cost stripes
+};
 struct lvf_problem {
   lvf_ctx* ctx = nullptr;
   lvf_state* st = nullptr;
   lvf_batch *tc = nullptr, *tf = nullptr, *po = nullptr, *imu = nullptr, *prior = nullptr, *lidar = nullptr;
+  lvf_dense_prior* dprior = nullptr;            // borrowed (lvf_problem_set_dense_prior); its keyframes stay in the dense corner of the plan
   int n_kf = 0, n_lm = 0, d = 0, dp = 0, ldE = 0, dpad = 0, nb = 0;
   // layout of the factorised matrix S (see "elimination order" in solver_assemble.hip): [sparse (v,ba,bg) blocks | dense (v,ba,bg) blocks | poses | rhs row | pad]
   int ld = 0, off = 0, off_pose = 0, ndense = 0, aug = 0, sp_wstride = 0;
   lvf::SpLevels sp_levels{};
   std::vector<int> sp_tiles, sp_shmem;          // per level: workgroups per node, dynamic LDS bytes
   std::vector<int> sp_item0, sp_items;          // per level: its slice of sp_rows
-  std::vector<int32_t> plan_key;                // (n_kf, IMU index pairs) the current plan was built for
+  std::vector<int32_t> plan_key;                // (n_kf, IMU index pairs, keyframes of the dense prior) the current plan was built for
   lvf::DevBuf<lvf::SpNode> sp_nodes;
   lvf::DevBuf<int> sp_rows, sp_rows_nat, sp_owner, perm, iperm;      // sp_rows_nat: the natural-order unknown of every entry of sp_rows (-2 = the right-hand-side row)
   lvf::DevBuf<int> lm_kmin, lm_kmax, lm_order, lm_nactive;   // per-landmark keyframe track [kmin, kmax]; Schur row order; #rows with pose blocks
@@ -386,6 +399,14 @@ static inline LidarPoseArgs lidar_pose_args(const lvf_batch* b) { return LidarPo
 __global__ void k_lidar_lin(LidarPoseArgs L, int n_kf, const double* __restrict__ poses, const uint8_t* __restrict__ pose_const, double* __restrict__ B,
     int ld, double* __restrict__ gc, double* __restrict__ cost);
 __global__ void k_lidar_cost(LidarPoseArgs L, int n_kf, const double* __restrict__ poses, double* __restrict__ cost);
+// The dense keyframe prior (solver_dense_prior.hip): one workgroup.  B / gc: the lower triangle in the natural order (pose rows 6 k,
+// (v, ba, bg) rows dp + 9 k).  gout / Hout non-null: the materialised parity mode, gradient [m] and matrix [m][m] instead of B / gc.
+struct DensePriorArgs { int n_sel, m; GP<const int> kf; GP<const double> x0, info, eta; double c0; };
+static inline DensePriorArgs dense_prior_args(const lvf_dense_prior* d) { return DensePriorArgs{d->n_sel, d->m, d->kf.p, d->x0.p, d->info.p, d->eta.p, d->c0}; }
+constexpr int kDensePriorT = 256;
+__global__ void k_dense_prior_lin(DensePriorArgs P, int n_kf, StateP s, const uint8_t* __restrict__ pose_const, double* __restrict__ B, int ld,
+    double* __restrict__ gc, double* __restrict__ cost, double* __restrict__ gout, double* __restrict__ Hout);
+__global__ void k_dense_prior_cost(DensePriorArgs P, StateP s, double* __restrict__ cost);
 __global__ void k_prepare(PrepArgs a);
 __global__ void k_prepare_b(const PrepArgs* __restrict__ t);
 __global__ void k_prepare_bt(const PrepArgs* __restrict__ t);

@@ -45,6 +45,7 @@ int enqueue_cost(lvf_problem* p, const StateP& s, const lvf_state* imu_state_vie
     hipLaunchKernelGGL(k_cost_sq, dim3(grid(6 * p->prior->n)), dim3(kT), 0, q, 6 * p->prior->n, p->prior->res.p, cost_slot);
   }
   if (p->lidar && p->lidar->n) hipLaunchKernelGGL(k_lidar_cost, dim3(grid(p->lidar->n)), dim3(kT), 0, q, lidar_pose_args(p->lidar), p->n_kf, s.poses, cost_slot);
+  if (p->dprior) hipLaunchKernelGGL(k_dense_prior_cost, dim3(1), dim3(kDensePriorT), 0, q, dense_prior_args(p->dprior), s, cost_slot);
   LVF_HIP(hipGetLastError());
   return LVF_OK;
 }
@@ -436,7 +437,7 @@ static int chain_cost_decide_args(lvf_problem* p, Chain& c) {
 static void chain_fused_args(lvf_problem* p, Chain& c) {
   const int* done = &p->ctl.p->done;
   const StateP s2 = candidate_ptrs(p);
-  c.fused_ok = solver_env().fused_lin && c.fast && p->compact && !c.has_prior && !c.has_lidar && c.merged_level0 && p->n_lm > 0 && c.lin.nblocks > 0 && c.cost.nblocks > 0 &&
+  c.fused_ok = solver_env().fused_lin && c.fast && p->compact && !c.has_prior && !c.has_lidar && !c.has_dprior && c.merged_level0 && p->n_lm > 0 && c.lin.nblocks > 0 && c.cost.nblocks > 0 &&
                (!c.has_imu || (c.imu_in_cost && c.lin.v.imu.pre));
   p->acc1_ready = false;            // the second set is allocated and cleared by the first fused solve (ensure_acc1)
   if (c.fused_ok) {
@@ -473,6 +474,7 @@ int build_chain(lvf_problem* p) {
   c.has_imu = p->imu && p->imu->n;
   c.has_prior = p->prior && p->prior->n;
   c.has_lidar = p->lidar && p->lidar->n;
+  c.has_dprior = p->dprior != nullptr;
   {
     // LVF_EARLY_LEVELS=0: the classic order (A/B measurements); LVF_POISON_S fills S with NaN before the assembly, which only the classic form survives
     bool fits = true;
@@ -486,7 +488,7 @@ int build_chain(lvf_problem* p) {
   LVF_TRY(chain_solve_args(p, c));
   LVF_TRY(chain_cost_decide_args(p, c));
   chain_fused_args(p, c);
-  c.batchable = c.fast && p->compact && c.has_imu && !c.has_prior && !c.has_lidar && c.merged_level0 && c.lin.nblocks > 0 && c.cost.nblocks > 0;
+  c.batchable = c.fast && p->compact && c.has_imu && !c.has_prior && !c.has_lidar && !c.has_dprior && c.merged_level0 && c.lin.nblocks > 0 && c.cost.nblocks > 0;
   { const StateP sp = state_ptrs(p->st); std::memcpy(p->chain_state, &sp, sizeof(sp)); }
   p->chain_tcw = p->tc && p->tc->wblk.n ? p->tc->wblk.p : nullptr;
   p->chain_ready = true;
@@ -675,6 +677,9 @@ int enqueue_linearize(lvf_problem* p, double huber, bool gated, bool iteration, 
   }
   if (c.has_lidar)
     hipLaunchKernelGGL(k_lidar_lin, dim3(grid(p->lidar->n)), dim3(kT), 0, q, lidar_pose_args(p->lidar), p->n_kf, p->st->poses.p, p->pose_const.p, p->B.p, p->dpad, p->gc.p, cost);
+  if (c.has_dprior)
+    hipLaunchKernelGGL(k_dense_prior_lin, dim3(1), dim3(kDensePriorT), 0, q, dense_prior_args(p->dprior), p->n_kf, s, p->pose_const.p, p->B.p, p->dpad, p->gc.p, cost,
+                       (double*)nullptr, (double*)nullptr);
   LVF_HIP(hipGetLastError());
   p->linearized = true;
   return LVF_OK;
@@ -735,9 +740,9 @@ int enqueue_reduced_system(lvf_problem* p, const double* radius_dev, bool reset_
   // triangle — stays NaN; results must not change (tests/test_gpu_solver.py runs the parity cases this way too)
   if (solver_env().poison_s) LVF_HIP(hipMemsetAsync(p->S.p, 0xff, (size_t)p->ld * p->ld * 8, q));
   LVF_CHAIN_LAUNCH(p, ST_PREPARE, k_prepare, dim3(pa.nblocks), dim3(kT), pa.ride.nblocks > 0 ? c.prep_lds : 0, q, pa);
-  // (k_prior_lin and k_lidar_lin close the linearisation right ahead of this launch, so this stage's span holds them and its count names them.
+  // (k_prior_lin, k_lidar_lin and k_dense_prior_lin close the linearisation right ahead of this launch, so this stage's span holds them and its count names them.
   // The clock only runs inside enqueue_iteration, where windows with such blocks always linearise first: they never take the fused chain.)
-  stage_mark(p, ST_PREPARE, 1 + (c.has_prior ? 1 : 0) + (c.has_lidar ? 1 : 0));
+  stage_mark(p, ST_PREPARE, 1 + (c.has_prior ? 1 : 0) + (c.has_lidar ? 1 : 0) + (c.has_dprior ? 1 : 0));
   if (!early && c.early) p->accum_clean = false;       // the tap wrote S: the next iteration must clear it
   if (level0_done) *level0_done = false;
   if (p->n_lm) {
@@ -898,6 +903,7 @@ int enqueue_iteration(lvf_problem* p, bool end_zero, int fused) {
     hipLaunchKernelGGL(k_prior_cost, dim3((pb->n + 63) / 64), dim3(64), 0, q, P, p->poses2.p, p->scal.p + SC_COST_NEW);
   }
   if (c.has_lidar) hipLaunchKernelGGL(k_lidar_cost, dim3(grid(p->lidar->n)), dim3(kT), 0, q, lidar_pose_args(p->lidar), p->n_kf, p->poses2.p, p->scal.p + SC_COST_NEW);
+  if (c.has_dprior) hipLaunchKernelGGL(k_dense_prior_cost, dim3(1), dim3(kDensePriorT), 0, q, dense_prior_args(p->dprior), candidate_ptrs(p), p->scal.p + SC_COST_NEW);      // (reads velocity and biases too)
   if (ca.nblocks > 0) {
     if (!end_zero) ca.zero_wgs = 0;
     DecideArgs da = c.dec;
@@ -905,9 +911,9 @@ int enqueue_iteration(lvf_problem* p, bool end_zero, int fused) {
     LVF_CHAIN_LAUNCH(p, ST_COST, k_cost_decide, dim3(ca.nblocks + ca.zero_wgs), dim3(kT), 0, q, ca, da, end_zero ? 1 : 0);
     p->accum_clean = ca.zero_wgs > 0;
     if (p->accum_clean) p->linearized = false;         // the normal equations of this iteration are gone: no reduced-system tap
-    stage_mark(p, ST_COST, 1 + (c.has_imu && !c.imu_in_cost ? 1 : 0) + (c.has_prior ? 1 : 0) + (c.has_lidar ? 1 : 0));
+    stage_mark(p, ST_COST, 1 + (c.has_imu && !c.imu_in_cost ? 1 : 0) + (c.has_prior ? 1 : 0) + (c.has_lidar ? 1 : 0) + (c.has_dprior ? 1 : 0));
   } else {
-    stage_mark(p, ST_COST, (c.has_imu ? 1 : 0) + (c.has_prior ? 1 : 0) + (c.has_lidar ? 1 : 0));
+    stage_mark(p, ST_COST, (c.has_imu ? 1 : 0) + (c.has_prior ? 1 : 0) + (c.has_lidar ? 1 : 0) + (c.has_dprior ? 1 : 0));
     LVF_CHAIN_LAUNCH(p, ST_DECIDE, k_lm_decide, dim3(1), dim3(kDT), 0, q, c.dec);
     stage_mark(p, ST_DECIDE, 1);
   }

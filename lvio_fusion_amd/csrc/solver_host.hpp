@@ -95,6 +95,7 @@ struct Chain {
   bool fast = false;            // merged linearisation (sorted TwoFrame work list) available
   bool batchable = false;       // every launch of the iteration has a table form (fast + band Schur merged with sparse level 0 + no priors, no lidar planes)
   bool has_imu = false, has_prior = false, has_lidar = false, imu_in_cost = false;
+  bool has_dprior = false;      // a dense keyframe prior (solver_dense_prior.hip): like has_prior, no fused candidate pass and no table launches
   ZeroList zero_end{};
   ZeroList zero{};              // everything a linearisation accumulates into (explicit k_zero_multi when the accumulators are not known clean)
   ImuArgs imu_lin{}, imu_cost{};
@@ -173,6 +174,8 @@ bool handover_pending(const lvf_problem* p, const LmCtl& c);
 int rearm_after_handover(lvf_problem* p, LmCtl* c);
 int lm_iteration(lvf_problem* p, const lvf_solver_options* o, double* radius, double* decrease, IterOut* out);
 int wait_for_iteration(lvf_problem* p, int iter);
+// ---- solver_plan.hip
+int problem_set_dense_prior(lvf_problem* p, lvf_dense_prior* prior);
 // ---- solver_batch.hip
 void batch_orphan(lvf_problem_batch* b, lvf_problem* dying);
 // ---- solver_api.hip

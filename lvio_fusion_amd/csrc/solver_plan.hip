@@ -11,6 +11,12 @@ namespace lvf {
 // Elimination plan (host, <= a few hundred nodes): which (v, ba, bg) blocks are factorised sparsely, in which level, with which
 // neighbour rows; the S row of every unknown.  Rebuilt only when (n_kf, IMU index pairs) change.  LVF_SPARSE_VB=0 keeps every
 // block in the dense corner (the round-1 layout, poses last) for A/B measurements.
+//
+// A keyframe of the problem's dense prior (lvf_problem_set_dense_prior) is never CHOSEN for sparse elimination: the prior couples its
+// (v, ba, bg) block to its own pose, to the other keyframes of the prior and to their poses, none of which the ImuError adjacency knows, and
+// its terms reach B only after the early levels have formed their columns.  Kept in the dense corner, the block is assembled by k_prepare,
+// which runs behind the prior's launch and reads all of B.  It is still a neighbour row of the blocks that are eliminated, and still
+// blocked by them, exactly as today; a problem without such a prior builds the key and the plan it always built.
 static int build_elimination_plan(lvf_problem* p) {
   const int n = p->n_kf;
   std::vector<int32_t> key;
@@ -20,6 +26,14 @@ static int build_elimination_plan(lvf_problem* p) {
   if (imu && imu->n > 0) {
     key.push_back(have_idx ? 1 : 0);
     if (have_idx) { key.insert(key.end(), imu->host_kf1.begin(), imu->host_kf1.end()); key.insert(key.end(), imu->host_kf2.begin(), imu->host_kf2.end()); }
+  }
+  std::vector<char> pinned(n, 0);
+  if (p->dprior) {
+    std::vector<int32_t> kfs(p->dprior->kf_h);
+    std::sort(kfs.begin(), kfs.end());
+    key.push_back(INT32_MIN);                         // (no keyframe count or index is negative: the marker cannot be part of a key without a prior)
+    key.insert(key.end(), kfs.begin(), kfs.end());
+    for (int32_t k : kfs) if (k >= 0 && k < n) pinned[k] = 1;
   }
   if (key == p->plan_key && p->ld > 0) return LVF_OK;
   std::vector<std::vector<char>> va(n, std::vector<char>(n, 0)), pa(n, std::vector<char>(n, 0));
@@ -48,7 +62,7 @@ static int build_elimination_plan(lvf_problem* p) {
       std::vector<char> blocked(n, 0);
       std::vector<int> chosen;
       for (int k = 0; k < n; ++k) {
-        if (!alive2[k] || blocked[k]) continue;
+        if (!alive2[k] || blocked[k] || pinned[k]) continue;
         chosen.push_back(k);
         for (int u = 0; u < n; ++u) if (va2[k][u]) blocked[u] = 1;
       }
@@ -76,7 +90,7 @@ static int build_elimination_plan(lvf_problem* p) {
     std::vector<char> blocked(n, 0);
     std::vector<int> chosen;
     for (int k = 0; k < n; ++k) {
-      if (!alive[k] || blocked[k]) continue;
+      if (!alive[k] || blocked[k] || pinned[k]) continue;
       int m = 1;
       for (int u = 0; u < n; ++u) m += 9 * (va[k][u] && alive[u]) + 6 * pa[k][u];
       if (m > kSpMaxRows) continue;
@@ -354,6 +368,34 @@ int problem_configure(lvf_problem* p) {
   p->linearized = false;
   p->chain_ready = false;
   p->step_ready = false;
+  return LVF_OK;
+}
+
+int problem_configure(lvf_problem* p, lvf_dense_prior* prior) {
+  p->dprior = prior;
+  return problem_configure(p);
+}
+
+// lvf_problem_set_dense_prior: the prior's keyframes are part of the elimination plan's key, so a change of that set configures the problem
+// again (the constant flags, which a configure clears, are put back); the same set only swaps the pointer
+int problem_set_dense_prior(lvf_problem* p, lvf_dense_prior* prior) {
+  // (the prior attached so far is borrowed and may be gone already: what it sat on is read from the plan's key, never from the object)
+  std::vector<int32_t> was, now;
+  const auto mark = std::find(p->plan_key.begin(), p->plan_key.end(), INT32_MIN);
+  if (mark != p->plan_key.end()) was.assign(mark + 1, p->plan_key.end());
+  if (prior) now = prior->kf_h;
+  std::sort(now.begin(), now.end());
+  p->dprior = prior;
+  p->linearized = false;
+  p->chain_ready = false;
+  if (was == now && p->n_kf == p->st->n_kf) return LVF_OK;
+  const std::vector<uint8_t> bits = p->pose_const_h;
+  LVF_TRY(problem_configure(p));
+  if (bits.size() == p->pose_const_h.size() && !bits.empty()) {
+    p->pose_const_h = bits;
+    LVF_HIP(hipMemcpyAsync(p->pose_const.p, p->pose_const_h.data(), p->pose_const_h.size(), hipMemcpyHostToDevice, p->ctx->stream));
+    LVF_HIP(hipStreamSynchronize(p->ctx->stream));
+  }
   return LVF_OK;
 }
 

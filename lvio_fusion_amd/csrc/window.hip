@@ -116,8 +116,20 @@ struct lvf_window {
   Assembler assembled_by = Assembler::none;              // who made the block lists that sit in the batches (see begin_assembly)
   std::vector<int> slot_lm;                              // dense landmark slot -> index into lms (host assembly; the device's table is d_slot_lm)
   int n_tc = 0, n_tf = 0, n_po = 0, n_imu = 0, n_prior = 0, n_lm_problem = 0;
+  // Dense prior (lvf_window_set_dense_prior, lvf_window_slide_marginalize): kept on the host by keyframe id; `dprior` is its device copy by
+  // keyframe position, refreshed when the prior or the positions change and attached to the problem by every configure
+  std::vector<int64_t> dp_ids; std::vector<double> dp_x0, dp_info, dp_eta; double dp_c0 = 0.0;
+  std::vector<int32_t> dp_pos;                           // the positions `dprior` was last filled with (empty: stale)
+  lvf_dense_prior* dprior = nullptr;
+  // The sub-problem of the marginalising slide: a second persistent window over the departing keyframes and the first kept one, re-filled
+  // by every lvf_window_slide_marginalize (its device objects are grow-only like this window's).  In it the last keyframe gets no
+  // weak-constraint prior (is_sub) and the lidar segments are borrowed from this window.
+  lvf_window* sub = nullptr;
+  bool is_sub = false;
   ~lvf_window() {
+    if (sub) { sub->lidar_seg.clear(); delete sub; }
     if (prob) lvf_problem_destroy(prob);
+    if (dprior) lvf_dense_prior_destroy(dprior);
     for (lvf_batch* b : {tc, tf, po, imu, prior, rej, lidar}) if (b) lvf_batch_destroy(b);
     for (auto& kv : lidar_seg) lvf_batch_destroy(kv.second);
     if (st) lvf_state_destroy(st);
@@ -345,6 +357,8 @@ int lvf_window_slide(lvf_window* w, int64_t first_active_kf_id) {
     if (is != w->lidar_seg.end()) { lvf_batch_destroy(is->second); w->lidar_seg.erase(is); }
   }
   if (w->lidar) w->lidar_dirty = true;                     // (the positions of the keyframes that stay have changed)
+  for (int64_t id : w->dp_ids)
+    if (id < first_active_kf_id) { w->dp_ids.clear(); w->dp_pos.clear(); break; }      // a dense prior whose keyframe leaves is dropped
   w->kfs.erase(w->kfs.begin(), w->kfs.begin() + drop);
   w->kf_index.clear();
   for (size_t k = 0; k < w->kfs.size(); ++k) w->kf_index[w->kfs[k].id] = (int)k;
@@ -575,6 +589,7 @@ static int shape_imu_batch(lvf_window* w, StageWriter& sw, const std::vector<int
 struct PriorLists { std::vector<double> t, wt, v; std::vector<int32_t> a, b; };
 static int weak_prior(const lvf_window* w, int k, bool has_imu_block, int near_count, PriorLists& pl) {
   if (has_imu_block || near_count >= w->opt.weak_visual_threshold) return LVF_OK;
+  if (w->is_sub && k + 1 == (int)w->kfs.size()) return LVF_OK;      // the first kept keyframe of a marginalising slide: no prior of its own
   const lvf_window::Kf& f = w->kfs[k];
   double t7[7] = {0, 0, 0, 0, 0, 0, 0};
   if (k > 0) { LVF_TRY(lvf_relative_rpyxyz(w->kfs[k - 1].pose, f.pose, t7)); pl.a.push_back(k - 1); }
@@ -621,12 +636,35 @@ static void set_visual_counts(lvf_window* w, size_t ntc, size_t ntf, size_t npo,
   shape(po, npo, 0); po->n_table = (int)npo; po->sorted_by_kf = true;
 }
 
+namespace lvf { int dense_prior_assign(lvf_ctx* ctx, lvf_dense_prior** d, int n_sel, const int32_t* kf, const double* x0, const double* info, const double* eta, double c0); }      // solver_dense_prior.hip
+// the window's dense prior by keyframe POSITION, as the problem takes it (null: none); the device copy is refilled only when the prior or
+// the positions of its keyframes changed
+static int window_dense_prior(lvf_window* w, lvf_dense_prior** out) {
+  *out = nullptr;
+  if (w->dp_ids.empty()) return LVF_OK;
+  std::vector<int32_t> pos;
+  for (int64_t id : w->dp_ids) {
+    const auto it = w->kf_index.find(id);
+    LVF_REQUIRE(it != w->kf_index.end(), "lvf_window: the dense prior's keyframe %lld is not in the window", (long long)id);
+    pos.push_back(it->second);
+  }
+  if (pos != w->dp_pos || !w->dprior) {
+    LVF_TRY(lvf::dense_prior_assign(w->ctx, &w->dprior, (int)pos.size(), pos.data(), w->dp_x0.data(), w->dp_info.data(), w->dp_eta.data(), w->dp_c0));
+    w->dp_pos = pos;
+  }
+  *out = w->dprior;
+  return LVF_OK;
+}
+
 static int configure_problem(lvf_window* w) {
+  lvf_dense_prior* dense = nullptr;
+  LVF_TRY(window_dense_prior(w, &dense));
   if (!w->prob) {
     LVF_TRY(lvf_problem_create(w->ctx, w->st, w->tc, w->tf, w->po, w->imu, &w->prob));
     LVF_TRY(lvf_problem_set_pose_priors(w->prob, w->prior));
+    if (dense) LVF_TRY(problem_configure(w->prob, dense));
   } else {
-    LVF_TRY(problem_configure(w->prob));
+    LVF_TRY(problem_configure(w->prob, dense));      // (the prior's keyframes are part of the elimination plan's key)
   }
   return window_attach_lidar(w);
 }
@@ -1137,6 +1175,104 @@ int lvf_window_marginal(lvf_window* w, const lvf_solver_options* o, const int64_
   lvf_solver_summary summary;
   LVF_TRY(lvf_window_solve(w, &refresh, &summary));
   return lvf_problem_marginal(w->prob, o, kfs, n_sel, info, cov, stats);
+}
+
+// ---- the dense prior of the window and the marginalising slide
+int lvf_window_set_dense_prior(lvf_window* w, int n_sel, const int64_t* kf_ids, const double* x0, const double* info, const double* eta, double c0) {
+  LVF_REQUIRE(w, "lvf_window_set_dense_prior: null window");
+  if (n_sel == 0) { w->dp_ids.clear(); w->dp_pos.clear(); return LVF_OK; }
+  LVF_REQUIRE(n_sel >= 1 && n_sel <= 8, "lvf_window_set_dense_prior: %d keyframes (1 .. 8, or 0 to remove the prior)", n_sel);
+  LVF_REQUIRE(kf_ids && x0 && info, "lvf_window_set_dense_prior: null input array");
+  const int m = 15 * n_sel;
+  for (int i = 0; i < n_sel; ++i) {
+    LVF_REQUIRE(w->kf_index.count(kf_ids[i]), "lvf_window_set_dense_prior: keyframe %lld is not in the window", (long long)kf_ids[i]);
+    for (int j = 0; j < i; ++j) LVF_REQUIRE(kf_ids[j] != kf_ids[i], "lvf_window_set_dense_prior: keyframe %lld listed twice", (long long)kf_ids[i]);
+    double n2 = 0.0;
+    for (int c = 0; c < 16; ++c) LVF_REQUIRE(std::isfinite(x0[16 * i + c]), "lvf_window_set_dense_prior: x0 of keyframe %lld is not finite", (long long)kf_ids[i]);
+    for (int c = 0; c < 4; ++c) n2 += x0[16 * i + c] * x0[16 * i + c];
+    LVF_REQUIRE(n2 > 0.0, "lvf_window_set_dense_prior: x0 of keyframe %lld has a zero quaternion", (long long)kf_ids[i]);
+  }
+  for (int i = 0; i < m; ++i) {
+    for (int j = 0; j <= i; ++j) LVF_REQUIRE(std::isfinite(info[(size_t)i * m + j]), "lvf_window_set_dense_prior: info[%d][%d] is not finite", i, j);
+    LVF_REQUIRE(!eta || std::isfinite(eta[i]), "lvf_window_set_dense_prior: eta[%d] is not finite", i);
+  }
+  LVF_REQUIRE(std::isfinite(c0), "lvf_window_set_dense_prior: c0 is not finite");
+  w->dp_ids.assign(kf_ids, kf_ids + n_sel);
+  w->dp_x0.assign(x0, x0 + 16 * n_sel);
+  w->dp_info.assign(info, info + (size_t)m * m);
+  if (eta) w->dp_eta.assign(eta, eta + m); else w->dp_eta.assign(m, 0.0);
+  w->dp_c0 = c0;
+  w->dp_pos.clear();                         // the device copy is stale
+  return LVF_OK;
+}
+
+int lvf_window_get_dense_prior(const lvf_window* w, int* n_sel, int64_t* kf_ids, double* x0, double* info, double* eta, double* c0) {
+  LVF_REQUIRE(w && n_sel, "lvf_window_get_dense_prior: null argument");
+  const int n = (int)w->dp_ids.size();
+  *n_sel = n;
+  if (n == 0) return LVF_OK;
+  if (kf_ids) std::copy(w->dp_ids.begin(), w->dp_ids.end(), kf_ids);
+  if (x0) std::copy(w->dp_x0.begin(), w->dp_x0.end(), x0);
+  if (info) std::copy(w->dp_info.begin(), w->dp_info.end(), info);
+  if (eta) std::copy(w->dp_eta.begin(), w->dp_eta.end(), eta);
+  if (c0) *c0 = w->dp_c0;
+  return LVF_OK;
+}
+
+// The sub-problem over D (the departing keyframes) and s (the first kept one): every block BuildProblem's rules give for that keyframe
+// list that touches D — D's visual blocks, weak-constraint priors and lidar planes, the ImuError blocks along D and into s, the window's
+// dense prior — and nothing of s's own: no visual block (what kept frames see of D's landmarks lives on as PoseOnly blocks after the slide,
+// so no factor is counted twice and none is lost), no weak-constraint prior.  Its marginal on s becomes the window's dense prior.
+int lvf_window_slide_marginalize(lvf_window* w, int64_t first_active_kf_id, const lvf_solver_options* o, lvf_marginal_stats* stats) {
+  LVF_REQUIRE(w && o && stats, "lvf_window_slide_marginalize: null argument");
+  *stats = lvf_marginal_stats{0, 0, 0, 0.0};
+  size_t drop = 0;
+  while (drop < w->kfs.size() && w->kfs[drop].id < first_active_kf_id) ++drop;
+  if (drop == 0) return LVF_OK;
+  LVF_REQUIRE(drop < w->kfs.size(), "lvf_window_slide_marginalize: no keyframe at or after %lld would stay", (long long)first_active_kf_id);
+  const int64_t s_id = w->kfs[drop].id;
+  for (int64_t id : w->dp_ids)
+    LVF_REQUIRE(id <= s_id, "lvf_window_slide_marginalize: the window's dense prior sits on keyframe %lld, beyond the first kept keyframe %lld: it cannot be "
+                "absorbed into a prior on that keyframe alone (remove it, or slide further)", (long long)id, (long long)s_id);
+  LVF_TRY(lvf::enter(w->ctx));
+  if (!w->sub) {
+    lvf_window_options so = w->opt;
+    so.device_assembly = 0;                  // (re-filled from scratch at every slide: the resident tables of the device-side assembly have nothing to keep)
+    LVF_TRY(lvf_window_create(w->ctx, &w->left, &w->right, &so, &w->sub));
+    w->sub->is_sub = true;
+  }
+  lvf_window* q = w->sub;
+  q->kfs.assign(w->kfs.begin(), w->kfs.begin() + drop + 1);
+  q->kfs.back().obs.clear();
+  for (lvf_window::Kf& f : q->kfs) f.d_dirty = true;
+  q->kf_index.clear();
+  for (size_t k = 0; k < q->kfs.size(); ++k) q->kf_index[q->kfs[k].id] = (int)k;
+  q->departed = w->departed;
+  q->lms = w->lms; q->lm_index = w->lm_index; q->lm_free = w->lm_free; q->n_lm_live = w->n_lm_live;      // (indices are stable: the observations keep theirs)
+  q->lidar_seg.clear();
+  for (size_t k = 0; k < drop; ++k) {
+    const auto is = w->lidar_seg.find(w->kfs[k].id);
+    if (is != w->lidar_seg.end()) q->lidar_seg[is->first] = is->second;      // borrowed
+  }
+  q->lidar_dirty = q->lidar != nullptr || !q->lidar_seg.empty();
+  q->dp_ids = w->dp_ids; q->dp_x0 = w->dp_x0; q->dp_info = w->dp_info; q->dp_eta = w->dp_eta; q->dp_c0 = w->dp_c0; q->dp_pos.clear();
+  lvf_solver_options refresh = *o;
+  refresh.max_num_iterations = 0;
+  lvf_solver_summary summary;
+  const int kf_s = (int)drop;
+  std::vector<double> info(225), eta(15);
+  double c0 = 0.0;
+  int rc = lvf_window_solve(q, &refresh, &summary);
+  if (rc == LVF_OK) rc = lvf_problem_marginal_prior(q->prob, o, &kf_s, 1, info.data(), eta.data(), &c0, stats);
+  q->lidar_seg.clear();                      // (this window's segments: the slide below destroys the departing ones)
+  LVF_TRY(rc);
+  const lvf_window::Kf s = w->kfs[drop];
+  LVF_TRY(lvf_window_slide(w, first_active_kf_id));
+  w->dp_ids.clear(); w->dp_pos.clear();
+  if (stats->fail != 0) return LVF_OK;       // soft failure: the window has slid, without a prior
+  double x0[16];
+  std::memcpy(x0, s.pose, 56); std::memcpy(x0 + 7, s.vel, 24); std::memcpy(x0 + 10, s.ba, 24); std::memcpy(x0 + 13, s.bg, 24);
+  return lvf_window_set_dense_prior(w, 1, &s_id, x0, info.data(), eta.data(), c0);
 }
 
 }  // extern "C"
